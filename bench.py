@@ -1,6 +1,6 @@
 """Headline benchmark: 30-s EEG windows/sec on the hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N = 1 runs in this process; N > 1 without a torch.distributed.run environment re-executes itself as
         `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
         (one rank per GPU over RCCL); launched under torch.distributed.run directly it reads RANK / LOCAL_RANK / WORLD_SIZE.
@@ -9,11 +9,24 @@ A "step" is one LDM train step of the reference loop (/root/reference/src/traini
 on one synthetic batch of raw (B,1,3072) windows per GPU: draw timesteps + noise + eps on device, frozen
 AutoencoderKL [32,32,64] encode + sampling x scale_factor, add_noise, UNet(config_ldm.yaml) forward, MSE,
 hand-written backward, gradient all-reduce (N>1, RCCL), fused Adam, bf16 weight refresh.
-Secondary measurements (same JSON line, `parts`): the AEKL/GAN train step of BASELINE configs[1]
-(config_aekl_eeg_2_2_4_spec.yaml, spectral loss on, batch 256) and DDIM-50 sampling + decode.  Inputs are resident in HBM when the
-timed region starts.  Prints ONE JSON line on rank 0; `roofline` is measured live with HIP events
-around every launch of the dominant kernel class on the library's stream; `cpu_baseline` times the
-oracle (torch CPU fp32, same math) on this host's cores on a bounded sample (rank 0, N=1 only).
+Inputs are resident in HBM when the timed region starts, and the same arguments give the same inputs (weights, windows, noise)
+in every run.  Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times K steps and prints the line, whose
+`roofline`, `cpu_baseline` and `parts` are null.
+
+The last timed step starts from the state before warm-up (weights, Adam moments and step count, loss scale), restored outside the
+timed region, so what it computes depends on the arguments alone (see main()).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed (float32 .npy, about 8 MB in all):
+    loss.npy            the step's MSE loss, shape (1,)
+    grad_sample.npy     the UNet's flat fp32 gradient at 2**20 fixed positions (numpy default_rng(0), sorted)
+    params_sample.npy   the UNet's flat fp32 parameters after the optimizer step, at the same positions
+
+--full adds what takes runs of its own (--no-roofline / --no-parts / --no-cpu-baseline still leave one out):
+    roofline       measured live with HIP events around every launch of the dominant kernel class on the library's stream
+    parts          secondary workloads (single GPU): the AEKL/GAN train step of BASELINE configs[1] (config_aekl_eeg_2_2_4_spec.yaml,
+                   spectral loss on, batch 256), DDIM-50 sampling + decode, and the pixel-space DM train step of configs[4]
+    cpu_baseline   the oracle (torch CPU fp32, same math) on this host's cores on a bounded sample (rank 0, N=1 only)
+    comm           N > 1: the ranks the collective spans, the bare all-reduce and the exposed communication per step
 """
 import argparse
 import hashlib
@@ -97,7 +110,7 @@ def aekl_gan_step_bytes(num_channels, L, s, n_res=2, d_ch=64, d_layers=3, fused=
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256, help="windows per GPU per step (C4: 2048 / 8 GPUs)")
     ap.add_argument("--length", type=int, default=768, help="latent length (3072 / 4)")
@@ -106,7 +119,28 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-parts", action="store_true", help="skip the secondary AEKL-GAN / DDIM-50 measurements")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure roofline, parts, cpu_baseline and (N > 1) comm")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_SAMPLE = 1 << 20      # elements of the flat gradient / parameter buffers written by --dump-outputs
+
+
+def dump_outputs(out_dir, loss, unet):
+    """The last timed step's loss, and its gradient and updated parameters at DUMP_SAMPLE fixed positions of the flat buffers."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(unet.flat.numel())
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    idx = torch.from_numpy(idx).to(unet.flat.device)
+    outs = {"loss": loss.detach().reshape(-1), "grad_sample": unet.flat_grad[idx], "params_sample": unet.flat[idx]}
+    for name, t in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def _cpu_model():
@@ -340,6 +374,7 @@ def main():
     dev = torch.device("cuda", local)
     B, L = args.batch, args.length
     dtype = {"bf16": "bfloat16", "f16": "float16", "f32": "float32"}[args.dtype]
+    torch.manual_seed(0)       # the models' default init draws from torch's global generator: same weights in every run
 
     unet = UNetModel(**UNET_CFG, dtype=dtype, device=local)
     g = torch.Generator().manual_seed(42)
@@ -376,26 +411,48 @@ def main():
             gs.wait()
         scaler.step(opt); scaler.update()      # disabled scaler: plain opt.step()
 
+    def timed_steps(first, n):
+        """seconds for steps first .. first + n - 1, from a drained device to a drained device"""
+        if world > 1:
+            torch.distributed.barrier()
+        torch.cuda.synchronize()
+        t0 = time.time()
+        for i in range(first, first + n):
+            step(i)
+        if world > 1:
+            torch.distributed.barrier()
+        torch.cuda.synchronize()
+        return time.time() - t0
+
+    # The last timed step starts from the state saved here, before any step.  In every step the bias / GroupNorm gradients and the loss
+    # vary from run to run at fp32 rounding level (the order of atomic adds); carried through Adam and the bf16 weight refresh over
+    # many steps, that grows into visibly different weights and gradients.  Restarting the last step from this state keeps its
+    # outputs (--dump-outputs, final_loss) equal across runs up to that rounding.
+    start_state = (unet.flat.clone(), opt.m.clone(), opt.v.clone(), opt.step_count, scaler.state_dict())
+
+    def restore_start_state():
+        flat, m, v, opt.step_count, sc = start_state
+        unet.flat.copy_(flat); opt.m.copy_(m); opt.v.copy_(v)
+        scaler.load_state_dict(sc)
+        torch.cuda.synchronize()
+        unet.sync_weights()
+
     for i in range(args.warmup):
         step(i)
-    if world > 1:
-        torch.distributed.barrier()
-    torch.cuda.synchronize()
-    t0 = time.time()
-    for i in range(args.steps):
-        step(args.warmup + i)
-    if world > 1:
-        torch.distributed.barrier()
-    torch.cuda.synchronize()
-    dt = torch.tensor([time.time() - t0], device=dev)
+    elapsed = timed_steps(args.warmup, args.steps - 1)
+    restore_start_state()      # outside the timed region
+    elapsed += timed_steps(args.warmup + args.steps - 1, 1)
+    dt = torch.tensor([elapsed], device=dev)
     if world > 1:
         torch.distributed.all_reduce(dt, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(dt)
     final_loss = float(loss)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, unet)
 
     # ---- N > 1: make the record self-checking -- how many ranks the collective really spans, and what the exchange costs
     comm_info = None
-    if world > 1:
+    if world > 1 and args.full:
         import torch.distributed as dist
         n_grad = int(unet.flat_grad.numel())
         probe = torch.ones(1, device=dev)
@@ -439,7 +496,7 @@ def main():
                      "exposed_comm_ms_per_step": round(ms_step - 1e3 * float(loc), 3)}
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         ctx.prof_enable(True)
         ROOF_STEPS = 6      # 252 launches of the dominant class: two steps were too few to average out a transient (one run read 650 TF/s where the
         for i in range(ROOF_STEPS):      # rocprof trace of the same box gave 760)
@@ -490,7 +547,7 @@ def main():
 
     # ---- secondary workloads (rank 0 only; not part of `value`)
     parts = None
-    if rank == 0 and world == 1 and not args.no_parts:      # secondary workloads only on the single-GPU run
+    if rank == 0 and world == 1 and args.full and not args.no_parts:      # secondary workloads only on the single-GPU run
         parts = {}
         Ba = args.batch
         ae2 = AutoencoderKL(spatial_dims=1, in_channels=1, out_channels=1, num_channels=[2, 2, 4], latent_channels=1, num_res_blocks=2,
@@ -603,7 +660,7 @@ def main():
                                         "final_loss": round(float(ldm), 5), "gflop_per_window": 183.0}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     if rank == 0 and roofline is not None:

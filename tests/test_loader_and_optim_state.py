@@ -85,7 +85,7 @@ def test_window_loader_splits_and_shards(nights):
             f.write("FILE_NAME_EEG\nnot_there\n")
         WindowLoader(str(d), 8, path_ids=str(d / "ids_bad.csv"))
     with pytest.raises(ValueError, match="FILE_NAME_EEG"):
-        WindowLoader(str(d), 8, path_ids="/root/repo/tests/golden/make_golden_cases.py")
+        WindowLoader(str(d), 8, path_ids=os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_golden_cases.py"))
     # no ids: every recording in the directory; constant recording normalises to zeros (monai rescale_array)
     assert len(WindowLoader(str(d), 8).files) == 5
     from eegldm.entry.common import normalise_recording

@@ -31,7 +31,7 @@ for MODE in 0 1; do
     [ "$N" -le "$MAX" ] || continue
     echo "== bench.py --gpus $N  EEGLDM_NATIVE_COLLECTIVES=$MODE"
     EEGLDM_NATIVE_COLLECTIVES=$MODE timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N + 10 * MODE)) \
-      bench.py --gpus $N --steps 20 --warmup 5 --no-parts --no-cpu-baseline > /tmp/first_multigpu_${MODE}_$N.log 2>&1 || { tail -20 /tmp/first_multigpu_${MODE}_$N.log; echo "FAILED: bench --gpus $N mode $MODE"; exit 1; }
+      bench.py --gpus $N --steps 20 --warmup 5 --full --no-parts --no-cpu-baseline > /tmp/first_multigpu_${MODE}_$N.log 2>&1 || { tail -20 /tmp/first_multigpu_${MODE}_$N.log; echo "FAILED: bench --gpus $N mode $MODE"; exit 1; }
     summarise /tmp/first_multigpu_${MODE}_$N.log
   done
 done

@@ -173,7 +173,7 @@ def main(prof, tag):
                   open(os.path.join(P, f"{RND}_pmc_mfma_busy.json"), "w"), indent=1)
         print("wrote", RND + "_pmc_mfma_busy.json")
     kernel_table(os.path.join(prof, "trace_ldm"), os.path.join(P, f"{RND}_ldm_step_bf16_B256_kernel_stats_{tag}.txt"),
-                 "# EEGLDM_NO_SIDE_STREAM=1 rocprofv3 --kernel-trace --stats -- python bench.py --no-parts --no-cpu-baseline --steps 7")
+                 "# EEGLDM_NO_SIDE_STREAM=1 rocprofv3 --kernel-trace --stats -- python bench.py --full --no-parts --no-cpu-baseline --steps 7")
     kernel_table(os.path.join(prof, "trace_aekl"), os.path.join(P, f"{RND}_aekl_gan_step_bf16_B256_kernel_stats_{tag}.txt"),
                  "# EEGLDM_NO_SIDE_STREAM=1 rocprofv3 --kernel-trace --stats -- python tools/debug/aekl_bench.py 256 bfloat16   (8 steps)")
     kernel_table(os.path.join(prof, "trace_parts"), os.path.join(P, f"{RND}_ddim50_and_pixel_dm_kernel_stats_{tag}.txt"),

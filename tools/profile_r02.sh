@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof_r02; rm -rf $OUT; mkdir -p $OUT
 TAG=${1:-v1}
 export EEGLDM_NO_SIDE_STREAM=1          # one stream: a launch's duration is its own
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_ldm -o ldm -- python bench.py --no-parts --no-cpu-baseline --steps 7 > $OUT/bench_ldm_line.json 2> $OUT/trace_ldm.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_ldm -o ldm -- python bench.py --full --no-parts --no-cpu-baseline --steps 7 > $OUT/bench_ldm_line.json 2> $OUT/trace_ldm.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_aekl -o aekl -- python tools/debug/aekl_bench.py 256 bfloat16 > $OUT/aekl.txt 2> $OUT/trace_aekl.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_parts -o parts -- python tools/debug/parts_bench.py > $OUT/parts.txt 2> $OUT/trace_parts.log
 for C in FETCH_SIZE WRITE_SIZE; do

@@ -15,6 +15,6 @@ rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_aekl -o aekl -- pytho
 F=$(find $OUT/trace_aekl -name '*kernel_trace.csv' | head -1)
 python tools/step_timeline.py "$F" adam_kernel --seq > $OUT/seq_aekl.txt 2>&1
 unset EEGLDM_NO_SIDE_STREAM
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; tail -c 600 $OUT/bench.json
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; tail -c 600 $OUT/bench.json
 for G in 0 1; do EEGLDM_SAMPLE_GRAPH=$G python tools/debug/b1_trace.py 1 > $OUT/b1_graph$G.log 2>&1; tail -2 $OUT/b1_graph$G.log; done
 rm -rf $OUT/trace_ldm $OUT/trace_aekl
