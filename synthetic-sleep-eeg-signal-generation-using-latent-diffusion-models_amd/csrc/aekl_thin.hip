@@ -234,7 +234,7 @@ __device__ void f_heads_t(const ThinOp& o, const float* P, const Bufs& B, float*
       float mu = P[o.b + co], lv = P[o.b2 + co];
 #pragma unroll
       for (int ci = 0; ci < LAT; ci++) { mu = fmaf(P[o.w + co * LAT + ci], h[ci], mu); lv = fmaf(P[o.w2 + co * LAT + ci], h[ci], lv); }
-      const float lvc = fminf(20.f, fmaxf(-30.f, lv));
+      const float lvc = clamp_keep_nan(lv, -30.f, 20.f);
       const float sg = __expf(0.5f * lvc);
       const float e = eps ? eps[co * L + l] : 0.f;
       Z[co * L + l] = fmaf(e, sg, mu);
@@ -452,7 +452,7 @@ __device__ void b_heads_t(const ThinOp& o, const float* P, float* __restrict__ G
     for (int co = 0; co < LAT; co++) {
       const float dz = DZ[co * L + l], mu = tmu[co * L + l], lv = tlv[co * L + l];
       const bool inside = lv > -30.f && lv < 20.f;             // clamp passes the gradient strictly inside (torch.clamp)
-      const float lvc = fminf(20.f, fmaxf(-30.f, lv));
+      const float lvc = clamp_keep_nan(lv, -30.f, 20.f);
       const float sg = __expf(0.5f * lvc);
       const float e = eps ? eps[co * L + l] : 0.f;
       dmu[co] = fmaf(klw_over_B, mu, dz) + (dme ? dme[co * L + l] : 0.f);       // z = mu + eps sigma ; KL: d/dmu = mu

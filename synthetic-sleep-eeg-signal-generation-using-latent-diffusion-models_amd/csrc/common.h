@@ -62,7 +62,7 @@ extern std::atomic<int> g_eeg_live_ctx;      // contexts alive in this process (
 // ---------------------------------------------------------------- context
 struct WgradRec;      // one deferred weight-gradient problem (defined below, after GemmArgs)
 struct GemmGroup;
-struct ProfRec { int cls; double flops; hipEvent_t a, b; int M, N, K, taps, splitk; };
+struct ProfRec { int cls; double flops; hipEvent_t a, b; int M, N, K, taps, splitk; const char* kern = ""; };   // kern: which kernel family served the launch (eegldm_prof_dump)
 enum { PROF_CONV_FWD = 0, PROF_CONV_DGRAD = 1, PROF_CONV_WGRAD = 2, PROF_GEMM_NT = 3, PROF_GEMM_NN = 4, PROF_GEMM_TN = 5, PROF_NCLASS = 6 };
 
 struct eegldm_ctx {
@@ -176,6 +176,10 @@ template <typename T> __device__ __forceinline__ void st_f32(T* p, float v);
 template <> __device__ __forceinline__ void st_f32<float>(float* p, float v) { *p = v; }
 template <> __device__ __forceinline__ void st_f32<bf16_t>(bf16_t* p, float v) { *p = f32_to_bf16(v); }
 template <> __device__ __forceinline__ void st_f32<f16_t>(f16_t* p, float v) { p->v = __builtin_bit_cast(unsigned short, (_Float16)v); }
+
+// torch.clamp(v, lo, hi): a NaN stays NaN.  fminf / fmaxf return the non-NaN operand, so a bare fminf(hi, fmaxf(lo, v)) would turn a NaN
+// log-variance into lo and a NaN x0 into -1 -- a finite result where the reference (and GradScaler's overflow check) sees the NaN.
+__device__ __forceinline__ float clamp_keep_nan(float v, float lo, float hi) { return v != v ? v : fminf(hi, fmaxf(lo, v)); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -368,7 +368,7 @@ int conv_skinny_ex(eegldm_ctx* ctx, int dtype, const void* x, long ldx, const vo
   ProfRec rec; const bool prof = ctx->prof_on;
   if (prof) {
     rec.cls = taps == 3 ? PROF_CONV_FWD : PROF_GEMM_NT; rec.flops = 2.0 * (double)M * Cout * ((double)Cin * taps + (ext ? ext->Cin2 : 0));
-    rec.M = (int)M; rec.N = Cout; rec.K = Cin; rec.taps = taps; rec.splitk = 1;
+    rec.M = (int)M; rec.N = Cout; rec.K = Cin; rec.taps = taps; rec.splitk = 1; rec.kern = gn ? "conv_skinny_gn" : (ext ? "conv_skinny_ext" : "conv_skinny");
     HIP_TRY(hipEventCreate(&rec.a)); HIP_TRY(hipEventCreate(&rec.b));
     HIP_TRY(hipEventRecord(rec.a, ctx->stream));
   }

@@ -428,7 +428,7 @@ int conv_ws_try(eegldm_ctx* ctx, int dtype, const void* x, long ldx, const void*
   ProfRec rec; const bool prof = ctx->prof_on;          // same per-class accounting as gemm_launch (bench.py roofline leg)
   if (prof) {
     rec.cls = transposed ? PROF_CONV_DGRAD : PROF_CONV_FWD; rec.flops = 2.0 * (double)M * N * Kred * 3.0;
-    rec.M = (int)M; rec.N = N; rec.K = Kred; rec.taps = 3; rec.splitk = 1;
+    rec.M = (int)M; rec.N = N; rec.K = Kred; rec.taps = 3; rec.splitk = 1; rec.kern = "conv_ws";
     HIP_TRY(hipEventCreate(&rec.a)); HIP_TRY(hipEventCreate(&rec.b));
     HIP_TRY(hipEventRecord(rec.a, ctx->stream));
   }
@@ -474,7 +474,7 @@ int conv_ws2_try(eegldm_ctx* ctx, int dtype, int dgrad, const void* x, const voi
   ProfRec rec; const bool prof = ctx->prof_on;
   if (prof) {
     rec.cls = dgrad ? PROF_CONV_DGRAD : PROF_CONV_FWD; rec.flops = 2.0 * (double)M * 256 * 128 * 3.0;
-    rec.M = (int)M; rec.N = 256; rec.K = 128; rec.taps = 3; rec.splitk = 1;
+    rec.M = (int)M; rec.N = 256; rec.K = 128; rec.taps = 3; rec.splitk = 1; rec.kern = "conv_ws2";
     HIP_TRY(hipEventCreate(&rec.a)); HIP_TRY(hipEventCreate(&rec.b)); HIP_TRY(hipEventRecord(rec.a, ctx->stream));
   }
   const dim3 grid((unsigned)nbx, 2);

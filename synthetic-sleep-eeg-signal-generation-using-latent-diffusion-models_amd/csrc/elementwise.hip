@@ -370,7 +370,7 @@ __global__ void ddim_step_kernel(const float* __restrict__ mo, const float* __re
     if (pred == EEGLDM_PRED_EPSILON) { x0 = (s - sb * o) / sa; e = o; }
     else if (pred == EEGLDM_PRED_V) { x0 = sa * s - sb * o; e = sa * o + sb * s; }
     else { x0 = o; e = (s - sa * x0) / sb; }
-    if (clip) x0 = fminf(1.0f, fmaxf(-1.0f, x0));
+    if (clip) x0 = clamp_keep_nan(x0, -1.0f, 1.0f);
     prev[i] = sap * x0 + sbp * e;
     if (x0o) x0o[i] = x0;
   }
@@ -387,7 +387,7 @@ __global__ void ddim_step_eta_kernel(const float* __restrict__ mo, const float* 
     if (pred == EEGLDM_PRED_EPSILON) { x0 = (s - sb * o) / sa; e = o; }
     else if (pred == EEGLDM_PRED_V) { x0 = sa * s - sb * o; e = sa * o + sb * s; }
     else { x0 = o; e = (s - sa * x0) / sb; }
-    if (clip) x0 = fminf(1.0f, fmaxf(-1.0f, x0));
+    if (clip) x0 = clamp_keep_nan(x0, -1.0f, 1.0f);
     prev[i] = fmaf(sigma, nz[i], fmaf(sap, x0, dir * e));
     if (x0o) x0o[i] = x0;
   }
@@ -404,7 +404,7 @@ __global__ void ddpm_step_kernel(const float* __restrict__ mo, const float* __re
     if (pred == EEGLDM_PRED_EPSILON) x0 = (s - sb * o) / sa;
     else if (pred == EEGLDM_PRED_V) x0 = sa * s - sb * o;
     else x0 = o;
-    if (clip) x0 = fminf(1.0f, fmaxf(-1.0f, x0));
+    if (clip) x0 = clamp_keep_nan(x0, -1.0f, 1.0f);
     float m = c0 * x0 + ct * s;
     if (sigma != 0.0f) m += sigma * nz[i];
     prev[i] = m;

@@ -1184,7 +1184,7 @@ int gemm_launch_grouped(eegldm_ctx* ctx, const GemmArgs& a_in, const GemmGroup& 
   if (prof) {
     rec.cls = a.taps == 3 ? PROF_CONV_WGRAD : PROF_GEMM_TN;
     rec.flops = 2.0 * a.M * a.N * (double)a.K * a.taps * a.ngroup;
-    rec.M = a.M; rec.N = a.N; rec.K = a.K; rec.taps = a.taps; rec.splitk = a.splitk;
+    rec.M = a.M; rec.N = a.N; rec.K = a.K; rec.taps = a.taps; rec.splitk = a.splitk; rec.kern = "gemm_grouped";
     HIP_TRY(hipEventCreate(&rec.a)); HIP_TRY(hipEventCreate(&rec.b));
     HIP_TRY(hipEventRecord(rec.a, ctx->stream));
   }
@@ -1255,6 +1255,7 @@ int gemm_launch(eegldm_ctx* ctx, const GemmArgs& a_in) {
     // algorithmic work: the transposed (strided) dgrad multiplies a half-zero virtual signal; only the real taps count
     rec.flops = 2.0 * a.M * a.N * (double)a.K * a.taps * a.ztaps * a.batch / (a.ups > 1 ? a.ups : 1);
     rec.M = a.M; rec.N = a.N; rec.K = a.K; rec.taps = a.taps * a.ztaps; rec.splitk = a.splitk;
+    rec.kern = fold_dst ? "gemm_splitk_fold" : (a.b_kblk ? "gemm_kblk" : "gemm");
     HIP_TRY(hipEventCreate(&rec.a)); HIP_TRY(hipEventCreate(&rec.b));
     HIP_TRY(hipEventRecord(rec.a, ctx->stream));
   }
@@ -1278,7 +1279,7 @@ int gemm_launch(eegldm_ctx* ctx, const GemmArgs& a_in) {
     else if (a.B_alt) { GemmArgs b = a; b.B = a.B_alt; b.bmode = GB_NT; b.b_kblk = 1; rc = gemm_big_try(ctx, b); }
     if (rc < 0) return rc;
   }
-  if (rc == 1) rc = 0;
+  if (rc == 1) { rc = 0; rec.kern = "gemm_big"; }
   else if (a.dtype == EEGLDM_F32) rc = launch_modes<float>(ctx, a);
   else if (a.dtype == EEGLDM_BF16) rc = launch_modes<bf16_t>(ctx, a);
   else if (a.dtype == EEGLDM_F16) rc = launch_modes<f16_t>(ctx, a);

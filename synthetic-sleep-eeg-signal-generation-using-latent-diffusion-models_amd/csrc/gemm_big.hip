@@ -1207,7 +1207,7 @@ int gemm_big_xf_try(eegldm_ctx* ctx, const GemmArgs& g, const float* scale, cons
   static DevOnce once1, once2;
   ProfRec rec; const bool prof = ctx->prof_on;
   if (prof) {
-    rec.cls = PROF_CONV_FWD; rec.flops = 2.0 * g.M * g.N * (double)g.K * 3; rec.M = g.M; rec.N = g.N; rec.K = g.K; rec.taps = 3; rec.splitk = 1;
+    rec.cls = PROF_CONV_FWD; rec.flops = 2.0 * g.M * g.N * (double)g.K * 3; rec.M = g.M; rec.N = g.N; rec.K = g.K; rec.taps = 3; rec.splitk = 1; rec.kern = "gemm_big_xf";
     HIP_TRY(hipEventCreate(&rec.a)); HIP_TRY(hipEventCreate(&rec.b)); HIP_TRY(hipEventRecord(rec.a, ctx->stream));
   }
   if (act == 1) {
@@ -1247,7 +1247,7 @@ int gemm_big_skip_try(eegldm_ctx* ctx, const GemmArgs& g, const void* x2, long l
   ProfRec rec; const bool prof = ctx->prof_on;
   if (prof) {
     rec.cls = PROF_CONV_FWD; rec.flops = 2.0 * g.M * g.N * ((double)g.K * 3 + K2);
-    rec.M = g.M; rec.N = g.N; rec.K = g.K + K2 / 3; rec.taps = 3; rec.splitk = 1;
+    rec.M = g.M; rec.N = g.N; rec.K = g.K + K2 / 3; rec.taps = 3; rec.splitk = 1; rec.kern = "gemm_big_skip";
     HIP_TRY(hipEventCreate(&rec.a)); HIP_TRY(hipEventCreate(&rec.b));
     HIP_TRY(hipEventRecord(rec.a, ctx->stream));
   }

@@ -315,7 +315,7 @@ __global__ __launch_bounds__(NT) void reparam_kernel(const T* __restrict__ mu, c
   float s = 0.f;
   GRID_STRIDE(i, n) {
     const float m = ld_f32(mu + i);
-    const float l = fminf(20.0f, fmaxf(-30.0f, ld_f32(lv + i)));
+    const float l = clamp_keep_nan(ld_f32(lv + i), -30.0f, 20.0f);
     const float sg = expf(0.5f * l);
     sigma[i] = sg;
     st_f32(z + i, eps ? m + eps[i] * sg : m);

@@ -25,6 +25,10 @@ int op_conv_fwd(eegldm_ctx* ctx, int dtype, const void* x, long ldx, const void*
   EEG_CHECK(act_slope <= 0.f, "fused activation is only available on the thin-input direct conv");
   // stride 2, 64 -> 128 channels (the discriminator's second layer, config_aekl_eeg.yaml:30-40): a stride-1 conv of the weight-stationary kernel
   // over pairs of input rows (elementwise.hip s2ws_pack) -- HBM-bound at 3+ TB/s where the general implicit GEMM's 6-k-step tiles reach 2
+  // Non-finite semantics differ from the reference here: output row t is a 3-tap conv over the row pairs t - 1 .. t + 1 (input rows 2t - 2 ..
+  // 2t + 3) whose weight holds zero taps, and inf * 0 = NaN, so a NaN / inf in input row r makes every y[t] with 2t - 2 <= r <= 2t + 3 NaN (the
+  // reference: 2t - 1 <= r <= 2t + 1); in the data gradient a non-finite dy row t makes the dx row pairs t - 1 .. t + 1 NaN.  A non-finite
+  // gradient is flagged all the same (tests/test_gpu_rounding.py models exactly this spread).
   if (K == 3 && stride == 2 && pad_l == 1 && pad_r == 1 && Cin == 64 && Cout == 128 && ldx == Cin && Lin == 2 * Lout && !rowvec && !resid &&
       dtype != EEGLDM_F32 && !ctx->s2ws_f.empty()) {
     auto it = ctx->s2ws_f.find(w);
