@@ -290,6 +290,27 @@ int eegldm_fill(eegldm_ctx*, float* p, long n, float value);
 int eegldm_ldm_train_step(eegldm_unet*, const float* latents, const float* noise, const int64_t* t,
                           const float* acp, int pred_type, int B, int L, float grad_scale, float* loss);
 
+/* ------------------------------------------------------------------ class-conditional UNet (additive; ABI 8)
+ * UNetModel(num_classes=K) (unet.py:342,366,379-380,531-533): one more parameter, label_emb.weight [K][4 * model_channels] (fp32, entry
+ * right after time_embed.2.bias -- the reference's parameter order -- and outside the tail slice the grad hook reports), and
+ * emb = time_embed(t_emb) + label_emb[y] ahead of the SiLU and the ResBlocks' projections.  Labels are device int64 [B] and must lie in
+ * [0, K); a label outside the range adds nothing (no read outside the table) -- the host checks them before the call.  The forward copies
+ * them into the executor, so eegldm_unet_backward after eegldm_unet_forward_cond does not read the caller's buffer; the backward adds
+ * d label_emb[c] = sum over samples with y_b == c of d emb[b], folded in sample order (no atomics; classes absent from the batch get
+ * exactly nothing).  The unconditional entry points (eegldm_unet_forward, eegldm_ldm_train_step, eegldm_sample) return an error on a
+ * conditional UNet and vice versa. */
+int eegldm_unet_create_cond(eegldm_ctx*, const eegldm_unet_cfg* cfg, int num_classes, eegldm_unet** out);
+int eegldm_unet_forward_cond(eegldm_unet*, const float* x, const int64_t* t, const int64_t* labels, float* y, int B, int L, int training);
+/* eegldm_ldm_train_step with labels and classifier-free guidance training: each sample's label is replaced by null_class (in [0, K)) with
+ * probability p_uncond, drawn from Philox(seed, offset + b) (eegldm_label_dropout); the backward uses the replaced labels.  p_uncond == 0 is
+ * the plain conditional step. */
+int eegldm_ldm_train_step_cond(eegldm_unet*, const float* latents, const float* noise, const int64_t* t, const float* acp, int pred_type,
+                               int B, int L, float grad_scale, float* loss, const int64_t* labels, float p_uncond, int64_t null_class,
+                               uint64_t seed, uint64_t offset);
+/* The label dropout on its own: out[b] = labels[b], or null_class when word 0 of Philox(seed, offset + b) / 2^32 < p_uncond. */
+int eegldm_label_dropout(eegldm_ctx*, const int64_t* labels, int64_t* out, int B, float p_uncond, int64_t null_class, uint64_t seed,
+                         uint64_t offset);
+
 /* Round-6 prototype: nn.Conv1d(k 3, padding 1) over SiLU(GroupNorm(x)) -- the in_layers / out_layers pair of
  * /root/reference/src/models/unet.py:261-263,287-291 -- with the normalisation applied to the conv's operand tile inside LDS, so the
  * normalised tensor is never written (no-grad forward only: nothing is kept for a backward).  gn_stats: fp32 [B][G][2] = (mean, rstd) of x, as
@@ -428,6 +449,20 @@ int eegldm_sample(eegldm_unet*, eegldm_aekl* ae, const float* noise, const int64
                   const float* a_prev_host, const float* beta_t_host, int n_steps, int ancestral, int pred_type, int clip_sample,
                   float inv_scale_factor, uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
                   int* graph_used_host);
+/* Class-conditional sampling (a UNet from eegldm_unet_create_cond): labels_host is a HOST array of B classes in [0, num_classes).
+ * guidance_scale w != 1: classifier-free guidance -- every forward runs 2B rows (the B samples with their labels, then the same latents
+ * with null_class, which must lie in [0, num_classes) too) and ONE kernel forms out = out_u + w (out_c - out_u) in fp32 on the raw model
+ * output and applies the DDIM / DDPM step (eegldm_guided_step).  w == 1 does not run the null-class half: it is the plain conditional
+ * sampler.  The embedding rows of all (timestep, class) pairs are computed once per call.  eegldm_sample on a conditional UNet is an error. */
+int eegldm_sample_cond(eegldm_unet*, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
+                       const float* a_prev_host, const float* beta_t_host, int n_steps, int ancestral, int pred_type, int clip_sample,
+                       float inv_scale_factor, uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
+                       int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class);
+/* The guided step itself: model_out holds 2n values, the conditional outputs then the null-class outputs; o = o_u + w (o_c - o_u), then
+ * eegldm_ddim_step (ancestral == 0) or eegldm_ddpm_step (ancestral != 0; noise may be NULL when a_prev == 1) on `sample` (n values).
+ * prev2 (nullable) receives a second copy of the result. */
+int eegldm_guided_step(eegldm_ctx*, const float* model_out, float guidance_scale, const float* sample, const float* noise, float a_t,
+                       float a_prev, float beta_t, int ancestral, int pred_type, int clip_sample, float* prev, float* prev2, long n);
 
 /* ------------------------------------------------------------------ data-parallel collectives (RCCL over xGMI)
  * One communicator per process / GPU.  Stands where the reference gathers gradients with single-process nn.DataParallel

@@ -112,6 +112,10 @@ SIGNATURES = {
     "eegldm_unet_forward": [_vp, _vp, _vp, _vp, _i, _i, _i],
     "eegldm_unet_backward": [_vp, _vp, _vp],
     "eegldm_ldm_train_step": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
+    "eegldm_unet_create_cond": [_vp, _vp, _i, C.POINTER(_vp)],
+    "eegldm_unet_forward_cond": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i],
+    "eegldm_ldm_train_step_cond": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _f, C.c_int64, C.c_uint64, C.c_uint64],
+    "eegldm_label_dropout": [_vp, _vp, _vp, _i, _f, C.c_int64, C.c_uint64, C.c_uint64],
     "eegldm_l1_loss": [_vp, _vp, _vp, _vp, _vp, _l, _f],
     "eegldm_lsgan_loss": [_vp, _vp, _i, _vp, _vp, _l, _f],
     "eegldm_spectral_loss": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f],
@@ -132,6 +136,9 @@ SIGNATURES = {
     "eegldm_psd_multitaper": [_vp, _vp, _vp, C.POINTER(_f), _i, _f, _i, _vp, _i, _i],
     "eegldm_sample": [_vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _f, C.c_uint64, _vp, _vp,
                       _i, _i, _i, C.POINTER(_i)],
+    "eegldm_sample_cond": [_vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _f, C.c_uint64,
+                           _vp, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_int64), _f, C.c_int64],
+    "eegldm_guided_step": [_vp, _vp, _f, _vp, _vp, _f, _f, _f, _i, _i, _i, _vp, _vp, _l],
     "eegldm_disc_create": [_vp, _vp, C.POINTER(_vp)],
     "eegldm_disc_destroy": [_vp],
     "eegldm_disc_num_entries": [_vp],

@@ -88,21 +88,21 @@ class FlatModule:
 # ---------------------------------------------------------------------------------------------------------------- UNet
 class _UNetFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, net, x, t, _p):
-        out = net._forward_native(x, t)                 # (bumps net._tape_id)
-        ctx.net, ctx.tape = net, net._tape_id
-        ctx.save_for_backward(x, t)
+    def forward(ctx, net, x, t, labels, _p):
+        out = net._forward_native(x, t, labels)         # (bumps net._tape_id)
+        ctx.net, ctx.tape, ctx.has_labels = net, net._tape_id, labels is not None
+        ctx.save_for_backward(x, t, labels if labels is not None else t)
         return out
 
     @staticmethod
     def backward(ctx, dy):
         net = ctx.net
-        x, t = ctx.saved_tensors
-        if net._tape_id != ctx.tape:             # another native call rewrote the tape since: rebuild this call's tape
-            net._forward_native(x, t)
+        x, t, labels = ctx.saved_tensors
+        if net._tape_id != ctx.tape:             # another native call rewrote the tape since: rebuild this call's tape, with ITS labels
+            net._forward_native(x, t, labels if ctx.has_labels else None)
         net._adopt_grad()
         dx = net.backward(dy.contiguous(), need_dx=ctx.needs_input_grad[1])      # (bumps: the tape is consumed)
-        return None, dx, None, None
+        return None, dx, None, None, None
 
 
 # ---------------------------------------------------------------------------------------------------------------- AutoencoderKL

@@ -412,6 +412,28 @@ __global__ void ddpm_step_kernel(const float* __restrict__ mo, const float* __re
   }
 }
 
+// Classifier-free guidance fused into the scheduler step: mo holds the conditional outputs [0, n) and the null-class outputs [n, 2n);
+// o = o_u + w (o_c - o_u) in fp32 on the raw model output (whatever the prediction type), then the DDIM (eta 0) or the ancestral DDPM
+// step of the kernels above.  prev2 (optional) receives a second copy of prev: the null-class half of the sampler's 2B-row latent buffer.
+__global__ void cfg_step_kernel(const float* __restrict__ mo, float w, const float* __restrict__ x, const float* __restrict__ nz, int ancestral,
+                                float sa, float sb, float c0, float ct, float sigma, int pred, int clip, float* __restrict__ prev,
+                                float* __restrict__ prev2, long n) {
+  GRID_STRIDE(i, n) {
+    const float ou = mo[n + i];
+    const float o = ou + w * (mo[i] - ou), s = x[i];
+    float x0, e;
+    if (pred == EEGLDM_PRED_EPSILON) { x0 = (s - sb * o) / sa; e = o; }
+    else if (pred == EEGLDM_PRED_V) { x0 = sa * s - sb * o; e = sa * o + sb * s; }
+    else { x0 = o; e = (s - sa * x0) / sb; }
+    if (clip) x0 = clamp_keep_nan(x0, -1.0f, 1.0f);
+    float m;
+    if (ancestral) { m = c0 * x0 + ct * s; if (sigma != 0.0f) m += sigma * nz[i]; }
+    else m = c0 * x0 + ct * e;                      // DDIM: c0 = sqrt(a_prev), ct = sqrt(1 - a_prev)
+    prev[i] = m;
+    if (prev2) prev2[i] = m;
+  }
+}
+
 // ------------------------------------------------------------------ MSE (training.py:437)
 __global__ __launch_bounds__(NT) void mse_kernel(const float* __restrict__ p, const float* __restrict__ t, float* __restrict__ loss,
                                                  float* __restrict__ dp, long n, float inv_n, float gscale, float* __restrict__ parts) {
@@ -513,6 +535,55 @@ __global__ void randint_kernel(int64_t* __restrict__ out, long n, int64_t high, 
     out[i] = (int64_t)(v % (unsigned long long)high);
   }
 }
+
+// ------------------------------------------------------------------ class labels (unet.py:366,379-380,531-533)
+// emb = time_embed(t_emb) + label_emb(y): row gather-add into the fp32 embedding rows; a label outside [0, K) reads nothing
+__global__ void label_emb_add_kernel(float* __restrict__ emb, long ld, const int64_t* __restrict__ y, const float* __restrict__ table,
+                                     int B, int te, int K) {
+  GRID_STRIDE(i, (long)B * te) {
+    const int b = (int)(i / te), j = (int)(i - (long)b * te);
+    const int64_t c = y[b];
+    if (c >= 0 && c < K) emb[b * ld + j] += table[c * te + j];
+  }
+}
+// nn.Embedding's weight gradient as an ordered fold: thread (c, j) sums demb[b][j] over the samples with y_b == c in index order and adds
+// the sum once; a class absent from the batch leaves its row untouched.  No atomics: bit-reproducible in every mode.
+__global__ void label_emb_grad_kernel(const float* __restrict__ demb, long ld, const int64_t* __restrict__ y, int B, int te, int K,
+                                      float* __restrict__ dtable) {
+  GRID_STRIDE(i, (long)K * te) {
+    const int c = (int)(i / te), j = (int)(i - (long)c * te);
+    // every row is loaded and a select (not a branch) picks it, so the loads pipeline; adding 0 leaves s exact, same order
+    float s = 0.f; bool any = false;
+#pragma unroll 8
+    for (int b = 0; b < B; b++) {
+      const bool m = y[b] == c;
+      const float d = demb[b * ld + j];
+      s += m ? d : 0.0f; any |= m;
+    }
+    if (any) dtable[i] += s;
+  }
+}
+// classifier-free guidance training: label b -> null_class with probability p, drawn from word 0 of Philox(seed, offset + b)
+__global__ void label_dropout_kernel(const int64_t* __restrict__ y, int64_t* __restrict__ out, int B, float p, int64_t null_class,
+                                     unsigned long long seed, unsigned long long offset) {
+  GRID_STRIDE(i, (long)B) {
+    int64_t v = y[i];
+    if (p > 0.0f) {
+      unsigned r[4]; philox(seed, offset + (unsigned long long)i, r);
+      if ((float)r[0] * 2.3283064365386963e-10f < p) v = null_class;
+    }
+    out[i] = v;
+  }
+}
+// sampler: row b of out = row y_b of table (16-byte accesses; w % 4 == 0)
+__global__ void emb_gather_kernel(const float4* __restrict__ table, const int64_t* __restrict__ y, int K, int w4, float4* __restrict__ out, int B) {
+  GRID_STRIDE(i, (long)B * w4) {
+    const int b = (int)(i / w4), j = (int)(i - (long)b * w4);
+    int64_t c = y[b];
+    c = c < 0 ? 0 : (c >= K ? K - 1 : c);
+    out[i] = table[c * w4 + j];
+  }
+}
 }  // namespace
 
 // ================================================================== internal launchers (used by the executors)
@@ -526,6 +597,24 @@ __global__ void randint_kernel(int64_t* __restrict__ out, long n, int64_t high, 
 
 int ew_temb(eegldm_ctx* ctx, const int64_t* t, void* out, int B, int dim, int dtype) {
   DISPATCH_T(dtype, hipLaunchKernelGGL((temb_kernel<T>), dim3(grid1d((long)B * dim, ctx)), dim3(NT), 0, ctx->stream, t, (T*)out, B, dim));
+  LAUNCH_CHECK(); return 0;
+}
+int ew_label_emb_add(eegldm_ctx* ctx, float* emb, long ld, const int64_t* y, const float* table, int B, int te, int K) {
+  hipLaunchKernelGGL(label_emb_add_kernel, dim3(grid1d((long)B * te, ctx)), dim3(NT), 0, ctx->stream, emb, ld, y, table, B, te, K);
+  LAUNCH_CHECK(); return 0;
+}
+int ew_label_emb_grad(eegldm_ctx* ctx, const float* demb, long ld, const int64_t* y, int B, int te, int K, float* dtable) {
+  hipLaunchKernelGGL(label_emb_grad_kernel, dim3(grid1d((long)K * te, ctx)), dim3(NT), 0, ctx->stream, demb, ld, y, B, te, K, dtable);
+  LAUNCH_CHECK(); return 0;
+}
+int ew_label_dropout(eegldm_ctx* ctx, const int64_t* y, int64_t* out, int B, float p, int64_t null_class, uint64_t seed, uint64_t offset) {
+  hipLaunchKernelGGL(label_dropout_kernel, dim3(grid1d(B, ctx)), dim3(NT), 0, ctx->stream, y, out, B, p, null_class, seed, offset);
+  LAUNCH_CHECK(); return 0;
+}
+int ew_emb_gather(eegldm_ctx* ctx, const float* table, const int64_t* y, int K, int w, float* out, int B) {
+  EEG_CHECK(w % 4 == 0 && K >= 1, "embedding gather: width %d must be a multiple of 4", w);
+  hipLaunchKernelGGL(emb_gather_kernel, dim3(grid1d((long)B * (w / 4), ctx)), dim3(NT), 0, ctx->stream, (const float4*)table, y, K, w / 4,
+                     (float4*)out, B);
   LAUNCH_CHECK(); return 0;
 }
 int ew_silu(eegldm_ctx* ctx, const float* x, void* y, long n, int dtype) {
@@ -856,6 +945,35 @@ extern "C" int eegldm_ddpm_step_var(eegldm_ctx* ctx, const float* mo, const floa
   hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid1d(n, ctx)), dim3(NT), 0, ctx->stream, mo, x, noise, (float)sqrt((double)a_t), (float)sqrt(bt),
                      (float)c0, (float)ct, sigma, pred, clip, prev, x0, n);
   LAUNCH_CHECK(); return 0;
+}
+extern "C" int eegldm_guided_step(eegldm_ctx* ctx, const float* mo, float w, const float* x, const float* noise, float a_t, float a_prev,
+                                  float beta_t, int ancestral, int pred, int clip, float* prev, float* prev2, long n) {
+  EEG_CHECK(ctx && mo && x && prev, "null argument");
+  EEG_CHECK(pred >= 0 && pred <= 2, "prediction type %d", pred);
+  EEG_CHECK(a_t > 0.0f && a_t < 1.0f && a_prev > 0.0f && a_prev <= 1.0f, "bad schedule values");
+  // the coefficients exactly as eegldm_ddim_step / eegldm_ddpm_step derive them
+  float c0, ct, sigma = 0.0f;
+  if (ancestral) {
+    EEG_CHECK(beta_t > 0.0f && beta_t < 1.0f, "bad beta_t");
+    const double bt = 1.0 - (double)a_t, bp = 1.0 - (double)a_prev;
+    c0 = (float)(sqrt((double)a_prev) * (double)beta_t / bt); ct = (float)(sqrt(1.0 - (double)beta_t) * bp / bt);
+    double var = bp / bt * (double)beta_t;
+    if (var < 1e-20) var = 1e-20;
+    if (a_prev < 1.0f) { sigma = (float)sqrt(var); EEG_CHECK(noise, "noise is required for t > 0"); }
+  } else {
+    c0 = sqrtf(a_prev); ct = sqrtf(1.0f - a_prev);
+  }
+  const float sa = ancestral ? (float)sqrt((double)a_t) : sqrtf(a_t), sb = ancestral ? (float)sqrt(1.0 - (double)a_t) : sqrtf(1.0f - a_t);
+  hipLaunchKernelGGL(cfg_step_kernel, dim3(grid1d(n, ctx)), dim3(NT), 0, ctx->stream, mo, w, x, noise, ancestral, sa, sb, c0, ct, sigma,
+                     pred, clip, prev, prev2, n);
+  LAUNCH_CHECK(); return 0;
+}
+extern "C" int eegldm_label_dropout(eegldm_ctx* ctx, const int64_t* labels, int64_t* out, int B, float p_uncond, int64_t null_class,
+                                    uint64_t seed, uint64_t offset) {
+  EEG_CHECK(ctx && labels && out && B >= 0, "bad argument");
+  EEG_CHECK(p_uncond >= 0.0f && p_uncond <= 1.0f, "p_uncond %g outside [0, 1]", (double)p_uncond);
+  if (B == 0) return 0;
+  return ew_label_dropout(ctx, labels, out, B, p_uncond, null_class, seed, offset);
 }
 extern "C" int eegldm_mse_loss(eegldm_ctx* ctx, const float* p, const float* t, float* loss, float* dp, long n, float gscale) {
   HIP_TRY(hipMemsetAsync(loss, 0, sizeof(float), ctx->stream));

@@ -22,6 +22,14 @@ int ew_film_silu_fwd(eegldm_ctx*, const void* hn, long ldh, const float* emb, lo
 int ew_film_silu_bwd(eegldm_ctx*, const void* hn, long ldh, const float* emb, long lde, const void* da, long ldda, void* dhn, long lddh,
                      float* demb, long ldde, int B, int L, int C, int dtype);
 int ew_copy_rows(eegldm_ctx*, void* dst, long ldd, const void* src, long lds, long rows, int C, int dtype);
+// class labels (unet.py:379-380,531-533): emb[b] += table[y_b] (fp32 rows of width te; labels outside [0, K) add nothing)
+int ew_label_emb_add(eegldm_ctx*, float* emb, long ld, const int64_t* y, const float* table, int B, int te, int K);
+// d table[c] += sum over b with y_b == c of demb[b], samples folded in index order (one thread per (class, column), no atomics)
+int ew_label_emb_grad(eegldm_ctx*, const float* demb, long ld, const int64_t* y, int B, int te, int K, float* dtable);
+// out[b] = y[b], replaced by null_class with probability p (Philox(seed, offset + b), word 0); p == 0 is a plain copy
+int ew_label_dropout(eegldm_ctx*, const int64_t* y, int64_t* out, int B, float p, int64_t null_class, uint64_t seed, uint64_t offset);
+// out[b] = table[y_b] (rows of width w, y clamped into [0, K)): the sampler's per-row embedding gather
+int ew_emb_gather(eegldm_ctx*, const float* table, const int64_t* y, int K, int w, float* out, int B);
 
 // direct_conv.hip
 bool conv_is_thin(int Cin, int Cout, int dtype);

@@ -89,6 +89,7 @@ struct NetBase {
   float* emb_all = nullptr; int etot = 0;   // batched timestep-embedding projections (UNet)
   long emb_ld = 0;                           // row stride of emb_all: etot, or 0 when all samples share one precomputed row (sampler)
   const float* emb_shared = nullptr;         // set by the sampler for the duration of an eval forward (unet_set_shared_emb)
+  long emb_shared_ld = 0;                    // its row stride: 0 (one row for every sample) or etot (one gathered row per sample)
   // Eval-mode forward of a few-row launch (sampling one window per call): the second GroupNorm of a ResBlock is not launched -- conv1
   // (conv_skinny.hip) leaves the (sum, sum of squares) of every 16-row x 4-channel piece of its output in `fuse_stats` and conv2 folds
   // them per group and normalises its operand on load.  The normalised tensor and the (mean, rstd) pairs are then NOT on the tape: such a forward cannot be back-propagated.
@@ -136,8 +137,11 @@ eegldm_ctx* unet_ctx(const eegldm_unet* u);
 int unet_in_channels(const eegldm_unet* u);
 int unet_emb_width(const eegldm_unet* u);
 long unet_embed_work_floats(const eegldm_unet* u);
-int unet_embed_table(eegldm_unet* u, const int64_t* tsteps_dev, int n, float* table, float* work);
-void unet_set_shared_emb(eegldm_unet* u, const float* row);
+int unet_embed_table(eegldm_unet* u, const int64_t* tsteps_dev, const int64_t* labels_dev, int n, float* table, float* work);
+void unet_set_shared_emb(eegldm_unet* u, const float* rows, long ld);
+int unet_num_classes(const eegldm_unet* u);
+// eegldm_unet_forward / _forward_cond without the entry checks (labels: NULL for a model built without classes)
+int unet_forward_labels(eegldm_unet* u, const float* x, const int64_t* t, const int64_t* labels, float* y, int B, int L, int training);
 int unet_out_channels(const eegldm_unet* u);
 void sampler_release(const eegldm_unet* u);
 eegldm_ctx* aekl_ctx(const eegldm_aekl* a);

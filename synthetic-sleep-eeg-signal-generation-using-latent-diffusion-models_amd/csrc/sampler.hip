@@ -26,7 +26,12 @@ struct SamplerState {
   // embedding rows of all timesteps of a run (eager path): table [emb_cap][etot], scratch of the embedding MLP, timesteps on the device
   float *emb_table = nullptr, *emb_work = nullptr; int64_t* steps_dev = nullptr; int emb_cap = 0;
   float* emb_row = nullptr;      // graph path: the ONE row the captured forward reads; the step's table row is copied here before every replay
-  bool exec_reads_row = false;   // how `exec` was captured: reading emb_row (table mode) or recomputing the embedding from s.tt -- a replay in the other mode would use a stale timestep
+  // how `exec` was captured: 0 = recomputing the embedding from s.tt (and s.lab), 1 = reading emb_row, 2 = reading emb_rows -- a replay in
+  // another mode would use a stale timestep
+  int exec_mode = -1;
+  // class labels: one per forward row ([labels | null_class x B] with guidance), on the device and the host copy they came from; the table
+  // then has K rows per step (tab_t / tab_y: the (timestep, class) of each row) and emb_rows [rows][etot] receives each step's gathered rows
+  int64_t* lab = nullptr; std::vector<int64_t> lab_host, tab_t, tab_y; int64_t* tab_y_dev = nullptr; float* emb_rows = nullptr;
 };
 std::map<GraphKey, SamplerState>& states() { static std::map<GraphKey, SamplerState> m; return m; }
 // guards the map AND serialises eegldm_sample: a call swaps ctx->stream for its duration, so two concurrent calls on contexts that
@@ -53,6 +58,9 @@ void sampler_release(const eegldm_unet* u) {
     if (s.emb_work) (void)hipFree(s.emb_work);
     if (s.steps_dev) (void)hipFree(s.steps_dev);
     if (s.emb_row) (void)hipFree(s.emb_row);
+    if (s.lab) (void)hipFree(s.lab);
+    if (s.tab_y_dev) (void)hipFree(s.tab_y_dev);
+    if (s.emb_rows) (void)hipFree(s.emb_rows);
     if (s.ev_in) (void)hipEventDestroy(s.ev_in);
     if (s.ev_out) (void)hipEventDestroy(s.ev_out);
     if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -60,10 +68,12 @@ void sampler_release(const eegldm_unet* u) {
   }
 }
 
-extern "C" int eegldm_sample(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
-                             const float* a_prev_host, const float* beta_t_host, int n_steps, int ancestral, int pred_type, int clip_sample,
-                             float inv_scale_factor, uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
-                             int* graph_used_host) {
+// labels_host (class-conditional UNets; NULL otherwise): one class per sample.  guidance_scale != 1 runs every forward on 2B rows -- the B
+// samples with their labels, then the same latents with null_class -- and mixes the two outputs inside the scheduler step (cfg_step_kernel)
+static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
+                       const float* a_prev_host, const float* beta_t_host, int n_steps, int ancestral, int pred_type, int clip_sample,
+                       float inv_scale_factor, uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
+                       int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
   EEG_CHECK(u && noise && timesteps_host && a_t_host && a_prev_host, "null argument");
   EEG_CHECK(!ancestral || beta_t_host, "the ancestral (DDPM) step needs beta_t");
   EEG_CHECK(n_steps >= 1 && B >= 1 && L >= 1, "bad sizes");
@@ -72,15 +82,29 @@ extern "C" int eegldm_sample(eegldm_unet* u, eegldm_aekl* ae, const float* noise
   const int C = unet_in_channels(u);
   EEG_CHECK(unet_out_channels(u) == C, "sampling needs in_channels == out_channels");
   EEG_CHECK(!ae || aekl_ctx(ae) == ctx, "the autoencoder and the UNet must share one context");
-  const long n = (long)B * C * L;
+  const int K = unet_num_classes(u);
+  const bool cond = labels_host != nullptr;
+  const bool guided = cond && guidance_scale != 1.0f;      // w == 1 is the plain conditional sampler: the null-class half is not run
+  const int Bf = guided ? 2 * B : B;                        // rows of every forward
+  bool shared = true;                                       // every forward row reads the same embedding row (row stride 0)
+  if (cond) {
+    for (int b = 0; b < B; b++) {
+      EEG_CHECK(labels_host[b] >= 0 && labels_host[b] < K, "label %lld of sample %d outside [0, %d)", (long long)labels_host[b], b, K);
+      if (labels_host[b] != labels_host[0]) shared = false;
+    }
+    if (guided) { EEG_CHECK(null_class >= 0 && null_class < K, "null_class %lld outside [0, %d)", (long long)null_class, K); shared = false; }
+  }
+  const long n = (long)B * C * L, nf = (long)Bf * C * L;
   std::lock_guard<std::recursive_mutex> lock(states_mutex());
-  SamplerState& s = states()[GraphKey{u, B, L}];
+  SamplerState& s = states()[GraphKey{u, Bf, L}];
   if (!s.x) {
-    HIP_TRY(hipMalloc(&s.x, sizeof(float) * n)); HIP_TRY(hipMalloc(&s.out, sizeof(float) * n)); HIP_TRY(hipMalloc(&s.nz, sizeof(float) * n));
-    HIP_TRY(hipMalloc(&s.tt, sizeof(int64_t) * B));
+    // (nz too holds nf values: a guided call with B samples and a plain one with 2B share this state)
+    HIP_TRY(hipMalloc(&s.x, sizeof(float) * nf)); HIP_TRY(hipMalloc(&s.out, sizeof(float) * nf)); HIP_TRY(hipMalloc(&s.nz, sizeof(float) * nf));
+    HIP_TRY(hipMalloc(&s.tt, sizeof(int64_t) * Bf));
     HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
   }
+  if (cond && !s.lab) HIP_TRY(hipMalloc(&s.lab, sizeof(int64_t) * Bf));
   // the whole loop runs on the sampler's own stream (a capture cannot start on the NULL stream the caller may have given the context):
   // it waits for the caller's stream first and the caller's stream waits for it at the end
   hipStream_t caller = ctx->stream;
@@ -96,34 +120,49 @@ extern "C" int eegldm_sample(eegldm_unet* u, eegldm_aekl* ae, const float* noise
   }
   ctx->stream = run;
   HIP_TRY(hipMemcpyAsync(s.x, noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
+  if (guided) HIP_TRY(hipMemcpyAsync(s.x + n, noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));     // the null-class half: same latents
+  if (cond) {
+    HIP_TRY(hipStreamSynchronize(run));             // (the host arrays below are rewritten: an earlier call's copies from them must be done)
+    s.lab_host.assign(labels_host, labels_host + B);
+    if (guided) s.lab_host.resize(Bf, null_class);
+    HIP_TRY(hipMemcpyAsync(s.lab, s.lab_host.data(), sizeof(int64_t) * Bf, hipMemcpyHostToDevice, run));
+  }
+  const int64_t* fwd_lab = cond ? s.lab : nullptr;
 
-  auto set_t = [&](int64_t t) { hipLaunchKernelGGL(fill_i64_kernel, dim3((B + 255) / 256), dim3(256), 0, run, s.tt, B, t); };
+  auto set_t = [&](int64_t t) { hipLaunchKernelGGL(fill_i64_kernel, dim3((Bf + 255) / 256), dim3(256), 0, run, s.tt, Bf, t); };
   bool graph_ok = false;
   const int etot = unet_emb_width(u);
-  struct ClearEmb { eegldm_unet* u; ~ClearEmb() { unet_set_shared_emb(u, nullptr); } } clear_emb{u};
+  struct ClearEmb { eegldm_unet* u; ~ClearEmb() { unet_set_shared_emb(u, nullptr, 0); } } clear_emb{u};
   EEG_ENV_VAR(bool, no_table, getenv("EEGLDM_SAMPLE_NO_EMB_TABLE") != nullptr);
+  const bool table = !no_table;
+  const int mode = !table ? 0 : (shared ? 1 : 2);
+  if (mode == 2 && !s.emb_rows) HIP_TRY(hipMalloc(&s.emb_rows, sizeof(float) * (size_t)Bf * etot));
   if (use_graph && !ctx->prof_on && !s.capture_failed) {
     // Round 5: the captured forward reads its embedding projections from ONE fixed row (s.emb_row) that the loop below refills from the
     // table of all timesteps before every replay -- until round 4 the graph path recomputed the embedding MLP and the 21 projections
     // inside every replay (six launches, ~100 us at B = 1: 5 of the 10.6 ms by which the replayed DDIM-50 trailed the eager one).
-    if (!no_table) {
+    // Several classes in one batch: the rows of all forward rows are gathered into s.emb_rows instead (row stride etot).
+    if (mode == 1) {
       if (!s.emb_row) HIP_TRY(hipMalloc(&s.emb_row, sizeof(float) * (size_t)etot));
-      unet_set_shared_emb(u, s.emb_row);
+      unet_set_shared_emb(u, s.emb_row, 0);
+    } else if (mode == 2) {
+      unet_set_shared_emb(u, s.emb_rows, etot);
     }
-    if (s.exec && s.exec_reads_row != !no_table) {      // captured in the other embedding mode (the switch was flipped in-process): capture again
+    if (s.exec && s.exec_mode != mode) {      // captured in another embedding mode: capture again
       (void)hipGraphExecDestroy(s.exec); s.exec = nullptr;
       if (s.graph) { (void)hipGraphDestroy(s.graph); s.graph = nullptr; }
     }
     if (!s.exec) {
       // eager warm-up: grows the arena / workspaces (hipMalloc is not capturable), then capture the identical launch sequence
       set_t(timesteps_host[0]);
-      EEG_TRY(eegldm_unet_forward(u, s.x, s.tt, s.out, B, L, 0));
+      if (mode == 2) HIP_TRY(hipMemsetAsync(s.emb_rows, 0, sizeof(float) * (size_t)Bf * etot, run));
+      EEG_TRY(unet_forward_labels(u, s.x, s.tt, fwd_lab, s.out, Bf, L, 0));
       HIP_TRY(hipStreamSynchronize(run));
       int rc = 0;
       if (hipStreamBeginCapture(run, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        rc = eegldm_unet_forward(u, s.x, s.tt, s.out, B, L, 0);
+        rc = unet_forward_labels(u, s.x, s.tt, fwd_lab, s.out, Bf, L, 0);
         hipError_t e = hipStreamEndCapture(run, &s.graph);
-        if (rc == 0 && e == hipSuccess && s.graph && hipGraphInstantiate(&s.exec, s.graph, nullptr, nullptr, 0) == hipSuccess) { graph_ok = true; s.exec_reads_row = !no_table; }
+        if (rc == 0 && e == hipSuccess && s.graph && hipGraphInstantiate(&s.exec, s.graph, nullptr, nullptr, 0) == hipSuccess) { graph_ok = true; s.exec_mode = mode; }
       }
       if (!graph_ok) {
         (void)hipGetLastError();
@@ -138,34 +177,52 @@ extern "C" int eegldm_sample(eegldm_unet* u, eegldm_aekl* ae, const float* noise
   // Eager path: the timesteps are known up front and shared by all samples, so the timestep-embedding MLP and the ResBlocks' embedding
   // projections run ONCE for all n_steps (one batch of n_steps rows) instead of six launches (~100 us at B = 1) inside every step;
   // each forward then reads its step's row with row stride 0.  EEGLDM_SAMPLE_NO_EMB_TABLE=1 restores the per-step computation.
-  const bool table = !no_table;
-  if (!graph_ok) unet_set_shared_emb(u, nullptr);      // (a failed capture falls back to the eager path below)
+  // A class-conditional UNet: K rows per step (one per class), row i * K + c; the forward reads the row of its one class with row stride 0,
+  // or -- several classes or guidance -- each step gathers its rows into s.emb_rows (row stride etot).
+  if (!graph_ok) unet_set_shared_emb(u, mode == 2 ? s.emb_rows : nullptr, mode == 2 ? etot : 0);      // (a failed capture falls back to the eager path below)
+  const int Kt = cond ? K : 1;
+  const int rows = n_steps * Kt;
   if (table) {
-    if (s.emb_cap < n_steps) {
+    if (s.emb_cap < rows) {
       HIP_TRY(hipStreamSynchronize(run));
       if (s.emb_table) (void)hipFree(s.emb_table);
       if (s.emb_work) (void)hipFree(s.emb_work);
       if (s.steps_dev) (void)hipFree(s.steps_dev);
-      s.emb_table = nullptr; s.emb_work = nullptr; s.steps_dev = nullptr; s.emb_cap = 0;
-      HIP_TRY(hipMalloc(&s.emb_table, sizeof(float) * (size_t)n_steps * etot));
-      HIP_TRY(hipMalloc(&s.emb_work, sizeof(float) * (size_t)n_steps * unet_embed_work_floats(u)));
-      HIP_TRY(hipMalloc(&s.steps_dev, sizeof(int64_t) * n_steps));
-      s.emb_cap = n_steps;
+      if (s.tab_y_dev) (void)hipFree(s.tab_y_dev);
+      s.emb_table = nullptr; s.emb_work = nullptr; s.steps_dev = nullptr; s.tab_y_dev = nullptr; s.emb_cap = 0;
+      HIP_TRY(hipMalloc(&s.emb_table, sizeof(float) * (size_t)rows * etot));
+      HIP_TRY(hipMalloc(&s.emb_work, sizeof(float) * (size_t)rows * unet_embed_work_floats(u)));
+      HIP_TRY(hipMalloc(&s.steps_dev, sizeof(int64_t) * rows));
+      HIP_TRY(hipMalloc(&s.tab_y_dev, sizeof(int64_t) * rows));
+      s.emb_cap = rows;
     }
-    HIP_TRY(hipMemcpyAsync(s.steps_dev, timesteps_host, sizeof(int64_t) * n_steps, hipMemcpyHostToDevice, run));
-    EEG_TRY(unet_embed_table(u, s.steps_dev, n_steps, s.emb_table, s.emb_work));
+    if (cond) {
+      s.tab_t.resize(rows); s.tab_y.resize(rows);
+      for (int i = 0; i < n_steps; i++) for (int c = 0; c < K; c++) { s.tab_t[(size_t)i * K + c] = timesteps_host[i]; s.tab_y[(size_t)i * K + c] = c; }
+      HIP_TRY(hipMemcpyAsync(s.steps_dev, s.tab_t.data(), sizeof(int64_t) * rows, hipMemcpyHostToDevice, run));
+      HIP_TRY(hipMemcpyAsync(s.tab_y_dev, s.tab_y.data(), sizeof(int64_t) * rows, hipMemcpyHostToDevice, run));
+    } else {
+      HIP_TRY(hipMemcpyAsync(s.steps_dev, timesteps_host, sizeof(int64_t) * n_steps, hipMemcpyHostToDevice, run));
+    }
+    EEG_TRY(unet_embed_table(u, s.steps_dev, cond ? s.tab_y_dev : nullptr, rows, s.emb_table, s.emb_work));
     set_t(timesteps_host[0]);                       // s.tt is not read on this path; keep it defined
   }
 
+  const size_t row0 = cond ? (size_t)labels_host[0] : 0;
   for (int i = 0; i < n_steps; i++) {
-    if (table && graph_ok) HIP_TRY(hipMemcpyAsync(s.emb_row, s.emb_table + (size_t)i * etot, sizeof(float) * (size_t)etot, hipMemcpyDeviceToDevice, run));
-    else if (table) unet_set_shared_emb(u, s.emb_table + (size_t)i * etot);
+    const float* step_rows = table ? s.emb_table + (size_t)i * Kt * etot : nullptr;
+    if (mode == 2) EEG_TRY(ew_emb_gather(ctx, step_rows, s.lab, Kt, etot, s.emb_rows, Bf));
+    else if (table && graph_ok) HIP_TRY(hipMemcpyAsync(s.emb_row, step_rows + row0 * etot, sizeof(float) * (size_t)etot, hipMemcpyDeviceToDevice, run));
+    else if (table) unet_set_shared_emb(u, step_rows + row0 * etot, 0);
     else set_t(timesteps_host[i]);
     if (graph_ok) HIP_TRY(hipGraphLaunch(s.exec, run));
-    else EEG_TRY(eegldm_unet_forward(u, s.x, s.tt, s.out, B, L, 0));
-    if (ancestral) {
-      const bool last = a_prev_host[i] >= 1.0f;
-      if (!last) EEG_TRY(eegldm_randn(ctx, s.nz, n, noise_seed, (uint64_t)i * (uint64_t)((n + 3) / 4)));
+    else EEG_TRY(unet_forward_labels(u, s.x, s.tt, fwd_lab, s.out, Bf, L, 0));
+    const bool last = a_prev_host[i] >= 1.0f;
+    if (ancestral && !last) EEG_TRY(eegldm_randn(ctx, s.nz, n, noise_seed, (uint64_t)i * (uint64_t)((n + 3) / 4)));
+    if (guided) {
+      EEG_TRY(eegldm_guided_step(ctx, s.out, guidance_scale, s.x, last ? nullptr : s.nz, a_t_host[i], a_prev_host[i], ancestral ? beta_t_host[i] : 0.0f,
+                                 ancestral, pred_type, clip_sample, s.x, s.x + n, n));
+    } else if (ancestral) {
       EEG_TRY(eegldm_ddpm_step(ctx, s.out, s.x, last ? nullptr : s.nz, a_t_host[i], a_prev_host[i], beta_t_host[i], pred_type, clip_sample, s.x, nullptr, n));
     } else {
       EEG_TRY(eegldm_ddim_step(ctx, s.out, s.x, a_t_host[i], a_prev_host[i], pred_type, clip_sample, s.x, nullptr, n));
@@ -185,4 +242,26 @@ extern "C" int eegldm_sample(eegldm_unet* u, eegldm_aekl* ae, const float* noise
     HIP_TRY(hipStreamWaitEvent(caller, s.ev_out, 0));
   }
   return 0;
+}
+
+extern "C" int eegldm_sample(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
+                             const float* a_prev_host, const float* beta_t_host, int n_steps, int ancestral, int pred_type, int clip_sample,
+                             float inv_scale_factor, uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
+                             int* graph_used_host) {
+  EEG_CHECK(u, "null argument");
+  EEG_CHECK(unet_num_classes(u) == 0, "this UNet is class-conditional: use eegldm_sample_cond");
+  return sample_impl(u, ae, noise, timesteps_host, a_t_host, a_prev_host, beta_t_host, n_steps, ancestral, pred_type, clip_sample,
+                     inv_scale_factor, noise_seed, latents_out, windows_out, B, L, use_graph, graph_used_host, nullptr, 1.0f, 0);
+}
+
+extern "C" int eegldm_sample_cond(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
+                                  const float* a_prev_host, const float* beta_t_host, int n_steps, int ancestral, int pred_type, int clip_sample,
+                                  float inv_scale_factor, uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
+                                  int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
+  EEG_CHECK(u && labels_host, "null argument");
+  EEG_CHECK(unet_num_classes(u) > 0, "this UNet was built without classes: use eegldm_sample");
+  EEG_CHECK(guidance_scale == guidance_scale, "guidance_scale is NaN");
+  return sample_impl(u, ae, noise, timesteps_host, a_t_host, a_prev_host, beta_t_host, n_steps, ancestral, pred_type, clip_sample,
+                     inv_scale_factor, noise_seed, latents_out, windows_out, B, L, use_graph, graph_used_host, labels_host, guidance_scale,
+                     null_class);
 }

@@ -50,6 +50,10 @@ struct eegldm_unet : NetBase {
   std::vector<View> in_out;      // outputs of the input blocks (views into concat buffers)
   std::vector<View> cat;         // concat buffers per output block
   std::vector<RsTape> st;        // tapes of the Downsample / Upsample layers
+  // ---- class conditioning (unet.py:342,366,379-380): label_emb.weight [num_classes][te] right after time_embed.2.bias, outside the tail
+  // slice the grad hook reports early (its gradient is complete only after the embedding-MLP backward)
+  int num_classes = 0; long off_label = -1;
+  int64_t* labels = nullptr;     // tape: the labels the latest forward used (after any label dropout), a copy in the arena
 };
 
 namespace {
@@ -113,6 +117,10 @@ int build_plan(eegldm_unet* u) {
   u->off_te2_w = take((long)te * te); u->off_te2_b = take(te);
   u->add_entry("time_embed.0.weight", u->off_te0_w, 2, te, mc); u->add_entry("time_embed.0.bias", u->off_te0_b, 1, te);
   u->add_entry("time_embed.2.weight", u->off_te2_w, 2, te, te); u->add_entry("time_embed.2.bias", u->off_te2_b, 1, te);
+  if (u->num_classes > 0) {       // nn.Embedding(num_classes, time_embed_dim): the reference's named_parameters() order puts it here
+    u->off_label = take((long)u->num_classes * te);
+    u->add_entry("label_emb.weight", u->off_label, 2, u->num_classes, te);
+  }
   u->off_cin_w = take((long)mc * c.in_channels * 3); u->off_cin_b = take(mc);
   u->add_entry("input_blocks.0.0.weight", u->off_cin_w, 3, mc, c.in_channels, 3); u->add_entry("input_blocks.0.0.bias", u->off_cin_b, 1, mc);
 
@@ -223,7 +231,7 @@ int block_backward(eegldm_unet* u, const Block& b, View dout, const View& dx_des
 }  // namespace
 
 // ================================================================== C ABI
-extern "C" int eegldm_unet_create(eegldm_ctx* ctx, const eegldm_unet_cfg* cfg, eegldm_unet** out) {
+static int unet_create(eegldm_ctx* ctx, const eegldm_unet_cfg* cfg, int num_classes, eegldm_unet** out) {
   EEG_CHECK(ctx && cfg && out, "null argument");
   EEG_CHECK(cfg->num_heads >= 0 && cfg->num_heads <= 64 && cfg->num_heads_upsample <= 64, "bad num_heads");
   {      // every attention block: channels divisible by its head count, and head width a multiple of 8 (16-byte column views of the qkv rows)
@@ -240,12 +248,18 @@ extern "C" int eegldm_unet_create(eegldm_ctx* ctx, const eegldm_unet_cfg* cfg, e
   EEG_CHECK(cfg->n_mult >= 1 && cfg->n_mult <= 8 && cfg->n_attn >= 0 && cfg->n_attn <= 8, "bad channel_mult / attention_resolutions");
   EEG_CHECK(cfg->dtype == EEGLDM_F32 || cfg->dtype == EEGLDM_BF16 || cfg->dtype == EEGLDM_F16, "bad dtype");
   eegldm_unet* u = new eegldm_unet();
-  u->ctx = ctx; u->cfg = *cfg; u->dtype = cfg->dtype;
+  u->ctx = ctx; u->cfg = *cfg; u->dtype = cfg->dtype; u->num_classes = num_classes;
   int rc = build_plan(u);
   if (rc) { delete u; return rc; }
   *out = u;
   return 0;
 }
+extern "C" int eegldm_unet_create(eegldm_ctx* ctx, const eegldm_unet_cfg* cfg, eegldm_unet** out) { return unet_create(ctx, cfg, 0, out); }
+extern "C" int eegldm_unet_create_cond(eegldm_ctx* ctx, const eegldm_unet_cfg* cfg, int num_classes, eegldm_unet** out) {
+  EEG_CHECK(num_classes >= 1 && num_classes <= (1 << 20), "num_classes=%d must be >= 1", num_classes);
+  return unet_create(ctx, cfg, num_classes, out);
+}
+int unet_num_classes(const eegldm_unet* u) { return u->num_classes; }
 eegldm_ctx* unet_ctx(const eegldm_unet* u) { return u->ctx; }
 int unet_in_channels(const eegldm_unet* u) { return u->cfg.in_channels; }
 int unet_out_channels(const eegldm_unet* u) { return u->cfg.out_channels; }
@@ -286,29 +300,36 @@ extern "C" int eegldm_unet_sync_weights(eegldm_unet* u) {
   return u->sync_weights();
 }
 
-// temb -> Linear -> SiLU -> Linear -> SiLU -> every ResBlock's embedding projection in one Linear (unet.py:526-529, 316); n rows
-static int embed_chain(eegldm_unet* u, const int64_t* tsteps, int n, float* e0, float* h1e, float* a1e, float* emb, float* semb, float* emb_all) {
+// temb -> Linear -> SiLU -> Linear [+ label_emb(y)] -> SiLU -> every ResBlock's embedding projection in one Linear (unet.py:526-533, 316);
+// n rows; labels (class-conditional models only): device int64 [n]
+static int embed_chain(eegldm_unet* u, const int64_t* tsteps, const int64_t* labels, int n, float* e0, float* h1e, float* a1e, float* emb,
+                       float* semb, float* emb_all) {
   eegldm_ctx* ctx = u->ctx; const int mc = u->mc, te = u->te, F = EEGLDM_F32;
   EEG_TRY(ew_temb(ctx, tsteps, e0, n, mc, F));
   EEG_TRY(op_linear(ctx, F, e0, mc, u->P(u->off_te0_w), mc, u->P(u->off_te0_b), h1e, te, n, te, mc, 1));
   EEG_TRY(ew_silu(ctx, h1e, a1e, (long)n * te, F));
   EEG_TRY(op_linear(ctx, F, a1e, te, u->P(u->off_te2_w), te, u->P(u->off_te2_b), emb, te, n, te, te, 1));
+  if (u->num_classes > 0) EEG_TRY(ew_label_emb_add(ctx, emb, te, labels, u->P(u->off_label), n, te, u->num_classes));
   EEG_TRY(ew_silu(ctx, emb, semb, (long)n * te, F));
   return op_linear(ctx, F, semb, te, u->P(u->off_emb_w), te, u->P(u->off_emb_b), emb_all, u->etot, n, u->etot, te, 1);
 }
 // The sampler's timesteps are known before the loop starts and shared by all samples: their embedding rows as ONE batch
-// (table[i] = the etot projections of tsteps[i]; work: n * unet_embed_work_floats() floats), instead of six tiny launches per step.
+// (table[i] = the etot projections of (tsteps[i], labels[i]); work: n * unet_embed_work_floats() floats), instead of six tiny launches per step.
 int unet_emb_width(const eegldm_unet* u) { return u->etot; }
 long unet_embed_work_floats(const eegldm_unet* u) { return (long)u->mc + 4L * u->te; }
-int unet_embed_table(eegldm_unet* u, const int64_t* tsteps_dev, int n, float* table, float* work) {
+int unet_embed_table(eegldm_unet* u, const int64_t* tsteps_dev, const int64_t* labels_dev, int n, float* table, float* work) {
   EEG_CHECK(u && u->params && tsteps_dev && table && work && n > 0, "bad argument");
+  EEG_CHECK(u->num_classes == 0 || labels_dev, "a class-conditional UNet's embedding rows need labels");
   const long te = u->te;
   float* e0 = work; float* h1e = e0 + (long)n * u->mc; float* a1e = h1e + n * te; float* emb = a1e + n * te; float* semb = emb + n * te;
-  return embed_chain(u, tsteps_dev, n, e0, h1e, a1e, emb, semb, table);
+  return embed_chain(u, tsteps_dev, labels_dev, n, e0, h1e, a1e, emb, semb, table);
 }
-void unet_set_shared_emb(eegldm_unet* u, const float* row) { u->emb_shared = row; }
+void unet_set_shared_emb(eegldm_unet* u, const float* rows, long ld) { u->emb_shared = rows; u->emb_shared_ld = ld; }
 
-extern "C" int eegldm_unet_forward(eegldm_unet* u, const float* x, const int64_t* tsteps, float* y, int B, int L, int training) {
+// labels: the caller's device int64 [B] (class-conditional models; NULL otherwise).  They are copied into the arena -- through the label
+// dropout of classifier-free guidance training when p_uncond > 0 -- so that the backward does not depend on the caller's buffer.
+struct LabelArg { const int64_t* y = nullptr; float p_uncond = 0.f; int64_t null_class = 0; uint64_t seed = 0, offset = 0; };
+static int unet_forward_impl(eegldm_unet* u, const float* x, const int64_t* tsteps, const LabelArg& lab, float* y, int B, int L, int training) {
   EEG_CHECK(u && x && tsteps && y, "null argument");
   EEG_CHECK(u->params, "bind parameters first");
   EEG_CHECK(B > 0 && L > 0 && (L % (1 << (u->cfg.n_mult - 1))) == 0, "L=%d must be divisible by 2^(levels-1)", L);
@@ -340,10 +361,17 @@ extern "C" int eegldm_unet_forward(eegldm_unet* u, const float* x, const int64_t
 
   // ---- timestep embedding MLP + all ResBlock embedding projections (unet.py:526-529, 316).
   // Tiny (B x 4mc): always fp32 on the fp32 master weights, whatever the activation dtype.
+  u->labels = nullptr;
   if (u->emb_shared && !training) {
-    // the sampler computed this timestep's row once for the whole run (unet_embed_table): every sample shares it (row stride 0)
-    u->emb_all = const_cast<float*>(u->emb_shared); u->emb_ld = 0;
+    // the sampler computed this timestep's row once for the whole run (unet_embed_table): every sample shares it (row stride 0), or -- class
+    // labels -- it gathered each sample's row of the table into a buffer of row stride etot
+    u->emb_all = const_cast<float*>(u->emb_shared); u->emb_ld = u->emb_shared_ld;
   } else {
+    if (u->num_classes > 0) {
+      EEG_CHECK(lab.y, "a class-conditional UNet needs labels");
+      ALLOC_OR_FAIL(u->labels, (int64_t*)u->arena.alloc(sizeof(int64_t) * (size_t)B));
+      EEG_TRY(ew_label_dropout(ctx, lab.y, u->labels, B, lab.p_uncond, lab.null_class, lab.seed, lab.offset));
+    }
     auto fbuf = [&](long n) { return (float*)u->arena.alloc(sizeof(float) * (size_t)n); };
     ALLOC_OR_FAIL(u->e0, fbuf((long)B * mc));
     ALLOC_OR_FAIL(u->h1e, fbuf((long)B * te));
@@ -352,7 +380,7 @@ extern "C" int eegldm_unet_forward(eegldm_unet* u, const float* x, const int64_t
     ALLOC_OR_FAIL(u->semb, fbuf((long)B * te));
     ALLOC_OR_FAIL(u->emb_all, fbuf((long)B * u->etot));
     u->emb_ld = u->etot;
-    EEG_TRY(embed_chain(u, tsteps, B, u->e0, u->h1e, u->a1e, u->emb, u->semb, u->emb_all));
+    EEG_TRY(embed_chain(u, tsteps, u->labels, B, u->e0, u->h1e, u->a1e, u->emb, u->semb, u->emb_all));
   }
 
   // ---- concat buffers: output block j consumes [h (c1) | skip (ich)] where skip = input block n_in-1-j
@@ -400,11 +428,28 @@ extern "C" int eegldm_unet_forward(eegldm_unet* u, const float* x, const int64_t
   u->have_tape = !u->fused_used;      // a fused eval forward did not keep what the backward needs
   return 0;
 }
+int unet_forward_labels(eegldm_unet* u, const float* x, const int64_t* t, const int64_t* labels, float* y, int B, int L, int training) {
+  LabelArg lab; lab.y = labels;
+  return unet_forward_impl(u, x, t, lab, y, B, L, training);
+}
+extern "C" int eegldm_unet_forward(eegldm_unet* u, const float* x, const int64_t* tsteps, float* y, int B, int L, int training) {
+  EEG_CHECK(u, "null unet");
+  EEG_CHECK(u->num_classes == 0, "this UNet is class-conditional (%d classes): use eegldm_unet_forward_cond", u->num_classes);
+  return unet_forward_impl(u, x, tsteps, LabelArg(), y, B, L, training);
+}
+extern "C" int eegldm_unet_forward_cond(eegldm_unet* u, const float* x, const int64_t* tsteps, const int64_t* labels, float* y, int B, int L,
+                                        int training) {
+  EEG_CHECK(u && labels, "null argument");
+  EEG_CHECK(u->num_classes > 0, "this UNet was built without classes: use eegldm_unet_forward");
+  LabelArg lab; lab.y = labels;
+  return unet_forward_impl(u, x, tsteps, lab, y, B, L, training);
+}
 
 extern "C" int eegldm_unet_backward(eegldm_unet* u, const float* dy, float* dx_out) {
   EEG_CHECK(u && dy, "null argument");
   EEG_CHECK(u->have_tape, "call eegldm_unet_forward first (with training != 0: an eval-mode forward does not keep the activations)");
   EEG_CHECK(u->grads, "no gradient buffer bound");
+  EEG_CHECK(u->num_classes == 0 || u->labels, "the last forward used the sampler's embedding rows: no labels on the tape");
   eegldm_ctx* ctx = u->ctx; const int dt = u->dtype; const int mc = u->mc, te = u->te, B = u->B, L = u->L;
   const int cin = u->cfg.in_channels, cout = u->cfg.out_channels;
   const int n_in = (int)u->in_blocks.size(), n_out = (int)u->out_blocks.size();
@@ -482,6 +527,7 @@ extern "C" int eegldm_unet_backward(eegldm_unet* u, const float* dy, float* dx_o
   EEG_TRY(op_linear_dgrad(ctx, F, demb_all, E, u->P(u->off_emb_w), te, dsemb, te, B, E, te, 1));
   float* demb; ALLOC_OR_FAIL(demb, fbuf((long)B * te));
   EEG_TRY(ew_silu_bwd(ctx, dsemb, u->emb, demb, (long)B * te, F));
+  if (u->num_classes > 0) EEG_TRY(ew_label_emb_grad(ctx, demb, te, u->labels, B, te, u->num_classes, u->G(u->off_label)));   // emb = .. + label_emb(y)
   EEG_TRY(ew_colsum(ctx, demb, te, nullptr, 0, u->G(u->off_te2_b), 1, B, te, F));
   EEG_TRY(op_linear_wgrad(ctx, F, u->a1e, te, demb, te, u->G(u->off_te2_w), te, B, te, te));
   float* da1; ALLOC_OR_FAIL(da1, fbuf((long)B * te));
@@ -495,8 +541,8 @@ extern "C" int eegldm_unet_backward(eegldm_unet* u, const float* dy, float* dx_o
   return 0;
 }
 
-extern "C" int eegldm_ldm_train_step(eegldm_unet* u, const float* latents, const float* noise, const int64_t* t, const float* acp,
-                                     int pred_type, int B, int L, float grad_scale, float* loss) {
+static int ldm_train_step(eegldm_unet* u, const float* latents, const float* noise, const int64_t* t, const float* acp,
+                          int pred_type, int B, int L, float grad_scale, float* loss, const LabelArg& lab) {
   EEG_CHECK(u && latents && noise && t && acp && loss, "null argument");
   EEG_CHECK(pred_type == EEGLDM_PRED_EPSILON || pred_type == EEGLDM_PRED_V, "prediction type must be epsilon or v_prediction");
   eegldm_ctx* ctx = u->ctx;
@@ -511,9 +557,26 @@ extern "C" int eegldm_ldm_train_step(eegldm_unet* u, const float* latents, const
   }
   float *noisy = stage, *pred = stage + n, *target = stage + 2 * n, *dpred = stage + 3 * n;
   EEG_TRY(eegldm_add_noise(ctx, latents, noise, t, acp, noisy, B, (long)C * L));
-  EEG_TRY(eegldm_unet_forward(u, noisy, t, pred, B, L, 1));
+  EEG_TRY(unet_forward_impl(u, noisy, t, lab, pred, B, L, 1));
   const float* tgt = noise;
   if (pred_type == EEGLDM_PRED_V) { EEG_TRY(eegldm_get_velocity(ctx, latents, noise, t, acp, target, B, (long)C * L)); tgt = target; }
   EEG_TRY(eegldm_mse_loss(ctx, pred, tgt, loss, dpred, n, grad_scale));
   return eegldm_unet_backward(u, dpred, nullptr);
+}
+extern "C" int eegldm_ldm_train_step(eegldm_unet* u, const float* latents, const float* noise, const int64_t* t, const float* acp,
+                                     int pred_type, int B, int L, float grad_scale, float* loss) {
+  EEG_CHECK(u, "null unet");
+  EEG_CHECK(u->num_classes == 0, "this UNet is class-conditional (%d classes): use eegldm_ldm_train_step_cond", u->num_classes);
+  return ldm_train_step(u, latents, noise, t, acp, pred_type, B, L, grad_scale, loss, LabelArg());
+}
+extern "C" int eegldm_ldm_train_step_cond(eegldm_unet* u, const float* latents, const float* noise, const int64_t* t, const float* acp,
+                                          int pred_type, int B, int L, float grad_scale, float* loss, const int64_t* labels, float p_uncond,
+                                          int64_t null_class, uint64_t seed, uint64_t offset) {
+  EEG_CHECK(u && labels, "null argument");
+  EEG_CHECK(u->num_classes > 0, "this UNet was built without classes: use eegldm_ldm_train_step");
+  EEG_CHECK(p_uncond >= 0.0f && p_uncond <= 1.0f, "p_uncond %g outside [0, 1]", (double)p_uncond);
+  EEG_CHECK(p_uncond == 0.0f || (null_class >= 0 && null_class < u->num_classes), "null_class %lld outside [0, %d)", (long long)null_class,
+            u->num_classes);
+  LabelArg lab; lab.y = labels; lab.p_uncond = p_uncond; lab.null_class = null_class; lab.seed = seed; lab.offset = offset;
+  return ldm_train_step(u, latents, noise, t, acp, pred_type, B, L, grad_scale, loss, lab);
 }

@@ -54,6 +54,21 @@ def synthetic_windows(n, seed, length=3072, pad=36):
 
 WINDOW = 3000      # 30 s at 100 Hz (dataset.py:7-8)
 BORDER = 36        # BorderPadD(spatial_border=[36]) (dataset.py:18)
+EPOCH = 3000       # one scored sleep epoch: 30 s at 100 Hz
+STAGES_SUFFIX = ".stages.npy"     # R.npy's hypnogram: R.stages.npy (never taken for a recording)
+
+
+def stages_path(recording, path_stages=None):
+    """Where the stage codes of `recording` (R.npy) live: R.stages.npy beside it, or under `path_stages` with the same stem."""
+    stem = os.path.basename(recording)[:-4] if recording.endswith(".npy") else os.path.basename(recording)
+    return os.path.join(path_stages or os.path.dirname(recording), stem + STAGES_SUFFIX)
+
+
+def centre_label(stages, start):
+    """Stage code of the window cropped at `start`: the code of the 30-s epoch holding its centre sample start + 1500 (the centre rule of
+    get_center_label, run_sleep_decode.py:44-47); -1 (unscored) past the end of the hypnogram."""
+    e = (start + WINDOW // 2) // EPOCH
+    return int(stages[e]) if e < len(stages) else -1
 
 
 def normalise_recording(a):
@@ -105,10 +120,16 @@ class WindowLoader:
     and kept in memory, and `windows_per_recording` crops are drawn from it per epoch (1 = the reference's epoch definition).
     `shard=(rank, world)` gives every data-parallel rank its own slice of the file list (an epoch is the data once, not world
     times; `shard_files`: equal length on every rank, so all ranks run the same number of steps per epoch).  A run that names real
-    data (`path_ids` / `path_pre_processed`) and finds none raises instead of silently training on synthetic windows.  Crop offsets come from a numpy Generator seeded per loader (`crop_starts` can be injected for parity tests)."""
+    data (`path_ids` / `path_pre_processed`) and finds none raises instead of silently training on synthetic windows.  Crop offsets come from a numpy Generator seeded per loader (`crop_starts` can be injected for parity tests).
+
+    `stages=True` (or a `path_stages` directory): class labels for conditional training.  Every recording R.npy has a hypnogram R.stages.npy
+    beside it (or under `path_stages`): a 1-D integer array, one code per 30-s epoch from sample 0 of the stored recording, W 0, N1 1, N2 2,
+    N3/N4 3, REM 4 (run_sleep_decode.py:112-118), negative = unscored.  A window's label is the code of the epoch holding its centre sample;
+    a crop whose centre is unscored is drawn again (from the loader's Generator, also after an injected `crop_starts` value).  Batches then
+    carry 'label', int64 (B,)."""
 
     def __init__(self, path_pre_processed, batch_size, n_synthetic=0, seed=0, drop_last=False, shuffle=True, path_ids=None,
-                 dataset="edfx", shard=(0, 1), windows_per_recording=1, crop_starts=None):
+                 dataset="edfx", shard=(0, 1), windows_per_recording=1, crop_starts=None, stages=False, path_stages=None):
         self.batch_size, self.drop_last, self.shuffle = batch_size, drop_last, shuffle
         self.rng = np.random.default_rng(seed)
         self.wpr = max(1, int(windows_per_recording))
@@ -123,11 +144,21 @@ class WindowLoader:
                 raise FileNotFoundError(f"{len(missing)} recordings listed in {path_ids} are missing, e.g. {missing[0]}")
         else:
             files = sorted(glob.glob(os.path.join(path_pre_processed or "", "**", "*.npy"), recursive=True)) if path_pre_processed else []
+            files = [f for f in files if not f.endswith(STAGES_SUFFIX)]
         rank, world = shard
         if (path_ids or path_pre_processed) and not n_synthetic and not files:
             raise FileNotFoundError(f"no recordings found (path_ids={path_ids!r}, path_pre_processed={path_pre_processed!r}); "
                                     "refusing to fall back to synthetic windows for a run that named real data")
         files = shard_files(files, rank, world)
+        self.stage_files = None
+        if stages or path_stages:
+            if not files:
+                raise ValueError("stage labels need recordings (path_ids / path_pre_processed), not synthetic windows")
+            self.stage_files = [stages_path(f, path_stages) for f in files]
+            missing = [f for f in self.stage_files if not os.path.exists(f)]
+            if missing:
+                raise FileNotFoundError(f"{len(missing)} stage files are missing, e.g. {missing[0]}")
+            self.stage_codes = [None] * len(files)
         if files:
             self.files = files
             self.recordings = [None] * len(files)          # read + normalised on first use, then cached
@@ -147,25 +178,44 @@ class WindowLoader:
             self.recordings[r] = rec
         return self.recordings[r]
 
+    def _stages(self, r):
+        if self.stage_codes[r] is None:
+            st = np.load(self.stage_files[r])
+            if st.ndim != 1 or not np.issubdtype(st.dtype, np.integer):
+                raise ValueError(f"{self.stage_files[r]}: stage codes must be a 1-D integer array, got {st.dtype} {st.shape}")
+            self.stage_codes[r] = st.astype(np.int64)
+        return self.stage_codes[r]
+
     def _item(self, i):
         if self.windows is not None:
             return self.windows[i]
         rec = self._recording(i // self.wpr)
-        if self.crop_starts is not None:
-            s = int(self.crop_starts[i])
-        else:
-            s = int(self.rng.integers(0, rec.shape[0] - WINDOW + 1))       # RandSpatialCrop: every valid start, last one included
-        return crop_and_pad(rec, s)
+        draw = lambda: int(self.rng.integers(0, rec.shape[0] - WINDOW + 1))       # RandSpatialCrop: every valid start, last one included
+        s = int(self.crop_starts[i]) if self.crop_starts is not None else draw()
+        if self.stage_files is None:
+            return crop_and_pad(rec, s)
+        st = self._stages(i // self.wpr)
+        for _ in range(10000):
+            lab = centre_label(st, s)
+            if lab >= 0:
+                return crop_and_pad(rec, s), lab
+            s = draw()
+        raise ValueError(f"{self.files[i // self.wpr]}: no scored epoch under the centre of 10000 crops")
 
     def __iter__(self):
         order = self.rng.permutation(self.n) if self.shuffle else np.arange(self.n)
         for k in range(len(self)):
             idx = order[k * self.batch_size:(k + 1) * self.batch_size]
-            yield {"eeg": torch.from_numpy(np.stack([self._item(int(i)) for i in idx]))}
+            items = [self._item(int(i)) for i in idx]
+            if self.stage_files is None:
+                yield {"eeg": torch.from_numpy(np.stack(items))}
+            else:
+                yield {"eeg": torch.from_numpy(np.stack([w for w, _ in items])), "label": torch.tensor([c for _, c in items], dtype=torch.int64)}
 
 
 def rng_seed(base_seed, role, rank=0, world=1):
     """Distinct Philox key per (role, rank): base * 2^20 + role * 4096 + rank.  Roles: 1 timesteps, 2 posterior eps, 3 diffusion
-    noise, 4 autoencoder eps, 5-7 validation draws, 8 training loader (crop / shuffle / synthetic windows), 9 validation loader.  (seed + role + rank collides across ranks: rank r's noise stream == rank r+1's eps stream.)"""
+    noise, 4 autoencoder eps, 5-7 validation draws, 8 training loader (crop / shuffle / synthetic windows), 9 validation loader,
+    10 label dropout of classifier-free guidance training (p_uncond).  (seed + role + rank collides across ranks: rank r's noise stream == rank r+1's eps stream.)"""
     assert 0 <= rank < 4096 and 0 <= role < 256
     return (int(base_seed) << 20) + (int(role) << 12) + int(rank)

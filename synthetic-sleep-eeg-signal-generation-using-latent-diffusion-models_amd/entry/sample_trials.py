@@ -25,6 +25,11 @@ def parse_args(argv=None):
     p.add_argument("--latent_channels", type=int, default=1); p.add_argument("--type_dataset", default="edfx")
     p.add_argument("--prediction_type", default="v_prediction", help="sample_trials.py:141 uses v_prediction")
     p.add_argument("--batch", type=int, default=256); p.add_argument("--dtype", default="float32")
+    p.add_argument("--num_classes", type=int, default=None, help="class-conditional UNet (overrides unet_config.params.num_classes)")
+    p.add_argument("--class_label", type=int, default=None, help="the sleep stage of every window (W 0, N1 1, N2 2, N3 3, REM 4)")
+    p.add_argument("--labels_file", default=None, help=".npy / text file with one label per seed, seeds start_seed .. stop_seed - 1 in order")
+    p.add_argument("--null_class", type=int, default=None, help="classifier-free guidance: the unconditional class; --guidance_scale "
+                   "applies to a class-conditional UNet only when it is given")
     return p.parse_args(argv)
 
 
@@ -39,6 +44,21 @@ def main(args):
     stage1.load_state_dict(torch.load(os.path.join(args.best_model_path, "best_model.pth"), map_location="cpu"))
     up = dict(load_config(args.ldm_config_file_path)["model"]["params"]["unet_config"]["params"])
     up["in_channels"] = up["out_channels"] = args.latent_channels
+    if args.num_classes is not None:
+        up["num_classes"] = args.num_classes
+    labels = None
+    if up.get("num_classes") is not None:
+        if args.labels_file:
+            f = args.labels_file
+            labels = np.load(f) if f.endswith(".npy") else np.loadtxt(f, dtype=np.int64, ndmin=1)
+            labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+            if len(labels) != args.stop_seed - args.start_seed:
+                raise ValueError(f"{f}: {len(labels)} labels for {args.stop_seed - args.start_seed} seeds")
+        elif args.class_label is not None:
+            labels = np.full(args.stop_seed - args.start_seed, args.class_label, np.int64)
+        else:
+            raise ValueError("a class-conditional UNet needs --class_label or --labels_file")
+    guided = labels is not None and args.null_class is not None
     unet = UNetModel(**up, dtype=args.dtype, device=local)
     unet.load_state_dict(torch.load(os.path.join(args.diffusion_path, "best_model.pth"), map_location="cpu"))
     scale_factor = float(torch.load(os.path.join(args.diffusion_path, "checkpoint.pth"), map_location="cpu")["scale_factor"])
@@ -47,10 +67,14 @@ def main(args):
     seeds = list(range(args.start_seed + lo, args.start_seed + hi))
     for k in range(0, len(seeds), args.batch):
         chunk = seeds[k:k + args.batch]
-        windows, _ = sample_seeds(unet, stage1, sched, chunk, latent_len=up.get("image_size", 768), scale_factor=scale_factor)
+        lab = None if labels is None else labels[lo + k:lo + k + len(chunk)]
+        windows, _ = sample_seeds(unet, stage1, sched, chunk, latent_len=up.get("image_size", 768), scale_factor=scale_factor, labels=lab,
+                                  guidance_scale=args.guidance_scale if guided else 1.0, null_class=args.null_class if guided else None)
         arr = windows.cpu().numpy()
         for j, sd in enumerate(chunk):
             np.save(os.path.join(out, f"sample_{sd}.npy"), arr[j:j + 1])
+            if lab is not None:                         # the window's class beside it
+                np.save(os.path.join(out, f"sample_{sd}_label.npy"), lab[j:j + 1])
     return out
 
 

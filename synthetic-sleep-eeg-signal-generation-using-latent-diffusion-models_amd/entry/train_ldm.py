@@ -31,12 +31,18 @@ def parse_args(argv=None):
     p.add_argument("--grad_scaler", action="store_true", help="dynamic loss scaling as in the reference loop (training.py:334,441-443); always on with --dtype float16 (the reference's autocast dtype), bf16/fp32 do not need it")
     p.add_argument("--deterministic", action="store_true", help="bit-reproducible steps (eegldm.set_deterministic(): ordered reductions instead of fp32 atomics; "
                    "what torch.use_deterministic_algorithms(True) would be for the reference's loop)")
+    p.add_argument("--num_classes", type=int, default=None, help="class-conditional UNet (overrides unet_config.params.num_classes): "
+                   "labels from the loader's stage files (R.stages.npy beside each recording, or under --path_stages)")
+    p.add_argument("--path_stages", default=None)
+    p.add_argument("--p_uncond", type=float, default=0.0, help="classifier-free guidance training: probability of replacing a label by --null_class")
+    p.add_argument("--null_class", type=int, default=None, help="the unconditional class (default: num_classes - 1 when --p_uncond > 0)")
     return p.parse_args(argv)
 
 
 @torch.no_grad()
 def validate(unet, stage1, sched, loader, scale_factor, seeds, latent_channels):
-    """eval_ldm (training.py:455-497): mean epsilon-MSE over the validation windows, fixed noise stream.  `seeds` = the three Philox
+    """eval_ldm (training.py:455-497): mean epsilon-MSE over the validation windows, fixed noise stream (a class-conditional UNet is
+    scored with each window's own label).  `seeds` = the three Philox
     keys (timesteps, posterior eps, diffusion noise), each from `rng_seed` with its own role.  Returns (sum of per-window losses,
     number of windows) so that data-parallel ranks can add their shards up."""
     from .._lib import lib, check, ptr
@@ -53,7 +59,7 @@ def validate(unet, stage1, sched, loader, scale_factor, seeds, latent_channels):
         eps = randn(ctx, (B, latent_channels, Ll), seed=s_eps, offset=seen * per)
         noise = randn(ctx, eps.shape, seed=s_noise, offset=seen * per)
         e = stage1.encode_stage_2_inputs(x, eps=eps, scale_factor=scale_factor)
-        pred = unet(sched.add_noise(original_samples=e, noise=noise, timesteps=t), timesteps=t)
+        pred = unet(sched.add_noise(original_samples=e, noise=noise, timesteps=t), timesteps=t, y=batch.get("label"))
         check(lib.eegldm_mse_loss(ctx.h, ptr(pred), ptr(noise), ptr(out), None, pred.numel(), 1.0))
         tot += float(out) * B; n += B; seen += B
     unet.train()
@@ -82,6 +88,10 @@ def main(args):
     stage1.eval()
     up = dict(config.model.params.unet_config.params)
     up["in_channels"] = up["out_channels"] = args.latent_channels            # train_ldm.py:184-187
+    if args.num_classes is not None:
+        up["num_classes"] = args.num_classes
+    cond = up.get("num_classes") is not None                                  # UNetModel(**parameters) takes it from the yaml too
+    null_class = args.null_class if args.null_class is not None else (int(up["num_classes"]) - 1 if cond and args.p_uncond > 0 else None)
     unet = UNetModel(**up, dtype=args.dtype, device=local)
     D.broadcast_flat(unet.flat); unet.sync_weights(); D.broadcast_flat(stage1.flat); stage1.sync_weights()
     # train_ldm.py:199-200: monai-generative DDPMScheduler(beta_schedule="linear", 0.0015, 0.0195) = plain linspace of the betas
@@ -93,13 +103,14 @@ def main(args):
     scaler = GradScaler(enabled=args.grad_scaler or str(args.dtype) in ("float16", "fp16", "half"))      # fp16 activations: the loss scale is what keeps their gradients out of the subnormal range
     bs = max(1, config.train.batch_size // world)
     train = WindowLoader(args.path_pre_processed, bs, args.synthetic_windows, seed=rng_seed(config.train.seed, 8, rank, world), drop_last=config.train.drop_last,
-                         path_ids=args.path_train_ids, dataset=args.type_dataset, shard=(rank, world))
+                         path_ids=args.path_train_ids, dataset=args.type_dataset, shard=(rank, world), stages=cond, path_stages=args.path_stages)
     # validation: every rank scores its own shard (equal lengths, wrap-around: a recording may be scored twice when N % world != 0)
     # and the (sum, count) pairs are added over ranks -- model selection sees the WHOLE validation split, as the reference's does
     valid = WindowLoader(args.path_pre_processed, bs, 0, seed=rng_seed(config.train.seed, 9, 0, world), shuffle=False, path_ids=args.path_valid_ids,
-                         dataset=args.type_dataset, shard=(rank, world)) if args.path_valid_ids else None
+                         dataset=args.type_dataset, shard=(rank, world), stages=cond, path_stages=args.path_stages) if args.path_valid_ids else None
     v_seeds = tuple(rng_seed(config.train.seed, role, rank, world) for role in (5, 6, 7))
     s_t, s_eps, s_noise = (rng_seed(config.train.seed, role, rank, world) for role in (1, 2, 3))
+    s_lab = rng_seed(config.train.seed, 10, rank, world)
     dev, ctx = unet.device, unet.ctx
     first = next(iter(train))["eeg"].to(dev)
     z = stage1.encode_stage_2_inputs(first)
@@ -132,7 +143,8 @@ def main(args):
             noise = randn(ctx, eps.shape, seed=s_noise, offset=gstep * z[0].numel() * B)
             e = stage1.encode_stage_2_inputs(x, eps=eps, scale_factor=scale_factor)
             opt.zero_grad()
-            ldm_train_step(unet, sched, e, noise, t, loss_out=loss, grad_scale=scaler.get_scale(), grad_sync=gsync)
+            lab = dict(labels=batch["label"].to(dev), p_uncond=args.p_uncond, null_class=null_class, seed=s_lab, offset=gstep * B) if cond else {}
+            ldm_train_step(unet, sched, e, noise, t, loss_out=loss, grad_scale=scaler.get_scale(), grad_sync=gsync, **lab)
             gsync.wait()
             scaler.step(opt); scaler.update()
             steps += 1; gstep += 1; seen += B * world

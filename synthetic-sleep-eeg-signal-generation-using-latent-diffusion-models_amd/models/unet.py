@@ -1,6 +1,7 @@
 """`UNetModel` -- host-side mirror of the reference denoiser's interface
 (/root/reference/src/models/unet.py:330-563: same constructor kwargs, same
-`forward(x, timesteps=...)`, same 278-key `state_dict()`), executing on the
+`forward(x, timesteps=..., y=...)`, same 278-key `state_dict()` -- 279 with
+`label_emb.weight` when built with `num_classes`), executing on the
 hand-written HIP kernels of libeegldm.so through the C ABI.
 
 torch is used for device memory only.  Two ways to train: the fused native step
@@ -30,8 +31,11 @@ class UNetModel(FlatModule):
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError("dropout must be in [0, 1)")
         self.dropout = float(dropout)
-        if num_classes is not None or n_embed is not None:
-            raise NotImplementedError("class-conditional / codebook heads are not used by the reference configs")
+        if n_embed is not None:
+            raise NotImplementedError("codebook heads (n_embed) are not used by the reference configs")
+        if num_classes is not None and (int(num_classes) != num_classes or int(num_classes) < 1):
+            raise ValueError(f"num_classes must be a positive integer, got {num_classes!r}")
+        self.num_classes = None if num_classes is None else int(num_classes)
         num_heads, num_head_channels, num_heads_upsample = int(num_heads), int(num_head_channels), int(num_heads_upsample)
         if num_heads < 1 or num_head_channels == 0:
             raise ValueError("num_heads >= 1 and num_head_channels = -1 or > 0 (unet.py:146-153)")
@@ -58,7 +62,10 @@ class UNetModel(FlatModule):
         cfg.resample_layers = 0 if self.resblock_updown else 1                          # Downsample / Upsample layers (unet.py:462-470,493-498)
         cfg.resample_pool_only = 0 if self.conv_resample else 1
         h = C.c_void_p()
-        check(lib.eegldm_unet_create(self.ctx.h, C.byref(cfg), C.byref(h)))
+        if self.num_classes is None:
+            check(lib.eegldm_unet_create(self.ctx.h, C.byref(cfg), C.byref(h)))
+        else:                       # label_emb = nn.Embedding(num_classes, 4 * model_channels) (unet.py:379-380)
+            check(lib.eegldm_unet_create_cond(self.ctx.h, C.byref(cfg), self.num_classes, C.byref(h)))
         self.h = h
         if self.dropout > 0.0:      # nn.Dropout(p) of every ResBlock (unet.py:289): training-mode forwards only, masks from the device Philox stream
             self.set_dropout_seed(0x0D50)
@@ -83,10 +90,12 @@ class UNetModel(FlatModule):
     # ------------------------------------------------------------------ parameters
     def reset_parameters(self, generator=None):
         """torch.nn default init (kaiming_uniform(a=sqrt(5)) == U(+-1/sqrt(fan_in)) for weights and biases),
-        GroupNorm (1, 0), and the reference's zero_module layers (unet.py:39-45)."""
+        GroupNorm (1, 0), the reference's zero_module layers (unet.py:39-45) and nn.Embedding's N(0, 1) for label_emb."""
         sd = OrderedDict()
         for k, (_o, _n, shape) in self.entries.items():
-            if len(shape) == 1 and (".in_layers.0." in k or ".out_layers.0." in k or ".norm." in k or k.startswith("out.0.")):
+            if k == "label_emb.weight":
+                sd[k] = torch.randn(shape, generator=generator)
+            elif len(shape) == 1 and (".in_layers.0." in k or ".out_layers.0." in k or ".norm." in k or k.startswith("out.0.")):
                 sd[k] = torch.ones(shape) if k.endswith("weight") else torch.zeros(shape)
             elif k.endswith(_ZERO_INIT_SUFFIX):
                 sd[k] = torch.zeros(shape)
@@ -150,6 +159,8 @@ class UNetModel(FlatModule):
 
     # ------------------------------------------------------------------ compute
     def forward(self, x, timesteps=None, context=None, y=None, **kwargs):
+        if self.num_classes is not None:                 # unet.py:517-519 (same assertion text; y on an unconditional model is ignored)
+            assert y is not None, "must specify y if and only if the model is class-conditional"
         assert timesteps is not None, "need to implement no-timestep usage"      # unet.py:520-521 (same assertion text)
         x = x.to(self.device, torch.float32).contiguous()
         t = timesteps.to(self.device, torch.int64).contiguous()
@@ -171,15 +182,34 @@ class UNetModel(FlatModule):
             if (1 << lvl) in self.attention_resolutions and (L >> lvl) % vec != 0:
                 raise ValueError(f"attention at downsample rate {1 << lvl} sees T={L >> lvl} positions; this engine needs T to be a "
                                  f"multiple of {vec} ({'fp32' if vec == 4 else 'bf16'}): use L divisible by {vec << lvl}")
+        labels = None
+        if self.num_classes is not None:
+            assert tuple(torch.as_tensor(y).shape) == (B,)      # unet.py:531 (same assertion)
+            labels = self.check_labels(y)
         self._sync_if_stale()                            # a torch optimizer updated the flat parameter in place: refresh the compute copies
         if self.training and self._wants_graph(x):
-            return _UNetFn.apply(self, x, t, self._flat_param())
-        return self._forward_native(x, t)
+            return _UNetFn.apply(self, x, t, labels, self._flat_param())
+        return self._forward_native(x, t, labels)
 
-    def _forward_native(self, x, t):
+    def check_labels(self, y):
+        """Class labels as a device int64 tensor; raises IndexError (as nn.Embedding does) before anything is launched when one lies
+        outside [0, num_classes)."""
+        y = torch.as_tensor(y)
+        if y.dtype.is_floating_point or y.dtype == torch.bool:
+            raise TypeError(f"class labels must be integers, got {y.dtype}")
+        if y.numel():
+            lo, hi = int(y.min()), int(y.max())
+            if lo < 0 or hi >= self.num_classes:
+                raise IndexError(f"class label {lo if lo < 0 else hi} is out of range for num_classes={self.num_classes}")
+        return y.to(self.device, torch.int64).contiguous()
+
+    def _forward_native(self, x, t, labels=None):
         B, _c, L = x.shape
         out = torch.empty(B, self.out_channels, L, device=self.device, dtype=torch.float32)
-        check(lib.eegldm_unet_forward(self.h, ptr(x), ptr(t), ptr(out), B, L, 1 if self.training else 0))
+        if self.num_classes is None:
+            check(lib.eegldm_unet_forward(self.h, ptr(x), ptr(t), ptr(out), B, L, 1 if self.training else 0))
+        else:
+            check(lib.eegldm_unet_forward_cond(self.h, ptr(x), ptr(t), ptr(labels), ptr(out), B, L, 1 if self.training else 0))
         self._bump_tape()                                # the executor's single tape now belongs to THIS call (eegldm.autograd)
         return out
 

@@ -31,8 +31,33 @@ def _step_tables(scheduler):
     return ts, a_t, a_prev, beta, ancestral
 
 
+def _labels_host(unet, labels, B, guidance_scale, null_class):
+    """(labels as a host int64 list of B entries, null class) for a class-conditional UNet; checked before anything runs."""
+    if getattr(unet, "num_classes", None) is None:
+        if labels is not None or float(guidance_scale) != 1.0:
+            raise ValueError("labels / guidance_scale need a UNet built with num_classes")
+        return None, 0
+    if labels is None:
+        raise ValueError("a class-conditional UNet samples with labels: pass labels=")
+    lab = torch.as_tensor(labels).reshape(-1)
+    if lab.numel() == 1:
+        lab = lab.expand(B)
+    if lab.numel() != B:
+        raise ValueError(f"{lab.numel()} labels for {B} samples")
+    lab = [int(v) for v in unet.check_labels(lab).cpu()]
+    nc = 0
+    if float(guidance_scale) != 1.0:
+        if null_class is None:
+            raise ValueError("guidance_scale != 1 needs null_class")
+        nc = int(null_class)
+        if not 0 <= nc < unet.num_classes:
+            raise IndexError(f"null_class {nc} is out of range for num_classes={unet.num_classes}")
+    return lab, nc
+
+
 @torch.no_grad()
-def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, use_graph=None, seed=0, info=None):
+def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, use_graph=None, seed=0, info=None, labels=None,
+                guidance_scale=1.0, null_class=None):
     """noise (B, lat, Ll) on the device -> (windows (B, out, 3072 - 2*crop), final latents).  ONE native call
     (eegldm_sample): the scheduler loop, z / scale_factor and the decode run inside the library.  The UNet forward CAN be
     replayed from a hipGraph (use_graph=True or EEGLDM_SAMPLE_GRAPH=1) but that is no longer the default: measured on
@@ -40,12 +65,15 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     (sample_trials.py:149-163: 92.6 vs 87 ms per 50-step window -- ROCm's graph launch does not shorten the ~5 us per
     dependent kernel) and indistinguishable at batch 256, where launch overhead does not matter.
     `scheduler` may be a DDIMScheduler (eta 0) or a DDPMScheduler (ancestral steps; noise from the device Philox
-    stream `seed`).  info (optional dict) receives {"graph": bool}."""
+    stream `seed`).  info (optional dict) receives {"graph": bool}.
+    A UNet built with num_classes needs `labels` (one class per sample, or one for all).  guidance_scale w != 1 is classifier-free
+    guidance: out = out(null_class) + w (out(labels) - out(null_class)) on the raw model output, every forward on 2B rows."""
     unet.eval()
     x = noise.to(unet.device, torch.float32).contiguous()
     B, Cc, L = x.shape
     if Cc != unet.in_channels:
         raise ValueError(f"noise has {Cc} channels, the UNet takes {unet.in_channels}")
+    lab, nc = _labels_host(unet, labels, B, guidance_scale, null_class)
     ts, a_t, a_prev, beta, ancestral = _step_tables(scheduler)
     n = len(ts)
     if use_graph is None:
@@ -57,10 +85,13 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     if B == 0:
         return (win[:, :, crop:-crop] if crop else win), lat
     used = C.c_int(0)
-    check(lib.eegldm_sample(unet.h, autoencoder.h if autoencoder is not None else None, ptr(x), (C.c_int64 * n)(*ts),
-                            (C.c_float * n)(*a_t), (C.c_float * n)(*a_prev), (C.c_float * n)(*beta), n, 1 if ancestral else 0,
-                            PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor), int(seed),
-                            ptr(lat), ptr(win), B, L, 1 if use_graph else 0, C.byref(used)))
+    args = (unet.h, autoencoder.h if autoencoder is not None else None, ptr(x), (C.c_int64 * n)(*ts), (C.c_float * n)(*a_t),
+            (C.c_float * n)(*a_prev), (C.c_float * n)(*beta), n, 1 if ancestral else 0, PRED[scheduler.prediction_type],
+            int(scheduler.clip_sample), 1.0 / float(scale_factor), int(seed), ptr(lat), ptr(win), B, L, 1 if use_graph else 0, C.byref(used))
+    if lab is None:
+        check(lib.eegldm_sample(*args))
+    else:
+        check(lib.eegldm_sample_cond(*args, (C.c_int64 * B)(*lab), float(guidance_scale), nc))
     unet._bump_tape()
     if autoencoder is not None:
         autoencoder._bump_tape()
@@ -70,16 +101,25 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
 
 
 @torch.no_grad()
-def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36):
+def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, labels=None, guidance_scale=1.0, null_class=None):
     """The same loop driven from Python, one scheduler.step call per timestep (what round 1 shipped; kept as the
-    reference composition the native sampler is tested against, and for schedulers the native loop does not know)."""
+    reference composition the native sampler is tested against, and for schedulers the native loop does not know).
+    Class-conditional: the UNet is called with the labels and, for guidance_scale != 1, a second time with null_class; the two
+    outputs are mixed as out_u + w (out_c - out_u) ahead of scheduler.step."""
     unet.eval()
     x = noise.to(unet.device, torch.float32).contiguous()
     B = x.shape[0]
+    lab, nc = _labels_host(unet, labels, B, guidance_scale, null_class)
+    kw = {} if lab is None else {"y": torch.tensor(lab, dtype=torch.int64, device=unet.device)}
+    null = None if lab is None else torch.full((B,), nc, dtype=torch.int64, device=unet.device)
+    w = float(guidance_scale)
     tt = torch.empty(B, device=unet.device, dtype=torch.int64)
     for t in scheduler.timesteps:
         tt.fill_(int(t))
-        out = unet(x, timesteps=tt)
+        out = unet(x, timesteps=tt, **kw)
+        if lab is not None and w != 1.0:
+            out_u = unet(x, timesteps=tt, y=null)
+            out = out_u + w * (out - out_u)
         x, _ = scheduler.step(out, int(t), x)
     if autoencoder is None:      # pixel-space model (sample_trials_ddpm.py:99-104): the UNet output IS the window
         return (x[:, :, crop:-crop] if crop else x), x
@@ -100,11 +140,12 @@ def make_sampling_scheduler(num_inference_steps=50, prediction_type="epsilon", b
     return s
 
 
-def sample_seeds(unet, autoencoder, scheduler, seeds, latent_len=768, scale_factor=1.0, crop=36):
+def sample_seeds(unet, autoencoder, scheduler, seeds, latent_len=768, scale_factor=1.0, crop=36, labels=None, guidance_scale=1.0, null_class=None):
     """One window per seed (sample_trials.py:149-151 draws a fresh N(0,1) latent per seed), batched.
-    autoencoder=None samples a pixel-space model: latent_len is then the window length (3072)."""
+    autoencoder=None samples a pixel-space model: latent_len is then the window length (3072).  labels / guidance_scale / null_class:
+    class-conditional sampling (ddim_sample)."""
     lat = unet.in_channels
     noise = torch.empty(len(seeds), lat, latent_len, device=unet.device)
     for i, sd in enumerate(seeds):
         noise[i] = randn(unet.ctx, (lat, latent_len), seed=int(sd))
-    return ddim_sample(unet, autoencoder, scheduler, noise, scale_factor, crop)
+    return ddim_sample(unet, autoencoder, scheduler, noise, scale_factor, crop, labels=labels, guidance_scale=guidance_scale, null_class=null_class)

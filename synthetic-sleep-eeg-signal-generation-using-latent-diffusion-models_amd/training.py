@@ -187,20 +187,43 @@ def set_grad_hook(unet, fn):
     check(lib.eegldm_unet_set_grad_hook(unet.h, C.cast(thunk, C.c_void_p), None))
 
 
-def ldm_train_step(unet, scheduler, latents, noise, timesteps, loss_out=None, grad_scale=1.0, grad_sync=None):
+def ldm_train_step(unet, scheduler, latents, noise, timesteps, loss_out=None, grad_scale=1.0, grad_sync=None, labels=None, p_uncond=0.0,
+                   null_class=None, seed=0, offset=0):
     """add_noise -> UNet forward -> MSE against noise (epsilon) or velocity (v_prediction) -> backward.
     Accumulates into unet.flat_grad; returns the device scalar loss tensor.  grad_sync: an
     eegldm.distributed.OverlappedGradSync -- the tail of the gradient buffer is all-reduced while the input blocks'
-    backward still runs, the rest right after the call; the caller then only has to `grad_sync.wait()`."""
+    backward still runs, the rest right after the call; the caller then only has to `grad_sync.wait()`.
+    labels (a UNet built with num_classes): the class of every sample, (B,) integers.  Classifier-free guidance training: with
+    probability p_uncond a sample's label is replaced by null_class on the device, drawn from the Philox stream (seed, offset + b)
+    -- advance `offset` by B per step; the backward uses the replaced labels."""
     if loss_out is None:
         loss_out = torch.zeros(1, device=unet.device)
     B, _C, L = latents.shape
+    cond = getattr(unet, "num_classes", None) is not None
+    if cond != (labels is not None):
+        raise ValueError("labels must be given if and only if the UNet is class-conditional")
+    if cond:
+        lab = unet.check_labels(labels)
+        if tuple(lab.shape) != (B,):
+            raise ValueError(f"labels must have shape ({B},), got {tuple(lab.shape)}")
+        if not 0.0 <= float(p_uncond) <= 1.0:
+            raise ValueError(f"p_uncond={p_uncond} outside [0, 1]")
+        if float(p_uncond) > 0.0 and null_class is None:
+            raise ValueError("p_uncond > 0 needs null_class")
+        nc = 0 if null_class is None else int(null_class)
+        if null_class is not None and not 0 <= nc < unet.num_classes:
+            raise IndexError(f"null_class {nc} is out of range for num_classes={unet.num_classes}")
     if grad_sync is not None:
         grad_sync.begin()
         set_grad_hook(unet, grad_sync.on_ready)
     try:
-        check(lib.eegldm_ldm_train_step(unet.h, ptr(latents), ptr(noise), ptr(timesteps), ptr(scheduler._acp_dev),
-                                        PRED[scheduler.prediction_type], B, L, grad_scale, ptr(loss_out)))
+        if cond:
+            check(lib.eegldm_ldm_train_step_cond(unet.h, ptr(latents), ptr(noise), ptr(timesteps), ptr(scheduler._acp_dev),
+                                                 PRED[scheduler.prediction_type], B, L, grad_scale, ptr(loss_out), ptr(lab), float(p_uncond),
+                                                 nc, int(seed), int(offset)))
+        else:
+            check(lib.eegldm_ldm_train_step(unet.h, ptr(latents), ptr(noise), ptr(timesteps), ptr(scheduler._acp_dev),
+                                            PRED[scheduler.prediction_type], B, L, grad_scale, ptr(loss_out)))
     finally:
         unet._bump_tape()                    # forward + backward ran inside the call: an older autograd graph's tape is gone
         if grad_sync is not None:
@@ -247,6 +270,13 @@ def dm_train_step(unet, scheduler, images, noise, timesteps, spectral_weight=0.0
 def randn(ctx, shape, seed, offset=0, device=None):
     out = torch.empty(shape, device=device or torch.device("cuda", ctx.device), dtype=torch.float32)
     check(lib.eegldm_randn(ctx.h, ptr(out), out.numel(), seed, offset))
+    return out
+
+
+def label_dropout(ctx, labels, p_uncond, null_class, seed, offset=0):
+    """The label dropout of the conditional train step on its own: each label -> null_class with probability p_uncond."""
+    out = torch.empty_like(labels)
+    check(lib.eegldm_label_dropout(ctx.h, ptr(labels), ptr(out), labels.numel(), float(p_uncond), int(null_class), int(seed), int(offset)))
     return out
 
 
