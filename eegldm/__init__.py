@@ -11,3 +11,4 @@ _PKG = _os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__file__
 __path__.insert(0, _PKG)
 
 from ._lib import lib, LibraryMissing, check, Context, default_context, set_deterministic  # noqa: E402,F401
+from .training import EMA  # noqa: E402,F401

@@ -222,6 +222,19 @@ int eegldm_ddpm_step_var(eegldm_ctx*, const float* model_out, const float* sampl
 int eegldm_mse_loss(eegldm_ctx*, const float* pred, const float* target, float* loss, float* dpred, long n, float grad_scale);
 int eegldm_adam_step(eegldm_ctx*, float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
                      float beta2, float eps, int step, float grad_inv_scale);
+/* Weight EMA (exponential moving average of the parameters; the reference has none, diffusion code bases sample from one).
+ * The shadow is one more flat fp32 buffer beside the parameters.  All three are single streaming passes with 16-byte accesses on the part of
+ * the buffers that is 16-byte aligned (any n, any 4-byte-aligned address).  NULL buffers, n < 0 and overlapping buffers are rejected
+ * before the device is touched.
+ *   eegldm_adam_step_ema  eegldm_adam_step, then in the same pass ema = fma(one_minus_decay, p_new - ema, ema): p, m, v come out
+ *                         bit-identical to eegldm_adam_step and ema bit-identical to eegldm_adam_step + eegldm_ema_update
+ *   eegldm_ema_update     ema = fma(one_minus_decay, p - ema, ema) on its own (parameters updated by another optimizer)
+ *   eegldm_swap           exchanges a[0..n) and b[0..n) in place
+ * one_minus_decay = 1 - decay, rounded once from double by the caller.  A NaN / inf parameter gives a NaN / inf shadow value. */
+int eegldm_adam_step_ema(eegldm_ctx*, float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float beta1,
+                         float beta2, float eps, int step, float grad_inv_scale, float one_minus_decay);
+int eegldm_ema_update(eegldm_ctx*, float* ema, const float* p, long n, float one_minus_decay);
+int eegldm_swap(eegldm_ctx*, float* a, float* b, long n);
 /* found_inf[0] (device float) = 1 if any of g[0..n) is inf/nan, else 0 -- the check behind GradScaler.unscale_/step
  * (torch.cuda.amp.GradScaler at /root/reference/src/training/training.py:334,441-443). g must be 16-byte aligned. */
 int eegldm_grad_check_finite(eegldm_ctx*, const float* g, long n, float* found_inf);

@@ -1,6 +1,6 @@
 // HBM-bound elementwise / small-reduction kernels of the hot path: layout conversion,
 // weight packing, timestep embedding, SiLU, per-sample column sums, softmax, scheduler
-// arithmetic, MSE, Adam, Philox RNG.  One pass over the data each, 16-byte accesses where
+// arithmetic, MSE, Adam (+ weight EMA, buffer exchange), Philox RNG.  One pass over the data each, 16-byte accesses where
 // the layout allows.  Reference call sites are cited at each entry point.
 #include "common.h"
 #include "internal.h"
@@ -450,18 +450,90 @@ __global__ __launch_bounds__(NT) void mse_kernel(const float* __restrict__ p, co
   if (threadIdx.x == 0) { const float v = (red[0] + red[1] + red[2] + red[3]) * inv_n; if (parts) parts[blockIdx.x] = v; else atomicAdd(loss, v); }
 }
 
-// ------------------------------------------------------------------ Adam (torch.optim.Adam defaults, train_ldm.py:208)
+// ------------------------------------------------------------------ Adam (torch.optim.Adam defaults, train_ldm.py:208) and the weight EMA
+// The per-element arithmetic lives in ONE function per expression, contraction off and every fused multiply-add spelled out, so that
+// each kernel that inlines it rounds identically: eegldm_adam_step_ema must equal eegldm_adam_step followed by eegldm_ema_update bit
+// for bit (tests/test_gpu_ema.py).  The fmaf placement is the one the compiler had chosen for adam_kernel before the function existed
+// (same instruction stream): trajectories recorded with earlier builds are unchanged.
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float bc1,
+                                          float bc2_sqrt, float ginv) {
+#pragma clang fp contract(off)
+  const float gi = g * ginv;
+  const float mi = fmaf(b1, m, (1.0f - b1) * gi);
+  const float vi = fmaf(b2, v, ((1.0f - b2) * gi) * gi);
+  m = mi; v = vi;
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  p = fmaf(-(lr / bc1), mi / denom, p);
+}
+// e += c * (p - e), c = 1 - decay: one rounding in the difference, one in the fma.  No min / max anywhere: a NaN / inf parameter gives a
+// NaN / inf shadow value.
+__device__ __forceinline__ float ema_elem(float e, float p, float c) {
+#pragma clang fp contract(off)
+  return fmaf(c, p - e, e);
+}
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             long n, float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt, float ginv) {
   GRID_STRIDE(i, n) {
-    const float gi = g[i] * ginv;
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] -= (lr / bc1) * (mi / denom);
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_elem(pi, g[i], mi, vi, lr, b1, b2, eps, bc1, bc2_sqrt, ginv);
+    m[i] = mi; v[i] = vi; p[i] = pi;
   }
 }
+
+// Streaming passes over a flat fp32 buffer with 16-byte accesses.  Elements [0, head) and the last (n - head) % 4 go one by one, the
+// body [head, head + 4 * n4) as float4: the launcher picks `head` so that the body of EVERY buffer is 16-byte aligned, which needs all of
+// them to share one misalignment; if they do not, head = n and the whole range takes the scalar loop.  n is arbitrary.
+struct VecSplit { long head, n4, tail0, nedge; };
+__device__ __forceinline__ VecSplit vec_split(long n, long head) {
+  VecSplit s; s.head = head; s.n4 = (n - head) >> 2; s.tail0 = head + (s.n4 << 2); s.nedge = head + (n - s.tail0);
+  return s;
+}
+#define EDGE_INDEX(s, j) ((j) < (s).head ? (j) : (s).tail0 + ((j) - (s).head))
+__global__ __launch_bounds__(NT) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                      float* __restrict__ e, long n, long head, float lr, float b1, float b2, float eps,
+                                                      float bc1, float bc2_sqrt, float ginv, float c) {
+  const VecSplit s = vec_split(n, head);
+  f32x4* p4 = (f32x4*)(p + head); const f32x4* g4 = (const f32x4*)(g + head); f32x4* m4 = (f32x4*)(m + head); f32x4* v4 = (f32x4*)(v + head);
+  f32x4* e4 = (f32x4*)(e + head);
+  GRID_STRIDE(i, s.n4) {
+    f32x4 pv = p4[i], mv = m4[i], vv = v4[i], ev = e4[i];
+    const f32x4 gv = g4[i];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      float pk = pv[k], mk = mv[k], vk = vv[k];
+      adam_elem(pk, gv[k], mk, vk, lr, b1, b2, eps, bc1, bc2_sqrt, ginv);
+      pv[k] = pk; mv[k] = mk; vv[k] = vk;
+      ev[k] = ema_elem(ev[k], pk, c);
+    }
+    m4[i] = mv; v4[i] = vv; p4[i] = pv; e4[i] = ev;
+  }
+  GRID_STRIDE(j, s.nedge) {
+    const long i = EDGE_INDEX(s, j);
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_elem(pi, g[i], mi, vi, lr, b1, b2, eps, bc1, bc2_sqrt, ginv);
+    m[i] = mi; v[i] = vi; p[i] = pi;
+    e[i] = ema_elem(e[i], pi, c);
+  }
+}
+__global__ __launch_bounds__(NT) void ema_update_kernel(float* __restrict__ e, const float* __restrict__ p, long n, long head, float c) {
+  const VecSplit s = vec_split(n, head);
+  f32x4* e4 = (f32x4*)(e + head); const f32x4* p4 = (const f32x4*)(p + head);
+  GRID_STRIDE(i, s.n4) {
+    f32x4 ev = e4[i];
+    const f32x4 pv = p4[i];
+#pragma unroll
+    for (int k = 0; k < 4; k++) ev[k] = ema_elem(ev[k], pv[k], c);
+    e4[i] = ev;
+  }
+  GRID_STRIDE(j, s.nedge) { const long i = EDGE_INDEX(s, j); e[i] = ema_elem(e[i], p[i], c); }
+}
+__global__ __launch_bounds__(NT) void swap_kernel(float* __restrict__ a, float* __restrict__ b, long n, long head) {
+  const VecSplit s = vec_split(n, head);
+  f32x4* a4 = (f32x4*)(a + head); f32x4* b4 = (f32x4*)(b + head);
+  GRID_STRIDE(i, s.n4) { const f32x4 av = a4[i], bv = b4[i]; a4[i] = bv; b4[i] = av; }
+  GRID_STRIDE(j, s.nedge) { const long i = EDGE_INDEX(s, j); const float av = a[i], bv = b[i]; a[i] = bv; b[i] = av; }
+}
+#undef EDGE_INDEX
 
 // ------------------------------------------------------------------ Philox4x32-10 (perf-path RNG; parity runs pass noise in)
 __device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3, unsigned k0, unsigned k1) {
@@ -991,6 +1063,60 @@ extern "C" int eegldm_adam_step(eegldm_ctx* ctx, float* p, const float* g, float
   EEG_CHECK(step >= 1, "step starts at 1");
   const float bc1 = 1.0f - powf(b1, (float)step), bc2s = sqrtf(1.0f - powf(b2, (float)step));
   hipLaunchKernelGGL(adam_kernel, dim3(grid1d(n, ctx, 2)), dim3(NT), 0, ctx->stream, p, g, m, v, n, lr, b1, b2, eps, bc1, bc2s, ginv);
+  LAUNCH_CHECK(); return 0;
+}
+// ---- weight EMA (include/eegldm.h): fused into the Adam pass, on its own, and the buffer exchange behind EMA.applied()
+// Scalar elements ahead of the float4 body: 0..3 when every buffer has the same offset inside a 16-byte line, else all n of them.
+static long vec_head(long n, std::initializer_list<const void*> ptrs) {
+  const uintptr_t mis = (uintptr_t)*ptrs.begin() & 15;
+  for (const void* q : ptrs) if (((uintptr_t)q & 15) != mis) return n;
+  const long head = (long)(((16 - mis) & 15) >> 2);
+  return head < n ? head : n;
+}
+// blocks for n elements of which the body goes four per thread; 8 blocks per CU keep every CU's memory queue full
+static int grid_vec(long n, long head, eegldm_ctx* ctx) {
+  const long work = head >= n ? n : (n - head) >> 2;      // (the <= 6 edge elements fit the first block)
+  long blocks = (work + NT - 1) / NT, cap = (long)ctx->num_cu * 8;
+  if (blocks < 1) blocks = 1;
+  return (int)(blocks < cap ? blocks : cap);
+}
+static bool ranges_overlap(const float* a, const float* b, long n) { return a < b + n && b < a + n; }
+extern "C" int eegldm_adam_step_ema(eegldm_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1,
+                                    float b2, float eps, int step, float ginv, float one_minus_decay) {
+  EEG_CHECK(p && g && m && v && ema, "null buffer");
+  EEG_CHECK(n >= 0, "negative n (%ld)", n);
+  EEG_CHECK(ema != p && !ranges_overlap(ema, p, n) && !ranges_overlap(ema, g, n) && !ranges_overlap(ema, m, n) && !ranges_overlap(ema, v, n),
+            "the EMA buffer aliases a parameter / gradient / moment buffer");
+  EEG_CHECK(ctx, "null ctx");
+  EEG_CHECK(step >= 1, "step starts at 1");
+  EEG_CHECK(((uintptr_t)p & 3) == 0 && ((uintptr_t)g & 3) == 0 && ((uintptr_t)m & 3) == 0 && ((uintptr_t)v & 3) == 0 && ((uintptr_t)ema & 3) == 0, "buffers must be 4-byte aligned");
+  if (n == 0) return 0;
+  const float bc1 = 1.0f - powf(b1, (float)step), bc2s = sqrtf(1.0f - powf(b2, (float)step));      // as eegldm_adam_step
+  const long head = vec_head(n, {p, g, m, v, ema});
+  hipLaunchKernelGGL(adam_ema_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, p, g, m, v, ema, n, head, lr, b1, b2, eps,
+                     bc1, bc2s, ginv, one_minus_decay);
+  LAUNCH_CHECK(); return 0;
+}
+extern "C" int eegldm_ema_update(eegldm_ctx* ctx, float* ema, const float* p, long n, float one_minus_decay) {
+  EEG_CHECK(ema && p, "null buffer");
+  EEG_CHECK(n >= 0, "negative n (%ld)", n);
+  EEG_CHECK(ema != p && !ranges_overlap(ema, p, n), "the EMA buffer aliases the parameter buffer");
+  EEG_CHECK(ctx, "null ctx");
+  EEG_CHECK(((uintptr_t)p & 3) == 0 && ((uintptr_t)ema & 3) == 0, "buffers must be 4-byte aligned");
+  if (n == 0) return 0;
+  const long head = vec_head(n, {ema, p});
+  hipLaunchKernelGGL(ema_update_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, ema, p, n, head, one_minus_decay);
+  LAUNCH_CHECK(); return 0;
+}
+extern "C" int eegldm_swap(eegldm_ctx* ctx, float* a, float* b, long n) {
+  EEG_CHECK(a && b, "null buffer");
+  EEG_CHECK(n >= 0, "negative n (%ld)", n);
+  EEG_CHECK(a != b && !ranges_overlap(a, b, n), "the two buffers alias");
+  EEG_CHECK(ctx, "null ctx");
+  EEG_CHECK(((uintptr_t)a & 3) == 0 && ((uintptr_t)b & 3) == 0, "buffers must be 4-byte aligned");
+  if (n == 0) return 0;
+  const long head = vec_head(n, {a, b});
+  hipLaunchKernelGGL(swap_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, a, b, n, head);
   LAUNCH_CHECK(); return 0;
 }
 // GradScaler.unscale_/step support (training.py:334,441-443 use torch.cuda.amp.GradScaler): found_inf[0] = 1 if any gradient is

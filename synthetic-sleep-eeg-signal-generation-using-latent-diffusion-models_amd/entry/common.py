@@ -213,6 +213,33 @@ class WindowLoader:
                 yield {"eeg": torch.from_numpy(np.stack([w for w, _ in items])), "label": torch.tensor([c for _, c in items], dtype=torch.int64)}
 
 
+def add_ema_args(p):
+    p.add_argument("--ema_decay", type=float, default=None, help="keep an exponential moving average of the UNet weights with this decay "
+                   "(updated inside the Adam kernel); adds the 'ema' entry to checkpoint.pth and writes best_model_ema.pth / final_model_ema.pth")
+    p.add_argument("--ema_no_warmup", action="store_true", help="constant decay instead of min(decay, (1 + n) / (10 + n))")
+
+
+def cpu_state(sd):
+    return {k: v.cpu() for k, v in sd.items()}
+
+
+def ema_checkpoint_entry(ema, best_loss):
+    """The 'ema' entry of checkpoint.pth."""
+    return {"decay": ema.decay, "warmup": ema.warmup, "num_updates": ema.num_updates, "best_loss": best_loss, "shadow": cpu_state(ema.state_dict())}
+
+
+def ema_resume(ema, ck, rank=0):
+    """Restores shadow and update count from a loaded checkpoint.pth (call after the model's weights have been loaded); returns the EMA's
+    best validation loss.  A checkpoint without an EMA starts the average from the loaded weights."""
+    if "ema" in ck:
+        ema.load_state_dict(ck["ema"]["shadow"], num_updates=ck["ema"]["num_updates"])
+        return float(ck["ema"]["best_loss"])
+    ema.reset()
+    if rank == 0:
+        print("checkpoint.pth has no EMA: the average starts from the loaded weights")
+    return float("inf")
+
+
 def rng_seed(base_seed, role, rank=0, world=1):
     """Distinct Philox key per (role, rank): base * 2^20 + role * 4096 + rank.  Roles: 1 timesteps, 2 posterior eps, 3 diffusion
     noise, 4 autoencoder eps, 5-7 validation draws, 8 training loader (crop / shuffle / synthetic windows), 9 validation loader,

@@ -30,6 +30,7 @@ def parse_args(argv=None):
     p.add_argument("--labels_file", default=None, help=".npy / text file with one label per seed, seeds start_seed .. stop_seed - 1 in order")
     p.add_argument("--null_class", type=int, default=None, help="classifier-free guidance: the unconditional class; --guidance_scale "
                    "applies to a class-conditional UNet only when it is given")
+    p.add_argument("--use_ema", action="store_true", help="sample from best_model_ema.pth (a run trained with --ema_decay) instead of best_model.pth")
     return p.parse_args(argv)
 
 
@@ -60,7 +61,10 @@ def main(args):
             raise ValueError("a class-conditional UNet needs --class_label or --labels_file")
     guided = labels is not None and args.null_class is not None
     unet = UNetModel(**up, dtype=args.dtype, device=local)
-    unet.load_state_dict(torch.load(os.path.join(args.diffusion_path, "best_model.pth"), map_location="cpu"))
+    weights = os.path.join(args.diffusion_path, "best_model_ema.pth" if args.use_ema else "best_model.pth")
+    if args.use_ema and not os.path.exists(weights):
+        raise FileNotFoundError(f"--use_ema: {weights} not found (train with --ema_decay to have it written)")
+    unet.load_state_dict(torch.load(weights, map_location="cpu"))
     scale_factor = float(torch.load(os.path.join(args.diffusion_path, "checkpoint.pth"), map_location="cpu")["scale_factor"])
     sched = make_sampling_scheduler(args.num_inference_steps, prediction_type=args.prediction_type, device=local)
     lo, hi = D.shard_range(args.stop_seed - args.start_seed, rank, world)

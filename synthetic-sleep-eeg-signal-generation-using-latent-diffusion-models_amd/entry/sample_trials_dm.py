@@ -23,6 +23,7 @@ def parse_args(argv=None):
     p.add_argument("--num_inference_steps", type=int, default=200); p.add_argument("--spe", default="no-spectral")
     p.add_argument("--dataset", default="edfx"); p.add_argument("--prediction_type", default="v_prediction")
     p.add_argument("--batch", type=int, default=64); p.add_argument("--dtype", default="float32")
+    p.add_argument("--use_ema", action="store_true", help="sample from best_model_ema.pth (a run trained with --ema_decay) instead of best_model.pth")
     return p.parse_args(argv)
 
 
@@ -34,7 +35,10 @@ def main(args):
     up = dict(load_config(args.config_file)["model"]["params"]["unet_config"]["params"])
     up["in_channels"] = up["out_channels"] = 1                                   # sample_trials_ddpm.py:71-73
     unet = UNetModel(**up, dtype=args.dtype, device=local)
-    unet.load_state_dict(torch.load(os.path.join(args.diffusion_path, "best_model.pth"), map_location="cpu"))
+    weights = os.path.join(args.diffusion_path, "best_model_ema.pth" if args.use_ema else "best_model.pth")
+    if args.use_ema and not os.path.exists(weights):
+        raise FileNotFoundError(f"--use_ema: {weights} not found (train with --ema_decay to have it written)")
+    unet.load_state_dict(torch.load(weights, map_location="cpu"))
     sched = make_sampling_scheduler(args.num_inference_steps, prediction_type=args.prediction_type, device=local)
     lo, hi = D.shard_range(args.stop_seed - args.start_seed, rank, world)
     seeds = list(range(args.start_seed + lo, args.start_seed + hi))

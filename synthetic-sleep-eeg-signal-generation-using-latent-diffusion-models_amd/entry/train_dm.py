@@ -12,8 +12,8 @@ import torch
 from .. import distributed as D
 from ..models import UNetModel
 from ..schedulers import DDPMScheduler
-from ..training import Adam, GradScaler, dm_train_step, randint, randn
-from .common import WindowLoader, load_config, rng_seed, setup_run_dir
+from ..training import EMA, Adam, GradScaler, dm_train_step, randint, randn
+from .common import WindowLoader, add_ema_args, cpu_state, ema_checkpoint_entry, ema_resume, load_config, rng_seed, setup_run_dir
 
 
 def parse_args(argv=None):
@@ -27,6 +27,7 @@ def parse_args(argv=None):
     p.add_argument("--grad_scaler", action="store_true", help="dynamic loss scaling as training_diffusion.py:37 does (always on with --dtype float16)")
     p.add_argument("--deterministic", action="store_true", help="bit-reproducible steps (eegldm.set_deterministic(): ordered reductions instead of fp32 atomics; "
                    "what torch.use_deterministic_algorithms(True) would be for the reference's loop)")
+    add_ema_args(p)
     return p.parse_args(argv)
 
 
@@ -44,7 +45,8 @@ def main(args):
     unet = UNetModel(**up, dtype=args.dtype, device=local)
     D.broadcast_flat(unet.flat); unet.sync_weights()
     sched = DDPMScheduler(num_train_timesteps=1000, schedule="linear_beta", beta_start=0.0015, beta_end=0.0195, device=local)
-    opt = Adam(unet, lr=1e-4)
+    ema = EMA(unet, decay=args.ema_decay, warmup=not args.ema_no_warmup) if args.ema_decay is not None else None      # after the broadcast
+    opt = Adam(unet, lr=1e-4, ema=ema)
     # training_diffusion.py:37,149-151 pairs its fp16 autocast with a GradScaler: fp16 activation gradients under- / overflow without the loss scale
     scaler = GradScaler(enabled=args.grad_scaler or str(args.dtype) in ("float16", "fp16", "half"))
     spectral = args.spe == "spectral"
@@ -62,6 +64,8 @@ def main(args):
         if "scaler" in ck:
             scaler.load_state_dict(ck["scaler"])
         start_epoch, best, gstep = int(ck["epoch"]), float(ck["best_loss"]), int(ck.get("steps", 0))
+        if ema is not None:
+            ema_resume(ema, ck, rank)
         if rank == 0:
             print(f"Resuming from epoch {start_epoch} (best loss {best:.5f})")
     for epoch in range(start_epoch, config.train.n_epochs):
@@ -85,12 +89,19 @@ def main(args):
             if cur <= best:
                 best = cur
                 torch.save({k: v.cpu() for k, v in unet.state_dict().items()}, os.path.join(run_dir, "best_model.pth"))
-            torch.save({"epoch": epoch + 1, "diffusion": {k: v.cpu() for k, v in unet.state_dict().items()}, "optimizer": opt.state_dict(),
-                        "best_loss": best, "steps": gstep, "scaler": scaler.state_dict()}, os.path.join(run_dir, "checkpoint.pth"))
+                if ema is not None:            # selection is on the last training loss here: no loss of the averaged weights exists
+                    torch.save(cpu_state(ema.state_dict()), os.path.join(run_dir, "best_model_ema.pth"))
+            ck_out = {"epoch": epoch + 1, "diffusion": {k: v.cpu() for k, v in unet.state_dict().items()}, "optimizer": opt.state_dict(),
+                      "best_loss": best, "steps": gstep, "scaler": scaler.state_dict()}
+            if ema is not None:
+                ck_out["ema"] = ema_checkpoint_entry(ema, best)
+            torch.save(ck_out, os.path.join(run_dir, "checkpoint.pth"))
         if args.max_steps and steps >= args.max_steps:
             break
     if rank == 0:
         torch.save({k: v.cpu() for k, v in unet.state_dict().items()}, os.path.join(run_dir, "final_model.pth"))
+        if ema is not None:
+            torch.save(cpu_state(ema.state_dict()), os.path.join(run_dir, "final_model_ema.pth"))
     return run_dir
 
 

@@ -10,8 +10,8 @@ import torch
 from .. import distributed as D
 from ..models import AutoencoderKL, UNetModel
 from ..schedulers import DDPMScheduler
-from ..training import Adam, GradScaler, ldm_train_step, randint, randn
-from .common import ParseListAction, WindowLoader, load_config, rng_seed, setup_run_dir
+from ..training import EMA, Adam, GradScaler, ldm_train_step, randint, randn
+from .common import ParseListAction, WindowLoader, add_ema_args, cpu_state, ema_checkpoint_entry, ema_resume, load_config, rng_seed, setup_run_dir
 
 
 def parse_args(argv=None):
@@ -36,6 +36,7 @@ def parse_args(argv=None):
     p.add_argument("--path_stages", default=None)
     p.add_argument("--p_uncond", type=float, default=0.0, help="classifier-free guidance training: probability of replacing a label by --null_class")
     p.add_argument("--null_class", type=int, default=None, help="the unconditional class (default: num_classes - 1 when --p_uncond > 0)")
+    add_ema_args(p)
     return p.parse_args(argv)
 
 
@@ -99,7 +100,9 @@ def main(args):
     # what train_ldm uses; --schedule scaled_linear_beta selects it deliberately.
     sched = DDPMScheduler(num_train_timesteps=1000, schedule=args.schedule, beta_start=0.0015, beta_end=0.0195,
                           prediction_type=args.prediction_type, device=local)
-    opt = Adam(unet, lr=config.train.get("base_lr", 1e-4))
+    # (after the broadcast: every rank's shadow starts from the same weights and, gradients being averaged before Adam.step, stays identical)
+    ema = EMA(unet, decay=args.ema_decay, warmup=not args.ema_no_warmup) if args.ema_decay is not None else None
+    opt = Adam(unet, lr=config.train.get("base_lr", 1e-4), ema=ema)
     scaler = GradScaler(enabled=args.grad_scaler or str(args.dtype) in ("float16", "fp16", "half"))      # fp16 activations: the loss scale is what keeps their gradients out of the subnormal range
     bs = max(1, config.train.batch_size // world)
     train = WindowLoader(args.path_pre_processed, bs, args.synthetic_windows, seed=rng_seed(config.train.seed, 8, rank, world), drop_last=config.train.drop_last,
@@ -122,6 +125,7 @@ def main(args):
     loss = torch.zeros(1, device=dev)
     gsync = D.OverlappedGradSync(unet.flat_grad, ctx=unet.ctx, comm=D.make_comm(unet.ctx))   # no-op with one process; EEGLDM_NATIVE_COLLECTIVES=1: RCCL through the C ABI
     steps, t0, seen, best, start_epoch, gstep = 0, time.time(), 0, float("inf"), 0, 0      # gstep: steps over all invocations (RNG offsets)
+    best_ema = float("inf")
     if resume:
         # continue from {run_dir}/checkpoint.pth (keys as written below = training.py:381-387).  The reference computes `resume`
         # but always restarts at epoch 0 (train_ldm.py:113,210-211); here the run really continues, with the saved scale_factor
@@ -131,6 +135,8 @@ def main(args):
             scaler.load_state_dict(ck["scaler"])
         start_epoch, best, scale_factor = int(ck["epoch"]), float(ck["best_loss"]), float(ck["scale_factor"])
         gstep = int(ck.get("steps", 0))
+        if ema is not None:
+            best_ema = ema_resume(ema, ck, rank)
         if rank == 0:
             print(f"Resuming from epoch {start_epoch} (best loss {best:.5f}, scale factor {scale_factor})")
     for epoch in range(start_epoch, config.train.n_epochs):
@@ -155,19 +161,35 @@ def main(args):
         if do_eval and valid is not None:      # model selection on the validation split (training.py:356-380), epsilon MSE over its windows
             v_sum, v_n = D.allreduce_sum_scalars(validate(unet, stage1, sched, valid, scale_factor, v_seeds, args.latent_channels), like=loss)
             cur = v_sum / max(1.0, v_n)
+        cur_ema = None                         # no validation split: no loss of the averaged weights exists
+        if do_eval and valid is not None and ema is not None:      # the same windows and noise, scored with the averaged weights
+            with ema.applied():
+                e_sum, e_n = D.allreduce_sum_scalars(validate(unet, stage1, sched, valid, scale_factor, v_seeds, args.latent_channels), like=loss)
+            cur_ema = e_sum / max(1.0, e_n)
         if rank == 0:
             print(f"epoch {epoch}: loss {float(loss):.5f} | {seen/(time.time()-t0):.1f} windows/s", flush=True)
             if do_eval:
-                if cur <= best:
+                new_best = cur <= best
+                if new_best:
                     best = cur
                     torch.save({k: v.cpu() for k, v in unet.state_dict().items()}, os.path.join(run_dir, "best_model.pth"))
-                torch.save({"epoch": epoch + 1, "diffusion": {k: v.cpu() for k, v in unet.state_dict().items()}, "optimizer": opt.state_dict(),
-                            "best_loss": best, "scale_factor": torch.tensor(scale_factor), "scaler": scaler.state_dict(), "steps": gstep},
-                           os.path.join(run_dir, "checkpoint.pth"))
+                ck_out = {"epoch": epoch + 1, "diffusion": {k: v.cpu() for k, v in unet.state_dict().items()}, "optimizer": opt.state_dict(),
+                          "best_loss": best, "scale_factor": torch.tensor(scale_factor, dtype=torch.float64), "scaler": scaler.state_dict(), "steps": gstep}
+                # (float64: the Python float the run multiplies its latents with, exactly -- a resumed run then continues bit for bit)
+                if ema is not None:            # its own best on its own validation loss; without one, whenever best_model.pth is written
+                    if cur_ema is not None:
+                        new_best = cur_ema <= best_ema
+                        best_ema = min(best_ema, cur_ema)
+                    if new_best:
+                        torch.save(cpu_state(ema.state_dict()), os.path.join(run_dir, "best_model_ema.pth"))
+                    ck_out["ema"] = ema_checkpoint_entry(ema, best_ema)
+                torch.save(ck_out, os.path.join(run_dir, "checkpoint.pth"))
         if args.max_steps and steps >= args.max_steps:
             break
     if rank == 0:
         torch.save({k: v.cpu() for k, v in unet.state_dict().items()}, os.path.join(run_dir, "final_model.pth"))
+        if ema is not None:
+            torch.save(cpu_state(ema.state_dict()), os.path.join(run_dir, "final_model_ema.pth"))
     LAST_RUN.clear(); LAST_RUN.update(rank=rank, world=world, scale_factor=scale_factor, steps=steps, param_sum=float(unet.flat.double().sum()))
     return run_dir
 

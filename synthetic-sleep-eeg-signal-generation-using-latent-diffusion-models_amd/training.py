@@ -1,21 +1,125 @@
 """Train-step bodies of the reference loops, each one native call per phase:
   ldm_train_step  <-> /root/reference/src/training/training.py:419-443
   Adam            <-> torch.optim.Adam as used at /root/reference/src/train_ldm.py:208
+  EMA             exponential moving average of a model's weights, updated inside the Adam kernel (the reference has none)
 Gradients live in each model's flat fp32 buffer, so data-parallel training is ONE
 all-reduce over a contiguous tensor (see eegldm.distributed)."""
+import contextlib
 import ctypes as C
 
 import torch
 
 from ._lib import lib, check, ptr, PRED
+from .models._flat import pack_into, unpack
+
+
+class EMA:
+    """Exponential moving average of a model's weights: one more flat fp32 buffer (`shadow`) beside `model.flat`.
+
+        ema = EMA(unet, decay=0.9999)           # shadow = copy of unet.flat, num_updates = 0
+        opt = Adam(unet, lr=1e-4, ema=ema)      # every opt.step() also moves the shadow, inside the Adam kernel
+        with ema.applied():                     # the model computes with the averaged weights; the raw ones come back on exit
+            windows, _ = ddim_sample(unet, ...)
+
+    Update n + 1 is ``shadow += (1 - decay_at(n)) * (flat - shadow)``.  With `warmup` the decay ramps up as (1 + n) / (10 + n) until it
+    reaches `decay` (the rule of ADM-descended EMA helpers and of diffusers' EMAModel), so that the first updates are not dominated by
+    the random initial weights.  Works for any model shim with `flat` / `entries` / `sync_weights` (UNetModel, AutoencoderKL).
+    Data-parallel runs: build it after the parameters have been broadcast; gradients are averaged before Adam.step, so every rank's
+    shadow stays identical without a collective of its own."""
+
+    def __init__(self, model, decay=0.9999, warmup=True):
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"decay must lie in [0, 1), got {decay}")
+        self.model, self.decay, self.warmup = model, decay, bool(warmup)
+        self.shadow = model.flat.clone()
+        self.num_updates = 0
+        self._applied = False
+
+    def decay_at(self, n):
+        """The decay used by update number n + 1 (n = updates made so far)."""
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        return min(self.decay, (1 + n) / (10 + n)) if self.warmup else self.decay
+
+    def one_minus_decay(self):
+        """1 - decay of the NEXT update, in double; the C ABI takes it as a float (rounded once, at the call)."""
+        return 1.0 - self.decay_at(self.num_updates)
+
+    def _check_live(self, what):
+        if self._applied:
+            raise RuntimeError(f"{what} inside `with ema.applied()`: the model holds the averaged weights there")
+
+    def update(self):
+        """Stand-alone update from the model's current weights (parameters driven by torch.optim through the autograd bridge)."""
+        self._check_live("EMA.update()")
+        md = self.model
+        check(lib.eegldm_ema_update(md.ctx.h, ptr(self.shadow), ptr(md.flat), md.flat.numel(), self.one_minus_decay()))
+        self.num_updates += 1
+
+    def reset(self):
+        """shadow = the model's current weights, num_updates = 0 (a run resumed from a checkpoint that has no EMA)."""
+        self._check_live("EMA.reset()")
+        self.shadow.copy_(self.model.flat)
+        self.num_updates = 0
+
+    def _exchange(self):
+        md = self.model
+        check(lib.eegldm_swap(md.ctx.h, ptr(md.flat), ptr(self.shadow), md.flat.numel()))
+        md.sync_weights()                       # every derived copy (16-bit, K-blocked, paired-row) follows the flat buffer
+        bump = getattr(md, "_bump_tape", None)
+        if bump is not None:
+            bump()                              # an autograd graph built over the other weights must not reuse the executor's tape
+
+    @contextlib.contextmanager
+    def applied(self):
+        """Exchange `model.flat` and the shadow (one pass, in place) and refresh the model's weight copies; on exit exchange them back:
+        `model.flat` is bit-identical afterwards.  Does not nest."""
+        if self._applied:
+            raise RuntimeError("EMA.applied() does not nest")
+        self._exchange()
+        self._applied = True
+        try:
+            yield self.model
+        finally:
+            self._applied = False
+            self._exchange()
+
+    def copy_to(self, model=None):
+        """Overwrite the weights of `model` (default: the tracked one) with the average."""
+        self._check_live("EMA.copy_to()")
+        md = self.model if model is None else model
+        if md.flat.numel() != self.shadow.numel():
+            raise ValueError(f"the model has {md.flat.numel()} parameters, the EMA {self.shadow.numel()}")
+        md.flat.copy_(self.shadow.to(md.flat.device))
+        md.sync_weights()
+        bump = getattr(md, "_bump_tape", None)
+        if bump is not None:
+            bump()
+
+    def state_dict(self):
+        """The averaged weights as a plain model state dict: keys, order and tensor layout of `model.state_dict()`, so the file loads
+        into the reference's model and into this one unchanged.  `num_updates` travels separately (see the train scripts' "ema" entry)."""
+        self._check_live("EMA.state_dict()")
+        return unpack(self.shadow, self.model.entries)
+
+    def load_state_dict(self, sd, num_updates=None):
+        self._check_live("EMA.load_state_dict()")
+        pack_into(self.shadow, self.model.entries, sd)
+        if num_updates is not None:
+            self.num_updates = int(num_updates)
 
 
 class Adam:
     """torch.optim.Adam defaults (betas 0.9/0.999, eps 1e-8, no weight decay) as one fused HIP
-    kernel over the model's flat parameter buffer."""
+    kernel over the model's flat parameter buffer.  ema: an `EMA` of the same model, updated inside that kernel at every step
+    (a step that GradScaler skips therefore skips the EMA update too)."""
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        self.model, self.lr, self.betas, self.eps = model, lr, betas, eps
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, ema=None):
+        if ema is not None and ema.model is not model:
+            raise ValueError("the EMA tracks another model")
+        self.model, self.lr, self.betas, self.eps, self.ema = model, lr, betas, eps, ema
         self.m = torch.zeros_like(model.flat)
         self.v = torch.zeros_like(model.flat)
         self.step_count = 0
@@ -26,9 +130,18 @@ class Adam:
 
     def step(self, grad_inv_scale=1.0):
         self.step_count += 1
-        md = self.model
-        check(lib.eegldm_adam_step(md.ctx.h, ptr(md.flat), ptr(md.flat_grad), ptr(self.m), ptr(self.v), md.flat.numel(),
-                                   self.param_groups[0]["lr"], self.betas[0], self.betas[1], self.eps, self.step_count, grad_inv_scale))
+        md, ema = self.model, self.ema
+        if ema is None:
+            check(lib.eegldm_adam_step(md.ctx.h, ptr(md.flat), ptr(md.flat_grad), ptr(self.m), ptr(self.v), md.flat.numel(),
+                                       self.param_groups[0]["lr"], self.betas[0], self.betas[1], self.eps, self.step_count, grad_inv_scale))
+        else:                              # the same update + the EMA of the new weights in one pass over the buffers
+            if ema._applied:
+                self.step_count -= 1
+                raise RuntimeError("Adam.step() inside `with ema.applied()`: the model holds the averaged weights there")
+            check(lib.eegldm_adam_step_ema(md.ctx.h, ptr(md.flat), ptr(md.flat_grad), ptr(self.m), ptr(self.v), ptr(ema.shadow), md.flat.numel(),
+                                           self.param_groups[0]["lr"], self.betas[0], self.betas[1], self.eps, self.step_count, grad_inv_scale,
+                                           ema.one_minus_decay()))
+            ema.num_updates += 1
         md.sync_weights()
 
     # ---- checkpoint wire format: torch.optim.Adam's own state_dict layout, so that the optimizer entry of a reference
