@@ -42,7 +42,9 @@ extern "C" {
  *    eegldm_groupnorm_fwd_qstats (round 5's GroupNorm-from-producer-moments path measured no gain and was taken out, HISTORY.md).
  * 8 (round 6): eegldm_unet_cfg grows by num_head_channels, num_heads_upsample, use_scale_shift_norm, resample_layers, resample_pool_only
  *    (zero = the config_ldm.yaml behaviour); eegldm_resblock_create gains use_scale_shift_norm, eegldm_attnblock_create gains num_heads;
- *    + eegldm_ddim_step_eta, eegldm_ddpm_step_var, eegldm_unet_set_dropout, eegldm_dropout. */
+ *    + eegldm_ddim_step_eta, eegldm_ddpm_step_var, eegldm_unet_set_dropout, eegldm_dropout.
+ *    Added since without a version change (new symbols only): the class-conditional entry points, the weight EMA (eegldm_adam_step_ema,
+ *    eegldm_ema_update, eegldm_swap) and the multistep sampler (eegldm_multistep_step, eegldm_sample_multistep). */
 #define EEGLDM_ABI_VERSION 8
 
 /* Storage / operand type of activations and compute-copy weights (accumulation, statistics, master weights and optimizer state are
@@ -476,6 +478,28 @@ int eegldm_sample_cond(eegldm_unet*, eegldm_aekl* ae, const float* noise, const 
  * prev2 (nullable) receives a second copy of the result. */
 int eegldm_guided_step(eegldm_ctx*, const float* model_out, float guidance_scale, const float* sample, const float* noise, float a_t,
                        float a_prev, float beta_t, int ancestral, int pred_type, int clip_sample, float* prev, float* prev2, long n);
+
+/* Linear multistep sampling (DPM-Solver++ 2M, Lu et al. 2022; new symbols, ABI 8).  One step as ONE launch, solver-agnostic: everything the
+ * solver knows is in the three host-computed coefficients (schedulers.py multistep_coefficients).  Per element, in one pass:
+ *   o    = model_out                                   (guided != 0: model_out holds 2n values, the conditional outputs then the null-class
+ *                                                       outputs, and o = o_u + w (o_c - o_u) in fp32, as eegldm_guided_step forms it)
+ *   x0   = the data prediction from o, sample and a_t   (epsilon / v_prediction / sample, optional clamp to [-1, 1]: the arithmetic of
+ *                                                       eegldm_ddim_step)
+ *   prev = fma(cx, sample, fma(c0, x0, c1 * hist))      (c1 == 0: fma(cx, sample, c0 * x0), hist is not read)
+ *   hist = x0
+ * prev2 (a second copy of prev) and pred_x0 are nullable; hist may be NULL only when c1 == 0, and then nothing is read or written there;
+ * prev may be `sample` itself; no other two buffers may overlap.  First order (c1 = 0) with c0 = sqrt(a_prev) - cx sqrt(a_t),
+ * cx = sqrt((1 - a_prev) / (1 - a_t)) is the DDIM step. */
+int eegldm_multistep_step(eegldm_ctx*, const float* model_out, float guidance_scale, int guided, const float* sample, float* hist, float a_t,
+                          int pred_type, int clip_sample, float cx, float c0, float c1, float* prev, float* prev2, float* pred_x0, long n);
+/* The sampling loop of eegldm_sample / eegldm_sample_cond with eegldm_multistep_step as the step: cx_host / c0_host / c1_host (HOST arrays of
+ * n_steps entries) take the place of a_prev / beta_t, the history buffer belongs to the library, and c1_host[0] must be 0 (step 0 has no
+ * history).  labels_host NULL: an unconditional UNet; otherwise a class-conditional one with guidance as in eegldm_sample_cond.  Everything
+ * else -- embedding table, 2B-row guided forward, eager launches or graph replay, z * inv_scale_factor, decode -- is shared with them. */
+int eegldm_sample_multistep(eegldm_unet*, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
+                            const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int pred_type, int clip_sample,
+                            float inv_scale_factor, float* latents_out, float* windows_out, int B, int L, int use_graph, int* graph_used_host,
+                            const int64_t* labels_host, float guidance_scale, int64_t null_class);
 
 /* ------------------------------------------------------------------ data-parallel collectives (RCCL over xGMI)
  * One communicator per process / GPU.  Stands where the reference gathers gradients with single-process nn.DataParallel

@@ -142,6 +142,9 @@ SIGNATURES = {
     "eegldm_sample_cond": [_vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _f, C.c_uint64,
                            _vp, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_int64), _f, C.c_int64],
     "eegldm_guided_step": [_vp, _vp, _f, _vp, _vp, _f, _f, _f, _i, _i, _i, _vp, _vp, _l],
+    "eegldm_multistep_step": [_vp, _vp, _f, _i, _vp, _vp, _f, _i, _i, _f, _f, _f, _vp, _vp, _vp, _l],
+    "eegldm_sample_multistep": [_vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _f,
+                                _vp, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_int64), _f, C.c_int64],
     "eegldm_disc_create": [_vp, _vp, C.POINTER(_vp)],
     "eegldm_disc_destroy": [_vp],
     "eegldm_disc_num_entries": [_vp],

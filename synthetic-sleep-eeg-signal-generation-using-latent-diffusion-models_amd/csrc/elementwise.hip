@@ -515,6 +515,66 @@ __global__ __launch_bounds__(NT) void adam_ema_kernel(float* __restrict__ p, con
     e[i] = ema_elem(e[i], pi, c);
   }
 }
+// ------------------------------------------------------------------ linear multistep sampler step (DPM-Solver++ 2M; include/eegldm.h)
+// One launch per sampling step, whatever the solver: o = the model output (guided: o_u + w (o_c - o_u), the expression of cfg_step_kernel),
+// x0 from o by the prediction type with the arithmetic of ddim_step_kernel, prev = cx * sample + c0 * x0 + c1 * hist, hist <- x0.  The three
+// coefficients come from the host (schedulers.py multistep_coefficients).  The update is ONE function, contraction off and the fused
+// multiply-adds spelled out (as adam_elem / ema_elem), so the float4 body, the scalar edges and every caller round alike.
+__device__ __forceinline__ float multistep_x0(float o, float s, float sa, float sb, int pred, int clip) {
+  float x0;
+  if (pred == EEGLDM_PRED_EPSILON) x0 = (s - sb * o) / sa;
+  else if (pred == EEGLDM_PRED_V) x0 = sa * s - sb * o;
+  else x0 = o;
+  if (clip) x0 = clamp_keep_nan(x0, -1.0f, 1.0f);
+  return x0;
+}
+__device__ __forceinline__ float multistep_update(float s, float x0, float h, float cx, float c0, float c1) {
+#pragma clang fp contract(off)
+  const float m = c1 != 0.0f ? fmaf(c0, x0, c1 * h) : c0 * x0;      // c1 == 0 (first-order step): the history is not read
+  return fmaf(cx, s, m);
+}
+// mo: n values, or 2n when guided (conditional outputs, then null-class outputs).  prev may alias x (every element is read before it is
+// written, by the same thread); hist is NULL only with c1 == 0; prev2 / x0o are optional.
+__global__ __launch_bounds__(NT) void multistep_step_kernel(const float* __restrict__ mo, float w, int guided, const float* x, float* hist, float sa,
+                                                            float sb, int pred, int clip, float cx, float c0, float c1, float* prev, float* prev2,
+                                                            float* x0o, long n, long head) {
+  const VecSplit s = vec_split(n, head);
+  const f32x4* oc4 = (const f32x4*)(mo + head); const f32x4* ou4 = (const f32x4*)(mo + n + head); const f32x4* x4 = (const f32x4*)(x + head);
+  f32x4* h4 = (f32x4*)(hist + head); f32x4* p4 = (f32x4*)(prev + head); f32x4* q4 = (f32x4*)(prev2 + head); f32x4* z4 = (f32x4*)(x0o + head);
+  const bool two = c1 != 0.0f;
+  GRID_STRIDE(i, s.n4) {
+    f32x4 ov = oc4[i];
+    if (guided) {
+      const f32x4 uv = ou4[i];
+#pragma unroll
+      for (int k = 0; k < 4; k++) { const float ou = uv[k]; ov[k] = ou + w * (ov[k] - ou); }
+    }
+    const f32x4 xv = x4[i];
+    f32x4 hv = {0.0f, 0.0f, 0.0f, 0.0f}, pv, zv;
+    if (two) hv = h4[i];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      zv[k] = multistep_x0(ov[k], xv[k], sa, sb, pred, clip);
+      pv[k] = multistep_update(xv[k], zv[k], hv[k], cx, c0, c1);
+    }
+    p4[i] = pv;
+    if (prev2) q4[i] = pv;
+    if (hist) h4[i] = zv;
+    if (x0o) z4[i] = zv;
+  }
+  GRID_STRIDE(j, s.nedge) {
+    const long i = EDGE_INDEX(s, j);
+    float o = mo[i];
+    if (guided) { const float ou = mo[n + i]; o = ou + w * (o - ou); }
+    const float xs = x[i];
+    const float x0 = multistep_x0(o, xs, sa, sb, pred, clip);
+    const float m = multistep_update(xs, x0, two ? hist[i] : 0.0f, cx, c0, c1);
+    prev[i] = m;
+    if (prev2) prev2[i] = m;
+    if (hist) hist[i] = x0;
+    if (x0o) x0o[i] = x0;
+  }
+}
 __global__ __launch_bounds__(NT) void ema_update_kernel(float* __restrict__ e, const float* __restrict__ p, long n, long head, float c) {
   const VecSplit s = vec_split(n, head);
   f32x4* e4 = (f32x4*)(e + head); const f32x4* p4 = (const f32x4*)(p + head);
@@ -1106,6 +1166,35 @@ extern "C" int eegldm_ema_update(eegldm_ctx* ctx, float* ema, const float* p, lo
   if (n == 0) return 0;
   const long head = vec_head(n, {ema, p});
   hipLaunchKernelGGL(ema_update_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, ema, p, n, head, one_minus_decay);
+  LAUNCH_CHECK(); return 0;
+}
+// One linear multistep step as one launch (multistep_step_kernel).  The float4 body needs every buffer in use -- the null-class half of
+// model_out included -- at one offset inside a 16-byte line; otherwise the whole range goes one element at a time.
+extern "C" int eegldm_multistep_step(eegldm_ctx* ctx, const float* mo, float w, int guided, const float* x, float* hist, float a_t, int pred,
+                                     int clip, float cx, float c0, float c1, float* prev, float* prev2, float* x0, long n) {
+  EEG_CHECK(ctx && mo && x && prev, "null argument");
+  EEG_CHECK(n >= 0, "negative n (%ld)", n);
+  EEG_CHECK(pred >= 0 && pred <= 2, "prediction type %d", pred);
+  EEG_CHECK(a_t > 0.0f && a_t < 1.0f, "a_t %g outside (0, 1)", (double)a_t);
+  EEG_CHECK(!guided || w == w, "guidance_scale is NaN");
+  EEG_CHECK(cx == cx && c0 == c0 && c1 == c1, "a coefficient is NaN");
+  EEG_CHECK(hist || c1 == 0.0f, "c1 != 0 needs the history buffer");
+  const long nm = guided ? 2 * n : n;
+  // (a NULL buffer overlaps nothing; prev == sample is the one aliasing the kernel is written for)
+  auto ov = [](const float* p, long np, const float* q, long nq) { return p && q && p < q + nq && q < p + np; };
+  EEG_CHECK(!ov(mo, nm, prev, n) && !ov(mo, nm, prev2, n) && !ov(mo, nm, x0, n) && !ov(mo, nm, hist, n), "model_out aliases an output buffer");
+  EEG_CHECK(!ov(hist, n, x, n) && !ov(hist, n, prev, n) && !ov(hist, n, prev2, n) && !ov(hist, n, x0, n), "the history buffer aliases another buffer");
+  EEG_CHECK(!ov(prev2, n, prev, n) && !ov(prev2, n, x, n) && !ov(x0, n, prev, n) && !ov(x0, n, x, n) && !ov(x0, n, prev2, n),
+            "prev2 / pred_x0 alias another buffer");
+  EEG_CHECK(prev == x || !ov(prev, n, x, n), "prev may be sample itself, not a shifted view of it");
+  for (const void* q : {(const void*)mo, (const void*)x, (const void*)hist, (const void*)prev, (const void*)prev2, (const void*)x0})
+    EEG_CHECK(((uintptr_t)q & 3) == 0, "buffers must be 4-byte aligned");
+  if (n == 0) return 0;
+  long head = vec_head(n, {mo, x, prev});
+  for (const void* q : {(const void*)(guided ? mo + n : nullptr), (const void*)hist, (const void*)prev2, (const void*)x0})
+    if (q && head < n && ((uintptr_t)q & 15) != ((uintptr_t)mo & 15)) head = n;
+  hipLaunchKernelGGL(multistep_step_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, mo, w, guided ? 1 : 0, x, hist, sqrtf(a_t),
+                     sqrtf(1.0f - a_t), pred, clip, cx, c0, c1, prev, prev2, x0, n, head);
   LAUNCH_CHECK(); return 0;
 }
 extern "C" int eegldm_swap(eegldm_ctx* ctx, float* a, float* b, long n) {

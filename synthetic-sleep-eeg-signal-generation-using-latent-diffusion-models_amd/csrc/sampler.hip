@@ -21,6 +21,7 @@ struct GraphKey { const eegldm_unet* u; int B, L; bool operator<(const GraphKey&
 struct SamplerState {
   hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr;
   float *x = nullptr, *out = nullptr, *nz = nullptr; int64_t* tt = nullptr;
+  float* hist = nullptr;         // multistep solver: the previous step's data prediction, one value per latent (allocated on first use)
   hipStream_t stream = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;
   bool capture_failed = false;
   // embedding rows of all timesteps of a run (eager path): table [emb_cap][etot], scratch of the embedding MLP, timesteps on the device
@@ -53,6 +54,7 @@ void sampler_release(const eegldm_unet* u) {
     if (s.x) (void)hipFree(s.x);
     if (s.out) (void)hipFree(s.out);
     if (s.nz) (void)hipFree(s.nz);
+    if (s.hist) (void)hipFree(s.hist);
     if (s.tt) (void)hipFree(s.tt);
     if (s.emb_table) (void)hipFree(s.emb_table);
     if (s.emb_work) (void)hipFree(s.emb_work);
@@ -70,11 +72,15 @@ void sampler_release(const eegldm_unet* u) {
 
 // labels_host (class-conditional UNets; NULL otherwise): one class per sample.  guidance_scale != 1 runs every forward on 2B rows -- the B
 // samples with their labels, then the same latents with null_class -- and mixes the two outputs inside the scheduler step (cfg_step_kernel)
+// ms (eegldm_sample_multistep; NULL otherwise): the per-step coefficients of the linear multistep update, which then replaces the DDIM /
+// DDPM step -- one eegldm_multistep_step launch behind every forward; a_prev / beta_t / ancestral are not read
+struct MultistepCoef { const float *cx, *c0, *c1; };
 static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
                        const float* a_prev_host, const float* beta_t_host, int n_steps, int ancestral, int pred_type, int clip_sample,
                        float inv_scale_factor, uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
-                       int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
-  EEG_CHECK(u && noise && timesteps_host && a_t_host && a_prev_host, "null argument");
+                       int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class,
+                       const MultistepCoef* ms = nullptr) {
+  EEG_CHECK(u && noise && timesteps_host && a_t_host && (a_prev_host || ms), "null argument");
   EEG_CHECK(!ancestral || beta_t_host, "the ancestral (DDPM) step needs beta_t");
   EEG_CHECK(n_steps >= 1 && B >= 1 && L >= 1, "bad sizes");
   EEG_CHECK(latents_out || windows_out, "nothing to return: pass latents_out and/or windows_out");
@@ -105,6 +111,7 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
     HIP_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
   }
   if (cond && !s.lab) HIP_TRY(hipMalloc(&s.lab, sizeof(int64_t) * Bf));
+  if (ms && !s.hist) HIP_TRY(hipMalloc(&s.hist, sizeof(float) * nf));      // (nf: the state is shared like nz)
   // the whole loop runs on the sampler's own stream (a capture cannot start on the NULL stream the caller may have given the context):
   // it waits for the caller's stream first and the caller's stream waits for it at the end
   hipStream_t caller = ctx->stream;
@@ -217,6 +224,11 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
     else set_t(timesteps_host[i]);
     if (graph_ok) HIP_TRY(hipGraphLaunch(s.exec, run));
     else EEG_TRY(unet_forward_labels(u, s.x, s.tt, fwd_lab, s.out, Bf, L, 0));
+    if (ms) {
+      EEG_TRY(eegldm_multistep_step(ctx, s.out, guidance_scale, guided ? 1 : 0, s.x, s.hist, a_t_host[i], pred_type, clip_sample, ms->cx[i], ms->c0[i],
+                                    ms->c1[i], s.x, guided ? s.x + n : nullptr, nullptr, n));
+      continue;
+    }
     const bool last = a_prev_host[i] >= 1.0f;
     if (ancestral && !last) EEG_TRY(eegldm_randn(ctx, s.nz, n, noise_seed, (uint64_t)i * (uint64_t)((n + 3) / 4)));
     if (guided) {
@@ -264,4 +276,24 @@ extern "C" int eegldm_sample_cond(eegldm_unet* u, eegldm_aekl* ae, const float* 
   return sample_impl(u, ae, noise, timesteps_host, a_t_host, a_prev_host, beta_t_host, n_steps, ancestral, pred_type, clip_sample,
                      inv_scale_factor, noise_seed, latents_out, windows_out, B, L, use_graph, graph_used_host, labels_host, guidance_scale,
                      null_class);
+}
+
+// The same call with a linear multistep solver (DPM-Solver++ 2M, include/eegldm.h) in place of the DDIM / DDPM step.  labels_host NULL: an
+// unconditional UNet; non-NULL: a class-conditional one, guidance as in eegldm_sample_cond.
+extern "C" int eegldm_sample_multistep(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
+                                       const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int pred_type,
+                                       int clip_sample, float inv_scale_factor, float* latents_out, float* windows_out, int B, int L,
+                                       int use_graph, int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
+  EEG_CHECK(u && cx_host && c0_host && c1_host, "null argument");
+  EEG_CHECK(n_steps >= 1, "bad sizes");
+  EEG_CHECK(c1_host[0] == 0.0f, "step 0 has no history: c1[0] must be 0 (got %g)", (double)c1_host[0]);
+  if (labels_host) {
+    EEG_CHECK(unet_num_classes(u) > 0, "labels for a UNet built without classes");
+    EEG_CHECK(guidance_scale == guidance_scale, "guidance_scale is NaN");
+  } else {
+    EEG_CHECK(unet_num_classes(u) == 0, "this UNet is class-conditional: pass labels_host");
+  }
+  const MultistepCoef ms{cx_host, c0_host, c1_host};
+  return sample_impl(u, ae, noise, timesteps_host, a_t_host, nullptr, nullptr, n_steps, 0, pred_type, clip_sample, inv_scale_factor, 0,
+                     latents_out, windows_out, B, L, use_graph, graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class, &ms);
 }

@@ -8,7 +8,7 @@ import os
 import torch
 
 from ._lib import lib, check, ptr, PRED
-from .schedulers import DDIMScheduler
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler
 from .training import randn
 
 
@@ -29,6 +29,12 @@ def _step_tables(scheduler):
     a_prev = [float(acp[p]) if p >= 0 else float(final) for p in prev]
     beta = [float(scheduler.betas[t]) for t in ts]
     return ts, a_t, a_prev, beta, ancestral
+
+
+def _multistep_tables(scheduler):
+    """Host-side arrays for eegldm_sample_multistep: (timesteps, a_t, cx, c0, c1), the coefficients as set_timesteps computed them."""
+    ts = [int(t) for t in scheduler.timesteps]
+    return ts, [float(scheduler.alphas_cumprod[t]) for t in ts], list(scheduler.cx), list(scheduler.c0), list(scheduler.c1)
 
 
 def _labels_host(unet, labels, B, guidance_scale, null_class):
@@ -64,8 +70,9 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     MI355X (rounds 2 and 3) the replay is SLOWER than the eager launches at the reference's batch of one window per call
     (sample_trials.py:149-163: 92.6 vs 87 ms per 50-step window -- ROCm's graph launch does not shorten the ~5 us per
     dependent kernel) and indistinguishable at batch 256, where launch overhead does not matter.
-    `scheduler` may be a DDIMScheduler (eta 0) or a DDPMScheduler (ancestral steps; noise from the device Philox
-    stream `seed`).  info (optional dict) receives {"graph": bool}.
+    `scheduler` may be a DDIMScheduler (eta 0), a DDPMScheduler (ancestral steps; noise from the device Philox
+    stream `seed`) or a DPMSolverMultistepScheduler (DPM-Solver++ 2M through eegldm_sample_multistep: the same loop with one
+    eegldm_multistep_step launch behind every forward).  info (optional dict) receives {"graph": bool}.
     A UNet built with num_classes needs `labels` (one class per sample, or one for all).  guidance_scale w != 1 is classifier-free
     guidance: out = out(null_class) + w (out(labels) - out(null_class)) on the raw model output, every forward on 2B rows."""
     unet.eval()
@@ -74,7 +81,11 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     if Cc != unet.in_channels:
         raise ValueError(f"noise has {Cc} channels, the UNet takes {unet.in_channels}")
     lab, nc = _labels_host(unet, labels, B, guidance_scale, null_class)
-    ts, a_t, a_prev, beta, ancestral = _step_tables(scheduler)
+    multistep = isinstance(scheduler, DPMSolverMultistepScheduler)
+    if multistep:
+        ts, a_t, cx, c0, c1 = _multistep_tables(scheduler)
+    else:
+        ts, a_t, a_prev, beta, ancestral = _step_tables(scheduler)
     n = len(ts)
     if use_graph is None:
         use_graph = os.environ.get("EEGLDM_SAMPLE_GRAPH", "0") == "1" and os.environ.get("EEGLDM_NO_GRAPH") is None
@@ -85,19 +96,29 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     if B == 0:
         return (win[:, :, crop:-crop] if crop else win), lat
     used = C.c_int(0)
-    args = (unet.h, autoencoder.h if autoencoder is not None else None, ptr(x), (C.c_int64 * n)(*ts), (C.c_float * n)(*a_t),
-            (C.c_float * n)(*a_prev), (C.c_float * n)(*beta), n, 1 if ancestral else 0, PRED[scheduler.prediction_type],
-            int(scheduler.clip_sample), 1.0 / float(scale_factor), int(seed), ptr(lat), ptr(win), B, L, 1 if use_graph else 0, C.byref(used))
-    if lab is None:
-        check(lib.eegldm_sample(*args))
+    ae_h = autoencoder.h if autoencoder is not None else None
+    i64, f32 = (lambda v: (C.c_int64 * len(v))(*v)), (lambda v: (C.c_float * len(v))(*v))
+    tail = (ptr(lat), ptr(win), B, L, 1 if use_graph else 0, C.byref(used))
+    if multistep:
+        check(lib.eegldm_sample_multistep(unet.h, ae_h, ptr(x), i64(ts), f32(a_t), f32(cx), f32(c0), f32(c1), n, PRED[scheduler.prediction_type],
+                                          int(scheduler.clip_sample), 1.0 / float(scale_factor), *tail, None if lab is None else i64(lab),
+                                          float(guidance_scale), nc))
     else:
-        check(lib.eegldm_sample_cond(*args, (C.c_int64 * B)(*lab), float(guidance_scale), nc))
+        args = (unet.h, ae_h, ptr(x), i64(ts), f32(a_t), f32(a_prev), f32(beta), n, 1 if ancestral else 0, PRED[scheduler.prediction_type],
+                int(scheduler.clip_sample), 1.0 / float(scale_factor), int(seed), *tail)
+        if lab is None:
+            check(lib.eegldm_sample(*args))
+        else:
+            check(lib.eegldm_sample_cond(*args, i64(lab), float(guidance_scale), nc))
     unet._bump_tape()
     if autoencoder is not None:
         autoencoder._bump_tape()
     if info is not None:
         info["graph"] = bool(used.value)
     return (win[:, :, crop:-crop] if crop else win), lat
+
+
+sample = ddim_sample      # the neutral name: the sampler is whatever `scheduler` is
 
 
 @torch.no_grad()
@@ -131,9 +152,18 @@ def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, 
     return (sample[:, :, crop:-crop] if crop else sample), x
 
 
-def make_sampling_scheduler(num_inference_steps=50, prediction_type="epsilon", beta_start=0.0015, beta_end=0.0205, device=0):
+def make_sampling_scheduler(num_inference_steps=50, prediction_type="epsilon", beta_start=0.0015, beta_end=0.0205, device=0, sampler="ddim",
+                            solver_order=2):
     """DDIMScheduler as built at sample_trials.py:136-145 (scaled-linear betas, clip_sample=False).  The reference
-    script passes prediction_type="v_prediction" while training with epsilon: it is a parameter here."""
+    script passes prediction_type="v_prediction" while training with epsilon: it is a parameter here.
+    sampler="dpmpp_2m": DPMSolverMultistepScheduler on the same schedule (linspace grid, solver_order 2 unless given)."""
+    if sampler == "dpmpp_2m":
+        s = DPMSolverMultistepScheduler(num_train_timesteps=1000, schedule="scaled_linear_beta", beta_start=beta_start, beta_end=beta_end,
+                                        prediction_type=prediction_type, clip_sample=False, solver_order=solver_order, device=device)
+        s.set_timesteps(num_inference_steps)
+        return s
+    if sampler != "ddim":
+        raise ValueError('sampler must be "ddim" or "dpmpp_2m"')
     s = DDIMScheduler(num_train_timesteps=1000, schedule="scaled_linear_beta", beta_start=beta_start, beta_end=beta_end,
                       prediction_type=prediction_type, clip_sample=False, device=device)
     s.set_timesteps(num_inference_steps)
