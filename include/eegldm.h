@@ -44,7 +44,8 @@ extern "C" {
  *    (zero = the config_ldm.yaml behaviour); eegldm_resblock_create gains use_scale_shift_norm, eegldm_attnblock_create gains num_heads;
  *    + eegldm_ddim_step_eta, eegldm_ddpm_step_var, eegldm_unet_set_dropout, eegldm_dropout.
  *    Added since without a version change (new symbols only): the class-conditional entry points, the weight EMA (eegldm_adam_step_ema,
- *    eegldm_ema_update, eegldm_swap) and the multistep sampler (eegldm_multistep_step, eegldm_sample_multistep). */
+ *    eegldm_ema_update, eegldm_swap), the multistep sampler (eegldm_multistep_step, eegldm_sample_multistep) and editing (eegldm_edit_step,
+ *    eegldm_edit_start, eegldm_edit_window, eegldm_sample_edit). */
 #define EEGLDM_ABI_VERSION 8
 
 /* Storage / operand type of activations and compute-copy weights (accumulation, statistics, master weights and optimizer state are
@@ -500,6 +501,44 @@ int eegldm_sample_multistep(eegldm_unet*, eegldm_aekl* ae, const float* noise, c
                             const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int pred_type, int clip_sample,
                             float inv_scale_factor, float* latents_out, float* windows_out, int B, int L, int use_graph, int* graph_used_host,
                             const int64_t* labels_host, float guidance_scale, int64_t null_class);
+
+/* Editing: sampling that starts from an input (SDEdit) and keeps a masked region of it (inpainting); new symbols, ABI 8.
+ * `known` is the clean signal z0 in the sampler's space, `noise` the caller's ONE noise tensor (used for the start and for every
+ * re-noising; nothing is drawn), `mask` in [0, 1] per element, 1 = keep.  With k(a) = fma(sqrt(a), z0, sqrt(1 - a) * noise) (a == 1: z0):
+ *   start   x = k(a_t of the first executed step)
+ *   blend   after a step has produced x' at the noise level a_next:  x' <- mask == 0 ? x' : mask == 1 ? k(a_next)
+ *                                                                           : fma(mask, k(a_next), (1 - mask) * x')
+ * so an all-zero mask leaves the step's bytes and an all-one mask returns k(a_next) bit for bit.
+ *
+ * eegldm_edit_step: one sampling step and the blend in ONE launch.  coef_host == NULL: the DDIM (eta 0) step of eegldm_ddim_step /
+ * eegldm_guided_step onto a_prev = a_next; coef_host = HOST {cx, c0, c1}: the step of eegldm_multistep_step (a_next then only sets the
+ * blend's noise level).  guided / guidance_scale / hist / prev2 / pred_x0 and the aliasing rules are eegldm_multistep_step's (hist is
+ * optional in the DDIM form); hist and pred_x0 receive the model's own data prediction, not a blended one.  mask == NULL: no blend,
+ * known / noise are not read and the result is eegldm_ddim_step's / eegldm_multistep_step's, bit for bit (the guided DDIM form agrees
+ * with eegldm_guided_step to rounding: that kernel shares its update with the ancestral step and is contracted differently).
+ * known / noise / mask may not overlap an output. */
+int eegldm_edit_step(eegldm_ctx*, const float* model_out, float guidance_scale, int guided, const float* sample, float* hist, float a_t,
+                     float a_next, int pred_type, int clip_sample, const float* coef_host, const float* known, const float* noise,
+                     const float* mask, float* prev, float* prev2, float* pred_x0, long n);
+/* z0 (nullable) = scale_factor * z_mu and x_start (nullable) = k(a_start) of that z0, one launch; noise / a_start are read only for x_start. */
+int eegldm_edit_start(eegldm_ctx*, const float* z_mu, float scale_factor, const float* noise, float a_start, float* z0, float* x_start, long n);
+/* The window side.  mask_win (B, 1, Lw).  mask_lat (nullable; (B, C, Lw / down)): every channel's row is the min over the `down` window
+ * samples a latent position covers -- a position is kept only if all of them are.  out (nullable; (B, Co, Lw), may be `decoded` itself):
+ * the composite mask_win * input + (1 - mask_win) * decoded with the blend's exactness at 0 and 1 (kept samples are the input's bytes). */
+int eegldm_edit_window(eegldm_ctx*, const float* mask_win, int B, int Lw, int down, int C, float* mask_lat, const float* input,
+                       const float* decoded, int Co, float* out);
+/* The sampling loop of eegldm_sample_cond / eegldm_sample_multistep (deterministic steps only) with the edit block: timesteps_host /
+ * a_t_host / ... hold the n_steps EXECUTED steps (the tail of the scheduler's grid).  cx_host == NULL: DDIM with a_prev_host; otherwise the
+ * multistep form with cx_host / c0_host / c1_host (c1_host[0] == 0: the first executed step has no history) and a_next_host, the noise
+ * level each step lands on.  known == NULL: x starts from `noise` (plain sampling); else x = k(a_t_host[0]).
+ * With `known` every step is one eegldm_edit_step launch; mask (nullable, needs known): the blend runs inside it, and the null-class
+ * half of a guided run receives the blended latents.  labels_host NULL: an unconditional UNet.  known / noise / mask are device buffers of B * C * L floats that stay valid and
+ * unwritten during the call. */
+int eegldm_sample_edit(eegldm_unet*, eegldm_aekl* ae, const float* noise, const float* known, const float* mask, const int64_t* timesteps_host,
+                       const float* a_t_host, const float* a_prev_host, const float* cx_host, const float* c0_host, const float* c1_host,
+                       const float* a_next_host, int n_steps, int pred_type, int clip_sample, float inv_scale_factor, float* latents_out,
+                       float* windows_out, int B, int L, int use_graph, int* graph_used_host, const int64_t* labels_host, float guidance_scale,
+                       int64_t null_class);
 
 /* ------------------------------------------------------------------ data-parallel collectives (RCCL over xGMI)
  * One communicator per process / GPU.  Stands where the reference gathers gradients with single-process nn.DataParallel

@@ -145,6 +145,11 @@ SIGNATURES = {
     "eegldm_multistep_step": [_vp, _vp, _f, _i, _vp, _vp, _f, _i, _i, _f, _f, _f, _vp, _vp, _vp, _l],
     "eegldm_sample_multistep": [_vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _f,
                                 _vp, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_int64), _f, C.c_int64],
+    "eegldm_edit_step": [_vp, _vp, _f, _i, _vp, _vp, _f, _f, _i, _i, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _l],
+    "eegldm_edit_start": [_vp, _vp, _f, _vp, _f, _vp, _vp, _l],
+    "eegldm_edit_window": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp],
+    "eegldm_sample_edit": [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f),
+                           C.POINTER(_f), _i, _i, _i, _f, _vp, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_int64), _f, C.c_int64],
     "eegldm_disc_create": [_vp, _vp, C.POINTER(_vp)],
     "eegldm_disc_destroy": [_vp],
     "eegldm_disc_num_entries": [_vp],

@@ -575,6 +575,139 @@ __global__ __launch_bounds__(NT) void multistep_step_kernel(const float* __restr
     if (x0o) x0o[i] = x0;
   }
 }
+// ------------------------------------------------------------------ editing: sampling from an input, with a keep-mask (include/eegldm.h)
+// k = the known clean signal z0 noised to the level a (ka = sqrt(a), kb = sqrt(1 - a)) with the caller's noise; kb == 0 (a == 1) is z0
+// itself.  ONE function for the start kernel and for the blend inside the step, contraction off, so that both round alike.
+__device__ __forceinline__ float edit_renoise(float z0, float nz, float ka, float kb) {
+#pragma clang fp contract(off)
+  return kb != 0.0f ? fmaf(ka, z0, kb * nz) : ka * z0;
+}
+// m k + (1 - m) p.  m == 0 is p and m == 1 is k, bit for bit, whatever the other operand holds.
+__device__ __forceinline__ float edit_blend(float m, float k, float p) {
+#pragma clang fp contract(off)
+  if (m == 0.0f) return p;
+  if (m == 1.0f) return k;
+  return fmaf(m, k, (1.0f - m) * p);
+}
+// the DDIM (eta 0) update with the expressions of ddim_step_kernel / cfg_step_kernel (the compiler's own contraction, as there): the same bytes
+__device__ __forceinline__ float edit_ddim_update(float o, float s, float sa, float sb, float sap, float sbp, int pred, int clip, float& x0o) {
+  float x0, e;
+  if (pred == EEGLDM_PRED_EPSILON) { x0 = (s - sb * o) / sa; e = o; }
+  else if (pred == EEGLDM_PRED_V) { x0 = sa * s - sb * o; e = sa * o + sb * s; }
+  else { x0 = o; e = (s - sa * x0) / sb; }
+  if (clip) x0 = clamp_keep_nan(x0, -1.0f, 1.0f);
+  x0o = x0;
+  return sap * x0 + sbp * e;
+}
+// One sampling step plus the blend, one pass: the DDIM form (multistep == 0: p0 = sqrt(a_prev), p1 = sqrt(1 - a_prev)) or the multistep
+// form (p0, p1, p2 = cx, c0, c1), each plain or guided, then prev = blend(mask, renoise(known, noise), prev).  mask == NULL: no blend, and
+// known / noise are not read.  The history and pred_x0 receive the model's own x0.  prev may alias x, as in multistep_step_kernel.
+__global__ __launch_bounds__(NT) void edit_step_kernel(const float* __restrict__ mo, float w, int guided, const float* x, float* hist, float sa,
+                                                       float sb, int pred, int clip, int multistep, float p0, float p1, float p2,
+                                                       const float* __restrict__ known, const float* __restrict__ noise,
+                                                       const float* __restrict__ mask, float ka, float kb, float* prev, float* prev2,
+                                                       float* x0o, long n, long head) {
+  const VecSplit s = vec_split(n, head);
+  const f32x4* oc4 = (const f32x4*)(mo + head); const f32x4* ou4 = (const f32x4*)(mo + n + head); const f32x4* x4 = (const f32x4*)(x + head);
+  const f32x4* k4 = (const f32x4*)(known + head); const f32x4* n4 = (const f32x4*)(noise + head); const f32x4* m4 = (const f32x4*)(mask + head);
+  f32x4* h4 = (f32x4*)(hist + head); f32x4* q1 = (f32x4*)(prev + head); f32x4* q2 = (f32x4*)(prev2 + head); f32x4* z4 = (f32x4*)(x0o + head);
+  const bool two = multistep && p2 != 0.0f;
+  GRID_STRIDE(i, s.n4) {
+    f32x4 ov = oc4[i];
+    if (guided) {
+      const f32x4 uv = ou4[i];
+#pragma unroll
+      for (int k = 0; k < 4; k++) { const float ou = uv[k]; ov[k] = ou + w * (ov[k] - ou); }
+    }
+    const f32x4 xv = x4[i];
+    f32x4 hv = {0.0f, 0.0f, 0.0f, 0.0f}, pv, zv;
+    if (two) hv = h4[i];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      if (multistep) {
+        zv[k] = multistep_x0(ov[k], xv[k], sa, sb, pred, clip);
+        pv[k] = multistep_update(xv[k], zv[k], hv[k], p0, p1, p2);
+      } else {
+        float z;
+        pv[k] = edit_ddim_update(ov[k], xv[k], sa, sb, p0, p1, pred, clip, z);
+        zv[k] = z;
+      }
+    }
+    if (mask) {
+      const f32x4 kv = k4[i], nv = n4[i], mv = m4[i];
+#pragma unroll
+      for (int k = 0; k < 4; k++) pv[k] = edit_blend(mv[k], edit_renoise(kv[k], nv[k], ka, kb), pv[k]);
+    }
+    q1[i] = pv;
+    if (prev2) q2[i] = pv;
+    if (hist) h4[i] = zv;
+    if (x0o) z4[i] = zv;
+  }
+  GRID_STRIDE(j, s.nedge) {
+    const long i = EDGE_INDEX(s, j);
+    float o = mo[i];
+    if (guided) { const float ou = mo[n + i]; o = ou + w * (o - ou); }
+    const float xs = x[i];
+    float x0, m;
+    if (multistep) {
+      x0 = multistep_x0(o, xs, sa, sb, pred, clip);
+      m = multistep_update(xs, x0, two ? hist[i] : 0.0f, p0, p1, p2);
+    } else {
+      m = edit_ddim_update(o, xs, sa, sb, p0, p1, pred, clip, x0);
+    }
+    if (mask) m = edit_blend(mask[i], edit_renoise(known[i], noise[i], ka, kb), m);
+    prev[i] = m;
+    if (prev2) prev2[i] = m;
+    if (hist) hist[i] = x0;
+    if (x0o) x0o[i] = x0;
+  }
+}
+// The start of an edit run: z0 = sf * z_mu (sf == 1: z_mu itself) and x = renoise(z0, noise) at the first executed step's noise level;
+// either output may be left out.
+__global__ __launch_bounds__(NT) void edit_start_kernel(const float* __restrict__ zmu, float sf, const float* __restrict__ noise, float ka, float kb,
+                                                        float* __restrict__ z0o, float* __restrict__ xo, long n, long head) {
+  const VecSplit s = vec_split(n, head);
+  const f32x4* z4 = (const f32x4*)(zmu + head); const f32x4* n4 = (const f32x4*)(noise + head);
+  f32x4* o4 = (f32x4*)(z0o + head); f32x4* x4 = (f32x4*)(xo + head);
+  GRID_STRIDE(i, s.n4) {
+    f32x4 zv = z4[i];
+#pragma unroll
+    for (int k = 0; k < 4; k++) zv[k] = sf * zv[k];
+    if (z0o) o4[i] = zv;
+    if (xo) {
+      const f32x4 nv = n4[i];
+      f32x4 xv;
+#pragma unroll
+      for (int k = 0; k < 4; k++) xv[k] = edit_renoise(zv[k], nv[k], ka, kb);
+      x4[i] = xv;
+    }
+  }
+  GRID_STRIDE(j, s.nedge) {
+    const long i = EDGE_INDEX(s, j);
+    const float z = sf * zmu[i];
+    if (z0o) z0o[i] = z;
+    if (xo) xo[i] = edit_renoise(z, noise[i], ka, kb);
+  }
+}
+// Window side of an edit: (1) the keep-mask at the sampler's resolution, mask_lat[b][c][l] = min over the `down` window samples latent
+// position l covers (every one of the C channels receives the same row); (2) the composite out = blend(mask_win, input, decoded) over
+// Co channels.  Either half may be left out (mask_lat / out NULL).  One-off work of a sampling call: scalar accesses, any alignment.
+__global__ __launch_bounds__(NT) void edit_window_kernel(const float* __restrict__ mask_win, long n_lat, long n_win, int Lw, int down, int C,
+                                                         float* __restrict__ mask_lat, const float* __restrict__ input, const float* decoded,
+                                                         int Co, float* out) {
+  const int Ll = Lw / down;
+  GRID_STRIDE(i, n_lat) {
+    const long b = i / ((long)C * Ll); const int l = (int)(i % Ll);
+    const float* row = mask_win + b * Lw + (long)l * down;
+    float m = row[0];
+    for (int d = 1; d < down; d++) m = fminf(m, row[d]);
+    mask_lat[i] = m;
+  }
+  GRID_STRIDE(i, n_win) {
+    const long b = i / ((long)Co * Lw); const int t = (int)(i % Lw);
+    out[i] = edit_blend(mask_win[b * Lw + t], input[i], decoded[i]);
+  }
+}
 __global__ __launch_bounds__(NT) void ema_update_kernel(float* __restrict__ e, const float* __restrict__ p, long n, long head, float c) {
   const VecSplit s = vec_split(n, head);
   f32x4* e4 = (f32x4*)(e + head); const f32x4* p4 = (const f32x4*)(p + head);
@@ -1195,6 +1328,88 @@ extern "C" int eegldm_multistep_step(eegldm_ctx* ctx, const float* mo, float w, 
     if (q && head < n && ((uintptr_t)q & 15) != ((uintptr_t)mo & 15)) head = n;
   hipLaunchKernelGGL(multistep_step_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, mo, w, guided ? 1 : 0, x, hist, sqrtf(a_t),
                      sqrtf(1.0f - a_t), pred, clip, cx, c0, c1, prev, prev2, x0, n, head);
+  LAUNCH_CHECK(); return 0;
+}
+// ---- editing (include/eegldm.h): the step with the blend, the start of a run, the window-side mask pooling and composite
+// coef_host NULL: the DDIM form, a_next is its a_prev; else {cx, c0, c1} of the multistep form and a_next only sets the blend's noise level.
+extern "C" int eegldm_edit_step(eegldm_ctx* ctx, const float* mo, float w, int guided, const float* x, float* hist, float a_t, float a_next,
+                                int pred, int clip, const float* coef_host, const float* known, const float* noise, const float* mask,
+                                float* prev, float* prev2, float* x0, long n) {
+  EEG_CHECK(ctx && mo && x && prev, "null argument");
+  EEG_CHECK(n >= 0, "negative n (%ld)", n);
+  EEG_CHECK(pred >= 0 && pred <= 2, "prediction type %d", pred);
+  EEG_CHECK(a_t > 0.0f && a_t < 1.0f, "a_t %g outside (0, 1)", (double)a_t);
+  EEG_CHECK(a_next > 0.0f && a_next <= 1.0f, "a_next %g outside (0, 1]", (double)a_next);
+  EEG_CHECK(!guided || w == w, "guidance_scale is NaN");
+  EEG_CHECK(!mask || (known && noise), "a mask needs the known signal and the noise");
+  const bool ms = coef_host != nullptr;
+  float p0, p1, p2 = 0.0f;
+  if (ms) {
+    p0 = coef_host[0]; p1 = coef_host[1]; p2 = coef_host[2];
+    EEG_CHECK(p0 == p0 && p1 == p1 && p2 == p2, "a coefficient is NaN");
+    EEG_CHECK(hist || p2 == 0.0f, "c1 != 0 needs the history buffer");
+  } else {
+    p0 = sqrtf(a_next); p1 = sqrtf(1.0f - a_next);      // as eegldm_ddim_step / eegldm_guided_step derive them
+  }
+  const long nm = guided ? 2 * n : n;
+  auto ov = [](const float* p, long np, const float* q, long nq) { return p && q && p < q + nq && q < p + np; };
+  EEG_CHECK(!ov(mo, nm, prev, n) && !ov(mo, nm, prev2, n) && !ov(mo, nm, x0, n) && !ov(mo, nm, hist, n), "model_out aliases an output buffer");
+  EEG_CHECK(!ov(hist, n, x, n) && !ov(hist, n, prev, n) && !ov(hist, n, prev2, n) && !ov(hist, n, x0, n), "the history buffer aliases another buffer");
+  EEG_CHECK(!ov(prev2, n, prev, n) && !ov(prev2, n, x, n) && !ov(x0, n, prev, n) && !ov(x0, n, x, n) && !ov(x0, n, prev2, n),
+            "prev2 / pred_x0 alias another buffer");
+  EEG_CHECK(prev == x || !ov(prev, n, x, n), "prev may be sample itself, not a shifted view of it");
+  if (mask)
+    for (const float* q : {known, noise, mask})
+      EEG_CHECK(!ov(q, n, prev, n) && !ov(q, n, prev2, n) && !ov(q, n, x0, n) && !ov(q, n, hist, n), "known / noise / mask alias an output buffer");
+  for (const void* q : {(const void*)mo, (const void*)x, (const void*)hist, (const void*)prev, (const void*)prev2, (const void*)x0,
+                        (const void*)known, (const void*)noise, (const void*)mask})
+    EEG_CHECK(((uintptr_t)q & 3) == 0, "buffers must be 4-byte aligned");
+  if (n == 0) return 0;
+  long head = vec_head(n, {mo, x, prev});
+  for (const void* q : {(const void*)(guided ? mo + n : nullptr), (const void*)hist, (const void*)prev2, (const void*)x0,
+                        (const void*)(mask ? known : nullptr), (const void*)(mask ? noise : nullptr), (const void*)mask})
+    if (q && head < n && ((uintptr_t)q & 15) != ((uintptr_t)mo & 15)) head = n;
+  hipLaunchKernelGGL(edit_step_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, mo, w, guided ? 1 : 0, x, hist, sqrtf(a_t),
+                     sqrtf(1.0f - a_t), pred, clip, ms ? 1 : 0, p0, p1, p2, known, noise, mask, sqrtf(a_next), sqrtf(1.0f - a_next), prev, prev2,
+                     x0, n, head);
+  LAUNCH_CHECK(); return 0;
+}
+extern "C" int eegldm_edit_start(eegldm_ctx* ctx, const float* z_mu, float scale_factor, const float* noise, float a_start, float* z0,
+                                 float* x_start, long n) {
+  EEG_CHECK(ctx && z_mu && (z0 || x_start), "null argument");
+  EEG_CHECK(n >= 0, "negative n (%ld)", n);
+  EEG_CHECK(scale_factor == scale_factor, "scale_factor is NaN");
+  EEG_CHECK(!x_start || noise, "the noised start needs the noise");
+  EEG_CHECK(!x_start || (a_start > 0.0f && a_start <= 1.0f), "a_start %g outside (0, 1]", (double)a_start);
+  auto ov = [](const float* p, const float* q, long n) { return p && q && p < q + n && q < p + n; };
+  EEG_CHECK(!ov(z0, z_mu, n) && !ov(z0, noise, n) && !ov(x_start, z_mu, n) && !ov(x_start, noise, n) && !ov(z0, x_start, n), "an output aliases another buffer");
+  for (const void* q : {(const void*)z_mu, (const void*)noise, (const void*)z0, (const void*)x_start})
+    EEG_CHECK(((uintptr_t)q & 3) == 0, "buffers must be 4-byte aligned");
+  if (n == 0) return 0;
+  long head = vec_head(n, {z_mu});
+  for (const void* q : {(const void*)(x_start ? noise : nullptr), (const void*)z0, (const void*)x_start})
+    if (q && head < n && ((uintptr_t)q & 15) != ((uintptr_t)z_mu & 15)) head = n;
+  const float a = x_start ? a_start : 1.0f;
+  hipLaunchKernelGGL(edit_start_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, z_mu, scale_factor, noise, sqrtf(a), sqrtf(1.0f - a),
+                     z0, x_start, n, head);
+  LAUNCH_CHECK(); return 0;
+}
+extern "C" int eegldm_edit_window(eegldm_ctx* ctx, const float* mask_win, int B, int Lw, int down, int C, float* mask_lat, const float* input,
+                                  const float* decoded, int Co, float* out) {
+  EEG_CHECK(ctx && mask_win && (mask_lat || out), "null argument");
+  EEG_CHECK(B >= 0 && Lw >= 1 && down >= 1 && Lw % down == 0, "bad sizes (B %d, Lw %d, down %d)", B, Lw, down);
+  EEG_CHECK(!mask_lat || C >= 1, "bad channel count %d", C);
+  EEG_CHECK(!out || (input && decoded && Co >= 1), "the composite needs input, decoded and Co >= 1");
+  const long n_lat = mask_lat ? (long)B * C * (Lw / down) : 0, n_win = out ? (long)B * Co * Lw : 0, nm = (long)B * Lw;
+  auto ov = [](const float* p, long np, const float* q, long nq) { return p && q && p < q + nq && q < p + np; };
+  EEG_CHECK(!ov(mask_lat, n_lat, mask_win, nm) && !ov(mask_lat, n_lat, input, n_win) && !ov(mask_lat, n_lat, decoded, n_win) &&
+            !ov(mask_lat, n_lat, out, n_win) && !ov(out, n_win, mask_win, nm) && !ov(out, n_win, input, n_win), "an output aliases another buffer");
+  EEG_CHECK(out == decoded || !ov(out, n_win, decoded, n_win), "out may be decoded itself, not a shifted view of it");
+  for (const void* q : {(const void*)mask_win, (const void*)mask_lat, (const void*)input, (const void*)decoded, (const void*)out})
+    EEG_CHECK(((uintptr_t)q & 3) == 0, "buffers must be 4-byte aligned");
+  if (n_lat + n_win == 0) return 0;
+  hipLaunchKernelGGL(edit_window_kernel, dim3(grid1d(n_lat > n_win ? n_lat : n_win, ctx)), dim3(NT), 0, ctx->stream, mask_win, n_lat, n_win, Lw, down,
+                     C, mask_lat, input, decoded, Co, out);
   LAUNCH_CHECK(); return 0;
 }
 extern "C" int eegldm_swap(eegldm_ctx* ctx, float* a, float* b, long n) {

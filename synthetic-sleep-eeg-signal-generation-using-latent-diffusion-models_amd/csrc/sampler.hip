@@ -75,15 +75,21 @@ void sampler_release(const eegldm_unet* u) {
 // ms (eegldm_sample_multistep; NULL otherwise): the per-step coefficients of the linear multistep update, which then replaces the DDIM /
 // DDPM step -- one eegldm_multistep_step launch behind every forward; a_prev / beta_t / ancestral are not read
 struct MultistepCoef { const float *cx, *c0, *c1; };
+// ed (eegldm_sample_edit; NULL otherwise): x starts from `known` noised to a_t[0] with `noise` instead of from `noise`; with a mask, every
+// step is one eegldm_edit_step launch -- the same step plus the blend towards `known` noised to the level the step lands on (a_prev, or
+// a_next[i] in the multistep form); mask NULL: the same launch without the blend.
+struct EditBlock { const float *known, *mask, *a_next; };
 static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
                        const float* a_prev_host, const float* beta_t_host, int n_steps, int ancestral, int pred_type, int clip_sample,
                        float inv_scale_factor, uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
                        int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class,
-                       const MultistepCoef* ms = nullptr) {
+                       const MultistepCoef* ms = nullptr, const EditBlock* ed = nullptr) {
   EEG_CHECK(u && noise && timesteps_host && a_t_host && (a_prev_host || ms), "null argument");
   EEG_CHECK(!ancestral || beta_t_host, "the ancestral (DDPM) step needs beta_t");
   EEG_CHECK(n_steps >= 1 && B >= 1 && L >= 1, "bad sizes");
   EEG_CHECK(latents_out || windows_out, "nothing to return: pass latents_out and/or windows_out");
+  EEG_CHECK(!ed || (ed->known && !ancestral), "editing needs the known signal and a deterministic step");
+  EEG_CHECK(!ed || !ms || ed->a_next, "the multistep form needs a_next");
   eegldm_ctx* ctx = unet_ctx(u);
   const int C = unet_in_channels(u);
   EEG_CHECK(unet_out_channels(u) == C, "sampling needs in_channels == out_channels");
@@ -126,8 +132,9 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
     HIP_TRY(hipStreamWaitEvent(s.stream, s.ev_in, 0));
   }
   ctx->stream = run;
-  HIP_TRY(hipMemcpyAsync(s.x, noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
-  if (guided) HIP_TRY(hipMemcpyAsync(s.x + n, noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));     // the null-class half: same latents
+  if (ed) EEG_TRY(eegldm_edit_start(ctx, ed->known, 1.0f, noise, a_t_host[0], nullptr, s.x, n));
+  else HIP_TRY(hipMemcpyAsync(s.x, noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
+  if (guided) HIP_TRY(hipMemcpyAsync(s.x + n, ed ? s.x : noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));     // the null-class half: same latents
   if (cond) {
     HIP_TRY(hipStreamSynchronize(run));             // (the host arrays below are rewritten: an earlier call's copies from them must be done)
     s.lab_host.assign(labels_host, labels_host + B);
@@ -224,6 +231,12 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
     else set_t(timesteps_host[i]);
     if (graph_ok) HIP_TRY(hipGraphLaunch(s.exec, run));
     else EEG_TRY(unet_forward_labels(u, s.x, s.tt, fwd_lab, s.out, Bf, L, 0));
+    if (ed) {      // (without a mask too: an all-zero mask and no mask are then the same bytes in every form)
+      const float coef[3] = {ms ? ms->cx[i] : 0.0f, ms ? ms->c0[i] : 0.0f, ms ? ms->c1[i] : 0.0f};
+      EEG_TRY(eegldm_edit_step(ctx, s.out, guidance_scale, guided ? 1 : 0, s.x, ms ? s.hist : nullptr, a_t_host[i], ms ? ed->a_next[i] : a_prev_host[i],
+                               pred_type, clip_sample, ms ? coef : nullptr, ed->known, noise, ed->mask, s.x, guided ? s.x + n : nullptr, nullptr, n));
+      continue;
+    }
     if (ms) {
       EEG_TRY(eegldm_multistep_step(ctx, s.out, guidance_scale, guided ? 1 : 0, s.x, s.hist, a_t_host[i], pred_type, clip_sample, ms->cx[i], ms->c0[i],
                                     ms->c1[i], s.x, guided ? s.x + n : nullptr, nullptr, n));
@@ -296,4 +309,35 @@ extern "C" int eegldm_sample_multistep(eegldm_unet* u, eegldm_aekl* ae, const fl
   const MultistepCoef ms{cx_host, c0_host, c1_host};
   return sample_impl(u, ae, noise, timesteps_host, a_t_host, nullptr, nullptr, n_steps, 0, pred_type, clip_sample, inv_scale_factor, 0,
                      latents_out, windows_out, B, L, use_graph, graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class, &ms);
+}
+
+// The same loops from an input (include/eegldm.h): cx_host NULL = DDIM, else the multistep form.
+extern "C" int eegldm_sample_edit(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                                  const int64_t* timesteps_host, const float* a_t_host, const float* a_prev_host, const float* cx_host,
+                                  const float* c0_host, const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
+                                  float inv_scale_factor, float* latents_out, float* windows_out, int B, int L, int use_graph, int* graph_used_host,
+                                  const int64_t* labels_host, float guidance_scale, int64_t null_class) {
+  EEG_CHECK(u, "null argument");
+  EEG_CHECK(n_steps >= 1, "bad sizes");
+  EEG_CHECK(known || !mask, "a mask needs the known signal");
+  if (labels_host) {
+    EEG_CHECK(unet_num_classes(u) > 0, "labels for a UNet built without classes");
+    EEG_CHECK(guidance_scale == guidance_scale, "guidance_scale is NaN");
+  } else {
+    EEG_CHECK(unet_num_classes(u) == 0, "this UNet is class-conditional: pass labels_host");
+  }
+  const float w = labels_host ? guidance_scale : 1.0f;
+  const EditBlock ed{known, mask, a_next_host};
+  const EditBlock* edp = known ? &ed : nullptr;
+  if (!cx_host) {
+    EEG_CHECK(a_prev_host, "the DDIM form needs a_prev_host");
+    return sample_impl(u, ae, noise, timesteps_host, a_t_host, a_prev_host, nullptr, n_steps, 0, pred_type, clip_sample, inv_scale_factor, 0,
+                       latents_out, windows_out, B, L, use_graph, graph_used_host, labels_host, w, null_class, nullptr, edp);
+  }
+  EEG_CHECK(c0_host && c1_host, "null argument");
+  EEG_CHECK(c1_host[0] == 0.0f, "the first executed step has no history: c1[0] must be 0 (got %g)", (double)c1_host[0]);
+  EEG_CHECK(!known || a_next_host, "the multistep form needs a_next_host");
+  const MultistepCoef ms{cx_host, c0_host, c1_host};
+  return sample_impl(u, ae, noise, timesteps_host, a_t_host, nullptr, nullptr, n_steps, 0, pred_type, clip_sample, inv_scale_factor, 0,
+                     latents_out, windows_out, B, L, use_graph, graph_used_host, labels_host, w, null_class, &ms, edp);
 }

@@ -5,10 +5,11 @@ parameter (the reference hard-codes 200, sample_trials.py:144)."""
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from ._lib import lib, check, ptr, PRED
-from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, scheduler_edit_tables
 from .training import randn
 
 
@@ -61,9 +62,74 @@ def _labels_host(unet, labels, B, guidance_scale, null_class):
     return lab, nc
 
 
+def _edit_args(autoencoder, scheduler, noise_shape, init, strength, mask, composite, init_latents):
+    """Checks the arguments of a run that starts from an input, on the host and before anything runs; -> None without init / init_latents,
+    else dict(tab = the truncated tables, composite = bool).  Shapes: noise (B, C, L); init (B, in_channels, L * down) windows for an LDM,
+    (B, C, L) for a pixel-space model; init_latents (B, C, L); mask (B, 1, L * down), 1 = keep."""
+    from .schedulers import edit_start_index
+    edit_start_index(1, strength)           # the range of strength, whatever else is given
+    if init is None and init_latents is None:
+        if mask is not None:
+            raise ValueError("mask needs init (or init_latents): the kept samples have to come from somewhere")
+        if composite:
+            raise ValueError("composite needs init and mask")
+        if float(strength) != 1.0:
+            raise ValueError("strength needs init (or init_latents)")
+        return None
+    if init is not None and init_latents is not None:
+        raise ValueError("pass init (windows) or init_latents, not both")
+    tab = scheduler_edit_tables(scheduler, strength)        # (refuses the ancestral scheduler)
+    B, Cc, L = (int(v) for v in noise_shape)
+    down = autoencoder.down if autoencoder is not None else 1
+    if init is not None:
+        want = (B, autoencoder.in_channels, L * down) if autoencoder is not None else (B, Cc, L)
+        if tuple(init.shape) != want:
+            raise ValueError(f"init has shape {tuple(init.shape)}, expected {want}")
+        if autoencoder is not None and autoencoder.in_channels != autoencoder.out_channels and mask is not None and composite is not False:
+            raise ValueError("the composite needs an autoencoder with in_channels == out_channels")
+    elif tuple(init_latents.shape) != (B, Cc, L):
+        raise ValueError(f"init_latents has shape {tuple(init_latents.shape)}, expected {(B, Cc, L)}")
+    if mask is not None and tuple(mask.shape) != (B, 1, L * down):
+        raise ValueError(f"mask has shape {tuple(mask.shape)}, expected {(B, 1, L * down)}")
+    if composite and (mask is None or init is None):
+        raise ValueError("composite needs mask and init (windows)")
+    return dict(tab=tab, composite=(mask is not None and init is not None) if composite is None else bool(composite))
+
+
+def _edit_inputs(unet, autoencoder, x, scale_factor, init, mask, init_latents, native=True):
+    """-> (z0 (B, C, L), window-resolution mask or None, mask at the sampler's resolution or None, init on the device or None).  native: z0 and
+    the pooled mask come from eegldm_edit_start / eegldm_edit_window; else from torch ops (the host loop's reference composition)."""
+    dev = unet.device
+    B, Cc, L = x.shape
+    down = autoencoder.down if autoencoder is not None else 1
+    init_d = None if init is None else torch.as_tensor(init).to(dev, torch.float32).contiguous()
+    if init_latents is not None:
+        z0 = torch.as_tensor(init_latents).to(dev, torch.float32).contiguous()
+    elif autoencoder is None:
+        z0 = init_d
+    else:
+        z_mu, _sigma = autoencoder.encode(init_d)           # the posterior mean: no reparameterisation draw
+        if native:
+            z0 = torch.empty_like(z_mu)
+            check(lib.eegldm_edit_start(unet.ctx.h, ptr(z_mu), float(scale_factor), None, 1.0, ptr(z0), None, z0.numel()))
+        else:
+            z0 = z_mu * float(scale_factor)
+    m_win = m_lat = None
+    if mask is not None:
+        m_win = torch.as_tensor(mask).to(dev, torch.float32).contiguous()
+        if not bool(((m_win >= 0) & (m_win <= 1)).all()):
+            raise ValueError("mask values must lie in [0, 1]")
+        if native:
+            m_lat = torch.empty(B, Cc, L, device=dev, dtype=torch.float32)
+            check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_win), B, L * down, down, Cc, ptr(m_lat), None, None, 0, None))
+        else:
+            m_lat = (-torch.nn.functional.max_pool1d(-m_win, down, down)).expand(B, Cc, L).contiguous()
+    return z0, m_win, m_lat, init_d
+
+
 @torch.no_grad()
 def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, use_graph=None, seed=0, info=None, labels=None,
-                guidance_scale=1.0, null_class=None):
+                guidance_scale=1.0, null_class=None, init=None, strength=1.0, mask=None, composite=None, init_latents=None):
     """noise (B, lat, Ll) on the device -> (windows (B, out, 3072 - 2*crop), final latents).  ONE native call
     (eegldm_sample): the scheduler loop, z / scale_factor and the decode run inside the library.  The UNet forward CAN be
     replayed from a hipGraph (use_graph=True or EEGLDM_SAMPLE_GRAPH=1) but that is no longer the default: measured on
@@ -74,7 +140,15 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     stream `seed`) or a DPMSolverMultistepScheduler (DPM-Solver++ 2M through eegldm_sample_multistep: the same loop with one
     eegldm_multistep_step launch behind every forward).  info (optional dict) receives {"graph": bool}.
     A UNet built with num_classes needs `labels` (one class per sample, or one for all).  guidance_scale w != 1 is classifier-free
-    guidance: out = out(null_class) + w (out(labels) - out(null_class)) on the raw model output, every forward on 2B rows."""
+    guidance: out = out(null_class) + w (out(labels) - out(null_class)) on the raw model output, every forward on 2B rows.
+    init (windows; init_latents for callers who hold latents) starts the run from an input instead of from noise (eegldm_sample_edit): with
+    z0 = scale_factor * posterior mean of the encoded window (pixel-space model: the window itself) the last n_run = min(n, max(1,
+    round(strength * n))) steps of the grid run from x = sqrt(a_t) z0 + sqrt(1 - a_t) noise; `noise` is the one noise tensor of the call,
+    nothing else is drawn.  mask ((B, 1, window length), 1 = keep) regenerates only the samples marked 0: after every step the kept region
+    is reset to z0 noised to that step's level (inside the step's kernel); a latent position is kept only if all the window samples it
+    covers are.  composite (default: on with mask and init) returns mask * init + (1 - mask) * decoded windows, kept samples bit for bit.
+    The ancestral DDPMScheduler, mask without init and strength outside (0, 1] are refused."""
+    edit = _edit_args(autoencoder, scheduler, noise.shape, init, strength, mask, composite, init_latents)
     unet.eval()
     x = noise.to(unet.device, torch.float32).contiguous()
     B, Cc, L = x.shape
@@ -82,7 +156,10 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
         raise ValueError(f"noise has {Cc} channels, the UNet takes {unet.in_channels}")
     lab, nc = _labels_host(unet, labels, B, guidance_scale, null_class)
     multistep = isinstance(scheduler, DPMSolverMultistepScheduler)
-    if multistep:
+    if edit is not None:
+        tab = edit["tab"]
+        ts, a_t = tab["timesteps"], tab["a_t"]
+    elif multistep:
         ts, a_t, cx, c0, c1 = _multistep_tables(scheduler)
     else:
         ts, a_t, a_prev, beta, ancestral = _step_tables(scheduler)
@@ -99,7 +176,16 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     ae_h = autoencoder.h if autoencoder is not None else None
     i64, f32 = (lambda v: (C.c_int64 * len(v))(*v)), (lambda v: (C.c_float * len(v))(*v))
     tail = (ptr(lat), ptr(win), B, L, 1 if use_graph else 0, C.byref(used))
-    if multistep:
+    if edit is not None:
+        z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, scale_factor, init, mask, init_latents)
+        nul = C.POINTER(C.c_float)()
+        coef = (f32(tab["cx"]), f32(tab["c0"]), f32(tab["c1"])) if multistep else (nul, nul, nul)
+        check(lib.eegldm_sample_edit(unet.h, ae_h, ptr(x), ptr(z0), ptr(m_lat), i64(ts), f32(a_t), nul if multistep else f32(tab["a_prev"]), *coef,
+                                     f32(tab["a_next"]), n, PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor),
+                                     *tail, None if lab is None else i64(lab), float(guidance_scale), nc))
+        if edit["composite"]:
+            check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_win), B, L * down, down, 0, None, ptr(init_d), ptr(win), out_c, ptr(win)))
+    elif multistep:
         check(lib.eegldm_sample_multistep(unet.h, ae_h, ptr(x), i64(ts), f32(a_t), f32(cx), f32(c0), f32(c1), n, PRED[scheduler.prediction_type],
                                           int(scheduler.clip_sample), 1.0 / float(scale_factor), *tail, None if lab is None else i64(lab),
                                           float(guidance_scale), nc))
@@ -122,11 +208,15 @@ sample = ddim_sample      # the neutral name: the sampler is whatever `scheduler
 
 
 @torch.no_grad()
-def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, labels=None, guidance_scale=1.0, null_class=None):
+def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, labels=None, guidance_scale=1.0, null_class=None,
+                         init=None, strength=1.0, mask=None, composite=None, init_latents=None):
     """The same loop driven from Python, one scheduler.step call per timestep (what round 1 shipped; kept as the
     reference composition the native sampler is tested against, and for schedulers the native loop does not know).
     Class-conditional: the UNet is called with the labels and, for guidance_scale != 1, a second time with null_class; the two
-    outputs are mixed as out_u + w (out_c - out_u) ahead of scheduler.step."""
+    outputs are mixed as out_u + w (out_c - out_u) ahead of scheduler.step.  init / strength / mask / composite / init_latents as in
+    ddim_sample, composed from torch ops: the noised start, the blend m k + (1 - m) x after every scheduler.step, the min-pooled mask and
+    the composite."""
+    edit = _edit_args(autoencoder, scheduler, noise.shape, init, strength, mask, composite, init_latents)
     unet.eval()
     x = noise.to(unet.device, torch.float32).contiguous()
     B = x.shape[0]
@@ -135,20 +225,48 @@ def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, 
     null = None if lab is None else torch.full((B,), nc, dtype=torch.int64, device=unet.device)
     w = float(guidance_scale)
     tt = torch.empty(B, device=unet.device, dtype=torch.int64)
-    for t in scheduler.timesteps:
+    timesteps, first = scheduler.timesteps, {}
+    if edit is not None:
+        tab = edit["tab"]
+        nz = x
+        z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, scale_factor, init, mask, init_latents, native=False)
+
+        def renoise(a):
+            """sqrt(a) z0 + sqrt(1 - a) noise with the library's roundings (the product, then a fused multiply-add: the sum is formed in
+            float64, where the first product is exact): a bfloat16 UNet turns a last-bit difference of its input into a bfloat16 ulp."""
+            a = float(a)
+            if a >= 1.0:
+                return z0
+            a32 = np.float32(a)          # (numpy's float32 sqrt is correctly rounded, as the library's sqrtf; torch's scalar sqrt is not always)
+            ka, kb = float(np.sqrt(a32)), float(np.sqrt(np.float32(1.0) - a32))
+            return (z0.double() * ka + (nz * kb).double()).float()
+        x = renoise(tab["a_t"][0])
+        timesteps = tab["timesteps"]
+        if isinstance(scheduler, DPMSolverMultistepScheduler):
+            first = {"first_order": True}
+    for j, t in enumerate(timesteps):
         tt.fill_(int(t))
         out = unet(x, timesteps=tt, **kw)
         if lab is not None and w != 1.0:
             out_u = unet(x, timesteps=tt, y=null)
             out = out_u + w * (out - out_u)
-        x, _ = scheduler.step(out, int(t), x)
+        x, _ = scheduler.step(out, int(t), x, **(first if j == 0 else {}))
+        if edit is not None and m_lat is not None:
+            x = m_lat * renoise(tab["a_next"][j]) + (1.0 - m_lat) * x
+    comp = (lambda win: m_win * init_d + (1.0 - m_win) * win) if edit is not None and edit["composite"] else (lambda win: win)
     if autoencoder is None:      # pixel-space model (sample_trials_ddpm.py:99-104): the UNet output IS the window
-        return (x[:, :, crop:-crop] if crop else x), x
+        sample = comp(x)
+        return (sample[:, :, crop:-crop] if crop else sample), x
     z = x
     if float(scale_factor) != 1.0:
         z = x.clone()
-        check(lib.eegldm_axpy(unet.ctx.h, ptr(z), ptr(z), 1.0 / float(scale_factor) - 1.0, z.numel()))
-    sample = autoencoder.decode_stage_2_outputs(z)
+        alpha = 1.0 / float(scale_factor) - 1.0
+        if edit is not None:
+            # the native loop's value: 1 / scale_factor rounded to float32, then minus one in float32.  The double expression above can
+            # differ from it in the last bit, which a bfloat16 decoder turns into a bfloat16 ulp of a window sample now and then
+            alpha = float(np.float32(1.0 / float(scale_factor)) - np.float32(1.0))
+        check(lib.eegldm_axpy(unet.ctx.h, ptr(z), ptr(z), alpha, z.numel()))
+    sample = comp(autoencoder.decode_stage_2_outputs(z))
     return (sample[:, :, crop:-crop] if crop else sample), x
 
 

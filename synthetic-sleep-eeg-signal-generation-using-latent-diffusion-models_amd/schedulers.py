@@ -211,6 +211,62 @@ def multistep_coefficients(alphas_cumprod, timesteps, final_alpha_cumprod=1.0, s
     return cx, c0, c1
 
 
+def edit_start_index(num_inference_steps, strength):
+    """(i0, n_run) of a run that starts from an input: n_run = min(n, max(1, round(strength * n))) steps are executed, the grid's steps
+    i0 = n - n_run .. n - 1.  round is to nearest with ties away from zero (floor(v + 0.5)): strength 0.5 of 5 steps runs 3."""
+    import math
+    n, s = int(num_inference_steps), float(strength)
+    if n < 1:
+        raise ValueError("num_inference_steps must be >= 1")
+    if not 0.0 < s <= 1.0:          # (NaN fails both comparisons)
+        raise ValueError(f"strength must lie in (0, 1], got {strength}")
+    n_run = min(n, max(1, int(math.floor(s * n + 0.5))))
+    return n - n_run, n_run
+
+
+def edit_tables(alphas_cumprod, timesteps, strength, final_alpha_cumprod=1.0, ddim_ratio=None, multistep=None):
+    """Host-side tables of an edit run (sampling from an input, eegldm_sample_edit), truncated to the executed steps i0 .. n - 1 of the
+    grid `timesteps`:  -> dict(i0, timesteps, a_t, a_next [, a_prev] [, cx, c0, c1]).
+      ddim_ratio (DDIMScheduler: num_train_timesteps // num_inference_steps): a_prev[i] = acp[t_i - ratio], final_alpha_cumprod below
+        timestep 0; a_next = a_prev, the noise level a DDIM step lands on.
+      multistep (DPMSolverMultistepScheduler: dict(cx, c0, c1, solver_order, lower_order_final) of the FULL grid): a_next[i] = a_t[i + 1],
+        final_alpha_cumprod after the last step.  The first executed step has no history, so it is first order (c1 = 0; its cx, c0 are the
+        first-order coefficients of that step, multistep_coefficients with solver_order 1); every later entry is the full grid's.
+    Pure Python; the values are those the native loop receives as float32."""
+    ts = [int(t) for t in timesteps]
+    i0, _n_run = edit_start_index(len(ts), strength)
+    acp = alphas_cumprod
+    a_t = [float(acp[t]) for t in ts]
+    out = dict(i0=i0, timesteps=ts[i0:], a_t=a_t[i0:])
+    if (ddim_ratio is None) == (multistep is None):
+        raise ValueError("pass ddim_ratio or multistep")
+    if multistep is None:
+        prev = [t - int(ddim_ratio) for t in ts]
+        a_prev = [float(acp[p]) if p >= 0 else float(final_alpha_cumprod) for p in prev]
+        out["a_prev"] = a_prev[i0:]
+        out["a_next"] = a_prev[i0:]
+        return out
+    out["a_next"] = (a_t[1:] + [float(final_alpha_cumprod)])[i0:]
+    cx, c0, c1 = (list(multistep[k][i0:]) for k in ("cx", "c0", "c1"))
+    if c1[0] != 0.0:
+        fx, f0, _f1 = multistep_coefficients(acp, ts, final_alpha_cumprod, 1, multistep.get("lower_order_final", True))
+        cx[0], c0[0], c1[0] = fx[i0], f0[i0], 0.0
+    out["cx"], out["c0"], out["c1"] = cx, c0, c1
+    return out
+
+
+def scheduler_edit_tables(scheduler, strength):
+    """edit_tables for a DDIMScheduler or a DPMSolverMultistepScheduler after set_timesteps; the ancestral DDPMScheduler is refused."""
+    if isinstance(scheduler, DPMSolverMultistepScheduler):
+        ms = dict(cx=scheduler.cx, c0=scheduler.c0, c1=scheduler.c1, lower_order_final=scheduler.lower_order_final)
+        return edit_tables(scheduler.alphas_cumprod, scheduler.timesteps, strength, scheduler.final_alpha_cumprod, multistep=ms)
+    if isinstance(scheduler, DDIMScheduler):
+        return edit_tables(scheduler.alphas_cumprod, scheduler.timesteps, strength, scheduler.final_alpha_cumprod,
+                           ddim_ratio=scheduler.num_train_timesteps // scheduler.num_inference_steps)
+    raise ValueError("sampling from an input (init / mask) needs a deterministic sampler: DDIMScheduler or DPMSolverMultistepScheduler, "
+                     f"not {type(scheduler).__name__}")
+
+
 class DPMSolverMultistepScheduler(_Scheduler):
     """DPM-Solver++ (2M): a deterministic sampler that reuses the previous step's data prediction for a second-order update, one UNet
     forward per step like DDIM (multistep_coefficients has the formulas; solver_order=1 IS DDIM on the same grid).  `step` keeps the
@@ -239,11 +295,14 @@ class DPMSolverMultistepScheduler(_Scheduler):
         self.timesteps = torch.tensor(ts, dtype=torch.int64)
         self.cx, self.c0, self.c1 = multistep_coefficients(self.alphas_cumprod, ts, self.final_alpha_cumprod, self.solver_order,
                                                            self.lower_order_final)
+        # first-order coefficients of every step: the first step of a run that starts inside the grid (step(first_order=True))
+        self._cx1, self._c01, _ = multistep_coefficients(self.alphas_cumprod, ts, self.final_alpha_cumprod, 1, self.lower_order_final)
         self._index = {t: i for i, t in enumerate(ts)}
         self._hist, self._hist_step = None, -1
 
-    def step(self, model_output, timestep, sample):
-        """-> (pred_prev_sample, pred_original_sample)"""
+    def step(self, model_output, timestep, sample, first_order=False):
+        """-> (pred_prev_sample, pred_original_sample).  first_order=True: this step starts a run inside the grid (sampling from an
+        input): no history is read, the coefficients are the first-order ones of the step."""
         t = int(timestep)
         if t not in self._index:
             raise ValueError(f"timestep {t} is not on the grid of set_timesteps({self.num_inference_steps})")
@@ -252,11 +311,12 @@ class DPMSolverMultistepScheduler(_Scheduler):
         x = sample.to(self.device, torch.float32).contiguous()
         if self._hist is None or self._hist.shape != x.shape:
             self._hist, self._hist_step = torch.zeros_like(x), -1
-        if self.c1[i] != 0.0 and self._hist_step != i - 1:
+        cx, c0, c1 = (self._cx1[i], self._c01[i], 0.0) if first_order else (self.cx[i], self.c0[i], self.c1[i])
+        if c1 != 0.0 and self._hist_step != i - 1:
             raise RuntimeError(f"the second-order step at timestep {t} needs the step at timestep {int(self.timesteps[i - 1])} right before it")
         prev, x0 = torch.empty_like(x), torch.empty_like(x)
         check(lib.eegldm_multistep_step(self.ctx.h, ptr(mo), 0.0, 0, ptr(x), ptr(self._hist), float(self.alphas_cumprod[t]),
-                                        PRED[self.prediction_type], int(self.clip_sample), self.cx[i], self.c0[i], self.c1[i], ptr(prev), None,
+                                        PRED[self.prediction_type], int(self.clip_sample), cx, c0, c1, ptr(prev), None,
                                         ptr(x0), x.numel()))
         self._hist_step = i
         return prev, x0
