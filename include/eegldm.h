@@ -45,7 +45,8 @@ extern "C" {
  *    + eegldm_ddim_step_eta, eegldm_ddpm_step_var, eegldm_unet_set_dropout, eegldm_dropout.
  *    Added since without a version change (new symbols only): the class-conditional entry points, the weight EMA (eegldm_adam_step_ema,
  *    eegldm_ema_update, eegldm_swap), the multistep sampler (eegldm_multistep_step, eegldm_sample_multistep) and editing (eegldm_edit_step,
- *    eegldm_edit_start, eegldm_edit_window, eegldm_sample_edit). */
+ *    eegldm_edit_start, eegldm_edit_window, eegldm_sample_edit) and the weighted diffusion loss (eegldm_diffusion_loss, eegldm_loss_bins,
+ *    eegldm_ldm_train_step_weighted). */
 #define EEGLDM_ABI_VERSION 8
 
 /* Storage / operand type of activations and compute-copy weights (accumulation, statistics, master weights and optimizer state are
@@ -223,6 +224,23 @@ int eegldm_ddpm_step_var(eegldm_ctx*, const float* model_out, const float* sampl
                          float beta_t, int variance_large, int pred_type, int clip_sample, float* prev_sample, float* pred_x0, long n);
 /* loss = mean((pred-target)^2); dpred = 2 (pred-target) / n * grad_scale (nullable) */
 int eegldm_mse_loss(eegldm_ctx*, const float* pred, const float* target, float* loss, float* dpred, long n, float grad_scale);
+/* Weighted diffusion loss with per-sample losses (the reference trains on the plain F.mse_loss; Min-SNR-gamma, Hang et al. 2023, is a
+ * table here).  pred / x0 / noise / dpred: (B, n_per_sample) fp32; N = n_per_sample.  The target is noise (epsilon), x0 (sample), or
+ * sqrt(acp[t_b]) noise - sqrt(1 - acp[t_b]) x0 (v_prediction) formed in registers with the rounding of eegldm_get_velocity; the buffer a
+ * prediction type does not read may be NULL (x0 for epsilon, noise for sample; acp is read for v_prediction only).
+ *   m_b = (1 / N) sum_i (pred - target)^2,   w_b = wtab[t_b] (wtab NULL: 1),   loss = (1 / B) sum_b w_b m_b,
+ *   per_sample[b] (NULL ok) = m_b, unweighted,   dpred (NULL ok) = 2 (pred - target) / (B N) * grad_scale * w_b
+ * (with w_b = 1 the bytes of eegldm_mse_loss's dpred).  wtab is a device table indexed by timestep (schedulers.loss_weights); all knowledge
+ * of the weighting lives there.  Reductions: a written partial per (sample, 1024-element chunk), folded per sample in chunk order, the B
+ * weighted values then added in sample order -- no float atomics, bit-reproducible with or without EEGLDM_DETERMINISTIC.  16-byte accesses
+ * when the buffers in use share one offset inside a 16-byte line (scalar head / tail per sample), any 4-byte alignment otherwise.
+ * Timesteps must lie inside the tables. */
+int eegldm_diffusion_loss(eegldm_ctx*, const float* pred, const float* x0, const float* noise, const int64_t* t, const float* acp,
+                          const float* wtab, int pred_type, int B, long n_per_sample, float grad_scale, float* loss, float* per_sample,
+                          float* dpred);
+/* Loss by noise level: bin_sum[k] += per_sample[b] and bin_cnt[k] += 1 for k = t_b K / T (integer division), samples in ascending order
+ * (one workgroup: order-fixed).  bin_sum: K floats, bin_cnt: K int64, both accumulated into; timesteps outside [0, T) are not counted. */
+int eegldm_loss_bins(eegldm_ctx*, const float* per_sample, const int64_t* t, int B, int T, int K, float* bin_sum, int64_t* bin_cnt);
 int eegldm_adam_step(eegldm_ctx*, float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
                      float beta2, float eps, int step, float grad_inv_scale);
 /* Weight EMA (exponential moving average of the parameters; the reference has none, diffusion code bases sample from one).
@@ -323,6 +341,13 @@ int eegldm_unet_forward_cond(eegldm_unet*, const float* x, const int64_t* t, con
 int eegldm_ldm_train_step_cond(eegldm_unet*, const float* latents, const float* noise, const int64_t* t, const float* acp, int pred_type,
                                int B, int L, float grad_scale, float* loss, const int64_t* labels, float p_uncond, int64_t null_class,
                                uint64_t seed, uint64_t offset);
+/* eegldm_ldm_train_step / eegldm_ldm_train_step_cond with eegldm_diffusion_loss in place of get_velocity + mse_loss (two kernels instead of memset + mse_loss [+ get_velocity]), no
+ * target buffer, no float atomics in the loss.  wtab (NULL: all ones) weights sample b by wtab[t_b]; per_sample (NULL ok) receives the
+ * unweighted per-sample losses.  labels == NULL for an unconditional UNet (the four label arguments are then ignored); the checks of the
+ * two steps above apply. */
+int eegldm_ldm_train_step_weighted(eegldm_unet*, const float* latents, const float* noise, const int64_t* t, const float* acp, int pred_type,
+                                   int B, int L, float grad_scale, float* loss, const float* wtab, float* per_sample,
+                                   const int64_t* labels, float p_uncond, int64_t null_class, uint64_t seed, uint64_t offset);
 /* The label dropout on its own: out[b] = labels[b], or null_class when word 0 of Philox(seed, offset + b) / 2^32 < p_uncond. */
 int eegldm_label_dropout(eegldm_ctx*, const int64_t* labels, int64_t* out, int B, float p_uncond, int64_t null_class, uint64_t seed,
                          uint64_t offset);

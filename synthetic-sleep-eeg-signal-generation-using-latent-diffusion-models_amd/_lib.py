@@ -94,6 +94,8 @@ SIGNATURES = {
     "eegldm_ddim_step_eta": [_vp, _vp, _vp, _vp, _f, _f, _f, _i, _i, _vp, _vp, _l],
     "eegldm_ddpm_step_var": [_vp, _vp, _vp, _vp, _f, _f, _f, _i, _i, _i, _vp, _vp, _l],
     "eegldm_mse_loss": [_vp, _vp, _vp, _vp, _vp, _l, _f],
+    "eegldm_diffusion_loss": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _f, _vp, _vp, _vp],
+    "eegldm_loss_bins": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     "eegldm_adam_step": [_vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _i, _f],
     "eegldm_adam_step_ema": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _i, _f, _f],
     "eegldm_ema_update": [_vp, _vp, _vp, _l, _f],
@@ -118,6 +120,7 @@ SIGNATURES = {
     "eegldm_unet_create_cond": [_vp, _vp, _i, C.POINTER(_vp)],
     "eegldm_unet_forward_cond": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i],
     "eegldm_ldm_train_step_cond": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _f, C.c_int64, C.c_uint64, C.c_uint64],
+    "eegldm_ldm_train_step_weighted": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _f, C.c_int64, C.c_uint64, C.c_uint64],
     "eegldm_label_dropout": [_vp, _vp, _vp, _i, _f, C.c_int64, C.c_uint64, C.c_uint64],
     "eegldm_l1_loss": [_vp, _vp, _vp, _vp, _vp, _l, _f],
     "eegldm_lsgan_loss": [_vp, _vp, _i, _vp, _vp, _l, _f],

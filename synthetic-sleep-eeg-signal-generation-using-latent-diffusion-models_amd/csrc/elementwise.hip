@@ -1481,3 +1481,140 @@ extern "C" int eegldm_nearest2_fwd(eegldm_ctx* ctx, const void* x, long ldx, voi
 extern "C" int eegldm_nearest2_bwd(eegldm_ctx* ctx, const void* dy, long lddy, void* dx, long lddx, int B, int L, int C, int dtype) {
   return resample2(ctx, 1, dy, lddy, dx, lddx, B, L, C, dtype);
 }
+
+// ---- weighted diffusion loss with per-sample losses (include/eegldm.h; Min-SNR weighting lives in the host's table, schedulers.py loss_weights)
+// One block per (sample, chunk of DL_CHUNK elements): d = pred - target with the target formed in registers, a written partial sum of d^2 per
+// block, d pred scaled by the sample's weight.  A second, one-block kernel folds each sample's chunks in index order and then the B weighted
+// values in index order: no float atomics, the same bytes on every run whatever EEGLDM_DETERMINISTIC says.  The partials (B * nchunk floats)
+// live at the head of the context's written-partials buffer (eeg_det_buffer): in a process that never ran in deterministic mode the first
+// call allocates that buffer (32 MiB, once per context); every later call reuses it.
+constexpr int DL_CHUNK = 1024;      // one float4 per thread
+constexpr int DL_TILE = 1024;       // weighted per-sample values staged in LDS per round of the fold
+// velocity target with the rounding of add_noise_kernel (eegldm_get_velocity): the product sb * x rounded, then ONE fused multiply-add.
+// Contraction off and the fma spelled out, so that the float4 body and the scalar edges round alike and like that kernel.
+__device__ __forceinline__ float dl_target(float x, float nz, float sa, float sb, int pred) {
+#pragma clang fp contract(off)
+  if (pred == EEGLDM_PRED_EPSILON) return nz;
+  if (pred == EEGLDM_PRED_SAMPLE) return x;
+  return fmaf(sa, nz, -(sb * x));
+}
+// s += d^2; returns d pred = 2 d / n * gscale * w, the product ordered as mse_kernel's with the weight last (w == 1: the same bytes)
+__device__ __forceinline__ float dl_elem(float p, float tgt, float& s, float inv_n, float gscale, float w) {
+#pragma clang fp contract(off)
+  const float d = p - tgt;
+  s = fmaf(d, d, s);
+  return 2.0f * d * inv_n * gscale * w;
+}
+__global__ __launch_bounds__(NT) void diffusion_loss_kernel(const float* __restrict__ pred, const float* __restrict__ x0, const float* __restrict__ noise,
+                                                            const int64_t* __restrict__ t, const float* __restrict__ acp,
+                                                            const float* __restrict__ wtab, int ptype, long N, int nchunk, int head0, float inv_n,
+                                                            float gscale, float* __restrict__ parts, float* __restrict__ dpred) {
+  const long b = blockIdx.x / nchunk; const int c = (int)(blockIdx.x - b * nchunk);
+  const long start = b * N + (long)c * DL_CHUNK;
+  const long left = N - (long)c * DL_CHUNK, len = left < DL_CHUNK ? left : DL_CHUNK;
+  const int64_t tb = t[b];
+  float sa = 0.0f, sb = 0.0f;
+  if (ptype == EEGLDM_PRED_V) { const float a = acp[tb]; sa = sqrtf(a); sb = sqrtf(1.0f - a); }
+  const float w = wtab ? wtab[tb] : 1.0f;
+  // head0: scalar elements ahead of the 16-byte body at element 0 of the buffers (they share one misalignment), or -1: all scalar
+  long head = head0 < 0 ? len : (long)((head0 - (int)(start & 3)) & 3);
+  if (head > len) head = len;
+  const VecSplit s = vec_split(len, head);
+  const float* pp = pred + start; const float* xp = x0 ? x0 + start : nullptr; const float* zp = noise ? noise + start : nullptr;
+  float* dp = dpred ? dpred + start : nullptr;
+  float acc = 0.0f;
+  const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+  for (long i = threadIdx.x; i < s.n4; i += NT) {
+    const f32x4 pv = ((const f32x4*)(pp + head))[i];
+    const f32x4 xv = xp ? ((const f32x4*)(xp + head))[i] : zero4;
+    const f32x4 zv = zp ? ((const f32x4*)(zp + head))[i] : zero4;
+    f32x4 dv;
+#pragma unroll
+    for (int k = 0; k < 4; k++) dv[k] = dl_elem(pv[k], dl_target(xv[k], zv[k], sa, sb, ptype), acc, inv_n, gscale, w);
+    if (dp) ((f32x4*)(dp + head))[i] = dv;
+  }
+  for (long j = threadIdx.x; j < s.nedge; j += NT) {
+    const long i = j < s.head ? j : s.tail0 + (j - s.head);      // the scalar head, then the tail behind the float4 body
+    const float d = dl_elem(pp[i], dl_target(xp ? xp[i] : 0.0f, zp ? zp[i] : 0.0f, sa, sb, ptype), acc, inv_n, gscale, w);
+    if (dp) dp[i] = d;
+  }
+  acc = wave_sum(acc);
+  __shared__ float red[NT / 64];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) parts[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+// m_b = (sum of the sample's chunk partials, in chunk order) / N -> per_sample; loss = (sum_b w_b m_b, in sample order) / B
+__global__ __launch_bounds__(NT) void diffusion_loss_fold_kernel(const float* __restrict__ parts, int nchunk, const int64_t* __restrict__ t,
+                                                                 const float* __restrict__ wtab, int B, float n_per, float* __restrict__ per_sample,
+                                                                 float* __restrict__ loss) {
+#pragma clang fp contract(off)
+  __shared__ float wm[DL_TILE];
+  float total = 0.0f;
+  for (int b0 = 0; b0 < B; b0 += DL_TILE) {
+    const int nb = B - b0 < DL_TILE ? B - b0 : DL_TILE;
+    for (int i = threadIdx.x; i < nb; i += NT) {
+      const int b = b0 + i;
+      float s = parts[(long)b * nchunk];
+      for (int c = 1; c < nchunk; c++) s = s + parts[(long)b * nchunk + c];
+      const float m = s / n_per;
+      if (per_sample) per_sample[b] = m;
+      wm[i] = wtab ? wtab[t[b]] * m : m;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) for (int i = 0; i < nb; i++) total = total + wm[i];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = total / (float)B;
+}
+extern "C" int eegldm_diffusion_loss(eegldm_ctx* ctx, const float* pred, const float* x0, const float* noise, const int64_t* t, const float* acp,
+                                     const float* wtab, int pred_type, int B, long n_per_sample, float gscale, float* loss, float* per_sample,
+                                     float* dpred) {
+  EEG_CHECK(ctx && pred && t && loss, "null argument");
+  EEG_CHECK(pred_type == EEGLDM_PRED_EPSILON || pred_type == EEGLDM_PRED_V || pred_type == EEGLDM_PRED_SAMPLE, "prediction type %d", pred_type);
+  EEG_CHECK(B >= 1 && n_per_sample >= 1, "B (%d) and n_per_sample (%ld) must be >= 1", B, n_per_sample);
+  const bool use_x = pred_type != EEGLDM_PRED_EPSILON, use_z = pred_type != EEGLDM_PRED_SAMPLE;
+  EEG_CHECK((!use_x || x0) && (!use_z || noise), "the target of this prediction type needs %s", use_x && !x0 ? "x0" : "noise");
+  EEG_CHECK(pred_type != EEGLDM_PRED_V || acp, "v_prediction needs alphas_cumprod");
+  if (!use_x) x0 = nullptr;
+  if (!use_z) noise = nullptr;
+  const long n = (long)B * n_per_sample;
+  EEG_CHECK(!dpred || (!ranges_overlap(dpred, pred, n) && (!x0 || !ranges_overlap(dpred, x0, n)) && (!noise || !ranges_overlap(dpred, noise, n))),
+            "dpred aliases an input");
+  uintptr_t mis = (uintptr_t)pred & 15; bool same = true;
+  for (const void* q : {(const void*)pred, (const void*)x0, (const void*)noise, (const void*)dpred, (const void*)per_sample, (const void*)loss}) {
+    EEG_CHECK(((uintptr_t)q & 3) == 0, "buffers must be 4-byte aligned");
+  }
+  for (const void* q : {(const void*)x0, (const void*)noise, (const void*)dpred}) if (q && ((uintptr_t)q & 15) != mis) same = false;
+  const int head0 = same ? (int)(((16 - mis) & 15) >> 2) : -1;
+  const long nchunk_l = (n_per_sample + DL_CHUNK - 1) / DL_CHUNK;
+  EEG_CHECK(nchunk_l * B <= 0x7fffffffL, "B * ceil(n_per_sample / %d) = %ld blocks: too many", DL_CHUNK, nchunk_l * B);
+  const int nchunk = (int)nchunk_l;
+  float* parts = nullptr;
+  EEG_TRY(eeg_det_buffer(ctx, (size_t)nchunk * B * sizeof(float), &parts));
+  hipLaunchKernelGGL(diffusion_loss_kernel, dim3((unsigned)(nchunk * B)), dim3(NT), 0, ctx->stream, pred, x0, noise, t, acp, wtab, pred_type, n_per_sample,
+                     nchunk, head0, 1.0f / (float)n, gscale, parts, dpred);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(diffusion_loss_fold_kernel, dim3(1), dim3(NT), 0, ctx->stream, parts, nchunk, t, wtab, B, (float)n_per_sample, per_sample, loss);
+  LAUNCH_CHECK(); return 0;
+}
+// bin k = t_b K / T collects the per-sample losses of its timesteps: bin_sum[k] += m_b in ascending b (one thread per bin), bin_cnt[k] += 1.
+// Timesteps outside [0, T) are not counted.
+__global__ __launch_bounds__(NT) void loss_bins_kernel(const float* __restrict__ per_sample, const int64_t* __restrict__ t, int B, int64_t T, int K,
+                                                       float* __restrict__ bin_sum, int64_t* __restrict__ bin_cnt) {
+  for (int k = threadIdx.x; k < K; k += NT) {
+    float s = bin_sum[k]; int64_t n = bin_cnt[k];
+    for (int b = 0; b < B; b++) {
+      const int64_t tb = t[b];
+      if (tb >= 0 && tb < T && tb * K / T == k) { s += per_sample[b]; n++; }
+    }
+    bin_sum[k] = s; bin_cnt[k] = n;
+  }
+}
+extern "C" int eegldm_loss_bins(eegldm_ctx* ctx, const float* per_sample, const int64_t* t, int B, int T, int K, float* bin_sum, int64_t* bin_cnt) {
+  EEG_CHECK(ctx && per_sample && t && bin_sum && bin_cnt, "null argument");
+  EEG_CHECK(B >= 0 && T >= 1 && K >= 1, "B (%d) must be >= 0, T (%d) and K (%d) >= 1", B, T, K);
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(loss_bins_kernel, dim3(1), dim3(NT), 0, ctx->stream, per_sample, t, B, (int64_t)T, K, bin_sum, bin_cnt);
+  LAUNCH_CHECK(); return 0;
+}

@@ -542,7 +542,8 @@ extern "C" int eegldm_unet_backward(eegldm_unet* u, const float* dy, float* dx_o
 }
 
 static int ldm_train_step(eegldm_unet* u, const float* latents, const float* noise, const int64_t* t, const float* acp,
-                          int pred_type, int B, int L, float grad_scale, float* loss, const LabelArg& lab) {
+                          int pred_type, int B, int L, float grad_scale, float* loss, const LabelArg& lab, bool weighted = false,
+                          const float* wtab = nullptr, float* per_sample = nullptr) {
   EEG_CHECK(u && latents && noise && t && acp && loss, "null argument");
   EEG_CHECK(pred_type == EEGLDM_PRED_EPSILON || pred_type == EEGLDM_PRED_V, "prediction type must be epsilon or v_prediction");
   eegldm_ctx* ctx = u->ctx;
@@ -558,6 +559,10 @@ static int ldm_train_step(eegldm_unet* u, const float* latents, const float* noi
   float *noisy = stage, *pred = stage + n, *target = stage + 2 * n, *dpred = stage + 3 * n;
   EEG_TRY(eegldm_add_noise(ctx, latents, noise, t, acp, noisy, B, (long)C * L));
   EEG_TRY(unet_forward_impl(u, noisy, t, lab, pred, B, L, 1));
+  if (weighted) {      // target in registers, per-sample weight and losses: no target pass, no memset, no atomics (loss kernel + one-block fold)
+    EEG_TRY(eegldm_diffusion_loss(ctx, pred, latents, noise, t, acp, wtab, pred_type, B, (long)C * L, grad_scale, loss, per_sample, dpred));
+    return eegldm_unet_backward(u, dpred, nullptr);
+  }
   const float* tgt = noise;
   if (pred_type == EEGLDM_PRED_V) { EEG_TRY(eegldm_get_velocity(ctx, latents, noise, t, acp, target, B, (long)C * L)); tgt = target; }
   EEG_TRY(eegldm_mse_loss(ctx, pred, tgt, loss, dpred, n, grad_scale));
@@ -579,4 +584,21 @@ extern "C" int eegldm_ldm_train_step_cond(eegldm_unet* u, const float* latents, 
             u->num_classes);
   LabelArg lab; lab.y = labels; lab.p_uncond = p_uncond; lab.null_class = null_class; lab.seed = seed; lab.offset = offset;
   return ldm_train_step(u, latents, noise, t, acp, pred_type, B, L, grad_scale, loss, lab);
+}
+// The step above with eegldm_diffusion_loss in place of get_velocity + mse_loss: wtab[t_b] weights sample b (NULL: all ones), per_sample
+// (NULL ok) receives the unweighted per-sample losses.  labels == NULL for an unconditional UNet (the label arguments are then not read).
+extern "C" int eegldm_ldm_train_step_weighted(eegldm_unet* u, const float* latents, const float* noise, const int64_t* t, const float* acp,
+                                              int pred_type, int B, int L, float grad_scale, float* loss, const float* wtab, float* per_sample,
+                                              const int64_t* labels, float p_uncond, int64_t null_class, uint64_t seed, uint64_t offset) {
+  EEG_CHECK(u, "null unet");
+  LabelArg lab;
+  if (u->num_classes == 0) EEG_CHECK(!labels, "this UNet was built without classes: pass labels = NULL");
+  else {
+    EEG_CHECK(labels, "this UNet is class-conditional (%d classes): labels are required", u->num_classes);
+    EEG_CHECK(p_uncond >= 0.0f && p_uncond <= 1.0f, "p_uncond %g outside [0, 1]", (double)p_uncond);
+    EEG_CHECK(p_uncond == 0.0f || (null_class >= 0 && null_class < u->num_classes), "null_class %lld outside [0, %d)", (long long)null_class,
+              u->num_classes);
+    lab.y = labels; lab.p_uncond = p_uncond; lab.null_class = null_class; lab.seed = seed; lab.offset = offset;
+  }
+  return ldm_train_step(u, latents, noise, t, acp, pred_type, B, L, grad_scale, loss, lab, true, wtab, per_sample);
 }

@@ -219,6 +219,56 @@ def add_ema_args(p):
     p.add_argument("--ema_no_warmup", action="store_true", help="constant decay instead of min(decay, (1 + n) / (10 + n))")
 
 
+def add_loss_weighting_args(p):
+    p.add_argument("--loss_weighting", default=None, choices=["none", "min_snr"], help="weight every sample's loss by its noise level "
+                   "(schedulers.loss_weights; min_snr = Min-SNR-gamma, Hang et al. 2023) through the weighted native loss; adds the "
+                   "'loss_weighting' entry to checkpoint.pth.  Without the flag the step is the plain MSE, as before")
+    p.add_argument("--snr_gamma", type=float, default=5.0, help="the clamp of --loss_weighting min_snr")
+    p.add_argument("--loss_by_noise_level", type=int, default=0, metavar="K", help="print the loss in K equal timestep ranges (training: the epoch's "
+                   "steps; validation: against the prediction type's own target) and append them to {run_dir}/loss_by_noise_level.json")
+
+
+def step_weighting(args):
+    """Keywords of the train step for the parsed flags: {} without them (the plain exports), else loss_weighting / snr_gamma
+    (--loss_by_noise_level alone: "none", the weighted loss with every weight 1 -- it is the one that returns per-sample losses)."""
+    if args.loss_weighting is None and not args.loss_by_noise_level:
+        return {}
+    return dict(loss_weighting=args.loss_weighting or "none", snr_gamma=args.snr_gamma)
+
+
+def loss_weighting_resume(args, ck):
+    """checkpoint.pth against the command line: without --loss_weighting the checkpoint's setting is restored into `args`; a different
+    one is refused (the two halves of the run would optimise different objectives)."""
+    saved = ck.get("loss_weighting")
+    if args.loss_weighting is None:
+        if saved is not None:
+            args.loss_weighting, args.snr_gamma = saved["weighting"], float(saved["snr_gamma"])
+        return
+    mine = {"weighting": args.loss_weighting, "snr_gamma": float(args.snr_gamma)}
+    if saved is None or saved["weighting"] != mine["weighting"] or float(saved["snr_gamma"]) != mine["snr_gamma"]:
+        raise ValueError(f"checkpoint.pth was trained with loss_weighting {saved}, the command line asks for {mine}: start a new run directory "
+                         "or resume with the checkpoint's setting")
+
+
+def append_noise_level_record(run_dir, record):
+    """{run_dir}/loss_by_noise_level.json: a list with one record per evaluated epoch (kept across resumes)."""
+    import json
+    path = os.path.join(run_dir, "loss_by_noise_level.json")
+    records = []
+    if os.path.exists(path):
+        with open(path) as f:
+            records = json.load(f)
+    records.append(record)
+    with open(path, "w") as f:
+        json.dump(records, f, indent=1)
+    return path
+
+
+def format_noise_level_table(name, rows):
+    cells = " ".join(f"[{r['t_lo']}-{r['t_hi']}] " + (f"{r['mean']:.5f}" if r["mean"] is not None else "-") + f" ({r['count']})" for r in rows)
+    return f"  loss by noise level, {name}: {cells}"
+
+
 def cpu_state(sd):
     return {k: v.cpu() for k, v in sd.items()}
 

@@ -12,8 +12,9 @@ import torch
 from .. import distributed as D
 from ..models import UNetModel
 from ..schedulers import DDPMScheduler
-from ..training import EMA, Adam, GradScaler, dm_train_step, randint, randn
-from .common import WindowLoader, add_ema_args, cpu_state, ema_checkpoint_entry, ema_resume, load_config, rng_seed, setup_run_dir
+from ..training import EMA, Adam, GradScaler, NoiseLevelLoss, dm_train_step, randint, randn
+from .common import (WindowLoader, add_ema_args, add_loss_weighting_args, append_noise_level_record, cpu_state, ema_checkpoint_entry, ema_resume,
+                     format_noise_level_table, load_config, loss_weighting_resume, rng_seed, setup_run_dir, step_weighting)
 
 
 def parse_args(argv=None):
@@ -28,6 +29,7 @@ def parse_args(argv=None):
     p.add_argument("--deterministic", action="store_true", help="bit-reproducible steps (eegldm.set_deterministic(): ordered reductions instead of fp32 atomics; "
                    "what torch.use_deterministic_algorithms(True) would be for the reference's loop)")
     add_ema_args(p)
+    add_loss_weighting_args(p)
     return p.parse_args(argv)
 
 
@@ -64,27 +66,44 @@ def main(args):
         if "scaler" in ck:
             scaler.load_state_dict(ck["scaler"])
         start_epoch, best, gstep = int(ck["epoch"]), float(ck["best_loss"]), int(ck.get("steps", 0))
+        loss_weighting_resume(args, ck)
         if ema is not None:
             ema_resume(ema, ck, rank)
         if rank == 0:
             print(f"Resuming from epoch {start_epoch} (best loss {best:.5f})")
+    save_weighting = args.loss_weighting is not None             # (after the resume: a restored setting is written again)
+    wkw = step_weighting(args)                                   # {} without the flags: the plain MSE, as before
+    K = int(args.loss_by_noise_level)                            # this script has no validation split: the table is the epoch's training steps
+    train_levels = NoiseLevelLoss(sched.num_train_timesteps, K) if K else None
     for epoch in range(start_epoch, config.train.n_epochs):
         unet.train()
+        if train_levels is not None:
+            train_levels.reset()
         for batch in train:
             x = batch["eeg"].to(dev)
             B = x.shape[0]
             t = randint(ctx, B, sched.num_train_timesteps, seed=s_t, offset=gstep * B)
             noise = randn(ctx, tuple(x.shape), seed=s_noise, offset=gstep * x.numel())
             opt.zero_grad()
+            if train_levels is not None:
+                wkw["per_sample_out"] = torch.empty(B, device=dev)
             dm_train_step(unet, sched, x, noise, t, spectral_weight=1e-6, spectral_loss=spectral, loss_out=loss, grad_sync=gsync,
-                          grad_scale=scaler.get_scale())
+                          grad_scale=scaler.get_scale(), **wkw)
+            if train_levels is not None:
+                train_levels.add(wkw["per_sample_out"], t, ctx=ctx)
             gsync.wait()
             scaler.step(opt); scaler.update()
             steps += 1; gstep += 1; seen += B * world
             if args.max_steps and steps >= args.max_steps:
                 break
+        if K:                                  # every rank joins the sums; rank 0 prints and writes
+            record = {"epoch": epoch + 1, "steps": gstep, "prediction_type": sched.prediction_type, "bins": K,
+                      "train": train_levels.merge(like=loss).table(), "valid": None, "valid_ema": None}
         if rank == 0:
             print(f"epoch {epoch}: loss {float(loss):.5f} | {seen/(time.time()-t0):.1f} windows/s", flush=True)
+            if K:
+                print(format_noise_level_table("train", record["train"]), flush=True)
+                append_noise_level_record(run_dir, record)
             cur = float(loss)
             if cur <= best:
                 best = cur
@@ -95,6 +114,8 @@ def main(args):
                       "best_loss": best, "steps": gstep, "scaler": scaler.state_dict()}
             if ema is not None:
                 ck_out["ema"] = ema_checkpoint_entry(ema, best)
+            if save_weighting:
+                ck_out["loss_weighting"] = {"weighting": args.loss_weighting, "snr_gamma": float(args.snr_gamma)}
             torch.save(ck_out, os.path.join(run_dir, "checkpoint.pth"))
         if args.max_steps and steps >= args.max_steps:
             break

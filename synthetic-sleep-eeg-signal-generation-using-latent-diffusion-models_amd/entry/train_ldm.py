@@ -10,8 +10,9 @@ import torch
 from .. import distributed as D
 from ..models import AutoencoderKL, UNetModel
 from ..schedulers import DDPMScheduler
-from ..training import EMA, Adam, GradScaler, ldm_train_step, randint, randn
-from .common import ParseListAction, WindowLoader, add_ema_args, cpu_state, ema_checkpoint_entry, ema_resume, load_config, rng_seed, setup_run_dir
+from ..training import EMA, Adam, GradScaler, NoiseLevelLoss, ldm_train_step, randint, randn
+from .common import (ParseListAction, WindowLoader, add_ema_args, add_loss_weighting_args, append_noise_level_record, cpu_state, ema_checkpoint_entry,
+                     ema_resume, format_noise_level_table, load_config, loss_weighting_resume, rng_seed, setup_run_dir, step_weighting)
 
 
 def parse_args(argv=None):
@@ -37,15 +38,18 @@ def parse_args(argv=None):
     p.add_argument("--p_uncond", type=float, default=0.0, help="classifier-free guidance training: probability of replacing a label by --null_class")
     p.add_argument("--null_class", type=int, default=None, help="the unconditional class (default: num_classes - 1 when --p_uncond > 0)")
     add_ema_args(p)
+    add_loss_weighting_args(p)
     return p.parse_args(argv)
 
 
 @torch.no_grad()
-def validate(unet, stage1, sched, loader, scale_factor, seeds, latent_channels):
+def validate(unet, stage1, sched, loader, scale_factor, seeds, latent_channels, by_level=None):
     """eval_ldm (training.py:455-497): mean epsilon-MSE over the validation windows, fixed noise stream (a class-conditional UNet is
     scored with each window's own label).  `seeds` = the three Philox
     keys (timesteps, posterior eps, diffusion noise), each from `rng_seed` with its own role.  Returns (sum of per-window losses,
-    number of windows) so that data-parallel ranks can add their shards up."""
+    number of windows) so that data-parallel ranks can add their shards up.
+    by_level (a NoiseLevelLoss): also receives every window's loss against the prediction type's OWN target (eegldm_diffusion_loss,
+    unweighted) -- the returned sum, the model-selection criterion, is unchanged."""
     from .._lib import lib, check, ptr
     unet.eval()
     tot, n, dev, ctx = 0.0, 0, unet.device, unet.ctx
@@ -62,6 +66,12 @@ def validate(unet, stage1, sched, loader, scale_factor, seeds, latent_channels):
         e = stage1.encode_stage_2_inputs(x, eps=eps, scale_factor=scale_factor)
         pred = unet(sched.add_noise(original_samples=e, noise=noise, timesteps=t), timesteps=t, y=batch.get("label"))
         check(lib.eegldm_mse_loss(ctx.h, ptr(pred), ptr(noise), ptr(out), None, pred.numel(), 1.0))
+        if by_level is not None:
+            from .._lib import PRED
+            per, own = torch.empty(B, device=dev), torch.zeros(1, device=dev)
+            check(lib.eegldm_diffusion_loss(ctx.h, ptr(pred), ptr(e), ptr(noise), ptr(t), ptr(sched._acp_dev), None, PRED[sched.prediction_type],
+                                            B, pred[0].numel(), 1.0, ptr(own), ptr(per), None))
+            by_level.add(per, t, ctx=ctx)
         tot += float(out) * B; n += B; seen += B
     unet.train()
     return tot, n
@@ -135,12 +145,19 @@ def main(args):
             scaler.load_state_dict(ck["scaler"])
         start_epoch, best, scale_factor = int(ck["epoch"]), float(ck["best_loss"]), float(ck["scale_factor"])
         gstep = int(ck.get("steps", 0))
+        loss_weighting_resume(args, ck)
         if ema is not None:
             best_ema = ema_resume(ema, ck, rank)
         if rank == 0:
             print(f"Resuming from epoch {start_epoch} (best loss {best:.5f}, scale factor {scale_factor})")
+    save_weighting = args.loss_weighting is not None             # (after the resume: a restored setting is written again)
+    wkw = step_weighting(args)                                   # {} without the flags: the plain exports, as before
+    K = int(args.loss_by_noise_level)
+    train_levels = NoiseLevelLoss(sched.num_train_timesteps, K) if K else None
     for epoch in range(start_epoch, config.train.n_epochs):
         unet.train()
+        if train_levels is not None:
+            train_levels.reset()
         for batch in train:
             x = batch["eeg"].to(dev)
             B = x.shape[0]
@@ -150,7 +167,11 @@ def main(args):
             e = stage1.encode_stage_2_inputs(x, eps=eps, scale_factor=scale_factor)
             opt.zero_grad()
             lab = dict(labels=batch["label"].to(dev), p_uncond=args.p_uncond, null_class=null_class, seed=s_lab, offset=gstep * B) if cond else {}
-            ldm_train_step(unet, sched, e, noise, t, loss_out=loss, grad_scale=scaler.get_scale(), grad_sync=gsync, **lab)
+            if train_levels is not None:
+                wkw["per_sample_out"] = torch.empty(B, device=dev)
+            ldm_train_step(unet, sched, e, noise, t, loss_out=loss, grad_scale=scaler.get_scale(), grad_sync=gsync, **lab, **wkw)
+            if train_levels is not None:
+                train_levels.add(wkw["per_sample_out"], t, ctx=ctx)
             gsync.wait()
             scaler.step(opt); scaler.update()
             steps += 1; gstep += 1; seen += B * world
@@ -158,16 +179,27 @@ def main(args):
                 break
         do_eval = (epoch + 1) % config.train.get("eval_freq", 1) == 0 or bool(args.max_steps and steps >= args.max_steps)
         cur = float(loss)
+        lv, lv_ema = (NoiseLevelLoss(sched.num_train_timesteps, K), NoiseLevelLoss(sched.num_train_timesteps, K)) if K else (None, None)
         if do_eval and valid is not None:      # model selection on the validation split (training.py:356-380), epsilon MSE over its windows
-            v_sum, v_n = D.allreduce_sum_scalars(validate(unet, stage1, sched, valid, scale_factor, v_seeds, args.latent_channels), like=loss)
+            v_sum, v_n = D.allreduce_sum_scalars(validate(unet, stage1, sched, valid, scale_factor, v_seeds, args.latent_channels, by_level=lv), like=loss)
             cur = v_sum / max(1.0, v_n)
         cur_ema = None                         # no validation split: no loss of the averaged weights exists
         if do_eval and valid is not None and ema is not None:      # the same windows and noise, scored with the averaged weights
             with ema.applied():
-                e_sum, e_n = D.allreduce_sum_scalars(validate(unet, stage1, sched, valid, scale_factor, v_seeds, args.latent_channels), like=loss)
+                e_sum, e_n = D.allreduce_sum_scalars(validate(unet, stage1, sched, valid, scale_factor, v_seeds, args.latent_channels, by_level=lv_ema), like=loss)
             cur_ema = e_sum / max(1.0, e_n)
+        if K and do_eval:                      # every rank joins the sums; rank 0 prints and writes
+            record = {"epoch": epoch + 1, "steps": gstep, "prediction_type": sched.prediction_type, "bins": K,
+                      "train": train_levels.merge(like=loss).table(),
+                      "valid": lv.merge(like=loss).table() if valid is not None else None,
+                      "valid_ema": lv_ema.merge(like=loss).table() if valid is not None and ema is not None else None}
         if rank == 0:
             print(f"epoch {epoch}: loss {float(loss):.5f} | {seen/(time.time()-t0):.1f} windows/s", flush=True)
+            if K and do_eval:
+                for name in ("train", "valid", "valid_ema"):
+                    if record[name] is not None:
+                        print(format_noise_level_table(name, record[name]), flush=True)
+                append_noise_level_record(run_dir, record)
             if do_eval:
                 new_best = cur <= best
                 if new_best:
@@ -183,6 +215,8 @@ def main(args):
                     if new_best:
                         torch.save(cpu_state(ema.state_dict()), os.path.join(run_dir, "best_model_ema.pth"))
                     ck_out["ema"] = ema_checkpoint_entry(ema, best_ema)
+                if save_weighting:
+                    ck_out["loss_weighting"] = {"weighting": args.loss_weighting, "snr_gamma": float(args.snr_gamma)}
                 torch.save(ck_out, os.path.join(run_dir, "checkpoint.pth"))
         if args.max_steps and steps >= args.max_steps:
             break
@@ -190,7 +224,8 @@ def main(args):
         torch.save({k: v.cpu() for k, v in unet.state_dict().items()}, os.path.join(run_dir, "final_model.pth"))
         if ema is not None:
             torch.save(cpu_state(ema.state_dict()), os.path.join(run_dir, "final_model_ema.pth"))
-    LAST_RUN.clear(); LAST_RUN.update(rank=rank, world=world, scale_factor=scale_factor, steps=steps, param_sum=float(unet.flat.double().sum()))
+    LAST_RUN.clear(); LAST_RUN.update(rank=rank, world=world, scale_factor=scale_factor, steps=steps, param_sum=float(unet.flat.double().sum()),
+                                     loss_weighting=args.loss_weighting, snr_gamma=args.snr_gamma)
     return run_dir
 
 

@@ -300,18 +300,38 @@ def set_grad_hook(unet, fn):
     check(lib.eegldm_unet_set_grad_hook(unet.h, C.cast(thunk, C.c_void_p), None))
 
 
+def _weighting_args(scheduler, loss_weighting, snr_gamma, per_sample_out, B, device):
+    """-> (weighted, device table or None).  Raises before the device is touched."""
+    if loss_weighting is None:
+        if per_sample_out is not None:
+            raise ValueError('per_sample_out needs the weighted loss: pass loss_weighting ("none" leaves every sample at weight 1)')
+        return False, None
+    from .schedulers import device_loss_weights
+    wtab = device_loss_weights(scheduler, loss_weighting, snr_gamma)
+    if per_sample_out is not None:
+        if per_sample_out.dtype != torch.float32 or per_sample_out.numel() != B or not per_sample_out.is_contiguous():
+            raise ValueError(f"per_sample_out must be a contiguous float32 tensor of {B} elements")
+        if not per_sample_out.is_cuda or per_sample_out.device != torch.device(device):      # (a host pointer would reach the kernel)
+            raise ValueError(f"per_sample_out must live on the model's device {device}, got {per_sample_out.device}")
+    return True, wtab
+
+
 def ldm_train_step(unet, scheduler, latents, noise, timesteps, loss_out=None, grad_scale=1.0, grad_sync=None, labels=None, p_uncond=0.0,
-                   null_class=None, seed=0, offset=0):
+                   null_class=None, seed=0, offset=0, loss_weighting=None, snr_gamma=5.0, per_sample_out=None):
     """add_noise -> UNet forward -> MSE against noise (epsilon) or velocity (v_prediction) -> backward.
     Accumulates into unet.flat_grad; returns the device scalar loss tensor.  grad_sync: an
     eegldm.distributed.OverlappedGradSync -- the tail of the gradient buffer is all-reduced while the input blocks'
     backward still runs, the rest right after the call; the caller then only has to `grad_sync.wait()`.
     labels (a UNet built with num_classes): the class of every sample, (B,) integers.  Classifier-free guidance training: with
     probability p_uncond a sample's label is replaced by null_class on the device, drawn from the Philox stream (seed, offset + b)
-    -- advance `offset` by B per step; the backward uses the replaced labels."""
+    -- advance `offset` by B per step; the backward uses the replaced labels.
+    loss_weighting: None (default) = the plain MSE through the exports above.  "none" / "min_snr" / a (T,) table (schedulers.loss_weights,
+    snr_gamma) = the weighted step (eegldm_ldm_train_step_weighted): sample b counts wtab[t_b] in the loss and its gradient, and
+    per_sample_out (a (B,) float32 device tensor) receives the UNWEIGHTED per-sample losses (for NoiseLevelLoss)."""
+    B, _C, L = latents.shape
+    weighted, wtab = _weighting_args(scheduler, loss_weighting, snr_gamma, per_sample_out, B, unet.device)
     if loss_out is None:
         loss_out = torch.zeros(1, device=unet.device)
-    B, _C, L = latents.shape
     cond = getattr(unet, "num_classes", None) is not None
     if cond != (labels is not None):
         raise ValueError("labels must be given if and only if the UNet is class-conditional")
@@ -330,7 +350,12 @@ def ldm_train_step(unet, scheduler, latents, noise, timesteps, loss_out=None, gr
         grad_sync.begin()
         set_grad_hook(unet, grad_sync.on_ready)
     try:
-        if cond:
+        if weighted:
+            check(lib.eegldm_ldm_train_step_weighted(unet.h, ptr(latents), ptr(noise), ptr(timesteps), ptr(scheduler._acp_dev),
+                                                     PRED[scheduler.prediction_type], B, L, grad_scale, ptr(loss_out), ptr(wtab),
+                                                     ptr(per_sample_out), ptr(lab) if cond else None, float(p_uncond) if cond else 0.0,
+                                                     nc if cond else 0, int(seed), int(offset)))
+        elif cond:
             check(lib.eegldm_ldm_train_step_cond(unet.h, ptr(latents), ptr(noise), ptr(timesteps), ptr(scheduler._acp_dev),
                                                  PRED[scheduler.prediction_type], B, L, grad_scale, ptr(loss_out), ptr(lab), float(p_uncond),
                                                  nc, int(seed), int(offset)))
@@ -346,13 +371,17 @@ def ldm_train_step(unet, scheduler, latents, noise, timesteps, loss_out=None, gr
     return loss_out
 
 
-def dm_train_step(unet, scheduler, images, noise, timesteps, spectral_weight=0.0, spectral_loss=False, loss_out=None, grad_sync=None, grad_scale=1.0):
+def dm_train_step(unet, scheduler, images, noise, timesteps, spectral_weight=0.0, spectral_loss=False, loss_out=None, grad_sync=None, grad_scale=1.0,
+                  loss_weighting=None, snr_gamma=5.0, per_sample_out=None):
     """Pixel-space diffusion step of /root/reference/src/training/training_diffusion.py:141-151 (config_dm.yaml, BASELINE C5):
     epsilon prediction directly on the (B,1,3072) windows, loss = mse(noise_pred, noise) [+ spectral_weight *
     JukeboxLoss(sum)(noise_pred, noise)].  Composed from the same native calls as the latent step: add_noise, UNet forward,
     MSE (writes d pred), spectral loss (accumulates its gradient into d pred), hand-written backward.  Returns the loss tensor.
     grad_scale: the GradScaler's loss scale (training_diffusion.py:37,149-151 -- `scaler.scale(loss).backward()`): it multiplies d pred, i.e.
-    every gradient of the backward; the reported loss stays unscaled and the optimizer step divides the scale out again (GradScaler.step)."""
+    every gradient of the backward; the reported loss stays unscaled and the optimizer step divides the scale out again (GradScaler.step).
+    loss_weighting / snr_gamma / per_sample_out: as in ldm_train_step -- eegldm_diffusion_loss (target of the scheduler's prediction type) in
+    place of eegldm_mse_loss; the spectral term still accumulates into d pred afterwards, unweighted."""
+    weighted, wtab = _weighting_args(scheduler, loss_weighting, snr_gamma, per_sample_out, images.shape[0], unet.device)
     dev = unet.device
     if loss_out is None:
         loss_out = torch.zeros(1, device=dev)
@@ -362,7 +391,12 @@ def dm_train_step(unet, scheduler, images, noise, timesteps, spectral_weight=0.0
     noisy = scheduler.add_noise(original_samples=x, noise=nz, timesteps=timesteps)
     pred = unet(noisy, timesteps=timesteps)
     dpred = torch.empty_like(pred)
-    check(lib.eegldm_mse_loss(unet.ctx.h, ptr(pred), ptr(nz), ptr(loss_out), ptr(dpred), pred.numel(), float(grad_scale)))
+    if weighted:
+        t = timesteps.to(dev, torch.int64).contiguous()
+        check(lib.eegldm_diffusion_loss(unet.ctx.h, ptr(pred), ptr(x), ptr(nz), ptr(t), ptr(scheduler._acp_dev), ptr(wtab),
+                                        PRED[scheduler.prediction_type], B, Cc * L, float(grad_scale), ptr(loss_out), ptr(per_sample_out), ptr(dpred)))
+    else:
+        check(lib.eegldm_mse_loss(unet.ctx.h, ptr(pred), ptr(nz), ptr(loss_out), ptr(dpred), pred.numel(), float(grad_scale)))
     if spectral_loss:
         spec = torch.zeros(1, device=dev)
         check(lib.eegldm_spectral_loss(unet.ctx.h, ptr(pred), ptr(nz), ptr(spec), ptr(dpred), B, Cc, L, float(spectral_weight) * float(grad_scale)))
@@ -378,6 +412,88 @@ def dm_train_step(unet, scheduler, images, noise, timesteps, spectral_weight=0.0
     if grad_sync is not None:
         grad_sync.finish()
     return loss_out
+
+
+class NoiseLevelLoss:
+    """Loss by noise level: the unweighted per-sample losses of many steps, accumulated into `bins` equal ranges of the timestep
+    (bin k = t * bins // num_train_timesteps), so that a run can be read at the noise levels that matter instead of as one average over
+    values that differ by orders of magnitude.
+
+        nll = NoiseLevelLoss(1000, bins=10)
+        ldm_train_step(..., loss_weighting="min_snr", per_sample_out=per); nll.add(per, t)      # no host synchronisation
+        nll.table()  -> [{"t_lo", "t_hi", "count", "mean"}, ...]      (mean None for an empty bin)
+
+    Device tensors go through eegldm_loss_bins into fp32 / int64 device accumulators (samples in ascending order: order-fixed); numpy
+    arrays and CPU tensors are accumulated on the host in float64.  state() / merge() add several ranks' accumulators.
+    Precision of the device path: a bin's sum is ONE float32 running sum over everything added since reset(), so after n windows in a bin
+    its mean can be off by up to about n * 2^-24 relative (1e5 windows: below 1 %, typically 1e-4 to 1e-3) -- a monitoring table, not a
+    number to select models on at many digits.  reset() per epoch (as the train scripts do) or fold state() into a host accumulator
+    (load_state) more often where that matters."""
+
+    def __init__(self, num_train_timesteps, bins=10):
+        T, K = int(num_train_timesteps), int(bins)
+        if T < 1 or not 1 <= K <= T:
+            raise ValueError(f"bins must lie in [1, num_train_timesteps], got bins={bins}, num_train_timesteps={num_train_timesteps}")
+        self.num_train_timesteps, self.bins = T, K
+        self.reset()
+
+    def reset(self):
+        self._sum, self._cnt = [0.0] * self.bins, [0] * self.bins
+        self._dev = None            # (ctx, bin_sum float32 (K,), bin_cnt int64 (K,)) once a device tensor has been added
+
+    def add(self, per_sample, timesteps, ctx=None):
+        if torch.is_tensor(per_sample) and per_sample.is_cuda:
+            ps = per_sample.detach().reshape(-1).to(torch.float32).contiguous()
+            t = timesteps.to(ps.device, torch.int64).reshape(-1).contiguous()
+            if t.numel() != ps.numel():
+                raise ValueError(f"{ps.numel()} losses but {t.numel()} timesteps")
+            if self._dev is None:
+                from ._lib import default_context
+                c = ctx or default_context(ps.device.index or 0)
+                self._dev = (c, torch.zeros(self.bins, device=ps.device), torch.zeros(self.bins, dtype=torch.int64, device=ps.device))
+            c, bsum, bcnt = self._dev
+            check(lib.eegldm_loss_bins(c.h, ptr(ps), ptr(t), ps.numel(), self.num_train_timesteps, self.bins, ptr(bsum), ptr(bcnt)))
+            return self
+        ps = [float(v) for v in (per_sample.detach().reshape(-1).tolist() if torch.is_tensor(per_sample) else list(per_sample))]
+        ts = [int(v) for v in (timesteps.reshape(-1).tolist() if torch.is_tensor(timesteps) else list(timesteps))]
+        if len(ps) != len(ts):
+            raise ValueError(f"{len(ps)} losses but {len(ts)} timesteps")
+        for m, t in zip(ps, ts):
+            if 0 <= t < self.num_train_timesteps:
+                k = t * self.bins // self.num_train_timesteps
+                self._sum[k] += m; self._cnt[k] += 1
+        return self
+
+    def state(self):
+        """[sum_0 .. sum_{K-1}, count_0 .. count_{K-1}] as Python floats: host and device accumulators together (reads the device)."""
+        s, n = list(self._sum), list(self._cnt)
+        if self._dev is not None:
+            _c, bsum, bcnt = self._dev
+            s = [a + float(b) for a, b in zip(s, bsum.tolist())]; n = [a + int(b) for a, b in zip(n, bcnt.tolist())]
+        return [float(v) for v in s] + [float(v) for v in n]
+
+    def load_state(self, state):
+        K = self.bins
+        if len(state) != 2 * K:
+            raise ValueError(f"a state of {2 * K} numbers is expected, got {len(state)}")
+        self.reset()
+        self._sum, self._cnt = [float(v) for v in state[:K]], [int(round(float(v))) for v in state[K:]]
+        return self
+
+    def merge(self, like=None):
+        """Adds the accumulators of all ranks (distributed.allreduce_sum_scalars; one process: unchanged).  Every rank ends with the total."""
+        from . import distributed as D
+        return self.load_state(D.allreduce_sum_scalars(self.state(), like=like))
+
+    def table(self):
+        T, K = self.num_train_timesteps, self.bins
+        st = self.state()
+        rows = []
+        for k in range(K):
+            lo, hi = -(-k * T // K), -(-(k + 1) * T // K) - 1       # the timesteps t with t * K // T == k
+            n = int(st[K + k])
+            rows.append({"t_lo": lo, "t_hi": hi, "count": n, "mean": (st[k] / n) if n else None})
+        return rows
 
 
 def randn(ctx, shape, seed, offset=0, device=None):
