@@ -46,7 +46,7 @@ extern "C" {
  *    Added since without a version change (new symbols only): the class-conditional entry points, the weight EMA (eegldm_adam_step_ema,
  *    eegldm_ema_update, eegldm_swap), the multistep sampler (eegldm_multistep_step, eegldm_sample_multistep) and editing (eegldm_edit_step,
  *    eegldm_edit_start, eegldm_edit_window, eegldm_sample_edit) and the weighted diffusion loss (eegldm_diffusion_loss, eegldm_loss_bins,
- *    eegldm_ldm_train_step_weighted). */
+ *    eegldm_ldm_train_step_weighted) and global gradient-norm clipping (eegldm_grad_norm, eegldm_adam_step_clip, eegldm_grad_scale_by). */
 #define EEGLDM_ABI_VERSION 8
 
 /* Storage / operand type of activations and compute-copy weights (accumulation, statistics, master weights and optimizer state are
@@ -256,6 +256,28 @@ int eegldm_adam_step_ema(eegldm_ctx*, float* p, const float* g, float* m, float*
                          float beta2, float eps, int step, float grad_inv_scale, float one_minus_decay);
 int eegldm_ema_update(eegldm_ctx*, float* ema, const float* p, long n, float one_minus_decay);
 int eegldm_swap(eegldm_ctx*, float* a, float* b, long n);
+/* Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, L2 norm over the whole flat gradient) without a host read.
+ * state: 8 device floats owned by the caller, zeroed once; eegldm_grad_norm leaves
+ *   state[0]  sqrt(sum_i (g[i] * pre_scale)^2): the norm of the un-scaled gradient (pre_scale = 1 / loss scale)
+ *   state[1]  coef = min(1, max_norm / (state[0] + 1e-6f)) in fp32, exactly that expression (torch's clip_coef_clamped; max_norm = +inf gives
+ *             1 for a finite norm; a NaN norm gives NaN, an infinite one 0 or, with max_norm = +inf, NaN -- as in torch; nothing is skipped)
+ *   state[2]  1 if any g[i] is inf / NaN, else 0 (the answer of eegldm_grad_check_finite)
+ *   state[3]  += 1 when coef < 1 (steps clipped)     state[4]  += 1 (calls)     state[5]  = max(state[5], state[0])     state[6..7]  untouched
+ * Reduction: one fp32 partial per chunk of 16384 elements (a constant: no dependence on the device or the grid), inside a chunk a fixed
+ * per-thread order of fused multiply-adds (16-byte loads on the aligned body, scalar head and tail; any n >= 0, any 4-byte alignment), a
+ * wave butterfly and a pairwise sum of the waves; a one-block kernel then folds the partials in index order in double.  No float atomics, no
+ * memset: the same bits on every run, with or without EEGLDM_DETERMINISTIC.  The partials live in the context's written-partials buffer
+ * (as eegldm_diffusion_loss's): the first call on a context that has not used that buffer allocates it (32 MiB, once), and a call that
+ * needs more than it holds (n above 6.8e10) synchronises the stream to regrow it; every other call is launches only.  A finite |g[i] * pre_scale| above 1.8e19 overflows the fp32 sum of squares (as torch's fp32 norm does).
+ * NULL buffers, n < 0, max_norm <= 0 and a NaN max_norm are rejected before the device is touched (state stays as it was).
+ *   eegldm_adam_step_clip  eegldm_adam_step (ema NULL) / eegldm_adam_step_ema with grad_inv_scale * state[1] -- ONE fp32 product, read from
+ *                          the device -- in place of grad_inv_scale: with state[1] == 1 the bytes of those exports, with state[1] = c the bytes
+ *                          they give for the host float grad_inv_scale * c.  g is not modified.  Refusals as eegldm_adam_step_ema.
+ *   eegldm_grad_scale_by   g[i] *= state[1] in place: the second half of a stand-alone clip_grad_norm_ (parameters stepped by another optimizer) */
+int eegldm_grad_norm(eegldm_ctx*, const float* g, long n, float pre_scale, float max_norm, float* state);
+int eegldm_adam_step_clip(eegldm_ctx*, float* p, const float* g, float* m, float* v, float* ema /* nullable */, long n, float lr, float beta1,
+                          float beta2, float eps, int step, float grad_inv_scale, float one_minus_decay, const float* state);
+int eegldm_grad_scale_by(eegldm_ctx*, float* g, long n, const float* state);
 /* found_inf[0] (device float) = 1 if any of g[0..n) is inf/nan, else 0 -- the check behind GradScaler.unscale_/step
  * (torch.cuda.amp.GradScaler at /root/reference/src/training/training.py:334,441-443). g must be 16-byte aligned. */
 int eegldm_grad_check_finite(eegldm_ctx*, const float* g, long n, float* found_inf);

@@ -100,6 +100,9 @@ SIGNATURES = {
     "eegldm_adam_step_ema": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _i, _f, _f],
     "eegldm_ema_update": [_vp, _vp, _vp, _l, _f],
     "eegldm_swap": [_vp, _vp, _vp, _l],
+    "eegldm_grad_norm": [_vp, _vp, _l, _f, _f, _vp],
+    "eegldm_adam_step_clip": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _i, _f, _f, _vp],
+    "eegldm_grad_scale_by": [_vp, _vp, _l, _vp],
     "eegldm_grad_check_finite": [_vp, _vp, _l, _vp],
     "eegldm_randn": [_vp, _vp, _l, C.c_uint64, C.c_uint64],
     "eegldm_randint": [_vp, _vp, _l, C.c_int64, C.c_uint64, C.c_uint64],

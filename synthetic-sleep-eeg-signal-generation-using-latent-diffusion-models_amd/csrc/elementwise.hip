@@ -515,6 +515,118 @@ __global__ __launch_bounds__(NT) void adam_ema_kernel(float* __restrict__ p, con
     e[i] = ema_elem(e[i], pi, c);
   }
 }
+// ------------------------------------------------------------------ global gradient-norm clipping (include/eegldm.h)
+// The clipped update is the update above with ginv * state[1]: the coefficient stays on the device (eegldm_grad_norm wrote it), one fp32
+// product per thread, everything else through adam_elem / ema_elem -- with state[1] == 1 the bytes of adam_kernel / adam_ema_kernel.
+template <bool EMA>
+__global__ __launch_bounds__(NT) void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                       float* __restrict__ e, long n, long head, float lr, float b1, float b2, float eps,
+                                                       float bc1, float bc2_sqrt, float ginv0, const float* __restrict__ state, float c) {
+  float ginv;
+  {
+#pragma clang fp contract(off)
+    ginv = ginv0 * state[1];
+  }
+  const VecSplit s = vec_split(n, head);
+  f32x4* p4 = (f32x4*)(p + head); const f32x4* g4 = (const f32x4*)(g + head); f32x4* m4 = (f32x4*)(m + head); f32x4* v4 = (f32x4*)(v + head);
+  f32x4* e4 = EMA ? (f32x4*)(e + head) : nullptr;
+  GRID_STRIDE(i, s.n4) {
+    f32x4 pv = p4[i], mv = m4[i], vv = v4[i], ev;
+    if (EMA) ev = e4[i];
+    const f32x4 gv = g4[i];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      float pk = pv[k], mk = mv[k], vk = vv[k];
+      adam_elem(pk, gv[k], mk, vk, lr, b1, b2, eps, bc1, bc2_sqrt, ginv);
+      pv[k] = pk; mv[k] = mk; vv[k] = vk;
+      if (EMA) ev[k] = ema_elem(ev[k], pk, c);
+    }
+    m4[i] = mv; v4[i] = vv; p4[i] = pv;
+    if (EMA) e4[i] = ev;
+  }
+  GRID_STRIDE(j, s.nedge) {
+    const long i = EDGE_INDEX(s, j);
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_elem(pi, g[i], mi, vi, lr, b1, b2, eps, bc1, bc2_sqrt, ginv);
+    m[i] = mi; v[i] = vi; p[i] = pi;
+    if (EMA) e[i] = ema_elem(e[i], pi, c);
+  }
+}
+__global__ __launch_bounds__(NT) void grad_scale_by_kernel(float* __restrict__ g, long n, long head, const float* __restrict__ state) {
+  const float c = state[1];
+  const VecSplit s = vec_split(n, head);
+  f32x4* g4 = (f32x4*)(g + head);
+  GRID_STRIDE(i, s.n4) {
+    f32x4 gv = g4[i];
+#pragma unroll
+    for (int k = 0; k < 4; k++) gv[k] = gv[k] * c;
+    g4[i] = gv;
+  }
+  GRID_STRIDE(j, s.nedge) { const long i = EDGE_INDEX(s, j); g[i] = g[i] * c; }
+}
+// Sum of squares of g * pre_scale, one block per chunk of GN_CHUNK elements whatever the device: the chunking, and with it every bit of the
+// result, depends on n and on g's offset inside a 16-byte line only.  Thread t adds its float4s t, t + NT, ... (at most GN_CHUNK / 4 / NT = 16
+// of them, four fused multiply-adds each, in element order), then at most one scalar edge element; a butterfly over the wave and a pairwise
+// sum of the four waves follow.  parts[c] = the chunk's sum, parts[nchunk + c] = 1 if the chunk holds an inf / NaN (of g itself), else 0.
+constexpr int GN_CHUNK = 16384;
+constexpr int GN_TILE = 2048;       // partials staged in LDS per round of the fold
+__global__ __launch_bounds__(NT) void grad_norm_partial_kernel(const float* __restrict__ g, long n, int head0, float pre_scale, long nchunk,
+                                                               float* __restrict__ parts) {
+#pragma clang fp contract(off)
+  const long start = (long)blockIdx.x * GN_CHUNK;
+  const long left = n - start, len = left < GN_CHUNK ? left : GN_CHUNK;
+  const long head = head0 < len ? head0 : len;      // (start is a multiple of 4: every chunk has g's misalignment)
+  const VecSplit s = vec_split(len, head);
+  const float* gp = g + start;
+  const f32x4* g4 = (const f32x4*)(gp + head);
+  float acc = 0.0f, fin = 0.0f;
+#pragma unroll 4
+  for (long i = threadIdx.x; i < s.n4; i += NT) {
+    const f32x4 gv = g4[i];
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const float x = gv[k] * pre_scale; acc = fmaf(x, x, acc); fin += gv[k] - gv[k]; }      // (x - x): 0 for a finite x, NaN otherwise
+  }
+  for (long j = threadIdx.x; j < s.nedge; j += NT) {
+    const long i = EDGE_INDEX(s, j);
+    const float x = gp[i] * pre_scale; acc = fmaf(x, x, acc); fin += gp[i] - gp[i];
+  }
+  acc = wave_sum(acc);
+  __shared__ float red[NT / 64];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  const int bad = __syncthreads_or(fin != 0.0f);
+  if (threadIdx.x == 0) { parts[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]); parts[nchunk + blockIdx.x] = bad ? 1.0f : 0.0f; }
+}
+// One block: the partials in index order, in double -- thread t folds the 8 consecutive partials [8 t, 8 t + 8) of a tile, thread 0 then adds
+// the threads' sums in thread order.  state: see include/eegldm.h.
+__global__ __launch_bounds__(NT) void grad_norm_fold_kernel(const float* __restrict__ parts, long nchunk, float max_norm, float* __restrict__ state) {
+#pragma clang fp contract(off)
+  __shared__ float tile[GN_TILE];
+  __shared__ double seg[NT];
+  constexpr int PER = GN_TILE / NT;
+  double total = 0.0;
+  int bad = 0;
+  for (long c0 = 0; c0 < nchunk; c0 += GN_TILE) {
+    const int nb = (int)(nchunk - c0 < GN_TILE ? nchunk - c0 : GN_TILE);
+    for (int i = threadIdx.x; i < nb; i += NT) { tile[i] = parts[c0 + i]; bad |= parts[nchunk + c0 + i] != 0.0f; }
+    __syncthreads();
+    double sseg = 0.0;
+    for (int k = 0; k < PER; k++) { const int i = threadIdx.x * PER + k; if (i < nb) sseg = sseg + (double)tile[i]; }
+    seg[threadIdx.x] = sseg;
+    __syncthreads();
+    if (threadIdx.x == 0) { const int nseg = (nb + PER - 1) / PER; for (int i = 0; i < nseg; i++) total = total + seg[i]; }
+    __syncthreads();
+  }
+  bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(total);      // one rounding: the double sum and its root carry 2^-53
+    const float q = max_norm / (norm + 1e-6f);
+    const float coef = q < 1.0f ? q : (q != q ? q : 1.0f);      // torch's clamp(max = 1): a NaN stays a NaN
+    state[0] = norm; state[1] = coef; state[2] = bad ? 1.0f : 0.0f;
+    if (coef < 1.0f) state[3] = state[3] + 1.0f;
+    state[4] = state[4] + 1.0f;
+    state[5] = fmaxf(state[5], norm);
+  }
+}
 // ------------------------------------------------------------------ linear multistep sampler step (DPM-Solver++ 2M; include/eegldm.h)
 // One launch per sampling step, whatever the solver: o = the model output (guided: o_u + w (o_c - o_u), the expression of cfg_step_kernel),
 // x0 from o by the prediction type with the arithmetic of ddim_step_kernel, prev = cx * sample + c0 * x0 + c1 * hist, hist <- x0.  The three
@@ -1299,6 +1411,60 @@ extern "C" int eegldm_ema_update(eegldm_ctx* ctx, float* ema, const float* p, lo
   if (n == 0) return 0;
   const long head = vec_head(n, {ema, p});
   hipLaunchKernelGGL(ema_update_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, ema, p, n, head, one_minus_decay);
+  LAUNCH_CHECK(); return 0;
+}
+// ---- global gradient-norm clipping (include/eegldm.h): the norm pass, the clipped Adam (+ EMA) update, the in-place scale
+extern "C" int eegldm_grad_norm(eegldm_ctx* ctx, const float* g, long n, float pre_scale, float max_norm, float* state) {
+  EEG_CHECK(ctx && g && state, "null argument");
+  EEG_CHECK(n >= 0, "negative n (%ld)", n);
+  EEG_CHECK(max_norm > 0.0f, "max_norm must be > 0 (got %g)", (double)max_norm);      // (a NaN fails the comparison)
+  EEG_CHECK(((uintptr_t)g & 3) == 0 && ((uintptr_t)state & 3) == 0, "buffers must be 4-byte aligned");
+  EEG_CHECK(!(state < g + n && g < state + 8), "the state buffer aliases the gradient");
+  const long nchunk = (n + GN_CHUNK - 1) / GN_CHUNK;
+  EEG_CHECK(nchunk <= 0x7fffffffL, "ceil(n / %d) = %ld blocks: too many", GN_CHUNK, nchunk);
+  float* parts = nullptr;
+  EEG_TRY(eeg_det_buffer(ctx, (size_t)(2 * nchunk + 1) * sizeof(float), &parts));
+  if (nchunk > 0) {
+    const int head0 = (int)(((16 - ((uintptr_t)g & 15)) & 15) >> 2);
+    hipLaunchKernelGGL(grad_norm_partial_kernel, dim3((unsigned)nchunk), dim3(NT), 0, ctx->stream, g, n, head0, pre_scale, nchunk, parts);
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(grad_norm_fold_kernel, dim3(1), dim3(NT), 0, ctx->stream, parts, nchunk, max_norm, state);
+  LAUNCH_CHECK(); return 0;
+}
+extern "C" int eegldm_adam_step_clip(eegldm_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1,
+                                     float b2, float eps, int step, float ginv, float one_minus_decay, const float* state) {
+  EEG_CHECK(p && g && m && v && state, "null buffer");
+  EEG_CHECK(n >= 0, "negative n (%ld)", n);
+  EEG_CHECK(!ema || (ema != p && !ranges_overlap(ema, p, n) && !ranges_overlap(ema, g, n) && !ranges_overlap(ema, m, n) && !ranges_overlap(ema, v, n)),
+            "the EMA buffer aliases a parameter / gradient / moment buffer");
+  for (const float* q : {(const float*)p, (const float*)m, (const float*)v, (const float*)ema})
+    EEG_CHECK(!q || !(state < q + n && q < state + 8), "the state buffer aliases a buffer the update writes");
+  EEG_CHECK(ctx, "null ctx");
+  EEG_CHECK(step >= 1, "step starts at 1");
+  EEG_CHECK(((uintptr_t)p & 3) == 0 && ((uintptr_t)g & 3) == 0 && ((uintptr_t)m & 3) == 0 && ((uintptr_t)v & 3) == 0 && ((uintptr_t)ema & 3) == 0 &&
+            ((uintptr_t)state & 3) == 0, "buffers must be 4-byte aligned");
+  if (n == 0) return 0;
+  const float bc1 = 1.0f - powf(b1, (float)step), bc2s = sqrtf(1.0f - powf(b2, (float)step));      // as eegldm_adam_step
+  if (ema) {
+    const long head = vec_head(n, {p, g, m, v, ema});
+    hipLaunchKernelGGL(adam_clip_kernel<true>, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, p, g, m, v, ema, n, head, lr, b1, b2, eps,
+                       bc1, bc2s, ginv, state, one_minus_decay);
+  } else {
+    const long head = vec_head(n, {p, g, m, v});
+    hipLaunchKernelGGL(adam_clip_kernel<false>, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, p, g, m, v, (float*)nullptr, n, head, lr, b1,
+                       b2, eps, bc1, bc2s, ginv, state, 0.0f);
+  }
+  LAUNCH_CHECK(); return 0;
+}
+extern "C" int eegldm_grad_scale_by(eegldm_ctx* ctx, float* g, long n, const float* state) {
+  EEG_CHECK(ctx && g && state, "null argument");
+  EEG_CHECK(n >= 0, "negative n (%ld)", n);
+  EEG_CHECK(((uintptr_t)g & 3) == 0 && ((uintptr_t)state & 3) == 0, "buffers must be 4-byte aligned");
+  EEG_CHECK(n == 0 || !(state < g + n && g < state + 8), "the state buffer aliases the gradient");
+  if (n == 0) return 0;
+  const long head = vec_head(n, {g});
+  hipLaunchKernelGGL(grad_scale_by_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, g, n, head, state);
   LAUNCH_CHECK(); return 0;
 }
 // One linear multistep step as one launch (multistep_step_kernel).  The float4 body needs every buffer in use -- the null-class half of

@@ -236,6 +236,7 @@ class OverlappedGradSync:
         self.bucket = int(bucket_elems)
         self.works = []
         self.done = []          # (start, end) ranges already launched
+        self.rounds = 0         # begin() calls so far: gradient exchanges started (one per optimizer step, also under accumulation)
         self._post_scale = True
         if comm is None:        # AVG-or-SUM is agreed on here, once and by all ranks -- not inside the backward's gradient hook
             probe_mean_op(flat_grad)
@@ -248,6 +249,7 @@ class OverlappedGradSync:
 
     def begin(self):
         self.works, self.done = [], []
+        self.rounds += 1
 
     def _launch(self, a, b):
         if self.comm is not None:     # ordered after the Context's stream inside the library; one group of bucketed ncclAvg collectives

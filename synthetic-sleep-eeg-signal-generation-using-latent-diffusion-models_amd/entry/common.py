@@ -250,6 +250,88 @@ def loss_weighting_resume(args, ck):
                          "or resume with the checkpoint's setting")
 
 
+def _positive_float(text):
+    x = float(text)
+    if not x > 0.0:
+        raise argparse.ArgumentTypeError(f"must be > 0 (inf = measure only), got {text}")
+    return x
+
+
+def _positive_int(text):
+    k = int(text)
+    if k < 1:
+        raise argparse.ArgumentTypeError(f"must be >= 1, got {text}")
+    return k
+
+
+def add_grad_clip_args(p, accum=True):
+    p.add_argument("--max_grad_norm", type=_positive_float, default=None, help="clip the global L2 norm of the gradient to this value before every "
+                   "optimizer step (on the device, inside the Adam launch; after the all-reduce in data-parallel runs); adds the grad-norm "
+                   "figures to the epoch line and the 'grad_clip' entry to checkpoint.pth")
+    if accum:
+        p.add_argument("--grad_accum_steps", type=_positive_int, default=None, metavar="K", help="one optimizer step (and one all-reduce) per K "
+                       "micro-batches, each counted 1 / K (default 1); --max_steps keeps counting micro-batches")
+
+
+def accum_plan(i, n_batches, K, steps_left=None):
+    """Micro-batch i (0-based) of an epoch of n_batches, groups of K, at most steps_left further micro-batches allowed (None: no limit)
+    -> (zero, last, k): zero the gradient before it, all-reduce and step after it, and it is the group's k-th micro-batch.  Groups start
+    at the epoch's first batch; the one cut short by the epoch's end or by the step limit is stepped with its k < K micro-batches, the
+    gradient scaled by K / k (accum_factor) so that the update is the mean over what was seen."""
+    K = int(K)
+    end = n_batches if steps_left is None else min(n_batches, int(steps_left))
+    j = i % K
+    return j == 0, (j == K - 1 or i == end - 1), j + 1
+
+
+def accum_factor(K, k):
+    return float(K) / float(k)
+
+
+def accum_schedule(n_batches, K, steps_left=None):
+    """The whole epoch as a list of {"zero", "sync", "step", "factor"} (factor: the multiplier of grad_inv_scale at a step, else None)."""
+    end = n_batches if steps_left is None else min(n_batches, int(steps_left))
+    out = []
+    for i in range(end):
+        zero, last, k = accum_plan(i, n_batches, K, steps_left)
+        out.append({"zero": zero, "sync": last, "step": last, "factor": accum_factor(K, k) if last else None})
+    return out
+
+
+def grad_clip_entry(args):
+    """The 'grad_clip' entry of checkpoint.pth, or None when neither flag was given (nor restored)."""
+    mg, ga = getattr(args, "max_grad_norm", None), getattr(args, "grad_accum_steps", None)
+    if mg is None and ga is None:
+        return None
+    return {"max_grad_norm": None if mg is None else float(mg), "grad_accum_steps": int(ga or 1)}
+
+
+def grad_clip_resume(args, ck, rank=0):
+    """checkpoint.pth against the command line: a flag that was not given takes the checkpoint's value; one that was given wins, and a
+    difference is reported in one line."""
+    saved = ck.get("grad_clip")
+    if saved is None:
+        return
+    changed = []
+    for name in ("max_grad_norm", "grad_accum_steps"):
+        if not hasattr(args, name):
+            continue
+        mine, theirs = getattr(args, name), saved.get(name)
+        if mine is None:
+            setattr(args, name, theirs)
+        elif theirs is not None and mine != theirs:
+            changed.append(f"{name} {theirs} -> {mine}")
+    if changed and rank == 0:
+        print("grad_clip: the command line overrides checkpoint.pth (" + ", ".join(changed) + ")")
+
+
+def format_clip_stats(opt, name=""):
+    """The epoch line's grad-norm part (one host read), then the counters start again."""
+    st = opt.clip_stats()
+    opt.reset_clip_stats()
+    return f" | grad norm{name} {st['last_norm']:.4f}, max {st['max_norm_seen']:.4f}, clipped {st['clipped']}/{st['steps']}"
+
+
 def append_noise_level_record(run_dir, record):
     """{run_dir}/loss_by_noise_level.json: a list with one record per evaluated epoch (kept across resumes)."""
     import json

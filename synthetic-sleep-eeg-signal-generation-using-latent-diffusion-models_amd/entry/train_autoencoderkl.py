@@ -16,7 +16,8 @@ import torch
 from .. import distributed as D
 from ..models import AutoencoderKL, PatchDiscriminator
 from ..training import Adam, aekl_train_step, randn
-from .common import ParseListAction, WindowLoader, load_config, rng_seed, setup_run_dir
+from .common import (ParseListAction, WindowLoader, add_grad_clip_args, format_clip_stats, grad_clip_entry, grad_clip_resume, load_config, rng_seed,
+                     setup_run_dir)
 
 
 def parse_args(argv=None):
@@ -33,6 +34,7 @@ def parse_args(argv=None):
     p.add_argument("--max_steps", type=int, default=0); p.add_argument("--output_dir", default=None)
     p.add_argument("--deterministic", action="store_true", help="bit-reproducible steps (eegldm.set_deterministic(): ordered reductions instead of fp32 atomics; "
                    "what torch.use_deterministic_algorithms(True) would be for the reference's loop)")
+    add_grad_clip_args(p, accum=False)      # (no accumulation here: BatchNorm statistics are per micro-batch)
     return p.parse_args(argv)
 
 
@@ -60,7 +62,8 @@ def main(args):
         raise ValueError("--dtype float16 is not supported by train_autoencoderkl (no loss scaling in the AEKL / GAN step): use bfloat16 or float32")
     model = AutoencoderKL(**ae_args, dtype=args.dtype, device=local)
     disc = PatchDiscriminator(**dict(config.patchdiscriminator.params), dtype=args.dtype, device=local)
-    opt_g, opt_d = Adam(model, lr=config.models.optimizer_g_lr), Adam(disc, lr=config.models.optimizer_d_lr)
+    opt_g = Adam(model, lr=config.models.optimizer_g_lr, max_grad_norm=args.max_grad_norm)      # each clips against its own model's norm
+    opt_d = Adam(disc, lr=config.models.optimizer_d_lr, max_grad_norm=args.max_grad_norm)
     adv_w, kl_w = config.models.adv_weight, config.models.kl_weight
     spec_w = config.models.get("spectral_weight", 0.0)
     bs = max(1, config.train.batch_size // world)
@@ -78,6 +81,9 @@ def main(args):
         opt_g.load_state_dict(ck["optimizer_g"]); opt_d.load_state_dict(ck["optimizer_d"])
         start_epoch, best = ck["epoch"], ck["best_loss"]
         steps = int(ck.get("steps", 0))       # global step = the RNG offset of the reparameterisation noise: a resumed run must not replay it
+        grad_clip_resume(args, ck, rank)
+        if args.max_grad_norm != opt_g.max_grad_norm:
+            opt_g.set_max_grad_norm(args.max_grad_norm); opt_d.set_max_grad_norm(args.max_grad_norm)
         init_batch = ck.get("init_batch")     # written by the reference (train_autoencoderkl.py:327) and read unconditionally on its resume (:182)
     # identical replicas: parameters of both networks and the discriminator's BatchNorm running statistics come from rank 0
     D.broadcast_flat(model.flat); model.sync_weights()
@@ -108,7 +114,8 @@ def main(args):
         acc = torch.tensor(D.allreduce_sum_scalars(acc.tolist(), like=losses)) / world       # logged losses: mean over the replicas' batches
         if rank == 0:
             print(f"epoch {epoch}: recons {acc[0]/n:.5f} spectral {acc[1]/n:.3f} kl {acc[2]/n:.3f} gen {acc[3]/n:.5f} disc {(acc[4]+acc[5])/(2*n):.5f} "
-                  f"| {seen/(time.time()-t0):.1f} windows/s", flush=True)
+                  f"| {seen/(time.time()-t0):.1f} windows/s"
+                  + (format_clip_stats(opt_g, " g") + format_clip_stats(opt_d, " d") if args.max_grad_norm is not None else ""), flush=True)
         if (epoch + 1) % config.train.val_interval == 0 or (args.max_steps and steps_run >= args.max_steps):
             model.eval()
             v_sum, v_n = 0.0, 0
@@ -121,9 +128,12 @@ def main(args):
                 if vl <= best:
                     best = vl
                     torch.save({k: v.cpu() for k, v in model.state_dict().items()}, os.path.join(run_dir, "best_model.pth"))
-                torch.save({"epoch": epoch + 1, "state_dict": {k: v.cpu() for k, v in model.state_dict().items()},
-                            "discriminator": {k: v.cpu() for k, v in disc.state_dict().items()}, "optimizer_g": opt_g.state_dict(),
-                            "optimizer_d": opt_d.state_dict(), "best_loss": best, "init_batch": init_batch, "steps": steps}, os.path.join(run_dir, "checkpoint.pth"))
+                ck_out = {"epoch": epoch + 1, "state_dict": {k: v.cpu() for k, v in model.state_dict().items()},
+                          "discriminator": {k: v.cpu() for k, v in disc.state_dict().items()}, "optimizer_g": opt_g.state_dict(),
+                          "optimizer_d": opt_d.state_dict(), "best_loss": best, "init_batch": init_batch, "steps": steps}
+                if grad_clip_entry(args) is not None:
+                    ck_out["grad_clip"] = grad_clip_entry(args)
+                torch.save(ck_out, os.path.join(run_dir, "checkpoint.pth"))
             best = D.broadcast_scalar(best, src=0, like=losses)
         if args.max_steps and steps_run >= args.max_steps:
             break

@@ -13,8 +13,8 @@ from .. import distributed as D
 from ..models import UNetModel
 from ..schedulers import DDPMScheduler
 from ..training import EMA, Adam, GradScaler, NoiseLevelLoss, dm_train_step, randint, randn
-from .common import (WindowLoader, add_ema_args, add_loss_weighting_args, append_noise_level_record, cpu_state, ema_checkpoint_entry, ema_resume,
-                     format_noise_level_table, load_config, loss_weighting_resume, rng_seed, setup_run_dir, step_weighting)
+from .common import (WindowLoader, accum_factor, accum_plan, add_ema_args, add_grad_clip_args, add_loss_weighting_args, append_noise_level_record, cpu_state, ema_checkpoint_entry, ema_resume,
+                     format_clip_stats, format_noise_level_table, grad_clip_entry, grad_clip_resume, load_config, loss_weighting_resume, rng_seed, setup_run_dir, step_weighting)
 
 
 def parse_args(argv=None):
@@ -30,6 +30,7 @@ def parse_args(argv=None):
                    "what torch.use_deterministic_algorithms(True) would be for the reference's loop)")
     add_ema_args(p)
     add_loss_weighting_args(p)
+    add_grad_clip_args(p)
     return p.parse_args(argv)
 
 
@@ -48,7 +49,7 @@ def main(args):
     D.broadcast_flat(unet.flat); unet.sync_weights()
     sched = DDPMScheduler(num_train_timesteps=1000, schedule="linear_beta", beta_start=0.0015, beta_end=0.0195, device=local)
     ema = EMA(unet, decay=args.ema_decay, warmup=not args.ema_no_warmup) if args.ema_decay is not None else None      # after the broadcast
-    opt = Adam(unet, lr=1e-4, ema=ema)
+    opt = Adam(unet, lr=1e-4, ema=ema, max_grad_norm=args.max_grad_norm)
     # training_diffusion.py:37,149-151 pairs its fp16 autocast with a GradScaler: fp16 activation gradients under- / overflow without the loss scale
     scaler = GradScaler(enabled=args.grad_scaler or str(args.dtype) in ("float16", "fp16", "half"))
     spectral = args.spe == "spectral"
@@ -67,32 +68,40 @@ def main(args):
             scaler.load_state_dict(ck["scaler"])
         start_epoch, best, gstep = int(ck["epoch"]), float(ck["best_loss"]), int(ck.get("steps", 0))
         loss_weighting_resume(args, ck)
+        grad_clip_resume(args, ck, rank)
+        if args.max_grad_norm != opt.max_grad_norm:
+            opt.set_max_grad_norm(args.max_grad_norm)
         if ema is not None:
             ema_resume(ema, ck, rank)
         if rank == 0:
             print(f"Resuming from epoch {start_epoch} (best loss {best:.5f})")
     save_weighting = args.loss_weighting is not None             # (after the resume: a restored setting is written again)
     wkw = step_weighting(args)                                   # {} without the flags: the plain MSE, as before
+    GA = int(args.grad_accum_steps or 1)                         # micro-batches per optimizer step
     K = int(args.loss_by_noise_level)                            # this script has no validation split: the table is the epoch's training steps
     train_levels = NoiseLevelLoss(sched.num_train_timesteps, K) if K else None
     for epoch in range(start_epoch, config.train.n_epochs):
         unet.train()
         if train_levels is not None:
             train_levels.reset()
-        for batch in train:
+        left = args.max_steps - steps if args.max_steps else None
+        for i, batch in enumerate(train):
+            zero, last, k = accum_plan(i, len(train), GA, left)
             x = batch["eeg"].to(dev)
             B = x.shape[0]
             t = randint(ctx, B, sched.num_train_timesteps, seed=s_t, offset=gstep * B)
             noise = randn(ctx, tuple(x.shape), seed=s_noise, offset=gstep * x.numel())
-            opt.zero_grad()
+            if zero:
+                opt.zero_grad()
             if train_levels is not None:
                 wkw["per_sample_out"] = torch.empty(B, device=dev)
-            dm_train_step(unet, sched, x, noise, t, spectral_weight=1e-6, spectral_loss=spectral, loss_out=loss, grad_sync=gsync,
-                          grad_scale=scaler.get_scale(), **wkw)
+            dm_train_step(unet, sched, x, noise, t, spectral_weight=1e-6, spectral_loss=spectral, loss_out=loss, grad_sync=gsync if last else None,
+                          grad_scale=scaler.get_scale() / GA, **wkw)
             if train_levels is not None:
                 train_levels.add(wkw["per_sample_out"], t, ctx=ctx)
-            gsync.wait()
-            scaler.step(opt); scaler.update()
+            if last:                       # one all-reduce and one optimizer step per group; a short group counts its k micro-batches K / k
+                gsync.wait()
+                scaler.step(opt, accum_factor(GA, k)); scaler.update()
             steps += 1; gstep += 1; seen += B * world
             if args.max_steps and steps >= args.max_steps:
                 break
@@ -100,7 +109,7 @@ def main(args):
             record = {"epoch": epoch + 1, "steps": gstep, "prediction_type": sched.prediction_type, "bins": K,
                       "train": train_levels.merge(like=loss).table(), "valid": None, "valid_ema": None}
         if rank == 0:
-            print(f"epoch {epoch}: loss {float(loss):.5f} | {seen/(time.time()-t0):.1f} windows/s", flush=True)
+            print(f"epoch {epoch}: loss {float(loss):.5f} | {seen/(time.time()-t0):.1f} windows/s" + (format_clip_stats(opt) if opt.max_grad_norm is not None else ""), flush=True)
             if K:
                 print(format_noise_level_table("train", record["train"]), flush=True)
                 append_noise_level_record(run_dir, record)
@@ -116,6 +125,8 @@ def main(args):
                 ck_out["ema"] = ema_checkpoint_entry(ema, best)
             if save_weighting:
                 ck_out["loss_weighting"] = {"weighting": args.loss_weighting, "snr_gamma": float(args.snr_gamma)}
+            if grad_clip_entry(args) is not None:
+                ck_out["grad_clip"] = grad_clip_entry(args)
             torch.save(ck_out, os.path.join(run_dir, "checkpoint.pth"))
         if args.max_steps and steps >= args.max_steps:
             break

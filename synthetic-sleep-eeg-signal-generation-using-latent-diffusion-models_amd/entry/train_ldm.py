@@ -2,6 +2,7 @@
 /root/reference/src/train_ldm.py + src/training/training.py::train_ldm (flags, yaml schema, checkpoint keys
 training.py:381-397).  One process per GPU under torch.distributed.run for data parallelism."""
 import argparse
+import hashlib
 import os
 import time
 
@@ -11,8 +12,8 @@ from .. import distributed as D
 from ..models import AutoencoderKL, UNetModel
 from ..schedulers import DDPMScheduler
 from ..training import EMA, Adam, GradScaler, NoiseLevelLoss, ldm_train_step, randint, randn
-from .common import (ParseListAction, WindowLoader, add_ema_args, add_loss_weighting_args, append_noise_level_record, cpu_state, ema_checkpoint_entry,
-                     ema_resume, format_noise_level_table, load_config, loss_weighting_resume, rng_seed, setup_run_dir, step_weighting)
+from .common import (ParseListAction, WindowLoader, accum_factor, accum_plan, add_ema_args, add_grad_clip_args, add_loss_weighting_args, append_noise_level_record, cpu_state, ema_checkpoint_entry,
+                     ema_resume, format_clip_stats, format_noise_level_table, grad_clip_entry, grad_clip_resume, load_config, loss_weighting_resume, rng_seed, setup_run_dir, step_weighting)
 
 
 def parse_args(argv=None):
@@ -39,6 +40,7 @@ def parse_args(argv=None):
     p.add_argument("--null_class", type=int, default=None, help="the unconditional class (default: num_classes - 1 when --p_uncond > 0)")
     add_ema_args(p)
     add_loss_weighting_args(p)
+    add_grad_clip_args(p)
     return p.parse_args(argv)
 
 
@@ -112,7 +114,7 @@ def main(args):
                           prediction_type=args.prediction_type, device=local)
     # (after the broadcast: every rank's shadow starts from the same weights and, gradients being averaged before Adam.step, stays identical)
     ema = EMA(unet, decay=args.ema_decay, warmup=not args.ema_no_warmup) if args.ema_decay is not None else None
-    opt = Adam(unet, lr=config.train.get("base_lr", 1e-4), ema=ema)
+    opt = Adam(unet, lr=config.train.get("base_lr", 1e-4), ema=ema, max_grad_norm=args.max_grad_norm)
     scaler = GradScaler(enabled=args.grad_scaler or str(args.dtype) in ("float16", "fp16", "half"))      # fp16 activations: the loss scale is what keeps their gradients out of the subnormal range
     bs = max(1, config.train.batch_size // world)
     train = WindowLoader(args.path_pre_processed, bs, args.synthetic_windows, seed=rng_seed(config.train.seed, 8, rank, world), drop_last=config.train.drop_last,
@@ -146,34 +148,42 @@ def main(args):
         start_epoch, best, scale_factor = int(ck["epoch"]), float(ck["best_loss"]), float(ck["scale_factor"])
         gstep = int(ck.get("steps", 0))
         loss_weighting_resume(args, ck)
+        grad_clip_resume(args, ck, rank)
+        if args.max_grad_norm != opt.max_grad_norm:
+            opt.set_max_grad_norm(args.max_grad_norm)
         if ema is not None:
             best_ema = ema_resume(ema, ck, rank)
         if rank == 0:
             print(f"Resuming from epoch {start_epoch} (best loss {best:.5f}, scale factor {scale_factor})")
     save_weighting = args.loss_weighting is not None             # (after the resume: a restored setting is written again)
     wkw = step_weighting(args)                                   # {} without the flags: the plain exports, as before
+    GA = int(args.grad_accum_steps or 1)                         # micro-batches per optimizer step
     K = int(args.loss_by_noise_level)
     train_levels = NoiseLevelLoss(sched.num_train_timesteps, K) if K else None
     for epoch in range(start_epoch, config.train.n_epochs):
         unet.train()
         if train_levels is not None:
             train_levels.reset()
-        for batch in train:
+        left = args.max_steps - steps if args.max_steps else None
+        for i, batch in enumerate(train):
+            zero, last, k = accum_plan(i, len(train), GA, left)
             x = batch["eeg"].to(dev)
             B = x.shape[0]
             t = randint(ctx, B, sched.num_train_timesteps, seed=s_t, offset=gstep * B)
             eps = randn(ctx, (B, args.latent_channels, x.shape[2] // stage1.down), seed=s_eps, offset=gstep * z[0].numel() * B)
             noise = randn(ctx, eps.shape, seed=s_noise, offset=gstep * z[0].numel() * B)
             e = stage1.encode_stage_2_inputs(x, eps=eps, scale_factor=scale_factor)
-            opt.zero_grad()
+            if zero:
+                opt.zero_grad()
             lab = dict(labels=batch["label"].to(dev), p_uncond=args.p_uncond, null_class=null_class, seed=s_lab, offset=gstep * B) if cond else {}
             if train_levels is not None:
                 wkw["per_sample_out"] = torch.empty(B, device=dev)
-            ldm_train_step(unet, sched, e, noise, t, loss_out=loss, grad_scale=scaler.get_scale(), grad_sync=gsync, **lab, **wkw)
+            ldm_train_step(unet, sched, e, noise, t, loss_out=loss, grad_scale=scaler.get_scale() / GA, grad_sync=gsync if last else None, **lab, **wkw)
             if train_levels is not None:
                 train_levels.add(wkw["per_sample_out"], t, ctx=ctx)
-            gsync.wait()
-            scaler.step(opt); scaler.update()
+            if last:                       # one all-reduce and one optimizer step per group; a short group counts its k micro-batches K / k
+                gsync.wait()
+                scaler.step(opt, accum_factor(GA, k)); scaler.update()
             steps += 1; gstep += 1; seen += B * world
             if args.max_steps and steps >= args.max_steps:
                 break
@@ -194,7 +204,7 @@ def main(args):
                       "valid": lv.merge(like=loss).table() if valid is not None else None,
                       "valid_ema": lv_ema.merge(like=loss).table() if valid is not None and ema is not None else None}
         if rank == 0:
-            print(f"epoch {epoch}: loss {float(loss):.5f} | {seen/(time.time()-t0):.1f} windows/s", flush=True)
+            print(f"epoch {epoch}: loss {float(loss):.5f} | {seen/(time.time()-t0):.1f} windows/s" + (format_clip_stats(opt) if opt.max_grad_norm is not None else ""), flush=True)
             if K and do_eval:
                 for name in ("train", "valid", "valid_ema"):
                     if record[name] is not None:
@@ -217,6 +227,8 @@ def main(args):
                     ck_out["ema"] = ema_checkpoint_entry(ema, best_ema)
                 if save_weighting:
                     ck_out["loss_weighting"] = {"weighting": args.loss_weighting, "snr_gamma": float(args.snr_gamma)}
+                if grad_clip_entry(args) is not None:
+                    ck_out["grad_clip"] = grad_clip_entry(args)
                 torch.save(ck_out, os.path.join(run_dir, "checkpoint.pth"))
         if args.max_steps and steps >= args.max_steps:
             break
@@ -225,7 +237,9 @@ def main(args):
         if ema is not None:
             torch.save(cpu_state(ema.state_dict()), os.path.join(run_dir, "final_model_ema.pth"))
     LAST_RUN.clear(); LAST_RUN.update(rank=rank, world=world, scale_factor=scale_factor, steps=steps, param_sum=float(unet.flat.double().sum()),
-                                     loss_weighting=args.loss_weighting, snr_gamma=args.snr_gamma)
+                                     loss_weighting=args.loss_weighting, snr_gamma=args.snr_gamma, opt_steps=opt.step_count, sync_rounds=gsync.rounds,
+                                     flat_sha1=hashlib.sha1(unet.flat.cpu().numpy().tobytes()).hexdigest(),
+                                     grad_norm_bits=None if opt.max_grad_norm is None else int(opt.grad_norm.view(torch.int32)))
     return run_dir
 
 

@@ -111,12 +111,26 @@ class EMA:
             self.num_updates = int(num_updates)
 
 
+def _check_max_norm(max_norm, what="max_grad_norm"):
+    x = float(max_norm)
+    if not x > 0.0:                        # (a NaN fails the comparison)
+        raise ValueError(f"{what} must be > 0 (inf = measure only), got {max_norm}")
+    return x
+
+
 class Adam:
     """torch.optim.Adam defaults (betas 0.9/0.999, eps 1e-8, no weight decay) as one fused HIP
     kernel over the model's flat parameter buffer.  ema: an `EMA` of the same model, updated inside that kernel at every step
-    (a step that GradScaler skips therefore skips the EMA update too)."""
+    (a step that GradScaler skips therefore skips the EMA update too).
+    max_grad_norm: clip the global L2 norm of the (un-scaled) gradient to this value, as torch.nn.utils.clip_grad_norm_ before the step
+    would: one more read of the gradient (eegldm_grad_norm), the coefficient stays on the device and multiplies into the update
+    (eegldm_adam_step_clip) -- no host read, no rescaling pass, `flat_grad` is left as it is.  None (default): the calls made without it.
+    `grad_norm` is a device view of the last norm; `clip_stats()` reads the counters (one host read).  Not optimizer state: `state_dict()`
+    keeps torch's layout.  Data-parallel runs: step after the all-reduce -- every rank computes the same coefficient from the averaged gradient."""
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, ema=None):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, ema=None, max_grad_norm=None):
+        if max_grad_norm is not None:
+            max_grad_norm = _check_max_norm(max_grad_norm)
         if ema is not None and ema.model is not model:
             raise ValueError("the EMA tracks another model")
         self.model, self.lr, self.betas, self.eps, self.ema = model, lr, betas, eps, ema
@@ -124,20 +138,74 @@ class Adam:
         self.v = torch.zeros_like(model.flat)
         self.step_count = 0
         self.param_groups = [{"lr": lr}]
+        self.max_grad_norm, self._clip, self._norm_for, self._clip_snap = None, None, None, None
+        self.set_max_grad_norm(max_grad_norm)
+
+    def set_max_grad_norm(self, max_grad_norm):
+        """Turns clipping on (a value > 0; inf measures the norm without clipping) or off (None).  The counters start from zero."""
+        self.max_grad_norm = None if max_grad_norm is None else _check_max_norm(max_grad_norm)
+        self._clip = None if self.max_grad_norm is None else torch.zeros(8, device=self.model.flat.device)      # the `state` of include/eegldm.h
+        self._norm_for = self._clip_snap = None
 
     def zero_grad(self, set_to_none=True):
         self.model.zero_grad()
 
+    @property
+    def grad_norm(self):
+        """Device scalar: the global norm the last step (or GradScaler.unscale_) measured, before clipping."""
+        self._need_clip("grad_norm")
+        return self._clip[0]
+
+    def _need_clip(self, what):
+        if self._clip is None:
+            raise RuntimeError(f"{what} needs Adam(max_grad_norm=...)")
+
+    def clip_stats(self):
+        """{"last_norm", "max_norm_seen", "clipped", "steps"} since the last reset_clip_stats() (reads the device, after waiting for the
+        context's stream: also right for a Context with a stream of its own)."""
+        self._need_clip("clip_stats()")
+        self.model.ctx.sync()
+        s = self._clip.tolist()
+        return {"last_norm": s[0], "max_norm_seen": s[5], "clipped": int(s[3]), "steps": int(s[4])}
+
+    def reset_clip_stats(self):
+        self._need_clip("reset_clip_stats()")
+        self._clip[3:6].zero_()
+
+    def _norm_pass(self, pre_scale, snapshot=False):
+        """The norm pass of the coming step (GradScaler.unscale_ runs it ahead of step(), which then does not repeat it).
+        snapshot: keep the counters so that a skipped step can put them back (_norm_discard): a 3-float device copy on torch's current
+        stream, which is the context's stream for the default Context (use_torch_stream=True) -- the GradScaler path needs that one."""
+        md = self.model
+        self._clip_snap = self._clip[3:6].clone() if snapshot else None
+        check(lib.eegldm_grad_norm(md.ctx.h, ptr(md.flat_grad), md.flat_grad.numel(), pre_scale, self.max_grad_norm, ptr(self._clip)))
+        self._norm_for = float(pre_scale)
+
+    def _norm_discard(self):
+        if self._clip_snap is not None:
+            self._clip[3:6].copy_(self._clip_snap)
+        self._norm_for = self._clip_snap = None
+
     def step(self, grad_inv_scale=1.0):
         self.step_count += 1
         md, ema = self.model, self.ema
-        if ema is None:
+        if ema is not None and ema._applied:
+            self.step_count -= 1
+            raise RuntimeError("Adam.step() inside `with ema.applied()`: the model holds the averaged weights there")
+        if self._clip is not None:             # norm of the un-scaled gradient, then the update with grad_inv_scale * coef (read on the device)
+            if self._norm_for is None or self._norm_for != float(grad_inv_scale):
+                self._norm_pass(grad_inv_scale)
+            self._norm_for = self._clip_snap = None
+            check(lib.eegldm_adam_step_clip(md.ctx.h, ptr(md.flat), ptr(md.flat_grad), ptr(self.m), ptr(self.v),
+                                            None if ema is None else ptr(ema.shadow), md.flat.numel(), self.param_groups[0]["lr"], self.betas[0],
+                                            self.betas[1], self.eps, self.step_count, grad_inv_scale, 0.0 if ema is None else ema.one_minus_decay(),
+                                            ptr(self._clip)))
+            if ema is not None:
+                ema.num_updates += 1
+        elif ema is None:
             check(lib.eegldm_adam_step(md.ctx.h, ptr(md.flat), ptr(md.flat_grad), ptr(self.m), ptr(self.v), md.flat.numel(),
                                        self.param_groups[0]["lr"], self.betas[0], self.betas[1], self.eps, self.step_count, grad_inv_scale))
         else:                              # the same update + the EMA of the new weights in one pass over the buffers
-            if ema._applied:
-                self.step_count -= 1
-                raise RuntimeError("Adam.step() inside `with ema.applied()`: the model holds the averaged weights there")
             check(lib.eegldm_adam_step_ema(md.ctx.h, ptr(md.flat), ptr(md.flat_grad), ptr(self.m), ptr(self.v), ptr(ema.shadow), md.flat.numel(),
                                            self.param_groups[0]["lr"], self.betas[0], self.betas[1], self.eps, self.step_count, grad_inv_scale,
                                            ema.one_minus_decay()))
@@ -236,25 +304,36 @@ class GradScaler:
     def scale(self, outputs):
         return outputs * self.get_scale() if self._enabled else outputs
 
-    def unscale_(self, optimizer):
-        """Records whether optimizer.model's gradients hold an inf/nan (the division itself happens inside the Adam kernel)."""
+    def unscale_(self, optimizer, inv_scale_mult=1.0):
+        """Records whether optimizer.model's gradients hold an inf/nan (the division itself happens inside the Adam kernel).
+        A clipping optimizer (Adam(max_grad_norm=...)): the norm pass of the coming step runs here, with pre_scale = inv_scale_mult / scale,
+        and its inf/nan flag is the one read -- the gradient is not read a second time for the check.
+        inv_scale_mult: a further factor on 1 / scale (a gradient-accumulation group cut short: K / k)."""
         if not self._enabled:
             return
         md = optimizer.model
+        if getattr(optimizer, "max_grad_norm", None) is not None:
+            optimizer._norm_pass(float(inv_scale_mult) / self._scale, snapshot=True)
+            md.ctx.sync()
+            self._found_inf = bool(float(optimizer._clip[2]) != 0.0)
+            return
         if self._flag is None or self._flag.device != md.flat_grad.device:
             self._flag = torch.zeros(1, device=md.flat_grad.device)
         check(lib.eegldm_grad_check_finite(md.ctx.h, ptr(md.flat_grad), md.flat_grad.numel(), ptr(self._flag)))
         md.ctx.sync()
         self._found_inf = bool(float(self._flag) != 0.0)
 
-    def step(self, optimizer):
+    def step(self, optimizer, inv_scale_mult=1.0):
+        clipping = getattr(optimizer, "max_grad_norm", None) is not None
         if not self._enabled:
-            return optimizer.step()
-        if self._found_inf is None:
-            self.unscale_(optimizer)
+            return optimizer.step() if inv_scale_mult == 1.0 else optimizer.step(grad_inv_scale=float(inv_scale_mult))
+        if self._found_inf is None or (clipping and optimizer._norm_for != float(inv_scale_mult) / self._scale):
+            self.unscale_(optimizer, inv_scale_mult)
         if self._found_inf:
+            if clipping:
+                optimizer._norm_discard()   # the skipped step does not count: the clip counters go back to what they were
             return None                     # skipped: parameters, moments and the optimizer's step count stay as they are
-        return optimizer.step(grad_inv_scale=1.0 / self._scale)
+        return optimizer.step(grad_inv_scale=float(inv_scale_mult) / self._scale)
 
     def update(self, new_scale=None):
         if not self._enabled:
@@ -282,6 +361,20 @@ class GradScaler:
             return
         self._scale, self._growth_factor, self._backoff_factor = float(sd["scale"]), float(sd["growth_factor"]), float(sd["backoff_factor"])
         self._growth_interval, self._growth_tracker = int(sd["growth_interval"]), int(sd["_growth_tracker"])
+
+
+def clip_grad_norm_(model, max_norm):
+    """torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) on `model.flat_grad`, for parameters stepped by another optimizer (the
+    autograd bridge + torch.optim): the norm pass, then flat_grad *= min(1, max_norm / (norm + 1e-6)) in place -- two launches, no host
+    read.  Returns the norm before clipping as a device scalar tensor."""
+    max_norm = _check_max_norm(max_norm, "max_norm")
+    state = getattr(model, "_clip_state", None)
+    if state is None or state.device != model.flat_grad.device:
+        state = model._clip_state = torch.zeros(8, device=model.flat_grad.device)
+    g = model.flat_grad
+    check(lib.eegldm_grad_norm(model.ctx.h, ptr(g), g.numel(), 1.0, max_norm, ptr(state)))
+    check(lib.eegldm_grad_scale_by(model.ctx.h, ptr(g), g.numel(), ptr(state)))
+    return state[0].clone()
 
 
 GRAD_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_long, C.c_long)
