@@ -46,7 +46,8 @@ extern "C" {
  *    Added since without a version change (new symbols only): the class-conditional entry points, the weight EMA (eegldm_adam_step_ema,
  *    eegldm_ema_update, eegldm_swap), the multistep sampler (eegldm_multistep_step, eegldm_sample_multistep) and editing (eegldm_edit_step,
  *    eegldm_edit_start, eegldm_edit_window, eegldm_sample_edit) and the weighted diffusion loss (eegldm_diffusion_loss, eegldm_loss_bins,
- *    eegldm_ldm_train_step_weighted) and global gradient-norm clipping (eegldm_grad_norm, eegldm_adam_step_clip, eegldm_grad_scale_by). */
+ *    eegldm_ldm_train_step_weighted) and global gradient-norm clipping (eegldm_grad_norm, eegldm_adam_step_clip, eegldm_grad_scale_by)
+ *    and long recordings (eegldm_canvas_gather, eegldm_canvas_step, eegldm_canvas_compose, eegldm_sample_long). */
 #define EEGLDM_ABI_VERSION 8
 
 /* Storage / operand type of activations and compute-copy weights (accumulation, statistics, master weights and optimizer state are
@@ -586,6 +587,50 @@ int eegldm_sample_edit(eegldm_unet*, eegldm_aekl* ae, const float* noise, const 
                        const float* a_next_host, int n_steps, int pred_type, int clip_sample, float inv_scale_factor, float* latents_out,
                        float* windows_out, int B, int L, int use_graph, int* graph_used_host, const int64_t* labels_host, float guidance_scale,
                        int64_t null_class);
+
+/* Long recordings: overlapped-window sampling on one latent canvas (MultiDiffusion, Bar-Tal et al. 2023); new symbols, ABI 8.
+ * A recording is ONE noisy canvas (R, C, Lc) longer than the window the UNet was trained on.  Window k covers canvas positions
+ * [k S, k S + L) with the stride S = L - (2 m + r), so Lc = (W - 1) S + L; all R * W windows are rows of one forward batch (recording-major:
+ * row rec * W + k).  Inside a window the first and last m positions that have a neighbour carry weight 0 (`margin`: where the network sees
+ * a conv boundary and its trained-in padding), the next r positions ramp linearly (`ramp`), the interior has weight 1; a recording's free
+ * start and end keep weight 1.  In the overlap of windows k and k + 1, with j' = p - (k + 1) S, window k + 1 has the weight
+ *   u = 0 (j' < m),   u = (j' - m + 0.5) / r (m <= j' < m + r),   u = 1 (afterwards)        and window k has 1 - u.
+ * L >= 3 m + 2 r is required: then S >= 1 and at most two windows carry weight anywhere.  m = r = 0: independent windows side by side.
+ * fp32 throughout, any 4-byte alignment of every pointer (16-byte accesses wherever an address allows), no atomics, no memset: every
+ * output element has exactly one writer, so results repeat bit for bit.
+ *
+ * eegldm_canvas_gather: win[rec * W + k][c][l] = canvas[rec][c][k S + l]; win2 (nullable) receives a second copy (the null-class half of
+ * a guided forward's input).  Any 1 <= S <= L. */
+int eegldm_canvas_gather(eegldm_ctx*, const float* canvas, int R, int C, int W, int L, int S, float* win, float* win2);
+/* eegldm_canvas_step: one sampling step of the whole canvas, ONE launch.  model_out holds the forward's output for the R * W window
+ * rows ((R W, C, L); guided != 0: twice that, the conditional rows then the null-class rows).  For each canvas element xc:
+ *   o    = model_out at that position of each window with non-zero weight there (guided: o_u + w (o_c - o_u), as eegldm_multistep_step)
+ *   x0_k = the data prediction from o, xc and a_t, the arithmetic of eegldm_multistep_step (epsilon / v_prediction / sample, optional clamp)
+ *   x0   = u == 0 ? x0_k : u == 1 ? x0_{k+1} : fma(u, x0_{k+1}, (1 - u) * x0_k)        (a window with weight 0 is not read)
+ *   prev = fma(cx, xc, fma(c0, x0, c1 * hist))      (c1 == 0: fma(cx, xc, c0 * x0), hist is not read);    hist = x0
+ * prev goes to canvas_out (may be `canvas` itself) and to EVERY window row that covers the position, weight-0 windows included, in win
+ * and win2 (both nullable; (R W, C, L)): the next forward's input is complete without a gather.  hist (canvas-shaped; NULL only when
+ * c1 == 0) and pred_x0 (nullable, canvas-shaped) receive the fused prediction.  The update is linear in (x, x0), so fusing the x0 of two
+ * windows that share xc equals fusing their updated samples (MultiDiffusion's average).  W == 1 and m == r == 0 are
+ * eegldm_multistep_step on the same values, bit for bit.  No two buffers may overlap except canvas_out == canvas. */
+int eegldm_canvas_step(eegldm_ctx*, const float* model_out, float guidance_scale, int guided, const float* canvas, float* hist, float a_t,
+                       int pred_type, int clip_sample, float cx, float c0, float c1, int R, int C, int W, int L, int m, int r, float* canvas_out,
+                       float* win, float* win2, float* pred_x0);
+/* eegldm_canvas_compose: the decoded windows (R W, Co, Lw) cross-faded onto the recording (R, Co, (W - 1) Sw + Lw) with the layout at
+ * window resolution (Sw == Lw - (2 mw + rw): the latent layout times the autoencoder's downsampling factor): the bytes of the owning
+ * window where u is 0 or 1, fma(u, b, (1 - u) * a) inside a ramp. */
+int eegldm_canvas_compose(eegldm_ctx*, const float* decoded, int R, int Co, int W, int Lw, int Sw, int mw, int rw, float* out);
+/* The loop of eegldm_sample_multistep on R canvases of W windows each: canvas = noise ((R, C, Lc), device), gather, then per step one
+ * forward on the R * W rows (2 R W when guided) and ONE eegldm_canvas_step launch; canvas_out (nullable, (R, C, Lc)) receives the final
+ * canvas; recording_out (nullable, (R, Co, down * Lc)) the cross-fade (eegldm_canvas_compose) of the R * W windows decoded from the
+ * gathered canvas times inv_scale_factor -- with ae == NULL (pixel-space model) the canvas itself (down = 1).  labels_host: R * W classes,
+ * recording-major, or NULL for an unconditional UNet; guidance as in eegldm_sample_cond.  cx_host / c0_host / c1_host as in
+ * eegldm_sample_multistep (c1_host[0] == 0); solver_order = 1 in schedulers.py is DDIM on the same grid.  Embedding table, eager launches
+ * or graph replay are shared with the other loops (the forward state is the one of B = R * W rows). */
+int eegldm_sample_long(eegldm_unet*, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
+                       const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int pred_type, int clip_sample,
+                       float inv_scale_factor, float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
+                       int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class);
 
 /* ------------------------------------------------------------------ data-parallel collectives (RCCL over xGMI)
  * One communicator per process / GPU.  Stands where the reference gathers gradients with single-process nn.DataParallel

@@ -820,6 +820,195 @@ __global__ __launch_bounds__(NT) void edit_window_kernel(const float* __restrict
     out[i] = edit_blend(mask_win[b * Lw + t], input[i], decoded[i]);
   }
 }
+// ------------------------------------------------------------------ long recordings: overlapped windows on one canvas (include/eegldm.h)
+// Window k of a recording covers canvas positions [k S, k S + L), S = L - (2 m + r).  Position p belongs to the LAST window k1 whose
+// zero-weight margin it has left (k1 S + m <= p; k1 = 0 below S + m); jp = p - k1 S.  Inside the ramp (k1 >= 1, jp < m + r) window k1 has
+// weight u = (jp - m + 0.5) / r and window k1 - 1 has 1 - u; everywhere else window k1 has weight 1 and no other window is read.
+struct CanvasGeo { int C, W, L, S, m, r, Lc; };
+struct CanvasAt { int k1, jp; bool ramp; };
+__device__ __forceinline__ CanvasAt canvas_at(const CanvasGeo& g, int p) {
+  CanvasAt a;
+  a.k1 = p < g.S + g.m ? 0 : min(g.W - 1, (p - g.m) / g.S);
+  a.jp = p - a.k1 * g.S;
+  a.ramp = a.k1 >= 1 && a.jp < g.m + g.r;
+  return a;
+}
+__device__ __forceinline__ float canvas_u(const CanvasGeo& g, int jp) { return ((float)(jp - g.m) + 0.5f) / (float)g.r; }
+// the windows that cover p, weight-0 ones included
+__device__ __forceinline__ int canvas_kmin(const CanvasGeo& g, int p) { return p < g.L ? 0 : (p - g.L) / g.S + 1; }
+__device__ __forceinline__ int canvas_kmax(const CanvasGeo& g, int p) { return min(g.W - 1, p / g.S); }
+// (1 - u) a + u b with the exactness of edit_blend at both ends
+__device__ __forceinline__ float canvas_fuse(float u, float a, float b) {
+#pragma clang fp contract(off)
+  if (u == 0.0f) return a;
+  if (u == 1.0f) return b;
+  return fmaf(u, b, (1.0f - u) * a);
+}
+// N = 4: one 16-byte access when the address allows it, else four 4-byte ones; N = 1: one element
+template <int N> __device__ __forceinline__ void canvas_ld(const float* p, float (&v)[4]) {
+  if (N == 4 && ((uintptr_t)p & 15) == 0) {
+    const f32x4 t = *(const f32x4*)p;
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] = t[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < N; k++) v[k] = p[k];
+  }
+}
+template <int N> __device__ __forceinline__ void canvas_st(float* p, const float (&v)[4]) {
+  if (N == 4 && ((uintptr_t)p & 15) == 0) {
+    f32x4 t;
+#pragma unroll
+    for (int k = 0; k < 4; k++) t[k] = v[k];
+    *(f32x4*)p = t;
+  } else {
+#pragma unroll
+    for (int k = 0; k < N; k++) p[k] = v[k];
+  }
+}
+// four consecutive flat indices from i form ONE span when they lie in one row of length `len` (*row, *p: the row and position of i)
+__device__ __forceinline__ bool canvas_one_row(long i, int len, long* row, int* p) {
+  *row = i / len; *p = (int)(i - *row * len);
+  return *p + 3 < len;
+}
+struct CanvasStepArgs {
+  const float* mo; float w; int guided; const float* canvas; float* hist; float sa, sb; int pred, clip; float cx, c0, c1;
+  float *out, *win, *win2, *x0o; long n_win;
+};
+// N canvas elements from position p of row `row` (= rec * C + c): all in one row, one owner window, one ramp state, one set of covering windows
+template <int N>
+__device__ __forceinline__ void canvas_step_span(const CanvasGeo& g, const CanvasStepArgs& a, long row, int p, const CanvasAt& at) {
+  const long ci = row * g.Lc + p;
+  const long rec = row / g.C; const int c = (int)(row - rec * g.C);
+  float xc[4], o[4], z[4], h[4] = {0.0f, 0.0f, 0.0f, 0.0f}, pv[4];
+  canvas_ld<N>(a.canvas + ci, xc);
+  const long wb = ((rec * g.W + at.k1) * g.C + c) * g.L + at.jp;       // the owner window's element, in model_out and in win
+  canvas_ld<N>(a.mo + wb, o);
+  if (a.guided) {
+    float ou[4];
+    canvas_ld<N>(a.mo + a.n_win + wb, ou);
+#pragma unroll
+    for (int k = 0; k < N; k++) o[k] = ou[k] + a.w * (o[k] - ou[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < N; k++) z[k] = multistep_x0(o[k], xc[k], a.sa, a.sb, a.pred, a.clip);
+  if (at.ramp) {
+    const long wa = wb - (long)g.C * g.L + g.S;                         // the same canvas position in window k1 - 1
+    float oa[4];
+    canvas_ld<N>(a.mo + wa, oa);
+    if (a.guided) {
+      float ou[4];
+      canvas_ld<N>(a.mo + a.n_win + wa, ou);
+#pragma unroll
+      for (int k = 0; k < N; k++) oa[k] = ou[k] + a.w * (oa[k] - ou[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < N; k++) z[k] = canvas_fuse(canvas_u(g, at.jp + k), multistep_x0(oa[k], xc[k], a.sa, a.sb, a.pred, a.clip), z[k]);
+  }
+  if (a.c1 != 0.0f) canvas_ld<N>(a.hist + ci, h);
+#pragma unroll
+  for (int k = 0; k < N; k++) pv[k] = multistep_update(xc[k], z[k], h[k], a.cx, a.c0, a.c1);
+  canvas_st<N>(a.out + ci, pv);
+  if (a.hist) canvas_st<N>(a.hist + ci, z);
+  if (a.x0o) canvas_st<N>(a.x0o + ci, z);
+  if (a.win) {
+    const int k1 = canvas_kmax(g, p);
+    for (int k = canvas_kmin(g, p); k <= k1; k++) {
+      const long off = ((rec * g.W + k) * g.C + c) * g.L + (p - k * g.S);
+      canvas_st<N>(a.win + off, pv);
+      if (a.win2) canvas_st<N>(a.win2 + off, pv);
+    }
+  }
+}
+// One sampling step on the canvas, one launch: n = R C Lc canvas elements, four per thread from `head` on (the canvas's own 16-byte
+// grid; every other buffer takes 16-byte accesses where its address allows).  A group of four that crosses a row end, a window's margin
+// or ramp edge, or the edge of a covering window goes element by element in the same thread; every output element has one writer.
+__global__ __launch_bounds__(NT) void canvas_step_kernel(CanvasGeo g, CanvasStepArgs a, long n, long head) {
+  const VecSplit s = vec_split(n, head);
+  GRID_STRIDE(q, s.n4) {
+    const long i = head + (q << 2);
+    long row; int p;
+    bool one = canvas_one_row(i, g.Lc, &row, &p);
+    CanvasAt at = canvas_at(g, p);
+    if (one) {
+      const CanvasAt e = canvas_at(g, p + 3);
+      one = e.k1 == at.k1 && e.ramp == at.ramp && canvas_kmin(g, p) == canvas_kmin(g, p + 3) && canvas_kmax(g, p) == canvas_kmax(g, p + 3);
+    }
+    if (one) { canvas_step_span<4>(g, a, row, p, at); continue; }
+    for (int k = 0; k < 4; k++) {
+      (void)canvas_one_row(i + k, g.Lc, &row, &p);
+      canvas_step_span<1>(g, a, row, p, canvas_at(g, p));
+    }
+  }
+  GRID_STRIDE(j, s.nedge) {
+    long row; int p;
+    (void)canvas_one_row(EDGE_INDEX(s, j), g.Lc, &row, &p);
+    canvas_step_span<1>(g, a, row, p, canvas_at(g, p));
+  }
+}
+// win[rec * W + k][c][l] = canvas[rec][c][k S + l] (and the same into win2): n = R W C L window elements on win's 16-byte grid
+template <int N>
+__device__ __forceinline__ void canvas_gather_span(const CanvasGeo& g, const float* canvas, float* win, float* win2, long wrow, int l) {
+  const long rk = wrow / g.C; const int c = (int)(wrow - rk * g.C);
+  const long rec = rk / g.W; const int k = (int)(rk - rec * g.W);
+  float v[4];
+  canvas_ld<N>(canvas + (rec * g.C + c) * g.Lc + (long)k * g.S + l, v);
+  canvas_st<N>(win + wrow * g.L + l, v);
+  if (win2) canvas_st<N>(win2 + wrow * g.L + l, v);
+}
+__global__ __launch_bounds__(NT) void canvas_gather_kernel(CanvasGeo g, const float* __restrict__ canvas, float* __restrict__ win,
+                                                           float* __restrict__ win2, long n, long head) {
+  const VecSplit s = vec_split(n, head);
+  GRID_STRIDE(q, s.n4) {
+    const long i = head + (q << 2);
+    long wrow; int l;
+    if (canvas_one_row(i, g.L, &wrow, &l)) { canvas_gather_span<4>(g, canvas, win, win2, wrow, l); continue; }
+    for (int k = 0; k < 4; k++) {
+      (void)canvas_one_row(i + k, g.L, &wrow, &l);
+      canvas_gather_span<1>(g, canvas, win, win2, wrow, l);
+    }
+  }
+  GRID_STRIDE(j, s.nedge) {
+    long wrow; int l;
+    (void)canvas_one_row(EDGE_INDEX(s, j), g.L, &wrow, &l);
+    canvas_gather_span<1>(g, canvas, win, win2, wrow, l);
+  }
+}
+// out[rec][c][p] = the owner window's decoded sample, cross-faded with its predecessor's inside the ramp (g at window resolution)
+template <int N>
+__device__ __forceinline__ void canvas_compose_span(const CanvasGeo& g, const float* dec, float* out, long row, int p, const CanvasAt& at) {
+  const long rec = row / g.C; const int c = (int)(row - rec * g.C);
+  const long wb = ((rec * g.W + at.k1) * g.C + c) * g.L + at.jp;
+  float v[4];
+  canvas_ld<N>(dec + wb, v);
+  if (at.ramp) {
+    float va[4];
+    canvas_ld<N>(dec + wb - (long)g.C * g.L + g.S, va);
+#pragma unroll
+    for (int k = 0; k < N; k++) v[k] = canvas_fuse(canvas_u(g, at.jp + k), va[k], v[k]);
+  }
+  canvas_st<N>(out + row * g.Lc + p, v);
+}
+__global__ __launch_bounds__(NT) void canvas_compose_kernel(CanvasGeo g, const float* __restrict__ dec, float* __restrict__ out, long n, long head) {
+  const VecSplit s = vec_split(n, head);
+  GRID_STRIDE(q, s.n4) {
+    const long i = head + (q << 2);
+    long row; int p;
+    bool one = canvas_one_row(i, g.Lc, &row, &p);
+    CanvasAt at = canvas_at(g, p);
+    if (one) { const CanvasAt e = canvas_at(g, p + 3); one = e.k1 == at.k1 && e.ramp == at.ramp; }
+    if (one) { canvas_compose_span<4>(g, dec, out, row, p, at); continue; }
+    for (int k = 0; k < 4; k++) {
+      (void)canvas_one_row(i + k, g.Lc, &row, &p);
+      canvas_compose_span<1>(g, dec, out, row, p, canvas_at(g, p));
+    }
+  }
+  GRID_STRIDE(j, s.nedge) {
+    long row; int p;
+    (void)canvas_one_row(EDGE_INDEX(s, j), g.Lc, &row, &p);
+    canvas_compose_span<1>(g, dec, out, row, p, canvas_at(g, p));
+  }
+}
 __global__ __launch_bounds__(NT) void ema_update_kernel(float* __restrict__ e, const float* __restrict__ p, long n, long head, float c) {
   const VecSplit s = vec_split(n, head);
   f32x4* e4 = (f32x4*)(e + head); const f32x4* p4 = (const f32x4*)(p + head);
@@ -1576,6 +1765,75 @@ extern "C" int eegldm_edit_window(eegldm_ctx* ctx, const float* mask_win, int B,
   if (n_lat + n_win == 0) return 0;
   hipLaunchKernelGGL(edit_window_kernel, dim3(grid1d(n_lat > n_win ? n_lat : n_win, ctx)), dim3(NT), 0, ctx->stream, mask_win, n_lat, n_win, Lw, down,
                      C, mask_lat, input, decoded, Co, out);
+  LAUNCH_CHECK(); return 0;
+}
+// ---- long recordings (include/eegldm.h): the slices of a canvas, one sampling step on it, the cross-fade of the decoded windows
+static int canvas_geo(int R, int C, int W, int L, int S, int m, int r, CanvasGeo* g) {
+  EEG_CHECK(R >= 1 && C >= 1 && W >= 1 && L >= 1, "bad sizes (R %d, C %d, W %d, L %d)", R, C, W, L);
+  EEG_CHECK(m >= 0 && r >= 0, "margin %d / ramp %d must be >= 0", m, r);
+  EEG_CHECK((long)L >= 3L * m + 2L * r, "window length %d < 3 * margin + 2 * ramp = %ld: more than two windows would carry weight", L, 3L * m + 2L * r);
+  EEG_CHECK(S == L - (2 * m + r) && S >= 1, "stride %d is not L - (2 margin + ramp) = %d >= 1", S, L - (2 * m + r));
+  const long Lc = (long)(W - 1) * S + L;
+  EEG_CHECK(Lc <= 0x7fffffffL - 4, "canvas length %ld: too long", Lc);
+  g->C = C; g->W = W; g->L = L; g->S = S; g->m = m; g->r = r; g->Lc = (int)Lc;
+  return 0;
+}
+static long canvas_head(const void* p, long n) {
+  const long head = (long)(((16 - ((uintptr_t)p & 15)) & 15) >> 2);
+  return head < n ? head : n;
+}
+extern "C" int eegldm_canvas_gather(eegldm_ctx* ctx, const float* canvas, int R, int C, int W, int L, int S, float* win, float* win2) {
+  EEG_CHECK(ctx && canvas && win, "null argument");
+  EEG_CHECK(R >= 1 && C >= 1 && W >= 1 && L >= 1 && S >= 1 && S <= L, "bad sizes (R %d, C %d, W %d, L %d, S %d)", R, C, W, L, S);
+  const long Lc = (long)(W - 1) * S + L, n = (long)R * W * C * L, nc = (long)R * C * Lc;
+  EEG_CHECK(Lc <= 0x7fffffffL - 4, "canvas length %ld: too long", Lc);
+  auto ov = [](const float* p, long np, const float* q, long nq) { return p && q && p < q + nq && q < p + np; };
+  EEG_CHECK(!ov(canvas, nc, win, n) && !ov(canvas, nc, win2, n) && !ov(win, n, win2, n), "the canvas / window buffers overlap");
+  for (const void* q : {(const void*)canvas, (const void*)win, (const void*)win2})
+    EEG_CHECK(((uintptr_t)q & 3) == 0, "buffers must be 4-byte aligned");
+  CanvasGeo g; g.C = C; g.W = W; g.L = L; g.S = S; g.m = 0; g.r = 0; g.Lc = (int)Lc;
+  const long head = canvas_head(win, n);
+  hipLaunchKernelGGL(canvas_gather_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, g, canvas, win, win2, n, head);
+  LAUNCH_CHECK(); return 0;
+}
+extern "C" int eegldm_canvas_step(eegldm_ctx* ctx, const float* mo, float w, int guided, const float* canvas, float* hist, float a_t, int pred,
+                                  int clip, float cx, float c0, float c1, int R, int C, int W, int L, int m, int r, float* canvas_out,
+                                  float* win, float* win2, float* x0) {
+  EEG_CHECK(ctx && mo && canvas && canvas_out, "null argument");
+  CanvasGeo g;
+  EEG_TRY(canvas_geo(R, C, W, L, L - (2 * m + r), m, r, &g));
+  EEG_CHECK(pred >= 0 && pred <= 2, "prediction type %d", pred);
+  EEG_CHECK(a_t > 0.0f && a_t < 1.0f, "a_t %g outside (0, 1)", (double)a_t);
+  EEG_CHECK(!guided || w == w, "guidance_scale is NaN");
+  EEG_CHECK(cx == cx && c0 == c0 && c1 == c1, "a coefficient is NaN");
+  EEG_CHECK(hist || c1 == 0.0f, "c1 != 0 needs the history buffer");
+  EEG_CHECK(win || !win2, "win2 needs win");
+  const long n = (long)R * C * g.Lc, nw = (long)R * W * C * L, nm = guided ? 2 * nw : nw;
+  auto ov = [](const float* p, long np, const float* q, long nq) { return p && q && p < q + nq && q < p + np; };
+  EEG_CHECK(!ov(mo, nm, canvas_out, n) && !ov(mo, nm, x0, n) && !ov(mo, nm, hist, n) && !ov(mo, nm, win, nw) && !ov(mo, nm, win2, nw),
+            "model_out aliases an output buffer");
+  EEG_CHECK(!ov(hist, n, canvas, n) && !ov(hist, n, canvas_out, n) && !ov(hist, n, x0, n) && !ov(hist, n, win, nw) && !ov(hist, n, win2, nw),
+            "the history buffer aliases another buffer");
+  EEG_CHECK(!ov(x0, n, canvas, n) && !ov(x0, n, canvas_out, n) && !ov(x0, n, win, nw) && !ov(x0, n, win2, nw), "pred_x0 aliases another buffer");
+  EEG_CHECK(!ov(win, nw, canvas, n) && !ov(win, nw, canvas_out, n) && !ov(win2, nw, canvas, n) && !ov(win2, nw, canvas_out, n) && !ov(win, nw, win2, nw),
+            "win / win2 alias another buffer");
+  EEG_CHECK(canvas_out == canvas || !ov(canvas_out, n, canvas, n), "canvas_out may be the canvas itself, not a shifted view of it");
+  for (const void* q : {(const void*)mo, (const void*)canvas, (const void*)hist, (const void*)canvas_out, (const void*)win, (const void*)win2, (const void*)x0})
+    EEG_CHECK(((uintptr_t)q & 3) == 0, "buffers must be 4-byte aligned");
+  CanvasStepArgs a{mo, w, guided ? 1 : 0, canvas, hist, sqrtf(a_t), sqrtf(1.0f - a_t), pred, clip, cx, c0, c1, canvas_out, win, win2, x0, nw};
+  const long head = canvas_head(canvas, n);
+  hipLaunchKernelGGL(canvas_step_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, g, a, n, head);
+  LAUNCH_CHECK(); return 0;
+}
+extern "C" int eegldm_canvas_compose(eegldm_ctx* ctx, const float* decoded, int R, int Co, int W, int Lw, int Sw, int mw, int rw, float* out) {
+  EEG_CHECK(ctx && decoded && out, "null argument");
+  CanvasGeo g;
+  EEG_TRY(canvas_geo(R, Co, W, Lw, Sw, mw, rw, &g));
+  const long n = (long)R * Co * g.Lc, nw = (long)R * W * Co * Lw;
+  EEG_CHECK(!(decoded < out + n && out < decoded + nw), "out overlaps the decoded windows");
+  EEG_CHECK(((uintptr_t)decoded & 3) == 0 && ((uintptr_t)out & 3) == 0, "buffers must be 4-byte aligned");
+  const long head = canvas_head(out, n);
+  hipLaunchKernelGGL(canvas_compose_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, g, decoded, out, n, head);
   LAUNCH_CHECK(); return 0;
 }
 extern "C" int eegldm_swap(eegldm_ctx* ctx, float* a, float* b, long n) {

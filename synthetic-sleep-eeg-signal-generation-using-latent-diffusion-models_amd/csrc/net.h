@@ -145,4 +145,6 @@ int unet_forward_labels(eegldm_unet* u, const float* x, const int64_t* t, const 
 int unet_out_channels(const eegldm_unet* u);
 void sampler_release(const eegldm_unet* u);
 eegldm_ctx* aekl_ctx(const eegldm_aekl* a);
+int aekl_out_channels(const eegldm_aekl* a);
+int aekl_down(const eegldm_aekl* a);      // window samples per latent position
 int entry_query(const NetBase* u, int i, char* name, int cap, long* offset, long* numel, int* ndim, int shape[3]);

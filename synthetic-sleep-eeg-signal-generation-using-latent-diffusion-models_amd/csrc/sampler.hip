@@ -22,6 +22,8 @@ struct SamplerState {
   hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr;
   float *x = nullptr, *out = nullptr, *nz = nullptr; int64_t* tt = nullptr;
   float* hist = nullptr;         // multistep solver: the previous step's data prediction, one value per latent (allocated on first use)
+  // long recordings: the canvas and its history (at most as many values as the window rows hold), the decoded windows ahead of the cross-fade
+  float *canvas = nullptr, *chist = nullptr, *dec = nullptr; size_t dec_cap = 0;
   hipStream_t stream = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;
   bool capture_failed = false;
   // embedding rows of all timesteps of a run (eager path): table [emb_cap][etot], scratch of the embedding MLP, timesteps on the device
@@ -55,6 +57,9 @@ void sampler_release(const eegldm_unet* u) {
     if (s.out) (void)hipFree(s.out);
     if (s.nz) (void)hipFree(s.nz);
     if (s.hist) (void)hipFree(s.hist);
+    if (s.canvas) (void)hipFree(s.canvas);
+    if (s.chist) (void)hipFree(s.chist);
+    if (s.dec) (void)hipFree(s.dec);
     if (s.tt) (void)hipFree(s.tt);
     if (s.emb_table) (void)hipFree(s.emb_table);
     if (s.emb_work) (void)hipFree(s.emb_work);
@@ -79,15 +84,22 @@ struct MultistepCoef { const float *cx, *c0, *c1; };
 // step is one eegldm_edit_step launch -- the same step plus the blend towards `known` noised to the level the step lands on (a_prev, or
 // a_next[i] in the multistep form); mask NULL: the same launch without the blend.
 struct EditBlock { const float *known, *mask, *a_next; };
+// lg (eegldm_sample_long; NULL otherwise; needs ms): the B = R * W forward rows are overlapping slices of R canvases (window length L,
+// margin m, ramp r: include/eegldm.h).  `noise` is canvas-shaped, x starts as its slices, and every step is one eegldm_canvas_step launch,
+// which updates the canvas AND rewrites the slices the next forward reads.  latents_out / windows_out are not used: the canvas goes to
+// canvas_out, the cross-faded decode (pixel-space model: the canvas itself) to recording_out.
+struct LongBlock { int R, W, m, r; float *canvas_out, *recording_out; };
 static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
                        const float* a_prev_host, const float* beta_t_host, int n_steps, int ancestral, int pred_type, int clip_sample,
                        float inv_scale_factor, uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
                        int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class,
-                       const MultistepCoef* ms = nullptr, const EditBlock* ed = nullptr) {
+                       const MultistepCoef* ms = nullptr, const EditBlock* ed = nullptr, const LongBlock* lg = nullptr) {
   EEG_CHECK(u && noise && timesteps_host && a_t_host && (a_prev_host || ms), "null argument");
   EEG_CHECK(!ancestral || beta_t_host, "the ancestral (DDPM) step needs beta_t");
   EEG_CHECK(n_steps >= 1 && B >= 1 && L >= 1, "bad sizes");
-  EEG_CHECK(latents_out || windows_out, "nothing to return: pass latents_out and/or windows_out");
+  EEG_CHECK(lg || latents_out || windows_out, "nothing to return: pass latents_out and/or windows_out");
+  EEG_CHECK(!lg || (ms && !ed && lg->R >= 1 && lg->W >= 1 && (long)lg->R * lg->W == B), "the canvas form needs the multistep coefficients and B == R * W");
+  EEG_CHECK(!lg || lg->canvas_out || lg->recording_out, "nothing to return: pass canvas_out and/or recording_out");
   EEG_CHECK(!ed || (ed->known && !ancestral), "editing needs the known signal and a deterministic step");
   EEG_CHECK(!ed || !ms || ed->a_next, "the multistep form needs a_next");
   eegldm_ctx* ctx = unet_ctx(u);
@@ -117,7 +129,13 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
     HIP_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
   }
   if (cond && !s.lab) HIP_TRY(hipMalloc(&s.lab, sizeof(int64_t) * Bf));
-  if (ms && !s.hist) HIP_TRY(hipMalloc(&s.hist, sizeof(float) * nf));      // (nf: the state is shared like nz)
+  if (ms && !lg && !s.hist) HIP_TRY(hipMalloc(&s.hist, sizeof(float) * nf));      // (nf: the state is shared like nz)
+  const int Sl = lg ? L - (2 * lg->m + lg->r) : 0;                 // (checked by the first eegldm_canvas_gather / eegldm_canvas_step below)
+  const long Lc = lg ? (long)(lg->W - 1) * Sl + L : 0, ncv = lg ? (long)lg->R * C * Lc : 0;
+  if (lg) {
+    EEG_CHECK(lg->m >= 0 && lg->r >= 0 && (long)L >= 3L * lg->m + 2L * lg->r && Sl >= 1, "window length %d, margin %d, ramp %d: needs m, r >= 0 and L >= 3 m + 2 r", L, lg->m, lg->r);
+    if (!s.canvas) { HIP_TRY(hipMalloc(&s.canvas, sizeof(float) * nf)); HIP_TRY(hipMalloc(&s.chist, sizeof(float) * nf)); }      // (ncv <= n <= nf)
+  }
   // the whole loop runs on the sampler's own stream (a capture cannot start on the NULL stream the caller may have given the context):
   // it waits for the caller's stream first and the caller's stream waits for it at the end
   hipStream_t caller = ctx->stream;
@@ -132,9 +150,12 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
     HIP_TRY(hipStreamWaitEvent(s.stream, s.ev_in, 0));
   }
   ctx->stream = run;
-  if (ed) EEG_TRY(eegldm_edit_start(ctx, ed->known, 1.0f, noise, a_t_host[0], nullptr, s.x, n));
+  if (lg) {
+    HIP_TRY(hipMemcpyAsync(s.canvas, noise, sizeof(float) * ncv, hipMemcpyDeviceToDevice, run));
+    EEG_TRY(eegldm_canvas_gather(ctx, s.canvas, lg->R, C, lg->W, L, Sl, s.x, guided ? s.x + n : nullptr));
+  } else if (ed) EEG_TRY(eegldm_edit_start(ctx, ed->known, 1.0f, noise, a_t_host[0], nullptr, s.x, n));
   else HIP_TRY(hipMemcpyAsync(s.x, noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
-  if (guided) HIP_TRY(hipMemcpyAsync(s.x + n, ed ? s.x : noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));     // the null-class half: same latents
+  if (guided && !lg) HIP_TRY(hipMemcpyAsync(s.x + n, ed ? s.x : noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));     // the null-class half: same latents
   if (cond) {
     HIP_TRY(hipStreamSynchronize(run));             // (the host arrays below are rewritten: an earlier call's copies from them must be done)
     s.lab_host.assign(labels_host, labels_host + B);
@@ -237,6 +258,11 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
                                pred_type, clip_sample, ms ? coef : nullptr, ed->known, noise, ed->mask, s.x, guided ? s.x + n : nullptr, nullptr, n));
       continue;
     }
+    if (lg) {
+      EEG_TRY(eegldm_canvas_step(ctx, s.out, guidance_scale, guided ? 1 : 0, s.canvas, s.chist, a_t_host[i], pred_type, clip_sample, ms->cx[i], ms->c0[i],
+                                 ms->c1[i], lg->R, C, lg->W, L, lg->m, lg->r, s.canvas, s.x, guided ? s.x + n : nullptr, nullptr));
+      continue;
+    }
     if (ms) {
       EEG_TRY(eegldm_multistep_step(ctx, s.out, guidance_scale, guided ? 1 : 0, s.x, s.hist, a_t_host[i], pred_type, clip_sample, ms->cx[i], ms->c0[i],
                                     ms->c1[i], s.x, guided ? s.x + n : nullptr, nullptr, n));
@@ -251,6 +277,26 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
       EEG_TRY(eegldm_ddpm_step(ctx, s.out, s.x, last ? nullptr : s.nz, a_t_host[i], a_prev_host[i], beta_t_host[i], pred_type, clip_sample, s.x, nullptr, n));
     } else {
       EEG_TRY(eegldm_ddim_step(ctx, s.out, s.x, a_t_host[i], a_prev_host[i], pred_type, clip_sample, s.x, nullptr, n));
+    }
+  }
+  if (lg) {
+    if (lg->canvas_out) HIP_TRY(hipMemcpyAsync(lg->canvas_out, s.canvas, sizeof(float) * ncv, hipMemcpyDeviceToDevice, run));
+    if (lg->recording_out && !ae) HIP_TRY(hipMemcpyAsync(lg->recording_out, s.canvas, sizeof(float) * ncv, hipMemcpyDeviceToDevice, run));    // pixel space
+    if (lg->recording_out && ae) {
+      // the slices of the final canvas, decoded window by window (one GroupNorm statistic per 30-s window, as in training), cross-faded
+      const int down = aekl_down(ae), Co = aekl_out_channels(ae);
+      EEG_TRY(eegldm_canvas_gather(ctx, s.canvas, lg->R, C, lg->W, L, Sl, s.x, nullptr));
+      if (inv_scale_factor != 1.0f) EEG_TRY(eegldm_axpy(ctx, s.x, s.x, inv_scale_factor - 1.0f, n));
+      const size_t nd = (size_t)B * Co * L * down;              // (a guided call and a plain one share this state at different B)
+      if (s.dec_cap < nd) {
+        HIP_TRY(hipStreamSynchronize(run));
+        if (s.dec) (void)hipFree(s.dec);
+        s.dec = nullptr; s.dec_cap = 0;
+        HIP_TRY(hipMalloc(&s.dec, sizeof(float) * nd));
+        s.dec_cap = nd;
+      }
+      EEG_TRY(eegldm_aekl_decode(ae, s.x, s.dec, B, L));
+      EEG_TRY(eegldm_canvas_compose(ctx, s.dec, lg->R, Co, lg->W, L * down, Sl * down, lg->m * down, lg->r * down, lg->recording_out));
     }
   }
   if (latents_out) HIP_TRY(hipMemcpyAsync(latents_out, s.x, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
@@ -340,4 +386,25 @@ extern "C" int eegldm_sample_edit(eegldm_unet* u, eegldm_aekl* ae, const float* 
   const MultistepCoef ms{cx_host, c0_host, c1_host};
   return sample_impl(u, ae, noise, timesteps_host, a_t_host, nullptr, nullptr, n_steps, 0, pred_type, clip_sample, inv_scale_factor, 0,
                      latents_out, windows_out, B, L, use_graph, graph_used_host, labels_host, w, null_class, &ms, edp);
+}
+
+// Long recordings (include/eegldm.h): R canvases of W overlapping windows each, sampled as one batch of R * W rows.
+extern "C" int eegldm_sample_long(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
+                                  const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int pred_type, int clip_sample,
+                                  float inv_scale_factor, float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
+                                  int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
+  EEG_CHECK(u && cx_host && c0_host && c1_host, "null argument");
+  EEG_CHECK(n_steps >= 1 && R >= 1 && W >= 1, "bad sizes");
+  EEG_CHECK((long)R * W <= 0x3fffffffL, "R * W = %ld rows: too many", (long)R * W);
+  EEG_CHECK(c1_host[0] == 0.0f, "step 0 has no history: c1[0] must be 0 (got %g)", (double)c1_host[0]);
+  if (labels_host) {
+    EEG_CHECK(unet_num_classes(u) > 0, "labels for a UNet built without classes");
+    EEG_CHECK(guidance_scale == guidance_scale, "guidance_scale is NaN");
+  } else {
+    EEG_CHECK(unet_num_classes(u) == 0, "this UNet is class-conditional: pass labels_host");
+  }
+  const MultistepCoef ms{cx_host, c0_host, c1_host};
+  const LongBlock lg{R, W, m, r, canvas_out, recording_out};
+  return sample_impl(u, ae, noise, timesteps_host, a_t_host, nullptr, nullptr, n_steps, 0, pred_type, clip_sample, inv_scale_factor, 0, nullptr,
+                     nullptr, R * W, L, use_graph, graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class, &ms, nullptr, &lg);
 }

@@ -297,3 +297,240 @@ def sample_seeds(unet, autoencoder, scheduler, seeds, latent_len=768, scale_fact
     for i, sd in enumerate(seeds):
         noise[i] = randn(unet.ctx, (lat, latent_len), seed=int(sd))
     return ddim_sample(unet, autoencoder, scheduler, noise, scale_factor, crop, labels=labels, guidance_scale=guidance_scale, null_class=null_class)
+
+
+# ------------------------------------------------------------------ long recordings: overlapped windows on one latent canvas
+class LongLayout:
+    """Where the W windows of one recording sit on its canvas and what each contributes (include/eegldm.h has the same text): window k
+    covers canvas positions [k S, k S + L), S = L - (2 m + r), Lc = (W - 1) S + L.  Host-side integers and float64 / float32 arrays."""
+
+    def __init__(self, n_windows, window_len, margin, ramp):
+        W, L, m, r = int(n_windows), int(window_len), int(margin), int(ramp)
+        if (W, L, m, r) != (n_windows, window_len, margin, ramp):
+            raise ValueError("n_windows, window_len, margin and ramp must be integers")
+        if W < 1 or m < 0 or r < 0:
+            raise ValueError(f"needs n_windows >= 1, margin >= 0 and ramp >= 0 (got {W}, {m}, {r})")
+        if L < 1 or L < 3 * m + 2 * r:
+            raise ValueError(f"window_len {L} < 3 * margin + 2 * ramp = {3 * m + 2 * r}: more than two windows would carry weight somewhere")
+        self.n_windows, self.window_len, self.margin, self.ramp = W, L, m, r
+        self.stride = L - (2 * m + r)
+        self.canvas_len = (W - 1) * self.stride + L
+        self.starts = [k * self.stride for k in range(W)]
+
+    def weights(self, k):
+        """float32 array (L,): the weight of window k at each of its positions.  u = (j - m + 0.5) / r is evaluated in float64 and rounded
+        once; the falling side is 1 - u in float32, the value the kernels form, so the two weights of a position sum to exactly 1."""
+        W, L, S, m, r = self.n_windows, self.window_len, self.stride, self.margin, self.ramp
+        if not 0 <= k < W:
+            raise IndexError(f"window {k} of {W}")
+        w = np.ones(L, np.float32)
+        u = ((np.arange(r, dtype=np.float64) + 0.5) / r).astype(np.float32) if r else np.zeros(0, np.float32)
+        if k > 0:
+            w[:m] = 0.0
+            w[m:m + r] = u
+        if k < W - 1:                                  # the next window's rising side, seen from this one: j = S + j'
+            w[S + m:S + m + r] = np.float32(1.0) - u
+            w[S + m + r:] = 0.0
+        return w
+
+    def scaled(self, down):
+        """The same layout at window resolution: m, r, S, L times the autoencoder's downsampling factor."""
+        d = int(down)
+        if d < 1:
+            raise ValueError("down must be >= 1")
+        return LongLayout(self.n_windows, self.window_len * d, self.margin * d, self.ramp * d)
+
+    def seams(self):
+        """[(first, stop)] canvas spans of the W - 1 ramps (empty spans when ramp == 0: the hard switch sits at `first`)."""
+        return [(k * self.stride + self.margin, k * self.stride + self.margin + self.ramp) for k in range(1, self.n_windows)]
+
+    def owner(self):
+        """(k1, j) int arrays (Lc,): the last window whose leading margin position p has left, and p's index inside it."""
+        p = np.arange(self.canvas_len)
+        k1 = np.where(p < self.stride + self.margin, 0, np.minimum(self.n_windows - 1, (p - self.margin) // self.stride))
+        return k1, p - k1 * self.stride
+
+
+def long_layout(n_windows, window_len, margin, ramp):
+    return LongLayout(n_windows, window_len, margin, ramp)
+
+
+def window_labels_from_hypnogram(stages, layout, down=1, sfreq=100.0, epoch_seconds=30.0):
+    """One class per window from a hypnogram (one stage per epoch): window k takes the stage at its centre time
+    (k S + L / 2) * down / sfreq seconds; a centre past the last epoch is an error."""
+    stages = np.asarray(stages).reshape(-1)
+    out = []
+    for k in range(layout.n_windows):
+        t = (k * layout.stride + layout.window_len / 2.0) * down / float(sfreq)
+        e = int(t // float(epoch_seconds))
+        if e >= len(stages):
+            raise ValueError(f"window {k} is centred at {t:.2f} s: the hypnogram has {len(stages)} epochs of {epoch_seconds} s")
+        out.append(int(stages[e]))
+    return np.asarray(out, np.int64)
+
+
+def _long_args(unet, autoencoder, scheduler, noise_shape, n_windows, margin, ramp, crop, labels):
+    """Host-side checks of a long-recording call, before anything touches the model or the device -> (layout, R, labels or None as
+    given, expanded to R * W)."""
+    if not isinstance(scheduler, DPMSolverMultistepScheduler):
+        raise ValueError("sample_long needs a DPMSolverMultistepScheduler (solver_order=1 is DDIM on the same grid)")
+    if len(noise_shape) != 3:
+        raise ValueError(f"noise has shape {tuple(noise_shape)}, expected (R, C, canvas length)")
+    R, Cc, Lc = (int(v) for v in noise_shape)
+    W = int(n_windows)
+    if W < 1:
+        raise ValueError("n_windows must be >= 1")
+    down = autoencoder.down if autoencoder is not None else 1
+    if margin is None:
+        margin = 2 * int(crop) // down
+    if ramp is None:
+        ramp = 4 * int(crop) // down
+    m, r = int(margin), int(ramp)
+    if m < 0 or r < 0:
+        raise ValueError("margin and ramp must be >= 0")
+    if W == 1:
+        L = Lc
+    else:
+        S, rem = divmod(Lc - (2 * m + r), W)           # Lc = (W - 1) S + L = W S + 2 m + r
+        if rem or S < 1:
+            raise ValueError(f"noise has length {Lc}: no window length gives {W} windows with margin {m} and ramp {r} "
+                             f"(needs (W - 1) * (L - {2 * m + r}) + L)")
+        L = S + 2 * m + r
+    lay = LongLayout(W, L, m, r)
+    if lay.canvas_len != Lc or R < 1:
+        raise ValueError(f"noise has shape {tuple(noise_shape)}, expected (R >= 1, C, {lay.canvas_len})")
+    if labels is not None:
+        lab = torch.as_tensor(labels).reshape(-1)
+        if lab.numel() == W:
+            lab = lab.repeat(R)
+        if lab.numel() != R * W:
+            raise ValueError(f"{lab.numel()} labels for {R} recordings of {W} windows: pass R * W (recording-major) or W")
+        labels = lab
+    return lay, R, labels
+
+
+@torch.no_grad()
+def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ramp=None, scale_factor=1.0, crop=36, labels=None,
+                guidance_scale=1.0, null_class=None, use_graph=None, info=None):
+    """noise (R, C, Lc) on the device -> (recording (R, out, down * Lc - 2 * crop), canvas (R, C, Lc)).  Overlapped-window sampling on one
+    latent canvas (MultiDiffusion): the R * W overlapping slices of the canvases are the rows of ONE forward batch, and behind every
+    forward ONE eegldm_canvas_step launch fuses the slices' data predictions with a partition-of-unity taper, takes the solver step on
+    the canvas and rewrites the slices.  The whole loop, the window-by-window decode and the cross-fade onto the recording are ONE native
+    call (eegldm_sample_long).  The window length follows from the noise: Lc = (W - 1) (L - (2 margin + ramp)) + L.
+    `scheduler`: a DPMSolverMultistepScheduler (order 1 or 2).  labels: R * W classes, recording-major (or W, the same for every
+    recording); guidance as in `sample`.  margin / ramp (latent positions) default to 2 crop / down and 4 crop / down -- 18 and 36 latents
+    for the 3072-sample window, stride 696 latents = 27.84 s: conventions derived from the training crop, NOT tuned against any seam
+    measure (tools/seam_report.py is what one tunes them by).  info (optional dict) receives {"graph": bool, "layout": LongLayout}."""
+    lay, R, labels = _long_args(unet, autoencoder, scheduler, noise.shape, n_windows, margin, ramp, crop, labels)
+    from .models import UNetModel
+    if not isinstance(unet, UNetModel):
+        raise TypeError("sample_long runs the native loop: unet must be a UNetModel")
+    unet.eval()
+    x = noise.to(unet.device, torch.float32).contiguous()
+    Cc = x.shape[1]
+    if Cc != unet.in_channels:
+        raise ValueError(f"noise has {Cc} channels, the UNet takes {unet.in_channels}")
+    W, L = lay.n_windows, lay.window_len
+    lab, nc = _labels_host(unet, labels, R * W, guidance_scale, null_class)
+    ts, a_t, cx, c0, c1 = _multistep_tables(scheduler)
+    if use_graph is None:
+        use_graph = os.environ.get("EEGLDM_SAMPLE_GRAPH", "0") == "1" and os.environ.get("EEGLDM_NO_GRAPH") is None
+    down = autoencoder.down if autoencoder is not None else 1
+    out_c = autoencoder.out_channels if autoencoder is not None else Cc
+    canvas = torch.empty_like(x)
+    rec = torch.empty(R, out_c, lay.canvas_len * down, device=unet.device, dtype=torch.float32)
+    used = C.c_int(0)
+    i64, f32 = (lambda v: (C.c_int64 * len(v))(*v)), (lambda v: (C.c_float * len(v))(*v))
+    check(lib.eegldm_sample_long(unet.h, autoencoder.h if autoencoder is not None else None, ptr(x), i64(ts), f32(a_t), f32(cx), f32(c0), f32(c1),
+                                 len(ts), PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor), ptr(canvas),
+                                 ptr(rec), R, W, L, lay.margin, lay.ramp, 1 if use_graph else 0, C.byref(used), None if lab is None else i64(lab),
+                                 float(guidance_scale), nc))
+    unet._bump_tape()
+    if autoencoder is not None:
+        autoencoder._bump_tape()
+    if info is not None:
+        info["graph"] = bool(used.value)
+        info["layout"] = lay
+    return (rec[:, :, crop:-crop] if crop else rec), canvas
+
+
+def _fma32(a, b, c):
+    """float32 fma(a, b, c) on tensors (a may be a Python float holding a float32 value): the product of two float32 is exact in
+    float64, the sum is rounded there and once more to float32."""
+    a = a.double() if torch.is_tensor(a) else float(a)
+    return (a * b.double() + c.double()).float()
+
+
+def _long_x0(o, x, a_t, prediction_type, clip_sample):
+    """The data prediction with the library's roundings: sqrt(a_t) and sqrt(1 - a_t) rounded to float32, the products feeding a
+    fused multiply-add."""
+    a32 = np.float32(a_t)
+    sa, sb = float(np.sqrt(a32)), float(np.sqrt(np.float32(1.0) - a32))
+    if prediction_type == "epsilon":
+        x0 = (_fma32(-sb, o, x).double() / sa).float()
+    elif prediction_type == "v_prediction":
+        x0 = _fma32(sa, x, -(o * sb))
+    else:
+        x0 = o
+    return x0.clamp(-1.0, 1.0) if clip_sample else x0
+
+
+def _long_crossfade(rows, lay):
+    """rows (R, W, Cc, L) -> (R, Cc, Lc): the owner window's value, fma(u, later, (1 - u) * earlier) inside the ramps (float32 roundings)."""
+    R, W, Cc, L = rows.shape
+    k1, j = lay.owner()
+    k1_t, j_t = torch.from_numpy(k1).to(rows.device), torch.from_numpy(j).to(rows.device)
+    out = rows[:, k1_t, :, j_t].permute(1, 2, 0).contiguous()                     # advanced indices first: (Lc, R, Cc) -> (R, Cc, Lc)
+    m, r, S = lay.margin, lay.ramp, lay.stride
+    if r:
+        u = torch.from_numpy(((np.arange(r, dtype=np.float64) + 0.5) / r).astype(np.float32)).to(rows.device)
+        for k in range(1, W):
+            later, earlier = rows[:, k, :, m:m + r], rows[:, k - 1, :, S + m:S + m + r]
+            out[:, :, k * S + m:k * S + m + r] = _fma32(u, later, (1.0 - u) * earlier)
+    return out
+
+
+@torch.no_grad()
+def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=None, ramp=None, scale_factor=1.0, crop=36, labels=None,
+                         guidance_scale=1.0, null_class=None, use_graph=None, info=None):
+    """The reference composition of sample_long in torch, none of the canvas kernels: slice the canvas, model(...) on all slices, the
+    guidance mix, x0 from the scheduler's formulas, the taper of layout.weights (as a cross-fade of the two windows that carry weight),
+    prev = cx x + c0 x0 + c1 hist on the canvas, then decode per window and cross-fade.  The float32 roundings are placed where the
+    library places them (fused multiply-adds are formed in float64 and rounded once more).  `unet` is any callable
+    model(x, timesteps=, [y=]) with .device / .eval(); use_graph is accepted and ignored."""
+    lay, R, labels = _long_args(unet, autoencoder, scheduler, noise.shape, n_windows, margin, ramp, crop, labels)
+    unet.eval()
+    dev = unet.device
+    x = noise.to(dev, torch.float32).contiguous().clone()
+    Cc = x.shape[1]
+    W, L, S = lay.n_windows, lay.window_len, lay.stride
+    lab, nc = _labels_host(unet, labels, R * W, guidance_scale, null_class)
+    kw = {} if lab is None else {"y": torch.tensor(lab, dtype=torch.int64, device=dev)}
+    null = None if lab is None else torch.full((R * W,), nc, dtype=torch.int64, device=dev)
+    w = float(np.float32(guidance_scale))
+    ts, a_t, cx, c0, c1 = _multistep_tables(scheduler)
+    tt = torch.empty(R * W, device=dev, dtype=torch.int64)
+    slices = lambda cv: torch.stack([cv[:, :, k * S:k * S + L] for k in range(W)], 1).reshape(R * W, Cc, L)
+    hist = None
+    for i, t in enumerate(ts):
+        tt.fill_(t)
+        win = slices(x)
+        out = unet(win, timesteps=tt, **kw).float()
+        if lab is not None and w != 1.0:
+            out_u = unet(win, timesteps=tt, y=null).float()
+            out = _fma32(w, out - out_u, out_u)
+        x0 = _long_crossfade(_long_x0(out, win, a_t[i], scheduler.prediction_type, scheduler.clip_sample).reshape(R, W, Cc, L), lay)
+        inner = _fma32(c0[i], x0, hist * c1[i]) if c1[i] != 0.0 else x0 * c0[i]
+        x = _fma32(cx[i], x, inner)
+        hist = x0
+    if info is not None:
+        info["graph"], info["layout"] = False, lay
+    if autoencoder is None:
+        return (x[:, :, crop:-crop] if crop else x), x
+    z = slices(x).contiguous()
+    if float(scale_factor) != 1.0:
+        # 1 / scale_factor rounded to float32, minus one in float32: the native loop's value (see ddim_sample_hostloop)
+        check(lib.eegldm_axpy(autoencoder.ctx.h, ptr(z), ptr(z), float(np.float32(1.0 / float(scale_factor)) - np.float32(1.0)), z.numel()))
+    dec = autoencoder.decode_stage_2_outputs(z)
+    rec = _long_crossfade(dec.reshape(R, W, dec.shape[1], dec.shape[2]), lay.scaled(autoencoder.down))
+    return (rec[:, :, crop:-crop] if crop else rec), x
