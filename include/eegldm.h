@@ -47,7 +47,8 @@ extern "C" {
  *    eegldm_ema_update, eegldm_swap), the multistep sampler (eegldm_multistep_step, eegldm_sample_multistep) and editing (eegldm_edit_step,
  *    eegldm_edit_start, eegldm_edit_window, eegldm_sample_edit) and the weighted diffusion loss (eegldm_diffusion_loss, eegldm_loss_bins,
  *    eegldm_ldm_train_step_weighted) and global gradient-norm clipping (eegldm_grad_norm, eegldm_adam_step_clip, eegldm_grad_scale_by)
- *    and long recordings (eegldm_canvas_gather, eegldm_canvas_step, eegldm_canvas_compose, eegldm_sample_long). */
+ *    and long recordings (eegldm_canvas_gather, eegldm_canvas_step, eegldm_canvas_compose, eegldm_sample_long) and their editing
+ *    (eegldm_canvas_edit_step, eegldm_sample_long_edit). */
 #define EEGLDM_ABI_VERSION 8
 
 /* Storage / operand type of activations and compute-copy weights (accumulation, statistics, master weights and optimizer state are
@@ -631,6 +632,34 @@ int eegldm_sample_long(eegldm_unet*, eegldm_aekl* ae, const float* noise, const 
                        const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int pred_type, int clip_sample,
                        float inv_scale_factor, float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
                        int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class);
+
+/* Repairing and extending real recordings: init and keep-mask on the canvas; new symbols, ABI 8.
+ * eegldm_canvas_edit_step: eegldm_canvas_step and the blend of eegldm_edit_step in ONE launch.  known / noise / mask are canvas-shaped
+ * ((R, C, Lc) fp32, any 4-byte alignment each, 16-byte accesses where an address allows), read at the canvas index.  Per canvas element
+ * the fused data prediction x0 and prev = fma(cx, xc, fma(c0, x0, c1 * hist)) are eegldm_canvas_step's, then
+ *   prev <- mask == 0 ? prev : mask == 1 ? k(a_next) : fma(mask, k(a_next), (1 - mask) * prev),
+ *   k(a) = fma(sqrt(a), known, sqrt(1 - a) * noise)  (a == 1: known)
+ * with the device functions of eegldm_edit_step / eegldm_edit_start, so all three round alike.  The blended value goes to canvas_out and
+ * to every covering window row of win / win2, weight-0 windows included (under guidance the null-class half receives the blended
+ * latents); hist and pred_x0 receive the model's own fused x0, not a blended one.  mask == NULL: known / noise are not read and the call
+ * IS eegldm_canvas_step (the same kernel).  An all-zero mask returns eegldm_canvas_step's bytes, an all-one mask k(a_next).  known / noise
+ * / mask may not overlap an output; the aliasing rules are otherwise eegldm_canvas_step's.  No atomics, no memset, one writer per
+ * output element. */
+int eegldm_canvas_edit_step(eegldm_ctx*, const float* model_out, float guidance_scale, int guided, const float* canvas, float* hist, float a_t,
+                            float a_next, int pred_type, int clip_sample, float cx, float c0, float c1, int R, int C, int W, int L, int m, int r,
+                            const float* known, const float* noise, const float* mask, float* canvas_out, float* win, float* win2,
+                            float* pred_x0);
+/* The loop of eegldm_sample_long from a real recording: known / mask (both nullable; device, (R, C, Lc), valid and unwritten during the
+ * call) and a_next_host.  All host arrays hold the n_steps EXECUTED steps (the tail of the grid, as in eegldm_sample_edit); a_next_host[i]
+ * is the noise level step i lands on; c1_host[0] == 0.  known == NULL: eegldm_sample_long (mask must be NULL too).  Otherwise the canvas
+ * starts as k(a_t_host[0]) (eegldm_edit_start on the R C Lc canvas elements), is gathered, and every step is one forward and ONE
+ * eegldm_canvas_edit_step launch (mask NULL: without the blend).  Everything else -- embedding table, 2 R W-row guided forward, eager
+ * launches or graph replay, the final gather, the window-by-window decode and the compose -- is eegldm_sample_long's. */
+int eegldm_sample_long_edit(eegldm_unet*, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                            const int64_t* timesteps_host, const float* a_t_host, const float* cx_host, const float* c0_host,
+                            const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample, float inv_scale_factor,
+                            float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph, int* graph_used_host,
+                            const int64_t* labels_host, float guidance_scale, int64_t null_class);
 
 /* ------------------------------------------------------------------ data-parallel collectives (RCCL over xGMI)
  * One communicator per process / GPU.  Stands where the reference gathers gradients with single-process nn.DataParallel

@@ -161,6 +161,11 @@ SIGNATURES = {
     "eegldm_canvas_compose": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "eegldm_sample_long": [_vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _f,
                            _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_int64), _f, C.c_int64],
+    "eegldm_canvas_edit_step": [_vp, _vp, _f, _i, _vp, _vp, _f, _f, _i, _i, _f, _f, _f, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp],
+    "eegldm_sample_long_edit": [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f),
+                                C.POINTER(_f), _i, _i, _i, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_int64), _f,
+                                C.c_int64],
     "eegldm_disc_create": [_vp, _vp, C.POINTER(_vp)],
     "eegldm_disc_destroy": [_vp],
     "eegldm_disc_num_entries": [_vp],

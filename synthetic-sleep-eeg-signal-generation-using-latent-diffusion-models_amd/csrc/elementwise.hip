@@ -875,9 +875,14 @@ struct CanvasStepArgs {
   const float* mo; float w; int guided; const float* canvas; float* hist; float sa, sb; int pred, clip; float cx, c0, c1;
   float *out, *win, *win2, *x0o; long n_win;
 };
-// N canvas elements from position p of row `row` (= rec * C + c): all in one row, one owner window, one ramp state, one set of covering windows
-template <int N>
-__device__ __forceinline__ void canvas_step_span(const CanvasGeo& g, const CanvasStepArgs& a, long row, int p, const CanvasAt& at) {
+// the blend of eegldm_canvas_edit_step: three canvas-shaped inputs and the noise level the step lands on (ka = sqrt(a_next), kb = sqrt(1 - a_next))
+struct CanvasEditArgs { const float *known, *noise, *mask; float ka, kb; };
+// N canvas elements from position p of row `row` (= rec * C + c): all in one row, one owner window, one ramp state, one set of covering windows.
+// EDIT (canvas_edit_step_kernel only; e is not read otherwise): prev <- edit_blend(mask, edit_renoise(known, noise), prev) ahead of the stores
+// of prev; hist / pred_x0 keep the model's own fused x0.
+template <int N, bool EDIT>
+__device__ __forceinline__ void canvas_step_span(const CanvasGeo& g, const CanvasStepArgs& a, const CanvasEditArgs& e, long row, int p,
+                                                 const CanvasAt& at) {
   const long ci = row * g.Lc + p;
   const long rec = row / g.C; const int c = (int)(row - rec * g.C);
   float xc[4], o[4], z[4], h[4] = {0.0f, 0.0f, 0.0f, 0.0f}, pv[4];
@@ -908,6 +913,14 @@ __device__ __forceinline__ void canvas_step_span(const CanvasGeo& g, const Canva
   if (a.c1 != 0.0f) canvas_ld<N>(a.hist + ci, h);
 #pragma unroll
   for (int k = 0; k < N; k++) pv[k] = multistep_update(xc[k], z[k], h[k], a.cx, a.c0, a.c1);
+  if (EDIT) {
+    float kn[4], nz[4], mk[4];
+    canvas_ld<N>(e.known + ci, kn);
+    canvas_ld<N>(e.noise + ci, nz);
+    canvas_ld<N>(e.mask + ci, mk);
+#pragma unroll
+    for (int k = 0; k < N; k++) pv[k] = edit_blend(mk[k], edit_renoise(kn[k], nz[k], e.ka, e.kb), pv[k]);
+  }
   canvas_st<N>(a.out + ci, pv);
   if (a.hist) canvas_st<N>(a.hist + ci, z);
   if (a.x0o) canvas_st<N>(a.x0o + ci, z);
@@ -923,7 +936,8 @@ __device__ __forceinline__ void canvas_step_span(const CanvasGeo& g, const Canva
 // One sampling step on the canvas, one launch: n = R C Lc canvas elements, four per thread from `head` on (the canvas's own 16-byte
 // grid; every other buffer takes 16-byte accesses where its address allows).  A group of four that crosses a row end, a window's margin
 // or ramp edge, or the edge of a covering window goes element by element in the same thread; every output element has one writer.
-__global__ __launch_bounds__(NT) void canvas_step_kernel(CanvasGeo g, CanvasStepArgs a, long n, long head) {
+template <bool EDIT>
+__device__ __forceinline__ void canvas_step_body(const CanvasGeo& g, const CanvasStepArgs& a, const CanvasEditArgs& e, long n, long head) {
   const VecSplit s = vec_split(n, head);
   GRID_STRIDE(q, s.n4) {
     const long i = head + (q << 2);
@@ -931,20 +945,28 @@ __global__ __launch_bounds__(NT) void canvas_step_kernel(CanvasGeo g, CanvasStep
     bool one = canvas_one_row(i, g.Lc, &row, &p);
     CanvasAt at = canvas_at(g, p);
     if (one) {
-      const CanvasAt e = canvas_at(g, p + 3);
-      one = e.k1 == at.k1 && e.ramp == at.ramp && canvas_kmin(g, p) == canvas_kmin(g, p + 3) && canvas_kmax(g, p) == canvas_kmax(g, p + 3);
+      const CanvasAt e3 = canvas_at(g, p + 3);
+      one = e3.k1 == at.k1 && e3.ramp == at.ramp && canvas_kmin(g, p) == canvas_kmin(g, p + 3) && canvas_kmax(g, p) == canvas_kmax(g, p + 3);
     }
-    if (one) { canvas_step_span<4>(g, a, row, p, at); continue; }
+    if (one) { canvas_step_span<4, EDIT>(g, a, e, row, p, at); continue; }
     for (int k = 0; k < 4; k++) {
       (void)canvas_one_row(i + k, g.Lc, &row, &p);
-      canvas_step_span<1>(g, a, row, p, canvas_at(g, p));
+      canvas_step_span<1, EDIT>(g, a, e, row, p, canvas_at(g, p));
     }
   }
   GRID_STRIDE(j, s.nedge) {
     long row; int p;
     (void)canvas_one_row(EDGE_INDEX(s, j), g.Lc, &row, &p);
-    canvas_step_span<1>(g, a, row, p, canvas_at(g, p));
+    canvas_step_span<1, EDIT>(g, a, e, row, p, canvas_at(g, p));
   }
+}
+__global__ __launch_bounds__(NT) void canvas_step_kernel(CanvasGeo g, CanvasStepArgs a, long n, long head) {
+  canvas_step_body<false>(g, a, CanvasEditArgs{}, n, head);
+}
+// The same step plus the blend towards the known signal noised to the level the step lands on (eegldm_canvas_edit_step with a mask): the
+// grouping is unchanged -- known / noise / mask are canvas-shaped, so a span of the canvas is a span of theirs.
+__global__ __launch_bounds__(NT) void canvas_edit_step_kernel(CanvasGeo g, CanvasStepArgs a, CanvasEditArgs e, long n, long head) {
+  canvas_step_body<true>(g, a, e, n, head);
 }
 // win[rec * W + k][c][l] = canvas[rec][c][k S + l] (and the same into win2): n = R W C L window elements on win's 16-byte grid
 template <int N>
@@ -1796,9 +1818,10 @@ extern "C" int eegldm_canvas_gather(eegldm_ctx* ctx, const float* canvas, int R,
   hipLaunchKernelGGL(canvas_gather_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, g, canvas, win, win2, n, head);
   LAUNCH_CHECK(); return 0;
 }
-extern "C" int eegldm_canvas_step(eegldm_ctx* ctx, const float* mo, float w, int guided, const float* canvas, float* hist, float a_t, int pred,
-                                  int clip, float cx, float c0, float c1, int R, int C, int W, int L, int m, int r, float* canvas_out,
-                                  float* win, float* win2, float* x0) {
+// e == NULL: eegldm_canvas_step; else eegldm_canvas_edit_step with a mask (the checks of the step, then those of the three edit inputs)
+static int canvas_step_launch(eegldm_ctx* ctx, const float* mo, float w, int guided, const float* canvas, float* hist, float a_t, int pred,
+                              int clip, float cx, float c0, float c1, int R, int C, int W, int L, int m, int r, float* canvas_out, float* win,
+                              float* win2, float* x0, const CanvasEditArgs* e) {
   EEG_CHECK(ctx && mo && canvas && canvas_out, "null argument");
   CanvasGeo g;
   EEG_TRY(canvas_geo(R, C, W, L, L - (2 * m + r), m, r, &g));
@@ -1822,8 +1845,33 @@ extern "C" int eegldm_canvas_step(eegldm_ctx* ctx, const float* mo, float w, int
     EEG_CHECK(((uintptr_t)q & 3) == 0, "buffers must be 4-byte aligned");
   CanvasStepArgs a{mo, w, guided ? 1 : 0, canvas, hist, sqrtf(a_t), sqrtf(1.0f - a_t), pred, clip, cx, c0, c1, canvas_out, win, win2, x0, nw};
   const long head = canvas_head(canvas, n);
-  hipLaunchKernelGGL(canvas_step_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, g, a, n, head);
+  if (!e) {
+    hipLaunchKernelGGL(canvas_step_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, g, a, n, head);
+    LAUNCH_CHECK(); return 0;
+  }
+  for (const float* q : {e->known, e->noise, e->mask}) {
+    EEG_CHECK(((uintptr_t)q & 3) == 0, "buffers must be 4-byte aligned");
+    EEG_CHECK(!ov(q, n, canvas_out, n) && !ov(q, n, x0, n) && !ov(q, n, hist, n) && !ov(q, n, win, nw) && !ov(q, n, win2, nw),
+              "known / noise / mask alias an output buffer");
+  }
+  hipLaunchKernelGGL(canvas_edit_step_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, g, a, *e, n, head);
   LAUNCH_CHECK(); return 0;
+}
+extern "C" int eegldm_canvas_step(eegldm_ctx* ctx, const float* mo, float w, int guided, const float* canvas, float* hist, float a_t, int pred,
+                                  int clip, float cx, float c0, float c1, int R, int C, int W, int L, int m, int r, float* canvas_out,
+                                  float* win, float* win2, float* x0) {
+  return canvas_step_launch(ctx, mo, w, guided, canvas, hist, a_t, pred, clip, cx, c0, c1, R, C, W, L, m, r, canvas_out, win, win2, x0, nullptr);
+}
+// mask == NULL: the launch of eegldm_canvas_step itself (known / noise are not read); else the same step with the blend inside it
+extern "C" int eegldm_canvas_edit_step(eegldm_ctx* ctx, const float* mo, float w, int guided, const float* canvas, float* hist, float a_t,
+                                       float a_next, int pred, int clip, float cx, float c0, float c1, int R, int C, int W, int L, int m, int r,
+                                       const float* known, const float* noise, const float* mask, float* canvas_out, float* win, float* win2,
+                                       float* x0) {
+  EEG_CHECK(a_next > 0.0f && a_next <= 1.0f, "a_next %g outside (0, 1]", (double)a_next);
+  EEG_CHECK(!mask || (known && noise), "a mask needs the known signal and the noise");
+  const CanvasEditArgs e{known, noise, mask, sqrtf(a_next), sqrtf(1.0f - a_next)};
+  return canvas_step_launch(ctx, mo, w, guided, canvas, hist, a_t, pred, clip, cx, c0, c1, R, C, W, L, m, r, canvas_out, win, win2, x0,
+                            mask ? &e : nullptr);
 }
 extern "C" int eegldm_canvas_compose(eegldm_ctx* ctx, const float* decoded, int R, int Co, int W, int Lw, int Sw, int mw, int rw, float* out) {
   EEG_CHECK(ctx && decoded && out, "null argument");

@@ -88,6 +88,8 @@ struct EditBlock { const float *known, *mask, *a_next; };
 // margin m, ramp r: include/eegldm.h).  `noise` is canvas-shaped, x starts as its slices, and every step is one eegldm_canvas_step launch,
 // which updates the canvas AND rewrites the slices the next forward reads.  latents_out / windows_out are not used: the canvas goes to
 // canvas_out, the cross-faded decode (pixel-space model: the canvas itself) to recording_out.
+// lg and ed together (eegldm_sample_long_edit): known / mask are canvas-shaped, the canvas starts as `known` noised to a_t[0] with `noise`,
+// and every step is one eegldm_canvas_edit_step launch (the canvas step and the blend; mask NULL: the canvas step alone).
 struct LongBlock { int R, W, m, r; float *canvas_out, *recording_out; };
 static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
                        const float* a_prev_host, const float* beta_t_host, int n_steps, int ancestral, int pred_type, int clip_sample,
@@ -98,7 +100,7 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
   EEG_CHECK(!ancestral || beta_t_host, "the ancestral (DDPM) step needs beta_t");
   EEG_CHECK(n_steps >= 1 && B >= 1 && L >= 1, "bad sizes");
   EEG_CHECK(lg || latents_out || windows_out, "nothing to return: pass latents_out and/or windows_out");
-  EEG_CHECK(!lg || (ms && !ed && lg->R >= 1 && lg->W >= 1 && (long)lg->R * lg->W == B), "the canvas form needs the multistep coefficients and B == R * W");
+  EEG_CHECK(!lg || (ms && lg->R >= 1 && lg->W >= 1 && (long)lg->R * lg->W == B), "the canvas form needs the multistep coefficients and B == R * W");
   EEG_CHECK(!lg || lg->canvas_out || lg->recording_out, "nothing to return: pass canvas_out and/or recording_out");
   EEG_CHECK(!ed || (ed->known && !ancestral), "editing needs the known signal and a deterministic step");
   EEG_CHECK(!ed || !ms || ed->a_next, "the multistep form needs a_next");
@@ -151,7 +153,8 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
   }
   ctx->stream = run;
   if (lg) {
-    HIP_TRY(hipMemcpyAsync(s.canvas, noise, sizeof(float) * ncv, hipMemcpyDeviceToDevice, run));
+    if (ed) EEG_TRY(eegldm_edit_start(ctx, ed->known, 1.0f, noise, a_t_host[0], nullptr, s.canvas, ncv));
+    else HIP_TRY(hipMemcpyAsync(s.canvas, noise, sizeof(float) * ncv, hipMemcpyDeviceToDevice, run));
     EEG_TRY(eegldm_canvas_gather(ctx, s.canvas, lg->R, C, lg->W, L, Sl, s.x, guided ? s.x + n : nullptr));
   } else if (ed) EEG_TRY(eegldm_edit_start(ctx, ed->known, 1.0f, noise, a_t_host[0], nullptr, s.x, n));
   else HIP_TRY(hipMemcpyAsync(s.x, noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
@@ -252,6 +255,12 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
     else set_t(timesteps_host[i]);
     if (graph_ok) HIP_TRY(hipGraphLaunch(s.exec, run));
     else EEG_TRY(unet_forward_labels(u, s.x, s.tt, fwd_lab, s.out, Bf, L, 0));
+    if (ed && lg) {
+      EEG_TRY(eegldm_canvas_edit_step(ctx, s.out, guidance_scale, guided ? 1 : 0, s.canvas, s.chist, a_t_host[i], ed->a_next[i], pred_type, clip_sample,
+                                      ms->cx[i], ms->c0[i], ms->c1[i], lg->R, C, lg->W, L, lg->m, lg->r, ed->known, noise, ed->mask, s.canvas, s.x,
+                                      guided ? s.x + n : nullptr, nullptr));
+      continue;
+    }
     if (ed) {      // (without a mask too: an all-zero mask and no mask are then the same bytes in every form)
       const float coef[3] = {ms ? ms->cx[i] : 0.0f, ms ? ms->c0[i] : 0.0f, ms ? ms->c1[i] : 0.0f};
       EEG_TRY(eegldm_edit_step(ctx, s.out, guidance_scale, guided ? 1 : 0, s.x, ms ? s.hist : nullptr, a_t_host[i], ms ? ed->a_next[i] : a_prev_host[i],
@@ -407,4 +416,32 @@ extern "C" int eegldm_sample_long(eegldm_unet* u, eegldm_aekl* ae, const float* 
   const LongBlock lg{R, W, m, r, canvas_out, recording_out};
   return sample_impl(u, ae, noise, timesteps_host, a_t_host, nullptr, nullptr, n_steps, 0, pred_type, clip_sample, inv_scale_factor, 0, nullptr,
                      nullptr, R * W, L, use_graph, graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class, &ms, nullptr, &lg);
+}
+
+// The same loop from a real recording (include/eegldm.h): the canvas form with the edit block.  known == NULL: eegldm_sample_long.
+extern "C" int eegldm_sample_long_edit(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                                       const int64_t* timesteps_host, const float* a_t_host, const float* cx_host, const float* c0_host,
+                                       const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
+                                       float inv_scale_factor, float* canvas_out, float* recording_out, int R, int W, int L, int m, int r,
+                                       int use_graph, int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
+  EEG_CHECK(known || !mask, "a mask needs the known signal");
+  EEG_CHECK(!known || a_next_host, "the run from an input needs a_next_host");
+  if (!known)
+    return eegldm_sample_long(u, ae, noise, timesteps_host, a_t_host, cx_host, c0_host, c1_host, n_steps, pred_type, clip_sample, inv_scale_factor,
+                              canvas_out, recording_out, R, W, L, m, r, use_graph, graph_used_host, labels_host, guidance_scale, null_class);
+  EEG_CHECK(u && cx_host && c0_host && c1_host, "null argument");
+  EEG_CHECK(n_steps >= 1 && R >= 1 && W >= 1, "bad sizes");
+  EEG_CHECK((long)R * W <= 0x3fffffffL, "R * W = %ld rows: too many", (long)R * W);
+  EEG_CHECK(c1_host[0] == 0.0f, "the first executed step has no history: c1[0] must be 0 (got %g)", (double)c1_host[0]);
+  if (labels_host) {
+    EEG_CHECK(unet_num_classes(u) > 0, "labels for a UNet built without classes");
+    EEG_CHECK(guidance_scale == guidance_scale, "guidance_scale is NaN");
+  } else {
+    EEG_CHECK(unet_num_classes(u) == 0, "this UNet is class-conditional: pass labels_host");
+  }
+  const MultistepCoef ms{cx_host, c0_host, c1_host};
+  const EditBlock ed{known, mask, a_next_host};
+  const LongBlock lg{R, W, m, r, canvas_out, recording_out};
+  return sample_impl(u, ae, noise, timesteps_host, a_t_host, nullptr, nullptr, n_steps, 0, pred_type, clip_sample, inv_scale_factor, 0, nullptr,
+                     nullptr, R * W, L, use_graph, graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class, &ms, &ed, &lg);
 }

@@ -409,9 +409,126 @@ def _long_args(unet, autoencoder, scheduler, noise_shape, n_windows, margin, ram
     return lay, R, labels
 
 
+def erode_mask(mask, erode):
+    """mask (R, 1, n), 1 = keep -> the mask with every kept region shrunk by `erode` samples on each side that borders a regenerated span:
+    out[t] = min(mask[t - erode .. t + erode]); samples past a free end of the recording do not count as regenerated.  Host-side torch
+    work, once per call."""
+    e = int(erode)
+    if e != erode or e < 0:
+        raise ValueError(f"mask_erode must be an integer >= 0 (got {erode})")
+    m = torch.as_tensor(mask)
+    if e == 0:
+        return m
+    return -torch.nn.functional.max_pool1d(-m.to(torch.float32), 2 * e + 1, 1, e)        # (max_pool1d pads with -inf: +inf for the min)
+
+
+def _long_edit_args(autoencoder, scheduler, lay, R, Cc, init, init_canvas, strength, mask, composite, mask_erode):
+    """Checks the arguments of a long-recording run that starts from an input, on the host and before anything runs; -> None without init /
+    init_canvas, else dict(tab = the truncated tables, composite = bool).  Shapes: init (R, in_channels, down * Lc) for an LDM, (R, C, Lc)
+    for a pixel-space model; init_canvas (R, C, Lc); mask (R, 1, down * Lc), 1 = keep."""
+    from .schedulers import edit_start_index
+    edit_start_index(1, strength)           # the range of strength, whatever else is given
+    if int(mask_erode) != mask_erode or mask_erode < 0:
+        raise ValueError(f"mask_erode must be an integer >= 0 (got {mask_erode})")
+    if init is None and init_canvas is None:
+        if mask is not None:
+            raise ValueError("mask needs init (or init_canvas): the kept samples have to come from somewhere")
+        if composite:
+            raise ValueError("composite needs init and mask")
+        if float(strength) != 1.0:
+            raise ValueError("strength needs init (or init_canvas)")
+        return None
+    if init is not None and init_canvas is not None:
+        raise ValueError("pass init (the recording) or init_canvas (latents), not both")
+    tab = scheduler_edit_tables(scheduler, strength)
+    down = autoencoder.down if autoencoder is not None else 1
+    Lc = lay.canvas_len
+    if init is not None:
+        want = (R, autoencoder.in_channels, Lc * down) if autoencoder is not None else (R, Cc, Lc)
+        if tuple(init.shape) != want:
+            raise ValueError(f"init has shape {tuple(init.shape)}, expected {want}")
+        if autoencoder is not None and autoencoder.in_channels != autoencoder.out_channels and mask is not None and composite is not False:
+            raise ValueError("the composite needs an autoencoder with in_channels == out_channels")
+    elif tuple(init_canvas.shape) != (R, Cc, Lc):
+        raise ValueError(f"init_canvas has shape {tuple(init_canvas.shape)}, expected {(R, Cc, Lc)}")
+    if mask is not None and tuple(mask.shape) != (R, 1, Lc * down):
+        raise ValueError(f"mask has shape {tuple(mask.shape)}, expected {(R, 1, Lc * down)}")
+    if composite and (mask is None or init is None):
+        raise ValueError("composite needs mask and init (the recording at window resolution)")
+    return dict(tab=tab, composite=(mask is not None and init is not None) if composite is None else bool(composite))
+
+
+def _slices_of(cv, lay):
+    """(R, C, Lc) -> (R * W, C, L) by torch slicing"""
+    R, Cc, _ = cv.shape
+    S, L = lay.stride, lay.window_len
+    return torch.stack([cv[:, :, k * S:k * S + L] for k in range(lay.n_windows)], 1).reshape(R * lay.n_windows, Cc, L)
+
+
+@torch.no_grad()
+def encode_long(autoencoder, recording, layout, scale_factor=1.0, native=True):
+    """recording (R, in_channels, down * Lc) at window resolution -- the `crop` zero samples at its two free ends included, as a training
+    window holds them -- -> z0 (R, C, Lc), the clean latent canvas of `layout` (the LATENT LongLayout).  Composed from existing exports:
+    eegldm_canvas_gather at window resolution, the posterior mean of the R * W windows (each encoded as its own row, so the encoder's
+    GroupNorm statistics span one 30-s window as in training; no reparameterisation draw), eegldm_edit_start for the scale, and
+    eegldm_canvas_compose with the latent layout: the owner window's latent outside the ramps, the cross-fade of the two inside.  A
+    zero-weight margin thereby discards exactly the latents that were encoded next to a window edge.  native=False: the same composition
+    in torch ops (the host loop's reference)."""
+    lay, down = layout, autoencoder.down
+    W, L, S = lay.n_windows, lay.window_len, lay.stride
+    rec = torch.as_tensor(recording).to(autoencoder.device, torch.float32).contiguous()
+    if rec.dim() != 3 or tuple(rec.shape[1:]) != (autoencoder.in_channels, lay.canvas_len * down):
+        raise ValueError(f"recording has shape {tuple(rec.shape)}, expected (R, {autoencoder.in_channels}, {lay.canvas_len * down})")
+    R, Ci = rec.shape[0], rec.shape[1]
+    big = lay.scaled(down)
+    if not native:
+        z_mu, _sigma = autoencoder.encode(_slices_of(rec, big).contiguous())
+        rows = z_mu * float(scale_factor)
+        return _long_crossfade(rows.reshape(R, W, rows.shape[1], L), lay)
+    h = autoencoder.ctx.h
+    win = torch.empty(R * W, Ci, L * down, device=rec.device, dtype=torch.float32)
+    check(lib.eegldm_canvas_gather(h, ptr(rec), R, Ci, W, L * down, S * down, ptr(win), None))
+    z_mu, _sigma = autoencoder.encode(win)
+    z_mu = z_mu.contiguous()
+    rows = torch.empty_like(z_mu)
+    check(lib.eegldm_edit_start(h, ptr(z_mu), float(scale_factor), None, 1.0, ptr(rows), None, rows.numel()))
+    z0 = torch.empty(R, rows.shape[1], lay.canvas_len, device=rec.device, dtype=torch.float32)
+    check(lib.eegldm_canvas_compose(h, ptr(rows), R, rows.shape[1], W, L, S, lay.margin, lay.ramp, ptr(z0)))
+    return z0
+
+
+def _long_edit_inputs(unet, autoencoder, lay, x, scale_factor, init, init_canvas, mask, mask_erode, native=True):
+    """-> (z0 (R, C, Lc), the mask as given on the device or None, the canvas keep-mask or None, init on the device or None).  The canvas
+    mask is the min-pool of eegldm_edit_window (B = R, Lw = down * Lc) over the mask eroded by mask_erode samples: canvas position p is
+    kept only if all the samples [p down, (p + 1) down) are.  native=False: torch ops."""
+    dev = unet.device
+    R, Cc, Lc = x.shape
+    down = autoencoder.down if autoencoder is not None else 1
+    init_d = None if init is None else torch.as_tensor(init).to(dev, torch.float32).contiguous()
+    if init_canvas is not None:
+        z0 = torch.as_tensor(init_canvas).to(dev, torch.float32).contiguous()
+    elif autoencoder is None:
+        z0 = init_d
+    else:
+        z0 = encode_long(autoencoder, init_d, lay, scale_factor, native=native)
+    m_win = m_lat = None
+    if mask is not None:
+        m_win = torch.as_tensor(mask).to(dev, torch.float32).contiguous()
+        if not bool(((m_win >= 0) & (m_win <= 1)).all()):
+            raise ValueError("mask values must lie in [0, 1]")
+        m_er = erode_mask(m_win, mask_erode).contiguous()
+        if native:
+            m_lat = torch.empty(R, Cc, Lc, device=dev, dtype=torch.float32)
+            check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_er), R, Lc * down, down, Cc, ptr(m_lat), None, None, 0, None))
+        else:
+            m_lat = (-torch.nn.functional.max_pool1d(-m_er, down, down)).expand(R, Cc, Lc).contiguous()
+    return z0, m_win, m_lat, init_d
+
+
 @torch.no_grad()
 def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ramp=None, scale_factor=1.0, crop=36, labels=None,
-                guidance_scale=1.0, null_class=None, use_graph=None, info=None):
+                guidance_scale=1.0, null_class=None, use_graph=None, info=None, init=None, init_canvas=None, strength=1.0, mask=None,
+                composite=None, mask_erode=0):
     """noise (R, C, Lc) on the device -> (recording (R, out, down * Lc - 2 * crop), canvas (R, C, Lc)).  Overlapped-window sampling on one
     latent canvas (MultiDiffusion): the R * W overlapping slices of the canvases are the rows of ONE forward batch, and behind every
     forward ONE eegldm_canvas_step launch fuses the slices' data predictions with a partition-of-unity taper, takes the solver step on
@@ -420,8 +537,22 @@ def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ram
     `scheduler`: a DPMSolverMultistepScheduler (order 1 or 2).  labels: R * W classes, recording-major (or W, the same for every
     recording); guidance as in `sample`.  margin / ramp (latent positions) default to 2 crop / down and 4 crop / down -- 18 and 36 latents
     for the 3072-sample window, stride 696 latents = 27.84 s: conventions derived from the training crop, NOT tuned against any seam
-    measure (tools/seam_report.py is what one tunes them by).  info (optional dict) receives {"graph": bool, "layout": LongLayout}."""
+    measure (tools/seam_report.py is what one tunes them by).  info (optional dict) receives {"graph": bool, "layout": LongLayout}.
+    Repairing, varying or continuing a REAL recording (eegldm_sample_long_edit: every step is then ONE eegldm_canvas_edit_step launch, the
+    canvas step and the blend).  init ((R, in_channels, down * Lc) for an LDM, (R, C, Lc) for a pixel-space model: the recording at window
+    resolution WITH the `crop` zero samples at its two free ends, as a training window holds them; init_canvas (R, C, Lc) for callers who hold latents)
+    starts the run from a real recording instead of from noise: z0 = encode_long(...), and the last n_run = min(n, max(1, round(strength *
+    n))) steps of the grid run from canvas = sqrt(a_t) z0 + sqrt(1 - a_t) noise (schedulers.edit_tables; the first executed step is first
+    order).  `noise` is the one noise tensor of the call; nothing else is drawn.  mask ((R, 1, down * Lc), 1 = keep) regenerates only the
+    samples marked 0: after every step the kept canvas positions are reset to z0 noised to the level the step landed on, inside the
+    step's kernel; a canvas position is kept only if all `down` samples it covers are.  composite (default: on with mask and init)
+    returns mask * init + (1 - mask) * recording, kept samples bit for bit; the crop applies afterwards.  mask_erode = e (window samples):
+    the canvas keep-mask is taken from the mask with every kept region shrunk by e samples beside each regenerated span -- the encoder's
+    receptive field contaminates the latents next to a regenerated or absent span -- while the composite uses the mask as given.  The
+    default is 0; no other default is proposed and NO value has been measured against anything.  Continuing a recording: init = the real
+    samples followed by zeros, mask = 1 over the real samples and 0 beyond."""
     lay, R, labels = _long_args(unet, autoencoder, scheduler, noise.shape, n_windows, margin, ramp, crop, labels)
+    edit = _long_edit_args(autoencoder, scheduler, lay, R, int(noise.shape[1]), init, init_canvas, strength, mask, composite, mask_erode)
     from .models import UNetModel
     if not isinstance(unet, UNetModel):
         raise TypeError("sample_long runs the native loop: unet must be a UNetModel")
@@ -441,6 +572,22 @@ def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ram
     rec = torch.empty(R, out_c, lay.canvas_len * down, device=unet.device, dtype=torch.float32)
     used = C.c_int(0)
     i64, f32 = (lambda v: (C.c_int64 * len(v))(*v)), (lambda v: (C.c_float * len(v))(*v))
+    if edit is not None:
+        tab = edit["tab"]
+        z0, m_win, m_lat, init_d = _long_edit_inputs(unet, autoencoder, lay, x, scale_factor, init, init_canvas, mask, mask_erode)
+        check(lib.eegldm_sample_long_edit(unet.h, autoencoder.h if autoencoder is not None else None, ptr(x), ptr(z0), ptr(m_lat), i64(tab["timesteps"]),
+                                          f32(tab["a_t"]), f32(tab["cx"]), f32(tab["c0"]), f32(tab["c1"]), f32(tab["a_next"]), len(tab["timesteps"]),
+                                          PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor), ptr(canvas),
+                                          ptr(rec), R, W, L, lay.margin, lay.ramp, 1 if use_graph else 0, C.byref(used),
+                                          None if lab is None else i64(lab), float(guidance_scale), nc))
+        if edit["composite"]:
+            check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_win), R, lay.canvas_len * down, down, 0, None, ptr(init_d), ptr(rec), out_c, ptr(rec)))
+        unet._bump_tape()
+        if autoencoder is not None:
+            autoencoder._bump_tape()
+        if info is not None:
+            info["graph"], info["layout"], info["n_run"] = bool(used.value), lay, len(tab["timesteps"])
+        return (rec[:, :, crop:-crop] if crop else rec), canvas
     check(lib.eegldm_sample_long(unet.h, autoencoder.h if autoencoder is not None else None, ptr(x), i64(ts), f32(a_t), f32(cx), f32(c0), f32(c1),
                                  len(ts), PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor), ptr(canvas),
                                  ptr(rec), R, W, L, lay.margin, lay.ramp, 1 if use_graph else 0, C.byref(used), None if lab is None else i64(lab),
@@ -492,13 +639,18 @@ def _long_crossfade(rows, lay):
 
 @torch.no_grad()
 def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=None, ramp=None, scale_factor=1.0, crop=36, labels=None,
-                         guidance_scale=1.0, null_class=None, use_graph=None, info=None):
+                         guidance_scale=1.0, null_class=None, use_graph=None, info=None, init=None, init_canvas=None, strength=1.0, mask=None,
+                         composite=None, mask_erode=0):
     """The reference composition of sample_long in torch, none of the canvas kernels: slice the canvas, model(...) on all slices, the
     guidance mix, x0 from the scheduler's formulas, the taper of layout.weights (as a cross-fade of the two windows that carry weight),
     prev = cx x + c0 x0 + c1 hist on the canvas, then decode per window and cross-fade.  The float32 roundings are placed where the
     library places them (fused multiply-adds are formed in float64 and rounded once more).  `unet` is any callable
-    model(x, timesteps=, [y=]) with .device / .eval(); use_graph is accepted and ignored."""
+    model(x, timesteps=, [y=]) with .device / .eval(); use_graph is accepted and ignored.
+    init / init_canvas / strength / mask / composite / mask_erode as in sample_long (mask_erode defaults to 0; no other value has been
+    measured against anything), composed from torch ops: the encode per window and its cross-fade, the noised start, the truncated
+    tables, the blend m k + (1 - m) x after every step with the library's roundings (_fma32), the min-pooled mask and the composite."""
     lay, R, labels = _long_args(unet, autoencoder, scheduler, noise.shape, n_windows, margin, ramp, crop, labels)
+    edit = _long_edit_args(autoencoder, scheduler, lay, R, int(noise.shape[1]), init, init_canvas, strength, mask, composite, mask_erode)
     unet.eval()
     dev = unet.device
     x = noise.to(dev, torch.float32).contiguous().clone()
@@ -509,6 +661,23 @@ def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=
     null = None if lab is None else torch.full((R * W,), nc, dtype=torch.int64, device=dev)
     w = float(np.float32(guidance_scale))
     ts, a_t, cx, c0, c1 = _multistep_tables(scheduler)
+    m_win = m_lat = init_d = None
+    if edit is not None:
+        tab = edit["tab"]
+        ts, a_t, cx, c0, c1, a_next = (tab[k] for k in ("timesteps", "a_t", "cx", "c0", "c1", "a_next"))
+        nz = x
+        z0, m_win, m_lat, init_d = _long_edit_inputs(unet, autoencoder, lay, x, scale_factor, init, init_canvas, mask, mask_erode, native=False)
+
+        def renoise(a):
+            """k(a) = fma(sqrt(a), z0, sqrt(1 - a) * noise), a == 1: z0 -- eegldm_edit_start's roundings"""
+            a32 = np.float32(a)
+            ka, kb = float(np.sqrt(a32)), float(np.sqrt(np.float32(1.0) - a32))
+            return _fma32(ka, z0, nz * kb) if kb != 0.0 else z0 * ka
+
+        def blend(mk, k, p):
+            """m == 0: p, m == 1: k, else fma(m, k, (1 - m) * p) -- the library's edit_blend"""
+            return torch.where(mk == 0, p, torch.where(mk == 1, k, _fma32(mk, k, (1.0 - mk) * p)))
+        x = renoise(a_t[0]).clone()
     tt = torch.empty(R * W, device=dev, dtype=torch.int64)
     slices = lambda cv: torch.stack([cv[:, :, k * S:k * S + L] for k in range(W)], 1).reshape(R * W, Cc, L)
     hist = None
@@ -523,14 +692,18 @@ def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=
         inner = _fma32(c0[i], x0, hist * c1[i]) if c1[i] != 0.0 else x0 * c0[i]
         x = _fma32(cx[i], x, inner)
         hist = x0
+        if m_lat is not None:
+            x = blend(m_lat, renoise(a_next[i]), x)
     if info is not None:
         info["graph"], info["layout"] = False, lay
+    comp = (lambda rec: blend(m_win, init_d, rec)) if edit is not None and edit["composite"] else (lambda rec: rec)
     if autoencoder is None:
-        return (x[:, :, crop:-crop] if crop else x), x
+        rec = comp(x)
+        return (rec[:, :, crop:-crop] if crop else rec), x
     z = slices(x).contiguous()
     if float(scale_factor) != 1.0:
         # 1 / scale_factor rounded to float32, minus one in float32: the native loop's value (see ddim_sample_hostloop)
         check(lib.eegldm_axpy(autoencoder.ctx.h, ptr(z), ptr(z), float(np.float32(1.0 / float(scale_factor)) - np.float32(1.0)), z.numel()))
     dec = autoencoder.decode_stage_2_outputs(z)
-    rec = _long_crossfade(dec.reshape(R, W, dec.shape[1], dec.shape[2]), lay.scaled(autoencoder.down))
+    rec = comp(_long_crossfade(dec.reshape(R, W, dec.shape[1], dec.shape[2]), lay.scaled(autoencoder.down)))
     return (rec[:, :, crop:-crop] if crop else rec), x
