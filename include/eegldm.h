@@ -748,6 +748,29 @@ int eegldm_usleep_forward(eegldm_usleep*, const float* x, float* y_pred, float* 
  * distance (compute_fid.py:412-414 = monai-generative FIDMetric: torch.mean, unbiased _cov, trace of the matrix square root). */
 int eegldm_feature_moments(eegldm_ctx*, const float* feats, long N, int D, double* sum, double* outer);
 
+/* ---- nearest-neighbour search (memorisation audit, precision / recall / coverage; csrc/knn.hip).  fp32 in and out; additive, ABI 8.
+ * Score s(i, j) = xbias[j] - 2 <q_i, x_j>, smaller is nearer: xbias = |x_j|^2 orders by squared Euclidean distance (d^2 = max(0, |q_i|^2 + s)),
+ * xbias = NULL (= 0) on rows of zero mean and unit norm orders by Pearson correlation (r = -s / 2), xbias = |x_j|^2 - radius_j^2 finds the
+ * nearest corpus BALL (|q_i|^2 + s <= 0: query i lies inside some ball).
+ * eegldm_knn_update merges one corpus chunk x (Nc rows, row j carries index index_base + j) into the running state best_s [Nq][k] fp32 /
+ * best_i [Nq][k] int64, sorted ascending by (score, index), which the caller initialises to +inf / -1.  self_base >= 0 skips the pair with
+ * index_base + j == self_base + i (neighbours inside one set); < 0: no pair is skipped.  ldq / ldx are row strides in floats (>= D), so a
+ * crop of a window is a view.  1 <= k <= 32, D >= 1; q, x, xbias, best_s need 4-byte alignment only (best_i 8).  A NaN score never enters a
+ * list; with fewer than k rows seen the tail stays +inf / -1.  The dot product of a pair is one fmaf chain in ascending k on the f32-input
+ * MFMA whatever the pair's place in a tile, slab or chunk, and nothing is accumulated across workgroups: the state after a sequence of calls
+ * depends only on the set of rows seen, bit for bit.  Workspace O(Nq * slabs * k) (the context's split-K buffer, main stream). */
+int eegldm_knn_update(eegldm_ctx*, const float* q, long ldq, const float* x, long ldx, const float* xbias, int Nq, int Nc, int D, int k,
+                      long index_base, long self_base, float* best_s, int64_t* best_i);
+/* out[n] = sum_d x[n][d]^2: one wave per row, lane l chains elements l, l + 64, ... with fmaf, then a fixed butterfly -- the value of a row
+ * does not depend on N or on the grid. */
+int eegldm_rows_sqnorm(eegldm_ctx*, const float* x, long ldx, long N, int D, float* out);
+/* out[n] = (x[n] - mean(x[n])) / |x[n] - mean(x[n])|_2, statistics in fp32 in the same fixed order; a constant row becomes all zeros. */
+int eegldm_rows_standardize(eegldm_ctx*, const float* x, long ldx, long N, int D, float* out, long ldout);
+/* out_d2[i][r] = sum_d (q[i][d] - x[j][d])^2 in direct form (no cancellation) for every slot whose index best_i[i][r] = index_base + j lies
+ * in this chunk (0 <= j < Nc); other slots are left as they are. */
+int eegldm_knn_rescore(eegldm_ctx*, const float* q, long ldq, const float* x, long ldx, int Nq, int D, int k, long index_base, long Nc,
+                       const int64_t* best_i, float* out_d2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -190,6 +190,10 @@ SIGNATURES = {
     "eegldm_usleep_bind": [_vp, _vp, _vp],
     "eegldm_usleep_forward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i],
     "eegldm_feature_moments": [_vp, _vp, _l, _i, _vp, _vp],
+    "eegldm_knn_update": [_vp, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _l, _l, _vp, _vp],
+    "eegldm_rows_sqnorm": [_vp, _vp, _l, _l, _i, _vp],
+    "eegldm_rows_standardize": [_vp, _vp, _l, _l, _i, _vp, _l],
+    "eegldm_knn_rescore": [_vp, _vp, _l, _vp, _l, _i, _i, _i, _l, _l, _vp, _vp],
     "eegldm_resblock_create": [_vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)],
     "eegldm_attnblock_create": [_vp, _i, _i, _i, C.POINTER(_vp)],
     "eegldm_block_destroy": [_vp],

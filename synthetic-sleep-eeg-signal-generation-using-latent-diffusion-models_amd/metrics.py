@@ -315,3 +315,343 @@ class FIDMetric:
         a = FeatureMoments(y_pred.shape[1], ctx=self.ctx).update(y_pred).finalize()
         b = FeatureMoments(y.shape[1], ctx=self.ctx).update(y).finalize()
         return torch.tensor(frechet_distance(a[0], a[1], b[0], b[1]), dtype=torch.float64)
+
+
+# ---------------------------------------------------------------------------------------------------- nearest neighbours on the device
+# k nearest neighbours of query rows in a corpus streamed chunk by chunk (csrc/knn.hip): the memorisation audit of generated windows and
+# precision / recall (Kynkaanniemi et al. 2019) / coverage (Naeem et al. 2020) on the features the FID already extracts.  Everything that
+# refuses an argument does so before the device is touched.
+MAX_NEIGHBOURS = 32
+KNN_METRICS = ("sqeuclidean", "correlation")
+
+
+def _rows2d(t, name):
+    if not torch.is_tensor(t):
+        t = torch.as_tensor(np.asarray(t))
+    if t.dim() != 2:
+        raise ValueError(f"{name}: a 2-D (rows, features) tensor is expected, got shape {tuple(t.shape)}")
+    return t
+
+
+def _check_k(k):
+    if int(k) != k or not 1 <= int(k) <= MAX_NEIGHBOURS:
+        raise ValueError(f"k must be an integer in 1..{MAX_NEIGHBOURS}, got {k!r}")
+    return int(k)
+
+
+def _check_dim(a, b, what):
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"{what}: feature dimensions differ ({a.shape[1]} and {b.shape[1]})")
+
+
+def _dev_rows(t, dev):
+    """fp32 on the device with a unit inner stride; a row stride >= D is kept, so a crop of a window stays a view."""
+    t = t.to(dev, torch.float32)
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t
+
+
+def _ld(t):
+    return max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def rows_sqnorm(x, ctx=None):
+    """|x_n|^2 of the rows of a device tensor (eegldm_rows_sqnorm: fixed summation order)."""
+    ctx = ctx or default_context(0)
+    out = torch.empty(x.shape[0], device=x.device)
+    if x.shape[0]:
+        check(lib.eegldm_rows_sqnorm(ctx.h, ptr(x), _ld(x), x.shape[0], x.shape[1], ptr(out)))
+    return out
+
+
+def rows_standardize(x, ctx=None):
+    """Rows with their mean removed and divided by their L2 norm (eegldm_rows_standardize); a constant row becomes zeros."""
+    ctx = ctx or default_context(0)
+    out = torch.empty(x.shape[0], x.shape[1], device=x.device)
+    if x.shape[0]:
+        check(lib.eegldm_rows_standardize(ctx.h, ptr(x), _ld(x), x.shape[0], x.shape[1], ptr(out), x.shape[1]))
+    return out
+
+
+class NearestNeighbours:
+    """Running k nearest corpus rows of every query row.  `update` merges one corpus chunk (eegldm_knn_update: f32 MFMA scores with a top-k
+    epilogue; no Nq x Nc matrix exists), `result` returns (dist (Nq, k) fp32, idx (Nq, k) int64), nearest first, ties by index; slots
+    beyond the rows seen hold inf / -1.  metric "sqeuclidean": squared Euclidean distance; "correlation": 1 - Pearson r (both sides are
+    standardised on the device).  `exclude_self_base=b`: query i is corpus row b + i and is not its own neighbour.  The result does not
+    depend on how the corpus is cut into chunks, bit for bit."""
+
+    def __init__(self, queries, k, metric="sqeuclidean", exclude_self_base=None, ctx=None):
+        q = _rows2d(queries, "queries")
+        self.k = _check_k(k)
+        if metric not in KNN_METRICS:
+            raise ValueError(f"metric must be one of {KNN_METRICS}, got {metric!r}")
+        if q.shape[0] == 0 or q.shape[1] == 0:
+            raise ValueError(f"empty queries: shape {tuple(q.shape)}")
+        if exclude_self_base is not None and int(exclude_self_base) < 0:
+            raise ValueError("exclude_self_base must be >= 0")
+        self.metric, self.self_base = metric, -1 if exclude_self_base is None else int(exclude_self_base)
+        self.ctx = ctx or default_context(0)
+        self.device = torch.device("cuda", self.ctx.device)
+        q = _dev_rows(q, self.device)
+        self.nq, self.dim = int(q.shape[0]), int(q.shape[1])
+        if metric == "correlation":
+            self.q, self.query_sqnorm = rows_standardize(q, self.ctx), None
+        else:
+            self.q, self.query_sqnorm = q, rows_sqnorm(q, self.ctx)
+        self.best_s = torch.full((self.nq, self.k), float("inf"), device=self.device)
+        self.best_i = torch.full((self.nq, self.k), -1, dtype=torch.int64, device=self.device)
+        self.seen = 0
+
+    def _prepare(self, chunk, radius2=None):
+        """-> (rows as the kernel scores them, xbias or None)"""
+        x = _dev_rows(chunk, self.device)
+        if self.metric == "correlation":
+            return rows_standardize(x, self.ctx), None
+        xb = rows_sqnorm(x, self.ctx)
+        if radius2 is not None:
+            xb = xb - radius2.to(self.device, torch.float32)
+        return x, xb
+
+    def _update_prepared(self, x, xbias, index_base):
+        check(lib.eegldm_knn_update(self.ctx.h, ptr(self.q), _ld(self.q), ptr(x), _ld(x), ptr(xbias), self.nq, x.shape[0], self.dim, self.k,
+                                    int(index_base), self.self_base, ptr(self.best_s), ptr(self.best_i)))
+
+    def update(self, corpus_chunk, index_base=None, radius2=None):
+        """Merge a chunk whose row j carries index index_base + j (default: the count of rows seen so far).  `radius2` (one value per row)
+        turns the rows into balls: the score becomes d^2 - radius^2 (see `margins`)."""
+        x = _rows2d(corpus_chunk, "corpus_chunk")
+        if x.shape[1] != self.dim:
+            raise ValueError(f"corpus_chunk has {x.shape[1]} features, the queries have {self.dim}")
+        if radius2 is not None and (self.metric != "sqeuclidean" or tuple(radius2.shape) != (x.shape[0],)):
+            raise ValueError("radius2 needs the sqeuclidean metric and one value per corpus row")
+        base = self.seen if index_base is None else int(index_base)
+        if base < 0:
+            raise ValueError("index_base must be >= 0")
+        if x.shape[0]:
+            xs, xb = self._prepare(x, radius2)
+            self._update_prepared(xs, xb, base)
+        self.seen += int(x.shape[0])
+        return self
+
+    def margins(self):
+        """|q_i|^2 + s: with `radius2` given to every update, d^2 - radius^2 of the nearest ball (<= 0: inside some ball)."""
+        return self.query_sqnorm[:, None] + self.best_s
+
+    def result(self, rescore=None):
+        """(dist, idx).  `rescore=chunk` (index_base 0), `(chunk, index_base)` or a list of such pairs replaces the distance of every
+        neighbour that lies in one of the chunks by the direct form sum (q - x)^2 (no cancellation: an exact copy gets 0) and re-sorts."""
+        if self.metric == "correlation":
+            dist = (1.0 + 0.5 * self.best_s).clamp_min(0.0)
+        else:
+            dist = self.margins().clamp_min(0.0)
+        idx = self.best_i.clone()
+        if rescore is None:
+            return dist, idx
+        pairs = rescore if isinstance(rescore, list) else [rescore if isinstance(rescore, tuple) else (rescore, 0)]
+        half = self.metric == "correlation"           # standardised rows: sum (zq - zx)^2 = 2 - 2 r
+        out = (2.0 * dist if half else dist).contiguous()
+        for chunk, base in pairs:
+            x = _rows2d(chunk, "rescore chunk")
+            if x.shape[1] != self.dim:
+                raise ValueError(f"rescore chunk has {x.shape[1]} features, the queries have {self.dim}")
+            if x.shape[0]:
+                xs, _ = self._prepare(x)
+                check(lib.eegldm_knn_rescore(self.ctx.h, ptr(self.q), _ld(self.q), ptr(xs), _ld(xs), self.nq, self.dim, self.k, int(base),
+                                             xs.shape[0], ptr(idx), ptr(out)))
+        return _sort_pairs(0.5 * out if half else out, idx)
+
+
+def _sort_pairs(dist, idx):
+    """Rows re-sorted by (distance, index); empty slots (inf, -1) stay last."""
+    by_index = torch.argsort(idx, dim=1, stable=True)
+    dist, idx = torch.gather(dist, 1, by_index), torch.gather(idx, 1, by_index)
+    by_dist = torch.argsort(dist, dim=1, stable=True)
+    return torch.gather(dist, 1, by_dist), torch.gather(idx, 1, by_dist)
+
+
+def knn(queries, corpus, k, metric="sqeuclidean", chunk=65536, exclude_self=False, rescore=False):
+    """One-shot form: (dist, idx) of the k nearest rows of `corpus` for every row of `queries`; host tensors are streamed to the device
+    `chunk` rows at a time.  `exclude_self`: queries and corpus are the same set and a row is not its own neighbour.  `rescore`: a second
+    pass over the chunks replaces the distances by their direct form."""
+    q, x = _rows2d(queries, "queries"), _rows2d(corpus, "corpus")
+    _check_k(k)
+    _check_dim(q, x, "queries / corpus")
+    if exclude_self and q.shape[0] != x.shape[0]:
+        raise ValueError(f"exclude_self needs the same set on both sides, got {q.shape[0]} and {x.shape[0]} rows")
+    if int(chunk) < 1:
+        raise ValueError("chunk must be >= 1")
+    nn = NearestNeighbours(q, k, metric, exclude_self_base=0 if exclude_self else None)
+    for s in range(0, x.shape[0], int(chunk)):
+        nn.update(x[s:s + int(chunk)], s)
+    c = int(chunk)
+    return nn.result(rescore=[(x[s:s + c], s) for s in range(0, x.shape[0], c)] if rescore else None)
+
+
+def kth_radius(feats, k=3, squared=False, chunk=65536):
+    """Distance from every row to its k-th nearest neighbour in its own set, the row itself excluded (direct-form distances)."""
+    f = _rows2d(feats, "feats")
+    _check_k(k)
+    if f.shape[0] <= int(k):
+        raise ValueError(f"kth_radius with k = {k} needs more than {k} rows, got {f.shape[0]}")
+    d2, _ = knn(f, f, k, "sqeuclidean", chunk=chunk, exclude_self=True, rescore=True)
+    r2 = d2[:, int(k) - 1].contiguous()
+    return r2 if squared else torch.sqrt(r2)
+
+
+def prc_from_tables(fake_margin, real_margin, real_nn_d2, real_r2):
+    """The three shares from the neighbour tables: fake_margin[i] = d^2 - radius^2 of the nearest real ball around fake row i (<= 0: inside),
+    real_margin likewise for real rows and fake balls, real_nn_d2[j] = squared distance from real row j to its nearest fake row,
+    real_r2[j] = its own squared radius."""
+    fm, rm = np.asarray(fake_margin, np.float64).reshape(-1), np.asarray(real_margin, np.float64).reshape(-1)
+    d2, r2 = np.asarray(real_nn_d2, np.float64).reshape(-1), np.asarray(real_r2, np.float64).reshape(-1)
+    if not len(fm) or not len(rm) or len(rm) != len(d2) or len(d2) != len(r2):
+        raise ValueError("neighbour tables of mismatched or zero length")
+    return {"precision": float(np.mean(fm <= 0.0)), "recall": float(np.mean(rm <= 0.0)), "coverage": float(np.mean(d2 <= r2)),
+            "n_real": int(len(rm)), "n_fake": int(len(fm))}
+
+
+def _ball_margins(queries, corpus, radius2, chunk):
+    nn = NearestNeighbours(queries, 1)
+    for s in range(0, corpus.shape[0], chunk):
+        nn.update(corpus[s:s + chunk], s, radius2=radius2[s:s + chunk])
+    return nn.margins()[:, 0]
+
+
+def precision_recall_coverage(real_feats, fake_feats, k=3, chunk=65536):
+    """precision = share of fake rows inside some real ball, recall = share of real rows inside some fake ball (balls: radius = distance to
+    the k-th neighbour in the own set), coverage = share of real rows whose nearest fake row lies within their own radius."""
+    real, fake = _rows2d(real_feats, "real_feats"), _rows2d(fake_feats, "fake_feats")
+    k = _check_k(k)
+    _check_dim(real, fake, "real_feats / fake_feats")
+    if real.shape[0] <= k or fake.shape[0] <= k:
+        raise ValueError(f"k = {k} needs more than {k} rows on both sides, got {real.shape[0]} and {fake.shape[0]}")
+    r2_real, r2_fake = kth_radius(real, k, squared=True, chunk=chunk), kth_radius(fake, k, squared=True, chunk=chunk)
+    fake_margin = _ball_margins(fake, real, r2_real, chunk)
+    real_margin = _ball_margins(real, fake, r2_fake, chunk)
+    d2, _ = knn(real, fake, 1, "sqeuclidean", chunk=chunk, rescore=True)
+    out = prc_from_tables(fake_margin.cpu().numpy(), real_margin.cpu().numpy(), d2[:, 0].cpu().numpy(), r2_real.cpu().numpy())
+    out["k"] = k
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- memorisation audit
+HOLDOUT_QUANTILES = (0.0, 0.001, 0.01, 0.05, 0.25, 0.5, 0.75, 1.0)
+
+
+def lag_crops(length, lags):
+    """Sample ranges of the lagged comparison: for the largest |lag| g the corpus is the centre crop [g, length - g) and a query
+    contributes, per lag l, the crop [g + l, length - g + l) -> (g, (lo, hi), {lag: (lo, hi)})."""
+    lags = tuple(int(l) for l in lags)
+    if not lags:
+        raise ValueError("at least one lag is needed (0 = no shift)")
+    g = max(abs(l) for l in lags)
+    if int(length) - 2 * g < 1:
+        raise ValueError(f"a lag of {g} samples leaves no samples of a window of {length}")
+    return g, (g, int(length) - g), {l: (g + l, int(length) - g + l) for l in lags}
+
+
+def merge_lag_tables(dists, idxs, k):
+    """Per query the k nearest (distance, index) pairs over all lags; an index found at several lags keeps its smallest distance."""
+    d, i = np.concatenate(dists, 1), np.concatenate(idxs, 1)
+    out_d, out_i = np.full((d.shape[0], k), np.inf, np.float32), np.full((d.shape[0], k), -1, np.int64)
+    for r in range(d.shape[0]):
+        order = np.lexsort((i[r], d[r]))
+        seen, n = set(), 0
+        for o in order:
+            if i[r, o] < 0 or int(i[r, o]) in seen:
+                continue
+            seen.add(int(i[r, o])); out_d[r, n], out_i[r, n] = d[r, o], i[r, o]; n += 1
+            if n == k:
+                break
+    return out_d, out_i
+
+
+def audit_summary(syn_dist, syn_idx, holdout_dist, quantile=0.01):
+    """The audit's record from the neighbour tables (numpy, (N, k)): threshold = the `quantile` of the held-out windows' nearest training
+    distance, flagged = the synthetic windows nearer to a training window than that.  `holdout_rank` is the share of held-out windows that
+    are nearer to the training set than the synthetic window.  No claim about what a flag means."""
+    if not 0.0 <= float(quantile) <= 1.0:
+        raise ValueError(f"quantile must lie in [0, 1], got {quantile}")
+    sd, si, hd = np.asarray(syn_dist, np.float64), np.asarray(syn_idx, np.int64), np.asarray(holdout_dist, np.float64)
+    if sd.ndim != 2 or hd.ndim != 2 or sd.shape != si.shape or not len(hd) or not len(sd):
+        raise ValueError("neighbour tables must be 2-D, non-empty and of equal shape")
+    h = np.sort(hd[:, 0])
+    thr = float(np.quantile(h, float(quantile)))
+    return {"nearest_distance": sd.tolist(), "nearest_index": si.tolist(),
+            "holdout_rank": (np.searchsorted(h, sd[:, 0], side="left") / len(h)).tolist(),
+            "holdout_quantiles": {str(p): float(np.quantile(h, p)) for p in HOLDOUT_QUANTILES},
+            "quantile": float(quantile), "threshold": thr, "flagged": np.nonzero(sd[:, 0] < thr)[0].tolist(),
+            "n_synthetic": int(len(sd)), "n_holdout": int(len(hd))}
+
+
+def _windows2d(w, name):
+    """(N, L) or (N, 1, L) -> (N, L); the loader's 3072-sample windows lose their 36-sample zero pads (as in fid_features)."""
+    if not torch.is_tensor(w):
+        w = torch.as_tensor(np.asarray(w))
+    if w.dim() == 3 and w.shape[1] == 1:
+        w = w[:, 0]
+    if w.dim() != 2:
+        raise ValueError(f"{name}: windows (N, L) or (N, 1, L) expected, got shape {tuple(w.shape)}")
+    if w.shape[1] == 3072:
+        w = w[:, 36:-36]
+    return w
+
+
+def memorisation_audit(synthetic, train_chunks, holdout, space="signal", k=1, lags=(0,), quantile=0.01, usleep=None, batch_size=256):
+    """Where do the synthetic windows sit, by their distance to the nearest training window, in the distribution of that same distance
+    for held-out real windows?  `train_chunks`: an iterable of window batches (the training set is streamed once).  space "signal":
+    1 - Pearson r on the samples, minimum over the sample offsets `lags`; "features": squared Euclidean distance on `fid_features` of
+    `usleep`.  Returns `audit_summary`'s dict plus the settings."""
+    syn, hold = _windows2d(synthetic, "synthetic"), _windows2d(holdout, "holdout")
+    k = _check_k(k)
+    if space not in ("signal", "features"):
+        raise ValueError(f"space must be 'signal' or 'features', got {space!r}")
+    if syn.shape[0] == 0 or hold.shape[0] == 0:
+        raise ValueError("empty queries: the audit needs synthetic and held-out windows")
+    _check_dim(syn, hold, "synthetic / holdout")
+    if not 0.0 <= float(quantile) <= 1.0:
+        raise ValueError(f"quantile must lie in [0, 1], got {quantile}")
+    _g, (c_lo, c_hi), crops = lag_crops(syn.shape[1], lags)
+    if space == "features":
+        if tuple(crops) != (0,):
+            raise ValueError("lags apply to space='signal' only")
+        if usleep is None:
+            raise ValueError("space='features' needs the U-Sleep feature extractor (usleep=)")
+    ns = int(syn.shape[0])
+    if space == "signal":
+        dev = torch.device("cuda", default_context(0).device)
+        queries = torch.cat([syn.to(dev, torch.float32), hold.to(dev, torch.float32)], 0)
+        searches = {l: NearestNeighbours(queries[:, lo:hi], k, "correlation") for l, (lo, hi) in crops.items()}
+        base = 0
+        for chunk in train_chunks:
+            x = _windows2d(chunk, "train chunk")
+            _check_dim(syn, x, "synthetic / train chunk")
+            if not x.shape[0]:
+                continue
+            xs = rows_standardize(_dev_rows(x.to(dev, torch.float32)[:, c_lo:c_hi], dev))
+            for nn in searches.values():
+                nn._update_prepared(xs, None, base)
+            base += int(x.shape[0])
+        tables = [nn.result() for nn in searches.values()]
+        if len(tables) == 1:
+            dist, idx = tables[0][0].cpu().numpy(), tables[0][1].cpu().numpy()
+        else:
+            dist, idx = merge_lag_tables([t[0].cpu().numpy() for t in tables], [t[1].cpu().numpy() for t in tables], k)
+    else:
+        def feats(w):
+            return torch.cat([fid_features(usleep, w[s:s + batch_size].unsqueeze(1)) for s in range(0, w.shape[0], batch_size)], 0)
+        nn = NearestNeighbours(torch.cat([feats(syn), feats(hold)], 0), k, "sqeuclidean")
+        for chunk in train_chunks:
+            x = _windows2d(chunk, "train chunk")
+            _check_dim(syn, x, "synthetic / train chunk")
+            if x.shape[0]:
+                nn.update(feats(x))
+        base = nn.seen
+        dist, idx = (t.cpu().numpy() for t in nn.result())
+    if base == 0:
+        raise ValueError("no training windows were given")
+    out = audit_summary(dist[:ns], idx[:ns], dist[ns:], quantile)
+    out.update({"space": space, "metric": "1 - pearson r" if space == "signal" else "squared euclidean distance of U-Sleep features",
+                "k": k, "lags": [int(l) for l in crops], "n_train": int(base)})
+    return out
