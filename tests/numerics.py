@@ -273,3 +273,207 @@ def check_b(got, ref, emul, fmt, route="", report=True, min_stat=100_000, min_sh
         print(format_report(st))
     assert not msgs, f"{route} [{fmt}]: " + "; ".join(msgs)
     return st
+
+
+# ---------------------------------------------------------------- attention (one head; q, k, v, dO, O as (B, T, C), P, dS as (B, T, T))
+# Staged references of softmax(alpha q k^T) v and its backward.  The kernels (csrc/attn.hip, and the GEMM + softmax composition of
+# ops.hip / elementwise.hip) store their 16-bit intermediates P and dS in caller-owned buffers and the later stages read those very
+# values, so each stage is judged on the operands the next one read: the products by check A / B as the convs are, the two row
+# operations (softmax, dS) by the bounds derived below.
+#
+# Relative error of exp on the device (the one figure of softmax_bound that this repository's source does not give):
+#   __expf (attn.hip) compiles to v_mul_f32 by fp32(log2 e), then v_exp_f32 (read from the gfx950 assembly).  AMD's public ISA
+#          reference guides ("Vega" Instruction Set Architecture and its GCN3 / CDNA relatives, VOP1 opcode table, V_EXP_F32:
+#          "Base2 exponent function. 1ULP accuracy, denormals are flushed") state 1 ulp (2u).  The constant's and the product's
+#          roundings move the argument by up to 2u |x| log2(e), the result by a relative 2u |x|; below x = -87.4 the result is
+#          under 2^-126 and softmax_bound's floor takes over, so |x| <= 88 bounds the term: 2u + 176u.
+#   expf   (elementwise.hip) is the device library's routine, 1 ulp (2u) in the HIP math-API tables.
+# These are stated accuracies, taken as they are; a measured figure would enter doubled.
+E_EXP_FUSED, E_EXP_COMPOSITION = 178 * U32, 2 * U32
+
+
+def attn_alpha(C):
+    """the exact 1 / sqrt(C); the kernels use fp32(1 / sqrtf(C)): that rounding and the fp32 multiplication by it are two of the four
+    spare roundings of gamma_n (both exact when C is a power of four)"""
+    return 1.0 / math.sqrt(C)
+
+
+def attn_logits(q, k, alpha):
+    return alpha * (q @ k.transpose(1, 2))
+
+
+def attn_softmax(s):
+    return torch.softmax(s, dim=-1)
+
+
+def attn_out(p, v):
+    return p @ v
+
+
+def attn_dprobs(do, v):
+    return do @ v.transpose(1, 2)
+
+
+def attn_dscores(p, dp, alpha):
+    """dS = alpha p (dP - sum_s dP p): the form the kernels evaluate (alpha p first; 0 x inf = NaN as there)"""
+    return (alpha * p) * (dp - (dp * p).sum(-1, keepdim=True))
+
+
+def attn_dq(ds, k):
+    return ds @ k
+
+
+def attn_dk(ds, q):
+    return ds.transpose(1, 2) @ q
+
+
+def attn_dv(p, do):
+    return p.transpose(1, 2) @ do
+
+
+def softmax_bound(s_ref, s_mag, C, e_exp):
+    """(p, d): the float64 softmax of the float64 logits and the absolute bound d = p r + f of a kernel that forms fp32 logits s' with
+    |s' - s| <= gamma(C) s_mag (s_mag = alpha sum|q||k|), then e = exp'(s' - m) with the row maximum m, S = fp32 sum of the T e's in
+    any order, p' = e (1 / S), and rounds once.  Sources of relative error:
+      logits  p' = e^(s + ds) / sum e^(s + ds), |ds| <= D = max_row gamma(C) s_mag, lies within e^(+-2D) of p:   expm1(2 D)
+      s' - m  one fp32 rounding: absolute error u |x| of the argument x = s - max_row s (|x'| <= |x| + 2D):        u (|x| + 2D)
+      exp'    relative error e_exp (E_EXP_FUSED / E_EXP_COMPOSITION above) of every e: the numerator carries
+              e_exp + u (|x| + 2D), the denominator the p-weighted mean of the same terms (the issue's r writes
+              e_exp once; a ratio of two inexact quantities carries it twice):                                    sum_s p_s (...)
+      sum     T positive terms in fp32, any order (gamma carries 4 spare u: 1 / S and e * (1 / S) are two):       gamma(T)
+      4u      slack for the second-order terms of all of the above
+    r = expm1(2D) + (e_exp + u (|x| + 2D)) + sum_s p_s (e_exp + u (|x_s| + 2D)) + gamma(T) + 4u.
+    f = 2^-126: an e or a product below the smallest normal fp32 number may be flushed to zero, an absolute error of less than
+    2^-126 (S >= 1 as the row maximum contributes e = 1, so 1 / S <= 1)."""
+    s_ref, s_mag = _f64(s_ref), _f64(s_mag)
+    T = s_ref.shape[-1]
+    p = torch.softmax(s_ref, dim=-1)
+    D = (gamma(C) * s_mag).amax(-1, keepdim=True)
+    x = (s_ref - s_ref.amax(-1, keepdim=True)).abs()
+    ex = e_exp + U32 * (x + 2 * D)
+    r = torch.expm1(2 * D) + ex + (p * ex).sum(-1, keepdim=True) + gamma(T) + 4 * U32
+    return p, p * r + 2.0 ** -126
+
+
+def dscores_bound(p, dp_ref, dp_mag, C, alpha):
+    """(dS, d): float64 dS = alpha p (dP - dl), dl = sum_s p_s dP_s, from the STORED probabilities p and the float64 dP = dO V^T, and
+    the absolute bound d of a kernel that holds dP' in fp32 with |dP' - dP| <= e_dP = gamma(C) dp_mag (dp_mag = sum|dO||V|), forms
+    the row dot dl' in fp32 in any order, |dl' - dl| <= e_dl = sum_s p_s e_dP_s + gamma(T) sum_s |dP_s| p_s, and evaluates
+    alpha' * p * (dP' - dl') with alpha' = fp32(alpha) (relative u), the subtraction (u (|dP| + |dl|)) and two products (2u), then
+    rounds once: d = alpha p (e_dP + e_dl + 4u (|dP| + |dl|)) + 2^-126.  Absolute, so the cancellation in dP - dl needs no special
+    case; the floor allows a product below the smallest normal fp32 number to be flushed to zero, as in softmax_bound."""
+    p, dp_ref, dp_mag = _f64(p), _f64(dp_ref), _f64(dp_mag)
+    T = p.shape[-1]
+    dl = (dp_ref * p).sum(-1, keepdim=True)
+    e_dp = gamma(C) * dp_mag
+    e_dl = (p * e_dp).sum(-1, keepdim=True) + gamma(T) * (dp_ref.abs() * p).sum(-1, keepdim=True)
+    ref = (alpha * p) * (dp_ref - dl)
+    d = alpha * p * (e_dp + e_dl + 4 * U32 * (dp_ref.abs() + dl.abs())) + 2.0 ** -126
+    return ref, d
+
+
+def _check_row_op(got, ref, d, fmt, emul, route, report, f16_subnormal_exact=False):
+    """P and dS: check A with the derived absolute bound d on every element; check B on the elements of magnitude >= 2^-120 whose
+    bound d is at most a quarter ulp.  Below 2^-120 the fp32 arithmetic of the row operation is in or next to its subnormal range
+    (flush-to-zero is allowed by the floor of the bound, and one fp32 subnormal rounding is many bf16-subnormal ulps).  Check B
+    presumes that the final rounding dominates the error; where the derived fp32 error exceeds the rounding step (the cancellation
+    dP - dl of a sharp row, logits whose own error is above an ulp of P) an error of many ulps is legitimate and the mean of such a
+    heavy-tailed quantity says nothing.
+    f16_subnormal_exact (P in fp16): every element whose RNE(ref) is a non-zero fp16 subnormal must EQUAL RNE(ref), unless ref lies
+    within d of a rounding midpoint (RNE(ref - d) != RNE(ref + d)); a kernel that flushes fp16 subnormals fails here by name."""
+    got, ref, d = _f64(got), _f64(ref), _f64(d)
+    st = check(got, ref, d / gamma(0), 0, fmt, route=route, report=False, min_stat=math.inf)
+    msgs = []
+    if fmt != "f32":
+        m = (ref.abs() >= 2.0 ** -120) & (d <= 0.25 * ulp(ref, fmt))
+        try:
+            stb = check_b(got[m], ref[m], _f64(emul)[m], fmt, route=route, report=False)
+            st.update(mismatch=stb["mismatch"], m_emul=stb["m_emul"], mean_ulp=stb["mean_ulp"])
+        except AssertionError as e:
+            msgs.append(str(e))
+    if f16_subnormal_exact and fmt == "f16":
+        r16 = rne(ref, "f16")
+        sub = (r16 != 0) & (r16.abs() < 2.0 ** -14) & (rne(ref - d, "f16") == rne(ref + d, "f16"))
+        wrong = sub & (got != r16)
+        st["f16_subnormal"] = int(sub.sum())
+        if bool(wrong.any()):
+            msgs.append(f"{route} [f16]: {int(wrong.sum())} of {int(sub.sum())} fp16-subnormal elements differ from RNE(ref)")
+    if report:
+        print(format_report(st) + (f" f16-subnormal={st['f16_subnormal']} all = RNE(ref)" if "f16_subnormal" in st and not msgs else ""))
+    assert not msgs, "; ".join(msgs)
+    return st
+
+
+def attention_stages(q, k, v, do, got, fmt, e_exp, route="", report=True, shared=None):
+    """Judge every stage of one attention forward + backward.  q, k, v, do: float64 (B, T, C) holding storage values; got: dict of
+    float64 tensors read back from the kernel under test -- P, O, dS, dQ, dK, dV, and on the composition path S and dP (the fp32
+    scratch buffers).  Stages missing from `got` are skipped.  Returns (failures: {stage: message}, stats: {stage: dict}); nothing is
+    raised, so that a caller can demand that a NAMED stage fails (the defect models) or that none does.  `shared` caches the
+    references that depend on the operands only (logits, softmax bound, dP) between calls with identical operands."""
+    (B, Tq, C), T = q.shape, k.shape[1]          # Tq query rows (a caller may judge a part of them), T keys
+    alpha = attn_alpha(C)
+    sh = shared if shared is not None else {}
+    if "s" not in sh:
+        sh["s"] = evaluate(attn_logits, q, k, alpha)
+        sh["p"] = softmax_bound(sh["s"][0], sh["s"][1], C, e_exp)
+        sh["dp"] = evaluate(attn_dprobs, do, v)
+    (s_ref, s_mag, s_emul), (p_ref, p_d), (dp_ref, dp_mag, dp_emul) = sh["s"], sh["p"], sh["dp"]
+    fails, stats = {}, {}
+
+    def run(stage, fn):
+        try:
+            stats[stage] = fn()
+        except AssertionError as e:
+            fails[stage] = str(e)
+
+    if "S" in got:
+        run("S", lambda: check(got["S"], s_ref, s_mag, C, "f32", route=f"{route} S = alpha q k^T", report=report))
+    if "P" in got:
+        emul_p = torch.softmax(s_emul, dim=-1) if fmt != "f32" else None       # fp32-accumulated logits, fp32 softmax
+        run("P", lambda: _check_row_op(got["P"], p_ref, p_d, fmt, emul_p, f"{route} P = softmax(S)", report, f16_subnormal_exact=True))
+        P = _f64(got["P"])
+        if "O" in got:
+            r, m, e = evaluate(attn_out, P, v)
+            run("O", lambda: check(got["O"], r, m, T, fmt, emul=e, route=f"{route} O = P_stored V", report=report))
+        if "dP" in got:
+            run("dP", lambda: check(got["dP"], dp_ref, dp_mag, C, "f32", route=f"{route} dP = dO V^T", report=report))
+        if "dS" in got:
+            ds_ref, ds_d = dscores_bound(P, dp_ref, dp_mag, C, alpha)
+            emul_ds = attn_dscores(P.float(), dp_emul, float(np.float32(alpha))) if fmt != "f32" else None
+            run("dS", lambda: _check_row_op(got["dS"], ds_ref, ds_d, fmt, emul_ds, f"{route} dS = alpha P (dP - dl)", report))
+        if "dV" in got:
+            r, m, e = evaluate(attn_dv, P, do)
+            run("dV", lambda: check(got["dV"], r, m, Tq, fmt, emul=e, route=f"{route} dV = P_stored^T dO", report=report))
+    if "dS" in got:
+        dS = _f64(got["dS"])
+        if "dQ" in got:
+            r, m, e = evaluate(attn_dq, dS, k)
+            run("dQ", lambda: check(got["dQ"], r, m, T, fmt, emul=e, route=f"{route} dQ = dS_stored K", report=report))
+        if "dK" in got:
+            r, m, e = evaluate(attn_dk, dS, q)
+            run("dK", lambda: check(got["dK"], r, m, Tq, fmt, emul=e, route=f"{route} dK = dS_stored^T Q", report=report))
+    return fails, stats
+
+
+def attention_nonfinite(q, k, v, do, got, route="", report=True):
+    """Non-finite operands (NaN / inf somewhere in q, k, v, dO): the non-finite PATTERN of every stage in `got` (P, O, dS, dQ, dK, dV)
+    must be that of the float64 reference evaluated end to end on the same operands, and the reference pattern must not be empty
+    (a case that poisons nothing tests nothing).  Returns {stage: message} of the stages whose pattern differs."""
+    a = attn_alpha(q.shape[-1])
+    q, k, v, do = _f64(q), _f64(k), _f64(v), _f64(do)
+    P = attn_softmax(attn_logits(q, k, a)); dS = attn_dscores(P, attn_dprobs(do, v), a)
+    ref = dict(P=P, O=attn_out(P, v), dS=dS, dQ=attn_dq(dS, k), dK=attn_dk(dS, q), dV=attn_dv(P, do))
+    fails = {}
+    for s, r in ref.items():
+        if s not in got:
+            continue
+        g = _f64(got[s])
+        nr, ng = ~torch.isfinite(r), ~torch.isfinite(g)
+        assert bool(nr.any()), f"{route} {s}: the reference has no non-finite element"
+        bad = nr != ng
+        if bool(bad.any()):
+            fails[s] = (f"{route} {s}: non-finite pattern differs in {int(bad.sum())} of {r.numel()} elements "
+                        f"(kernel {int(ng.sum())}, reference {int(nr.sum())} non-finite)")
+        elif report:
+            print(f"[nonfinite] {route} {s}: {int(nr.sum())} non-finite elements, same pattern as the reference")
+    return fails
