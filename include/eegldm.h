@@ -104,6 +104,11 @@ int eegldm_prof_dump(eegldm_ctx* ctx, const char* path_host);
  * A/B an execution path against its predecessor inside one process.  Models / contexts created BEFORE the call keep whatever
  * they built from the old values (weight copies, streams).  No reference counterpart. */
 int eegldm_debug_reload_env(void);
+/* developer aid: the kernel that served the calling thread's last eegldm_groupnorm_fwd (backward = 0) / _bwd (1) launch, as six ints:
+ * family (1 split kernels, 2 register-resident, 3 pipelined persistent backward, 4 flat G = 1, 5 wide flat forward), 4-wide loads (1 / 0),
+ * threads per block, rows- (flat: chunks-) per-thread instantiation, chunk width in channels, XCD-aware block order (1 / 0).
+ * The route-aware tests confirm from it that a case ran on the kernel it names.  No reference counterpart. */
+int eegldm_debug_gn_last_route(int backward, int* out6_host);
 /* EEGLDM_DETERMINISTIC=1 (environment variable, read like the developer switches; eegldm.set_deterministic() in the Python mirror):
  * bit-reproducible losses, parameter gradients and optimiser steps run to run.  Every order-dependent reduction -- fp32 atomics of
  * the bias / GroupNorm / thin-conv gradients and of the loss sums, fused column sums inside the weight-gradient GEMM, split-K without

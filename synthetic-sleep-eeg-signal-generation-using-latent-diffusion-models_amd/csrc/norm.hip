@@ -71,6 +71,18 @@ template <typename T, int V> __device__ __forceinline__ void storev(T* p, const 
   if constexpr (V == 4) store4<T>(p, v); else st_f32(p, v[0]);
 }
 
+// 1 / (elements per group) for the fp64 group sums.  16-bit engines: the fp64 reciprocal (a float one is inexact unless cpg * L is a power of
+// two, and the one-pass variance multiplies that error by mean^2 / var).  The fp32 engine keeps the float reciprocal it always had, widened,
+// and in the split backward the float product: its arithmetic, two-pass statistics included, is untouched so that its outputs stay bit-equal.
+template <typename T> __device__ __forceinline__ double gn_inv_n(int cpg, int L) {
+  if constexpr (sizeof(T) == 2) return 1.0 / ((double)cpg * (double)L);
+  else return (double)(1.0f / ((float)cpg * (float)L));
+}
+template <typename T> __device__ __forceinline__ float gn_split_group_mean(double sum, double inv_n) {
+  if constexpr (sizeof(T) == 2) return (float)(sum * inv_n);
+  else return (float)sum * (float)inv_n;
+}
+
 // thread -> (column-vector, row-lane) decomposition of a block
 struct ColMap { int TX, TY, ncols; };
 __device__ __forceinline__ ColMap colmap(int C, int V) {
@@ -299,12 +311,12 @@ __global__ __launch_bounds__(NT) void gn_bwd_apply_kernel(const T* __restrict__ 
   const ColMap cm = colmap(C, V);
   if (tid >= cm.TX * cm.TY) return;
   const int tx = tid % cm.TX, ty = tid / cm.TX;
-  const float inv_n = 1.0f / ((float)cpg * (float)L);
+  const double inv_n = gn_inv_n<T>(cpg, L);
   const int l0 = blockIdx.x * rows_per_block, l1 = min(L, l0 + rows_per_block);
   for (int col = tx; col < cm.ncols; col += cm.TX) {
     const int c = col * V, g = c / cpg;
     const float mean = stats[((long)b * G + g) * 2], rstd = stats[((long)b * G + g) * 2 + 1];
-    const float m1 = (float)gsums[((long)b * G + g) * 2] * inv_n, m2 = (float)gsums[((long)b * G + g) * 2 + 1] * inv_n;
+    const float m1 = gn_split_group_mean<T>(gsums[((long)b * G + g) * 2], inv_n), m2 = gn_split_group_mean<T>(gsums[((long)b * G + g) * 2 + 1], inv_n);
     float ga[V], be[V];
 #pragma unroll
     for (int k = 0; k < V; k++) { ga[k] = gamma[c + k]; be[k] = beta[c + k]; }
@@ -408,6 +420,8 @@ __global__ __launch_bounds__(NTH) void gn_fwd_resident_kernel(const T* __restric
   for (int i = threadIdx.x; i < 2 * RES_MAXG; i += NTH) red[i] = 0.0;
   typename Vec<T, 4>::type raw[RPT];
   const T* xb = x + (long)b * L * ldx + m.c;
+  float pv = 0.f;      // 16-bit engines: the group's first element, the pivot of the one-pass statistics below (first in the load queue)
+  if constexpr (sizeof(T) == 2) { if (m.act) pv = ld_f32<T>(x + (long)b * L * ldx + (m.c / cpg) * cpg); }
   if (m.act) {
 #pragma unroll
     for (int k = 0; k < RPT; k++) {
@@ -418,23 +432,29 @@ __global__ __launch_bounds__(NTH) void gn_fwd_resident_kernel(const T* __restric
   GN_TSTAMP(1);
   __syncthreads();
   GN_TSTAMP(2);
-  const float inv_n = 1.0f / ((float)cpg * (float)L);
+  const double inv_n = gn_inv_n<T>(cpg, L);
   float mean = 0.f, rstd = 0.f;
   if constexpr (sizeof(T) == 2) {
-    // 16-bit storage: ONE reduction round.  Sum and sum of squares are taken about a per-thread-independent shift of zero in fp32
-    // per thread (<= 48 elements), accumulated in fp64 across the block, and the variance is E[x^2] - mean^2 in fp64: the relative
-    // error of the fp32 partials (~1e-7) is amplified by 1 + mean^2 / var, harmless for activations whose mean is within tens of
-    // standard deviations, and far below the bf16 rounding of the output.  Saves the second barrier round of the two-pass form
-    // (mean first, then centred squares: 5.3 k of the block's 28 k cycles, tools/debug/gn_timing.py).  The fp32 engine keeps two passes.
-    // Measured at the stated edge (mean 30 x std, tests/test_gpu_rounding.py, 8 channels per group): the output stays within the hard
-    // bound derived from this arithmetic, but the fp16 output carries a mean bias of +0.07 ulp (8 % of its elements differ from the
-    // correctly rounded value) and the bf16 data gradient differs on 0.3 %: not harmless in fp16.  Open finding; the cause is not located.
+    // 16-bit storage: ONE reduction round.  Sum and sum of squares are taken in fp32 per thread (<= 48 elements) about a PIVOT that every
+    // thread of the (sample, group) shares -- the group's first element, one extra broadcast load issued with the rows -- accumulated in
+    // fp64 across the block, and mean = pivot + E[d], var = E[d^2] - E[d]^2 in fp64 with d = x - pivot.  The differences are exact in fp32
+    // for 16-bit inputs of similar magnitude, and the relative error of the fp32 partials (~1e-7) is amplified by 1 + (mean - pivot)^2 / var,
+    // a few units whatever the mean is.  Saves the second barrier round of the two-pass form (mean first, then centred squares: 5.3 k of
+    // the block's 28 k cycles, tools/debug/gn_timing.py).  The fp32 engine keeps two passes.
+    // What was found here: until this form the sums were taken about zero and scaled by a FLOAT 1 / n.  Both errors are ~1e-7 relative but
+    // enter var = E[x^2] - mean^2 multiplied by mean^2 / var (900 at mean 30 x std): the inexact reciprocal shifts var by
+    // e (E[x^2] - 2 mean^2) on every group alike (-2.7e-5 relative in bf16, whose partials are exact), and the fp32 partial of x^2 (4e4 after
+    // 48 elements of 30^2, fp16 squares need 2^-12) rounds without averaging out over a group's threads.  At mean 30 x std the fp16 output
+    // carried +0.07 ulp of bias (8 % of its elements off the correctly rounded value), the bf16 data gradient differed on 0.3 %
+    // (tests/test_groupnorm_numerics_cpu.py restates both arithmetics on the CPU; tests/test_gpu_groupnorm_rounding.py holds the kernels).
     float s1 = 0.f, s2 = 0.f;
     if (m.act) {
 #pragma unroll
       for (int k = 0; k < RPT; k++) {
         if (res_row(k, m.ty, m.TY, pair) < L) {
           float v[4]; unpack4<T>(raw[k], v);
+#pragma unroll
+          for (int j = 0; j < 4; j++) v[j] -= pv;
           s1 += (v[0] + v[1]) + (v[2] + v[3]);
           s2 = fmaf(v[0], v[0], s2); s2 = fmaf(v[1], v[1], s2); s2 = fmaf(v[2], v[2], s2); s2 = fmaf(v[3], v[3], s2);
         }
@@ -445,9 +465,9 @@ __global__ __launch_bounds__(NTH) void gn_fwd_resident_kernel(const T* __restric
     GN_TSTAMP(3);
     GN_TSTAMP(4);
     if (!m.act) return;
-    const double mu = red[m.gl] * (double)inv_n;
-    double var = red[RES_MAXG + m.gl] * (double)inv_n - mu * mu; if (var < 0.0) var = 0.0;
-    mean = (float)mu;
+    const double md = red[m.gl] * inv_n;
+    double var = red[RES_MAXG + m.gl] * inv_n - md * md; if (var < 0.0) var = 0.0;
+    mean = (float)((double)pv + md);
     rstd = rsqrtf((float)var + eps);
   } else {
   float s = 0.f;
@@ -461,7 +481,7 @@ __global__ __launch_bounds__(NTH) void gn_fwd_resident_kernel(const T* __restric
   __syncthreads();
   GN_TSTAMP(3);
   if (m.act) {
-    mean = (float)(red[m.gl] * (double)inv_n);
+    mean = (float)(red[m.gl] * inv_n);
     float q = 0.f;
 #pragma unroll
     for (int k = 0; k < RPT; k++) {
@@ -476,7 +496,7 @@ __global__ __launch_bounds__(NTH) void gn_fwd_resident_kernel(const T* __restric
   __syncthreads();
   GN_TSTAMP(4);
   if (!m.act) return;
-  rstd = rsqrtf((float)(red[RES_MAXG + m.gl] * (double)inv_n) + eps);
+  rstd = rsqrtf((float)(red[RES_MAXG + m.gl] * inv_n) + eps);
   }
   if (m.ty == 0 && (m.tx * 4) % cpg == 0) { float* st = stats + ((long)b * G + m.c / cpg) * 2; st[0] = mean; st[1] = rstd; }
   float ga[4], be[4];
@@ -676,8 +696,8 @@ __global__ __launch_bounds__(NTH) GN_BWD_ATTR void gn_bwd_resident_kernel(const 
   __syncthreads();
   GN_TSTAMP(4);
   if (m.act) {
-    const float inv_n = 1.0f / ((float)cpg * (float)L);
-    const float m1 = (float)(redg[2 * m.gl] * (double)inv_n), m2 = (float)(redg[2 * m.gl + 1] * (double)inv_n);
+    const double inv_n = gn_inv_n<T>(cpg, L);
+    const float m1 = (float)(redg[2 * m.gl] * inv_n), m2 = (float)(redg[2 * m.gl + 1] * inv_n);
     if (slots && m.ty == 0) {
       float* sl = slots + (size_t)(b % nslot) * 2 * C;
 #pragma unroll
@@ -825,7 +845,7 @@ __global__ __launch_bounds__(NTB) void gn_bwd_pipe_kernel(const bf16_t* __restri
     for (int i = 0; i < 3; i++) pipe_dma(es, ve + i * se, lds0 + 2 * PIPE_SLAB + (unsigned)(i * 16 + wave_u) * 1024u);
   };
   if (nk > 0) { issue_xd(slot * 8 + xc); if constexpr (HAS_ER) issue_e(slot * 8 + xc); }
-  const float inv_n = 1.0f / ((float)cpg * (float)L);
+  const double inv_n = gn_inv_n<T16>(cpg, L);
   const unsigned rowb = (unsigned)CC * 2u;
   const unsigned lrd0 = (unsigned)ty * rowb + (unsigned)tx * 8u, lrds = (unsigned)TY * rowb;      // this thread's piece of row ty; rows step by TY
   const unsigned lddxb = (unsigned)lddx * 2u;
@@ -886,7 +906,7 @@ __global__ __launch_bounds__(NTB) void gn_bwd_pipe_kernel(const bf16_t* __restri
     PIPE_BARRIER();
     PIPE_TSTAMP(k, 5);
     {
-      const float m1 = (float)(redg[2 * gl] * (double)inv_n), m2 = (float)(redg[2 * gl + 1] * (double)inv_n);
+      const float m1 = (float)(redg[2 * gl] * inv_n), m2 = (float)(redg[2 * gl + 1] * inv_n);
       if (slots && ty == 0) {
         float* sl = slots + (size_t)(b % ndg) * 2 * C;
 #pragma unroll
@@ -940,6 +960,15 @@ __global__ __launch_bounds__(NTB) void gn_bwd_pipe_kernel(const bf16_t* __restri
   }
 }
 
+
+// last forward / backward route (eegldm_debug_gn_last_route: the route-aware tests confirm that a case ran on the kernel it names).
+// family: 1 split kernels, 2 resident, 3 pipelined persistent backward, 4 flat G = 1, 5 wide flat forward; vec = 4-wide (1) or scalar (0)
+// loads of the split kernels; nth threads per block; rpt the rows-per-thread (flat: chunks-per-thread) instantiation; cc chunk width in
+// channels; xcd the XCD-aware block order.  Host-side bookkeeping, one record per host thread (thread_local: the
+// read-out reports the calling thread's own last launch), nothing the kernels read.
+struct GnRoute { int family, vec, nth, rpt, cc, xcd; };
+static thread_local GnRoute g_gn_route[2] = {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
+inline void gn_note(int bwd, int family, int vec, int nth, int rpt, int cc, int xcd) { g_gn_route[bwd] = GnRoute{family, vec, nth, rpt, cc, xcd}; }
 
 // chunk width for the resident kernels: the widest whole-group chunk (<= 256 channels, dividing C) whose rows fit the
 // per-thread register budget; 0 = not eligible (fall back to the split kernels)
@@ -1011,7 +1040,8 @@ int gn_fwd_t(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const
 #define GN_FWD_RES1(R, N) hipLaunchKernelGGL((gn_fwd_resident_kernel<T, R, N>), grid, dim3(N), 0, ctx->stream, (const T*)x, ldx, gamma, beta, \
                                          (T*)y, ldy, (T*)xr, ldxr, stats, L, C, G, eps, silu, resample, cc, xcd)
 #define GN_FWD_RES(R) do { if (nth == 1024) GN_FWD_RES1(R, 1024); else if (nth == 512) GN_FWD_RES1(R, 512); else GN_FWD_RES1(R, 256); } while (0)
-      if (rpt <= 6) GN_FWD_RES(6); else if (rpt <= 12) GN_FWD_RES(12); else { if constexpr (sizeof(T) == 2) GN_FWD_RES(24); }
+      gn_note(0, 2, 1, nth, rpt <= 6 ? 6 : 12, cc, xcd);
+      if (rpt <= 6) GN_FWD_RES(6); else GN_FWD_RES(12);      // resident_chunk never returns more than fwd_rpt_max rows per thread
 #undef GN_FWD_RES
 #undef GN_FWD_RES1
       LAUNCH_CHECK();
@@ -1020,6 +1050,7 @@ int gn_fwd_t(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const
   }
   double* sums = (double*)ctx->scratch;      // zero on entry (context creation / previous finalize)
   int rpb; int ls = pick_lsplit(B, L, C, ctx, &rpb);
+  gn_note(0, 1, V == 4, NT, 0, 0, 0);
   hipLaunchKernelGGL((gn_stats_kernel<T, V>), dim3(ls, B), dim3(NT), 0, ctx->stream, (const T*)x, ldx, sums, L, C, G, rpb);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(gn_finalize_kernel, dim3((B * G + 255) / 256), dim3(256), 0, ctx->stream, sums, stats, B * G,
@@ -1111,6 +1142,7 @@ int gn_bwd_t(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const
             HIP_TRY(hipFuncSetAttribute((const void*)gn_bwd_pipe_kernel<false, false, T>, hipFuncAttributeMaxDynamicSharedMemorySize, PIPE_LDS));
           }
           const dim3 grid((unsigned)(8 * nslot * nchunk));
+          gn_note(1, 3, 1, NTB, PIPE_RPT, pcc, 1);
 #define GN_BWD_PIPE(SL, ER) hipLaunchKernelGGL((gn_bwd_pipe_kernel<SL, ER, T>), grid, dim3(NTB), PIPE_LDS, ctx->stream, (const bf16_t*)x, ldx, gamma, beta, stats, \
                                            (const bf16_t*)dy, lddy, (bf16_t*)dx, lddx, (const bf16_t*)dxr, lddxr, slots, colsum_ps, ldps, B, L, C, G, pcc, ndg)
           if (silu) { if (dxr) GN_BWD_PIPE(true, true); else GN_BWD_PIPE(true, false); }
@@ -1173,6 +1205,7 @@ int gn_bwd_t(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const
 #define GN_BWD_RES1(R, RAW) do { if (silu) GN_BWD_RES2(R, RAW, true); else GN_BWD_RES2(R, RAW, false); } while (0)
 #define GN_BWD_RES(R) do { if (resample == 0 && raw0) GN_BWD_RES1(R, true); else GN_BWD_RES1(R, false); } while (0)
       constexpr int RLO = sizeof(T) == 2 ? 6 : 4, RHI = sizeof(T) == 2 ? 12 : 8;
+      gn_note(1, 2, 1, nth, rpt <= RLO ? RLO : RHI, cc, xcd);
       if (rpt <= RLO) GN_BWD_RES(RLO); else GN_BWD_RES(RHI);
 #undef GN_BWD_RES
 #undef GN_BWD_RES1
@@ -1193,6 +1226,7 @@ int gn_bwd_t(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const
   }
   double* gsums = (double*)ctx->scratch;     // zero on entry; shared with the forward sums (stream-ordered)
   int rpb; int ls = pick_lsplit(B, L, C, ctx, &rpb);
+  gn_note(1, 1, V == 4, NT, 0, 0, 0);
   float* slots = dgamma ? (float*)((char*)ctx->scratch + GN_SLOT_OFFSET) : nullptr;
   int nslot = GN_NSLOT;
   if (slots && eeg_deterministic()) {      // a slot per block: every partial row has one writer, the fold adds the rows in order
@@ -1291,23 +1325,29 @@ __global__ __launch_bounds__(FLAT_NT) void gn_flat_fwd_kernel(const T* __restric
   typename Chunk8<T>::raw_t raw[MAXCH];
 #pragma unroll
   for (int k = 0; k < MAXCH; k++) { const int ci = k * FLAT_NT + tid; if (ci < nch) raw[k] = Chunk8<T>::load(xs + (long)ci * 8); }
+  // statistics and xhat about the sample's first element pv (one value for the whole block): the fp32 sums and the subtraction of the
+  // mean then act on |x - pv| ~ std, not on |x| -- at a mean of m std the uncentred form carries ~2^-24 m of absolute error into xhat,
+  // the same on every element of the sample, which an fp16 output shows (tests/test_gpu_groupnorm_rounding.py)
+  const float pv = sizeof(T) == 2 ? ld_f32<T>(xs) : 0.f;      // the fp32 engine keeps its uncentred arithmetic (bit-equal outputs)
   float s[1] = {0.f};
 #pragma unroll
   for (int k = 0; k < MAXCH; k++) {
     if (k * FLAT_NT + tid < nch) {
       float v[8]; Chunk8<T>::unpack(raw[k], v);
+#pragma unroll
+      for (int j = 0; j < 8; j++) v[j] -= pv;
       s[0] += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
     }
   }
   flat_block_sum<1>(s, sm);
-  const float inv_n = 1.0f / (float)n, mean = s[0] * inv_n;
+  const float inv_n = 1.0f / (float)n, md = s[0] * inv_n, mean = pv + md;      // md = mean - pv
   float q[1] = {0.f};
 #pragma unroll
   for (int k = 0; k < MAXCH; k++) {
     if (k * FLAT_NT + tid < nch) {
       float v[8]; Chunk8<T>::unpack(raw[k], v);
 #pragma unroll
-      for (int j = 0; j < 8; j++) { const float d = v[j] - mean; q[0] = fmaf(d, d, q[0]); }
+      for (int j = 0; j < 8; j++) { const float d = (v[j] - pv) - md; q[0] = fmaf(d, d, q[0]); }
     }
   }
   flat_block_sum<1>(q, sm);
@@ -1323,7 +1363,10 @@ __global__ __launch_bounds__(FLAT_NT) void gn_flat_fwd_kernel(const T* __restric
     if (ci < nch) {
       float v[8], o[8]; Chunk8<T>::unpack(raw[k], v);
 #pragma unroll
-      for (int j = 0; j < 8; j++) { const float z = fmaf(fmaf(v[j], rstd, nmr), ga[j], be[j]); o[j] = silu ? silu_f(z) : z; }
+      for (int j = 0; j < 8; j++) {
+        const float xh = sizeof(T) == 2 ? ((v[j] - pv) - md) * rstd : fmaf(v[j], rstd, nmr);
+        const float z = fmaf(xh, ga[j], be[j]); o[j] = silu ? silu_f(z) : z;
+      }
       Chunk8<T>::store(ys + (long)ci * 8, o);
     }
   }
@@ -1415,25 +1458,31 @@ __global__ __launch_bounds__(WIDE_NT) void gn_flat_fwd_wide_kernel(const T* __re
   typename Chunk8<T>::raw_t raw[MAXCH];
 #pragma unroll
   for (int k = 0; k < MAXCH; k++) { const int ci = k * WIDE_NT + tid; if (ci < nch) raw[k] = Chunk8<T>::load(xs + (long)ci * 8); }
+  // statistics and xhat about the sample's first element pv (one value for the whole block): the fp32 sums and the subtraction of the
+  // mean then act on |x - pv| ~ std, not on |x| -- at a mean of m std the uncentred form carries ~2^-24 m of absolute error into xhat,
+  // the same on every element of the sample, which an fp16 output shows (tests/test_gpu_groupnorm_rounding.py)
+  const float pv = sizeof(T) == 2 ? ld_f32<T>(xs) : 0.f;      // the fp32 engine keeps its uncentred arithmetic (bit-equal outputs)
   float s[1] = {0.f};
 #pragma unroll
   for (int k = 0; k < MAXCH; k++) {
     if (k * WIDE_NT + tid < nch) {
       float v[8]; Chunk8<T>::unpack(raw[k], v);
+#pragma unroll
+      for (int j = 0; j < 8; j++) v[j] -= pv;
       s[0] += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
     }
   }
   flat_block_sum<1, WIDE_NT / 64>(s, sm);
 #pragma unroll
   for (int k = 0; k < MAXCH; k++) Chunk8<T>::touch(raw[k]);
-  const float inv_n = 1.0f / (float)n, mean = s[0] * inv_n;
+  const float inv_n = 1.0f / (float)n, md = s[0] * inv_n, mean = pv + md;      // md = mean - pv
   float q[1] = {0.f};
 #pragma unroll
   for (int k = 0; k < MAXCH; k++) {
     if (k * WIDE_NT + tid < nch) {
       float v[8]; Chunk8<T>::unpack(raw[k], v);
 #pragma unroll
-      for (int j = 0; j < 8; j++) { const float d = v[j] - mean; q[0] = fmaf(d, d, q[0]); }
+      for (int j = 0; j < 8; j++) { const float d = (v[j] - pv) - md; q[0] = fmaf(d, d, q[0]); }
     }
   }
   flat_block_sum<1, WIDE_NT / 64>(q, sm);
@@ -1453,7 +1502,10 @@ __global__ __launch_bounds__(WIDE_NT) void gn_flat_fwd_wide_kernel(const T* __re
     if (ci < nch) {
       float v[8], o[8]; Chunk8<T>::unpack(raw[k], v);
 #pragma unroll
-      for (int j = 0; j < 8; j++) { const float z = fmaf(fmaf(v[j], rstd, nmr), ga[j], be[j]); o[j] = silu ? silu_f(z) : z; }
+      for (int j = 0; j < 8; j++) {
+        const float xh = sizeof(T) == 2 ? ((v[j] - pv) - md) * rstd : fmaf(v[j], rstd, nmr);
+        const float z = fmaf(xh, ga[j], be[j]); o[j] = silu ? silu_f(z) : z;
+      }
       Chunk8<T>::store(ys + (long)ci * 8, o);
     }
   }
@@ -1467,6 +1519,7 @@ bool gn_flat_wide_ok(int L, int C, int G, int resample, long l0, long l1) {
 template <typename T>
 int gn_flat_fwd_wide(eegldm_ctx* ctx, const void* x, const float* gamma, const float* beta, void* y, float* stats, int B, int L, int C, float eps, int silu) {
   const int n = L * C;
+  gn_note(0, 5, 1, WIDE_NT, n <= WIDE_NT * 8 * 6 ? 6 : 12, C, 0);
   if (n <= WIDE_NT * 8 * 6) hipLaunchKernelGGL((gn_flat_fwd_wide_kernel<T, 6>), dim3(B), dim3(WIDE_NT), 0, ctx->stream, (const T*)x, gamma, beta, (T*)y, stats, n, C, eps, silu);
   else hipLaunchKernelGGL((gn_flat_fwd_wide_kernel<T, 12>), dim3(B), dim3(WIDE_NT), 0, ctx->stream, (const T*)x, gamma, beta, (T*)y, stats, n, C, eps, silu);
   LAUNCH_CHECK();
@@ -1481,6 +1534,7 @@ bool gn_flat_ok(int L, int C, int G, int resample, long l0, long l1, long l2, lo
 }
 template <typename T, int C>
 int gn_flat_fwd_c(eegldm_ctx* ctx, const void* x, const float* gamma, const float* beta, void* y, float* stats, int B, int n, float eps, int silu) {
+  gn_note(0, 4, 1, FLAT_NT, n <= FLAT_NT * 8 * 3 ? 3 : 12, C, 0);
   if (n <= FLAT_NT * 8 * 3) hipLaunchKernelGGL((gn_flat_fwd_kernel<T, C, 3>), dim3(B), dim3(FLAT_NT), 0, ctx->stream, (const T*)x, gamma, beta, (T*)y, stats, n, eps, silu);
   else hipLaunchKernelGGL((gn_flat_fwd_kernel<T, C, 12>), dim3(B), dim3(FLAT_NT), 0, ctx->stream, (const T*)x, gamma, beta, (T*)y, stats, n, eps, silu);
   LAUNCH_CHECK();
@@ -1498,6 +1552,7 @@ int gn_flat_fwd(eegldm_ctx* ctx, const void* x, const float* gamma, const float*
 template <typename T, int C>
 int gn_flat_bwd_c(eegldm_ctx* ctx, const void* x, const float* gamma, const float* beta, const float* stats, const void* dy, void* dx, const void* dxr,
                   float* slots, int B, int n, int silu, int nslot) {
+  gn_note(1, 4, 1, FLAT_NT, n <= FLAT_NT * 8 * 3 ? 3 : 12, C, 0);
   if (n <= FLAT_NT * 8 * 3) hipLaunchKernelGGL((gn_flat_bwd_kernel<T, C, 3>), dim3(B), dim3(FLAT_NT), 0, ctx->stream, (const T*)x, gamma, beta, stats, (const T*)dy, (T*)dx, (const T*)dxr, slots, n, silu, nslot);
   else hipLaunchKernelGGL((gn_flat_bwd_kernel<T, C, 12>), dim3(B), dim3(FLAT_NT), 0, ctx->stream, (const T*)x, gamma, beta, stats, (const T*)dy, (T*)dx, (const T*)dxr, slots, n, silu, nslot);
   LAUNCH_CHECK();
@@ -1644,6 +1699,13 @@ extern "C" int eegldm_groupnorm_bwd(eegldm_ctx* ctx, const void* x, long ldx, co
                                     int resample, const void* dxr, long lddxr, int dtype) {
   return op_groupnorm_bwd(ctx, x, ldx, gamma, beta, stats, dy, lddy, dx, lddx, dgamma, dbeta, B, L, C, G, fuse_silu, resample,
                           dxr, lddxr, dtype, nullptr, 0, nullptr);
+}
+
+extern "C" int eegldm_debug_gn_last_route(int backward, int* out6_host) {
+  if (!out6_host || backward < 0 || backward > 1) return EEGLDM_ERR_INVALID;
+  const GnRoute& r = g_gn_route[backward];
+  out6_host[0] = r.family; out6_host[1] = r.vec; out6_host[2] = r.nth; out6_host[3] = r.rpt; out6_host[4] = r.cc; out6_host[5] = r.xcd;
+  return 0;
 }
 
 #ifdef EEG_STAGE_TIMING

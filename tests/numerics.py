@@ -477,3 +477,53 @@ def attention_nonfinite(q, k, v, do, got, route="", report=True):
         elif report:
             print(f"[nonfinite] {route} {s}: {int(nr.sum())} non-finite elements, same pattern as the reference")
     return fails
+
+
+# ---------------------------------------------------------------- GroupNorm (NCL layout; any float dtype: float64 reference, float32 emulation)
+# y = act(xhat gamma + beta), xhat = (x - mean) rstd per (sample, group), rstd = 1 / sqrt(var + eps) with the biased variance; then the
+# resample the kernels fuse: 1 = avgpool2 of the OUTPUT (pairs of rows, after the activation), 2 = nearest x2.  xr is the same resample
+# of the INPUT (the residual branch of a ResBlock).  The backward takes dy at the resampled length and an optional addend dxr that
+# is a gradient arriving at xr's length, resampled back the same way and added to dx.
+def gn_stats(x, G, eps):
+    """(mean, var, rstd), each (B, G), in x's dtype"""
+    B = x.shape[0]
+    xg = x.reshape(B, G, -1)
+    mean = xg.mean(-1)
+    var = ((xg - mean[:, :, None]) ** 2).mean(-1)
+    return mean, var, 1.0 / torch.sqrt(var + eps)
+
+
+def gn_resample(t, resample):
+    if resample == 1:
+        return 0.5 * (t[:, :, 0::2] + t[:, :, 1::2])
+    if resample == 2:
+        return t.repeat_interleave(2, dim=2)
+    return t
+
+
+def gn_fwd(x, G, gamma, beta, eps=1e-6, silu=False, resample=0, torch_norm=False):
+    """torch_norm: z from torch.nn.functional.group_norm -- the fp32 emulation behind check B's m_emul (torch's own kernel, whose fp32
+    arithmetic on uncentred values is what an fp32 implementation is measured against); otherwise the centred formula, for float64"""
+    B, C, L = x.shape
+    if torch_norm:
+        z = F.group_norm(x, G, gamma, beta, eps=eps)
+    else:
+        mean, _var, rstd = gn_stats(x, G, eps)
+        rep = lambda t: t.repeat_interleave(C // G, dim=1)[:, :, None]
+        z = (x - rep(mean)) * rep(rstd) * gamma[:, None] + beta[:, None]
+    return gn_resample(F.silu(z) if silu else z, resample)
+
+
+def gn_xr(x, resample):
+    """the resampled copy of the input that the forward writes beside y (resample 1 and 2)"""
+    return gn_resample(x, resample)
+
+
+def gn_bwd(x, G, gamma, beta, dy, eps=1e-6, silu=False, resample=0, dxr=None, torch_norm=False):
+    """(dx, dgamma, dbeta) of sum(gn_fwd(x) dy) [+ sum(gn_xr(x) dxr)] by autograd in the dtype of x"""
+    xr = x.detach().clone().requires_grad_(True); gr = gamma.detach().clone().requires_grad_(True); br = beta.detach().clone().requires_grad_(True)
+    s = (gn_fwd(xr, G, gr, br, eps, silu, resample, torch_norm) * dy).sum()
+    if dxr is not None:
+        s = s + (gn_xr(xr, resample) * dxr).sum()
+    s.backward()
+    return xr.grad, gr.grad, br.grad
