@@ -75,7 +75,7 @@ void sampler_release(const eegldm_unet* u) {
   }
 }
 
-// labels_host (class-conditional UNets; NULL otherwise): one class per sample.  guidance_scale != 1 runs every forward on 2B rows -- the B
+// labels (class-conditional UNets; NULL otherwise): one class per sample.  guidance_scale != 1 runs every forward on 2B rows -- the B
 // samples with their labels, then the same latents with null_class -- and mixes the two outputs inside the scheduler step (cfg_step_kernel)
 // ms (eegldm_sample_multistep; NULL otherwise): the per-step coefficients of the linear multistep update, which then replaces the DDIM /
 // DDPM step -- one eegldm_multistep_step launch behind every forward; a_prev / beta_t / ancestral are not read
@@ -91,34 +91,41 @@ struct EditBlock { const float *known, *mask, *a_next; };
 // lg and ed together (eegldm_sample_long_edit): known / mask are canvas-shaped, the canvas starts as `known` noised to a_t[0] with `noise`,
 // and every step is one eegldm_canvas_edit_step launch (the canvas step and the blend; mask NULL: the canvas step alone).
 struct LongBlock { int R, W, m, r; float *canvas_out, *recording_out; };
-static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
-                       const float* a_prev_host, const float* beta_t_host, int n_steps, int ancestral, int pred_type, int clip_sample,
-                       float inv_scale_factor, uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
-                       int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class,
-                       const MultistepCoef* ms = nullptr, const EditBlock* ed = nullptr, const LongBlock* lg = nullptr) {
-  EEG_CHECK(u && noise && timesteps_host && a_t_host && (a_prev_host || ms), "null argument");
-  EEG_CHECK(!ancestral || beta_t_host, "the ancestral (DDPM) step needs beta_t");
-  EEG_CHECK(n_steps >= 1 && B >= 1 && L >= 1, "bad sizes");
-  EEG_CHECK(lg || latents_out || windows_out, "nothing to return: pass latents_out and/or windows_out");
+// One call of the loop.  The exports fill the leading members in the order of their own argument lists and name the rest.
+struct SampleCall {
+  eegldm_unet* u; eegldm_aekl* ae; const float* noise; const int64_t* timesteps; const float* a_t; int n_steps, pred_type, clip_sample;
+  float inv_scale_factor; float *latents_out, *windows_out; int B, L, use_graph; int* graph_used; const int64_t* labels; float guidance_scale;
+  int64_t null_class;
+  const float *a_prev = nullptr, *beta_t = nullptr; int ancestral = 0; uint64_t noise_seed = 0;      // the DDIM / DDPM step
+  const MultistepCoef* ms = nullptr; const EditBlock* ed = nullptr; const LongBlock* lg = nullptr;
+};
+static int sample_impl(const SampleCall& q) {
+  eegldm_unet* const u = q.u; eegldm_aekl* const ae = q.ae;
+  const int B = q.B, L = q.L;
+  const MultistepCoef* const ms = q.ms; const EditBlock* const ed = q.ed; const LongBlock* const lg = q.lg;
+  EEG_CHECK(u && q.noise && q.timesteps && q.a_t && (q.a_prev || ms), "null argument");
+  EEG_CHECK(!q.ancestral || q.beta_t, "the ancestral (DDPM) step needs beta_t");
+  EEG_CHECK(q.n_steps >= 1 && B >= 1 && L >= 1, "bad sizes");
+  EEG_CHECK(lg || q.latents_out || q.windows_out, "nothing to return: pass latents_out and/or windows_out");
   EEG_CHECK(!lg || (ms && lg->R >= 1 && lg->W >= 1 && (long)lg->R * lg->W == B), "the canvas form needs the multistep coefficients and B == R * W");
   EEG_CHECK(!lg || lg->canvas_out || lg->recording_out, "nothing to return: pass canvas_out and/or recording_out");
-  EEG_CHECK(!ed || (ed->known && !ancestral), "editing needs the known signal and a deterministic step");
+  EEG_CHECK(!ed || (ed->known && !q.ancestral), "editing needs the known signal and a deterministic step");
   EEG_CHECK(!ed || !ms || ed->a_next, "the multistep form needs a_next");
   eegldm_ctx* ctx = unet_ctx(u);
   const int C = unet_in_channels(u);
   EEG_CHECK(unet_out_channels(u) == C, "sampling needs in_channels == out_channels");
   EEG_CHECK(!ae || aekl_ctx(ae) == ctx, "the autoencoder and the UNet must share one context");
   const int K = unet_num_classes(u);
-  const bool cond = labels_host != nullptr;
-  const bool guided = cond && guidance_scale != 1.0f;      // w == 1 is the plain conditional sampler: the null-class half is not run
+  const bool cond = q.labels != nullptr;
+  const bool guided = cond && q.guidance_scale != 1.0f;      // w == 1 is the plain conditional sampler: the null-class half is not run
   const int Bf = guided ? 2 * B : B;                        // rows of every forward
   bool shared = true;                                       // every forward row reads the same embedding row (row stride 0)
   if (cond) {
     for (int b = 0; b < B; b++) {
-      EEG_CHECK(labels_host[b] >= 0 && labels_host[b] < K, "label %lld of sample %d outside [0, %d)", (long long)labels_host[b], b, K);
-      if (labels_host[b] != labels_host[0]) shared = false;
+      EEG_CHECK(q.labels[b] >= 0 && q.labels[b] < K, "label %lld of sample %d outside [0, %d)", (long long)q.labels[b], b, K);
+      if (q.labels[b] != q.labels[0]) shared = false;
     }
-    if (guided) { EEG_CHECK(null_class >= 0 && null_class < K, "null_class %lld outside [0, %d)", (long long)null_class, K); shared = false; }
+    if (guided) { EEG_CHECK(q.null_class >= 0 && q.null_class < K, "null_class %lld outside [0, %d)", (long long)q.null_class, K); shared = false; }
   }
   const long n = (long)B * C * L, nf = (long)Bf * C * L;
   std::lock_guard<std::recursive_mutex> lock(states_mutex());
@@ -145,7 +152,7 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
   // Eager launches (the default) stay on the caller's stream: a second stream is a second hardware queue, and alternating queues
   // measured +8 % on the one-window chain (47.5 vs 51.8 ms, the same as GPU_MAX_HW_QUEUES=1 gives with the own stream).
   EEG_ENV_VAR(bool, force_own, getenv("EEGLDM_SAMPLE_OWN_STREAM") != nullptr);
-  const bool own = use_graph || force_own;
+  const bool own = q.use_graph || force_own;
   const hipStream_t run = own ? s.stream : caller;
   if (own) {
     HIP_TRY(hipEventRecord(s.ev_in, caller));
@@ -153,16 +160,16 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
   }
   ctx->stream = run;
   if (lg) {
-    if (ed) EEG_TRY(eegldm_edit_start(ctx, ed->known, 1.0f, noise, a_t_host[0], nullptr, s.canvas, ncv));
-    else HIP_TRY(hipMemcpyAsync(s.canvas, noise, sizeof(float) * ncv, hipMemcpyDeviceToDevice, run));
+    if (ed) EEG_TRY(eegldm_edit_start(ctx, ed->known, 1.0f, q.noise, q.a_t[0], nullptr, s.canvas, ncv));
+    else HIP_TRY(hipMemcpyAsync(s.canvas, q.noise, sizeof(float) * ncv, hipMemcpyDeviceToDevice, run));
     EEG_TRY(eegldm_canvas_gather(ctx, s.canvas, lg->R, C, lg->W, L, Sl, s.x, guided ? s.x + n : nullptr));
-  } else if (ed) EEG_TRY(eegldm_edit_start(ctx, ed->known, 1.0f, noise, a_t_host[0], nullptr, s.x, n));
-  else HIP_TRY(hipMemcpyAsync(s.x, noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
-  if (guided && !lg) HIP_TRY(hipMemcpyAsync(s.x + n, ed ? s.x : noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));     // the null-class half: same latents
+  } else if (ed) EEG_TRY(eegldm_edit_start(ctx, ed->known, 1.0f, q.noise, q.a_t[0], nullptr, s.x, n));
+  else HIP_TRY(hipMemcpyAsync(s.x, q.noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
+  if (guided && !lg) HIP_TRY(hipMemcpyAsync(s.x + n, ed ? s.x : q.noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));     // the null-class half: same latents
   if (cond) {
     HIP_TRY(hipStreamSynchronize(run));             // (the host arrays below are rewritten: an earlier call's copies from them must be done)
-    s.lab_host.assign(labels_host, labels_host + B);
-    if (guided) s.lab_host.resize(Bf, null_class);
+    s.lab_host.assign(q.labels, q.labels + B);
+    if (guided) s.lab_host.resize(Bf, q.null_class);
     HIP_TRY(hipMemcpyAsync(s.lab, s.lab_host.data(), sizeof(int64_t) * Bf, hipMemcpyHostToDevice, run));
   }
   const int64_t* fwd_lab = cond ? s.lab : nullptr;
@@ -175,7 +182,7 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
   const bool table = !no_table;
   const int mode = !table ? 0 : (shared ? 1 : 2);
   if (mode == 2 && !s.emb_rows) HIP_TRY(hipMalloc(&s.emb_rows, sizeof(float) * (size_t)Bf * etot));
-  if (use_graph && !ctx->prof_on && !s.capture_failed) {
+  if (q.use_graph && !ctx->prof_on && !s.capture_failed) {
     // Round 5: the captured forward reads its embedding projections from ONE fixed row (s.emb_row) that the loop below refills from the
     // table of all timesteps before every replay -- until round 4 the graph path recomputed the embedding MLP and the 21 projections
     // inside every replay (six launches, ~100 us at B = 1: 5 of the 10.6 ms by which the replayed DDIM-50 trailed the eager one).
@@ -192,7 +199,7 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
     }
     if (!s.exec) {
       // eager warm-up: grows the arena / workspaces (hipMalloc is not capturable), then capture the identical launch sequence
-      set_t(timesteps_host[0]);
+      set_t(q.timesteps[0]);
       if (mode == 2) HIP_TRY(hipMemsetAsync(s.emb_rows, 0, sizeof(float) * (size_t)Bf * etot, run));
       EEG_TRY(unet_forward_labels(u, s.x, s.tt, fwd_lab, s.out, Bf, L, 0));
       HIP_TRY(hipStreamSynchronize(run));
@@ -210,7 +217,7 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
       }
     } else graph_ok = true;
   }
-  if (graph_used_host) *graph_used_host = graph_ok ? 1 : 0;
+  if (q.graph_used) *q.graph_used = graph_ok ? 1 : 0;
 
   // Eager path: the timesteps are known up front and shared by all samples, so the timestep-embedding MLP and the ResBlocks' embedding
   // projections run ONCE for all n_steps (one batch of n_steps rows) instead of six launches (~100 us at B = 1) inside every step;
@@ -219,7 +226,7 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
   // or -- several classes or guidance -- each step gathers its rows into s.emb_rows (row stride etot).
   if (!graph_ok) unet_set_shared_emb(u, mode == 2 ? s.emb_rows : nullptr, mode == 2 ? etot : 0);      // (a failed capture falls back to the eager path below)
   const int Kt = cond ? K : 1;
-  const int rows = n_steps * Kt;
+  const int rows = q.n_steps * Kt;
   if (table) {
     if (s.emb_cap < rows) {
       HIP_TRY(hipStreamSynchronize(run));
@@ -236,56 +243,56 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
     }
     if (cond) {
       s.tab_t.resize(rows); s.tab_y.resize(rows);
-      for (int i = 0; i < n_steps; i++) for (int c = 0; c < K; c++) { s.tab_t[(size_t)i * K + c] = timesteps_host[i]; s.tab_y[(size_t)i * K + c] = c; }
+      for (int i = 0; i < q.n_steps; i++) for (int c = 0; c < K; c++) { s.tab_t[(size_t)i * K + c] = q.timesteps[i]; s.tab_y[(size_t)i * K + c] = c; }
       HIP_TRY(hipMemcpyAsync(s.steps_dev, s.tab_t.data(), sizeof(int64_t) * rows, hipMemcpyHostToDevice, run));
       HIP_TRY(hipMemcpyAsync(s.tab_y_dev, s.tab_y.data(), sizeof(int64_t) * rows, hipMemcpyHostToDevice, run));
     } else {
-      HIP_TRY(hipMemcpyAsync(s.steps_dev, timesteps_host, sizeof(int64_t) * n_steps, hipMemcpyHostToDevice, run));
+      HIP_TRY(hipMemcpyAsync(s.steps_dev, q.timesteps, sizeof(int64_t) * q.n_steps, hipMemcpyHostToDevice, run));
     }
     EEG_TRY(unet_embed_table(u, s.steps_dev, cond ? s.tab_y_dev : nullptr, rows, s.emb_table, s.emb_work));
-    set_t(timesteps_host[0]);                       // s.tt is not read on this path; keep it defined
+    set_t(q.timesteps[0]);                       // s.tt is not read on this path; keep it defined
   }
 
-  const size_t row0 = cond ? (size_t)labels_host[0] : 0;
-  for (int i = 0; i < n_steps; i++) {
+  const size_t row0 = cond ? (size_t)q.labels[0] : 0;
+  for (int i = 0; i < q.n_steps; i++) {
     const float* step_rows = table ? s.emb_table + (size_t)i * Kt * etot : nullptr;
     if (mode == 2) EEG_TRY(ew_emb_gather(ctx, step_rows, s.lab, Kt, etot, s.emb_rows, Bf));
     else if (table && graph_ok) HIP_TRY(hipMemcpyAsync(s.emb_row, step_rows + row0 * etot, sizeof(float) * (size_t)etot, hipMemcpyDeviceToDevice, run));
     else if (table) unet_set_shared_emb(u, step_rows + row0 * etot, 0);
-    else set_t(timesteps_host[i]);
+    else set_t(q.timesteps[i]);
     if (graph_ok) HIP_TRY(hipGraphLaunch(s.exec, run));
     else EEG_TRY(unet_forward_labels(u, s.x, s.tt, fwd_lab, s.out, Bf, L, 0));
     if (ed && lg) {
-      EEG_TRY(eegldm_canvas_edit_step(ctx, s.out, guidance_scale, guided ? 1 : 0, s.canvas, s.chist, a_t_host[i], ed->a_next[i], pred_type, clip_sample,
-                                      ms->cx[i], ms->c0[i], ms->c1[i], lg->R, C, lg->W, L, lg->m, lg->r, ed->known, noise, ed->mask, s.canvas, s.x,
+      EEG_TRY(eegldm_canvas_edit_step(ctx, s.out, q.guidance_scale, guided ? 1 : 0, s.canvas, s.chist, q.a_t[i], ed->a_next[i], q.pred_type, q.clip_sample,
+                                      ms->cx[i], ms->c0[i], ms->c1[i], lg->R, C, lg->W, L, lg->m, lg->r, ed->known, q.noise, ed->mask, s.canvas, s.x,
                                       guided ? s.x + n : nullptr, nullptr));
       continue;
     }
     if (ed) {      // (without a mask too: an all-zero mask and no mask are then the same bytes in every form)
       const float coef[3] = {ms ? ms->cx[i] : 0.0f, ms ? ms->c0[i] : 0.0f, ms ? ms->c1[i] : 0.0f};
-      EEG_TRY(eegldm_edit_step(ctx, s.out, guidance_scale, guided ? 1 : 0, s.x, ms ? s.hist : nullptr, a_t_host[i], ms ? ed->a_next[i] : a_prev_host[i],
-                               pred_type, clip_sample, ms ? coef : nullptr, ed->known, noise, ed->mask, s.x, guided ? s.x + n : nullptr, nullptr, n));
+      EEG_TRY(eegldm_edit_step(ctx, s.out, q.guidance_scale, guided ? 1 : 0, s.x, ms ? s.hist : nullptr, q.a_t[i], ms ? ed->a_next[i] : q.a_prev[i],
+                               q.pred_type, q.clip_sample, ms ? coef : nullptr, ed->known, q.noise, ed->mask, s.x, guided ? s.x + n : nullptr, nullptr, n));
       continue;
     }
     if (lg) {
-      EEG_TRY(eegldm_canvas_step(ctx, s.out, guidance_scale, guided ? 1 : 0, s.canvas, s.chist, a_t_host[i], pred_type, clip_sample, ms->cx[i], ms->c0[i],
+      EEG_TRY(eegldm_canvas_step(ctx, s.out, q.guidance_scale, guided ? 1 : 0, s.canvas, s.chist, q.a_t[i], q.pred_type, q.clip_sample, ms->cx[i], ms->c0[i],
                                  ms->c1[i], lg->R, C, lg->W, L, lg->m, lg->r, s.canvas, s.x, guided ? s.x + n : nullptr, nullptr));
       continue;
     }
     if (ms) {
-      EEG_TRY(eegldm_multistep_step(ctx, s.out, guidance_scale, guided ? 1 : 0, s.x, s.hist, a_t_host[i], pred_type, clip_sample, ms->cx[i], ms->c0[i],
+      EEG_TRY(eegldm_multistep_step(ctx, s.out, q.guidance_scale, guided ? 1 : 0, s.x, s.hist, q.a_t[i], q.pred_type, q.clip_sample, ms->cx[i], ms->c0[i],
                                     ms->c1[i], s.x, guided ? s.x + n : nullptr, nullptr, n));
       continue;
     }
-    const bool last = a_prev_host[i] >= 1.0f;
-    if (ancestral && !last) EEG_TRY(eegldm_randn(ctx, s.nz, n, noise_seed, (uint64_t)i * (uint64_t)((n + 3) / 4)));
+    const bool last = q.a_prev[i] >= 1.0f;
+    if (q.ancestral && !last) EEG_TRY(eegldm_randn(ctx, s.nz, n, q.noise_seed, (uint64_t)i * (uint64_t)((n + 3) / 4)));
     if (guided) {
-      EEG_TRY(eegldm_guided_step(ctx, s.out, guidance_scale, s.x, last ? nullptr : s.nz, a_t_host[i], a_prev_host[i], ancestral ? beta_t_host[i] : 0.0f,
-                                 ancestral, pred_type, clip_sample, s.x, s.x + n, n));
-    } else if (ancestral) {
-      EEG_TRY(eegldm_ddpm_step(ctx, s.out, s.x, last ? nullptr : s.nz, a_t_host[i], a_prev_host[i], beta_t_host[i], pred_type, clip_sample, s.x, nullptr, n));
+      EEG_TRY(eegldm_guided_step(ctx, s.out, q.guidance_scale, s.x, last ? nullptr : s.nz, q.a_t[i], q.a_prev[i], q.ancestral ? q.beta_t[i] : 0.0f,
+                                 q.ancestral, q.pred_type, q.clip_sample, s.x, s.x + n, n));
+    } else if (q.ancestral) {
+      EEG_TRY(eegldm_ddpm_step(ctx, s.out, s.x, last ? nullptr : s.nz, q.a_t[i], q.a_prev[i], q.beta_t[i], q.pred_type, q.clip_sample, s.x, nullptr, n));
     } else {
-      EEG_TRY(eegldm_ddim_step(ctx, s.out, s.x, a_t_host[i], a_prev_host[i], pred_type, clip_sample, s.x, nullptr, n));
+      EEG_TRY(eegldm_ddim_step(ctx, s.out, s.x, q.a_t[i], q.a_prev[i], q.pred_type, q.clip_sample, s.x, nullptr, n));
     }
   }
   if (lg) {
@@ -295,7 +302,7 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
       // the slices of the final canvas, decoded window by window (one GroupNorm statistic per 30-s window, as in training), cross-faded
       const int down = aekl_down(ae), Co = aekl_out_channels(ae);
       EEG_TRY(eegldm_canvas_gather(ctx, s.canvas, lg->R, C, lg->W, L, Sl, s.x, nullptr));
-      if (inv_scale_factor != 1.0f) EEG_TRY(eegldm_axpy(ctx, s.x, s.x, inv_scale_factor - 1.0f, n));
+      if (q.inv_scale_factor != 1.0f) EEG_TRY(eegldm_axpy(ctx, s.x, s.x, q.inv_scale_factor - 1.0f, n));
       const size_t nd = (size_t)B * Co * L * down;              // (a guided call and a plain one share this state at different B)
       if (s.dec_cap < nd) {
         HIP_TRY(hipStreamSynchronize(run));
@@ -308,13 +315,13 @@ static int sample_impl(eegldm_unet* u, eegldm_aekl* ae, const float* noise, cons
       EEG_TRY(eegldm_canvas_compose(ctx, s.dec, lg->R, Co, lg->W, L * down, Sl * down, lg->m * down, lg->r * down, lg->recording_out));
     }
   }
-  if (latents_out) HIP_TRY(hipMemcpyAsync(latents_out, s.x, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
-  if (windows_out) {
+  if (q.latents_out) HIP_TRY(hipMemcpyAsync(q.latents_out, s.x, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
+  if (q.windows_out) {
     if (ae) {
-      if (inv_scale_factor != 1.0f) EEG_TRY(eegldm_axpy(ctx, s.x, s.x, inv_scale_factor - 1.0f, n));     // z / scale_factor (sample_trials.py:166)
-      EEG_TRY(eegldm_aekl_decode(ae, s.x, windows_out, B, L));
+      if (q.inv_scale_factor != 1.0f) EEG_TRY(eegldm_axpy(ctx, s.x, s.x, q.inv_scale_factor - 1.0f, n));     // z / scale_factor (sample_trials.py:166)
+      EEG_TRY(eegldm_aekl_decode(ae, s.x, q.windows_out, B, L));
     } else {
-      HIP_TRY(hipMemcpyAsync(windows_out, s.x, sizeof(float) * n, hipMemcpyDeviceToDevice, run));    // pixel-space model: x IS the window
+      HIP_TRY(hipMemcpyAsync(q.windows_out, s.x, sizeof(float) * n, hipMemcpyDeviceToDevice, run));    // pixel-space model: x IS the window
     }
   }
   if (own) {
@@ -330,8 +337,10 @@ extern "C" int eegldm_sample(eegldm_unet* u, eegldm_aekl* ae, const float* noise
                              int* graph_used_host) {
   EEG_CHECK(u, "null argument");
   EEG_CHECK(unet_num_classes(u) == 0, "this UNet is class-conditional: use eegldm_sample_cond");
-  return sample_impl(u, ae, noise, timesteps_host, a_t_host, a_prev_host, beta_t_host, n_steps, ancestral, pred_type, clip_sample,
-                     inv_scale_factor, noise_seed, latents_out, windows_out, B, L, use_graph, graph_used_host, nullptr, 1.0f, 0);
+  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph,
+               graph_used_host, nullptr, 1.0f, 0};
+  q.a_prev = a_prev_host; q.beta_t = beta_t_host; q.ancestral = ancestral; q.noise_seed = noise_seed;
+  return sample_impl(q);
 }
 
 extern "C" int eegldm_sample_cond(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
@@ -341,29 +350,41 @@ extern "C" int eegldm_sample_cond(eegldm_unet* u, eegldm_aekl* ae, const float* 
   EEG_CHECK(u && labels_host, "null argument");
   EEG_CHECK(unet_num_classes(u) > 0, "this UNet was built without classes: use eegldm_sample");
   EEG_CHECK(guidance_scale == guidance_scale, "guidance_scale is NaN");
-  return sample_impl(u, ae, noise, timesteps_host, a_t_host, a_prev_host, beta_t_host, n_steps, ancestral, pred_type, clip_sample,
-                     inv_scale_factor, noise_seed, latents_out, windows_out, B, L, use_graph, graph_used_host, labels_host, guidance_scale,
-                     null_class);
+  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph,
+               graph_used_host, labels_host, guidance_scale, null_class};
+  q.a_prev = a_prev_host; q.beta_t = beta_t_host; q.ancestral = ancestral; q.noise_seed = noise_seed;
+  return sample_impl(q);
 }
 
-// The same call with a linear multistep solver (DPM-Solver++ 2M, include/eegldm.h) in place of the DDIM / DDPM step.  labels_host NULL: an
-// unconditional UNet; non-NULL: a class-conditional one, guidance as in eegldm_sample_cond.
-extern "C" int eegldm_sample_multistep(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
-                                       const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int pred_type,
-                                       int clip_sample, float inv_scale_factor, float* latents_out, float* windows_out, int B, int L,
-                                       int use_graph, int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
-  EEG_CHECK(u && cx_host && c0_host && c1_host, "null argument");
-  EEG_CHECK(n_steps >= 1, "bad sizes");
-  EEG_CHECK(c1_host[0] == 0.0f, "step 0 has no history: c1[0] must be 0 (got %g)", (double)c1_host[0]);
+// What the multistep, edit and long exports check ahead of sample_impl.  multistep: the form needs its three coefficient arrays (false: the
+// DDIM form of eegldm_sample_edit, which has none).  R, W: the canvas forms' rows, else 1, 1.  step0: how the message names the step without
+// a history.  labels_host NULL: an unconditional UNet; non-NULL: a class-conditional one, guidance as in eegldm_sample_cond.
+static int sample_preamble(eegldm_unet* u, bool multistep, const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int R,
+                           int W, const char* step0, const int64_t* labels_host, float guidance_scale) {
+  EEG_CHECK(u && (!multistep || (cx_host && c0_host && c1_host)), "null argument");
+  EEG_CHECK(n_steps >= 1 && R >= 1 && W >= 1, "bad sizes");
+  EEG_CHECK((long)R * W <= 0x3fffffffL, "R * W = %ld rows: too many", (long)R * W);
+  if (multistep) EEG_CHECK(c1_host[0] == 0.0f, "%s has no history: c1[0] must be 0 (got %g)", step0, (double)c1_host[0]);
   if (labels_host) {
     EEG_CHECK(unet_num_classes(u) > 0, "labels for a UNet built without classes");
     EEG_CHECK(guidance_scale == guidance_scale, "guidance_scale is NaN");
   } else {
     EEG_CHECK(unet_num_classes(u) == 0, "this UNet is class-conditional: pass labels_host");
   }
+  return 0;
+}
+
+// The same call with a linear multistep solver (DPM-Solver++ 2M, include/eegldm.h) in place of the DDIM / DDPM step.
+extern "C" int eegldm_sample_multistep(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
+                                       const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int pred_type,
+                                       int clip_sample, float inv_scale_factor, float* latents_out, float* windows_out, int B, int L,
+                                       int use_graph, int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
+  EEG_TRY(sample_preamble(u, true, cx_host, c0_host, c1_host, n_steps, 1, 1, "step 0", labels_host, guidance_scale));
   const MultistepCoef ms{cx_host, c0_host, c1_host};
-  return sample_impl(u, ae, noise, timesteps_host, a_t_host, nullptr, nullptr, n_steps, 0, pred_type, clip_sample, inv_scale_factor, 0,
-                     latents_out, windows_out, B, L, use_graph, graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class, &ms);
+  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph,
+               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
+  q.ms = &ms;
+  return sample_impl(q);
 }
 
 // The same loops from an input (include/eegldm.h): cx_host NULL = DDIM, else the multistep form.
@@ -372,29 +393,17 @@ extern "C" int eegldm_sample_edit(eegldm_unet* u, eegldm_aekl* ae, const float* 
                                   const float* c0_host, const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
                                   float inv_scale_factor, float* latents_out, float* windows_out, int B, int L, int use_graph, int* graph_used_host,
                                   const int64_t* labels_host, float guidance_scale, int64_t null_class) {
-  EEG_CHECK(u, "null argument");
-  EEG_CHECK(n_steps >= 1, "bad sizes");
+  EEG_TRY(sample_preamble(u, cx_host != nullptr, cx_host, c0_host, c1_host, n_steps, 1, 1, "the first executed step", labels_host, guidance_scale));
   EEG_CHECK(known || !mask, "a mask needs the known signal");
-  if (labels_host) {
-    EEG_CHECK(unet_num_classes(u) > 0, "labels for a UNet built without classes");
-    EEG_CHECK(guidance_scale == guidance_scale, "guidance_scale is NaN");
-  } else {
-    EEG_CHECK(unet_num_classes(u) == 0, "this UNet is class-conditional: pass labels_host");
-  }
-  const float w = labels_host ? guidance_scale : 1.0f;
-  const EditBlock ed{known, mask, a_next_host};
-  const EditBlock* edp = known ? &ed : nullptr;
-  if (!cx_host) {
-    EEG_CHECK(a_prev_host, "the DDIM form needs a_prev_host");
-    return sample_impl(u, ae, noise, timesteps_host, a_t_host, a_prev_host, nullptr, n_steps, 0, pred_type, clip_sample, inv_scale_factor, 0,
-                       latents_out, windows_out, B, L, use_graph, graph_used_host, labels_host, w, null_class, nullptr, edp);
-  }
-  EEG_CHECK(c0_host && c1_host, "null argument");
-  EEG_CHECK(c1_host[0] == 0.0f, "the first executed step has no history: c1[0] must be 0 (got %g)", (double)c1_host[0]);
-  EEG_CHECK(!known || a_next_host, "the multistep form needs a_next_host");
+  EEG_CHECK(cx_host || a_prev_host, "the DDIM form needs a_prev_host");
+  EEG_CHECK(!cx_host || !known || a_next_host, "the multistep form needs a_next_host");
   const MultistepCoef ms{cx_host, c0_host, c1_host};
-  return sample_impl(u, ae, noise, timesteps_host, a_t_host, nullptr, nullptr, n_steps, 0, pred_type, clip_sample, inv_scale_factor, 0,
-                     latents_out, windows_out, B, L, use_graph, graph_used_host, labels_host, w, null_class, &ms, edp);
+  const EditBlock ed{known, mask, a_next_host};
+  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph,
+               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
+  if (cx_host) q.ms = &ms; else q.a_prev = a_prev_host;
+  if (known) q.ed = &ed;
+  return sample_impl(q);
 }
 
 // Long recordings (include/eegldm.h): R canvases of W overlapping windows each, sampled as one batch of R * W rows.
@@ -402,23 +411,12 @@ extern "C" int eegldm_sample_long(eegldm_unet* u, eegldm_aekl* ae, const float* 
                                   const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int pred_type, int clip_sample,
                                   float inv_scale_factor, float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
                                   int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
-  EEG_CHECK(u && cx_host && c0_host && c1_host, "null argument");
-  EEG_CHECK(n_steps >= 1 && R >= 1 && W >= 1, "bad sizes");
-  EEG_CHECK((long)R * W <= 0x3fffffffL, "R * W = %ld rows: too many", (long)R * W);
-  EEG_CHECK(c1_host[0] == 0.0f, "step 0 has no history: c1[0] must be 0 (got %g)", (double)c1_host[0]);
-  if (labels_host) {
-    EEG_CHECK(unet_num_classes(u) > 0, "labels for a UNet built without classes");
-    EEG_CHECK(guidance_scale == guidance_scale, "guidance_scale is NaN");
-  } else {
-    EEG_CHECK(unet_num_classes(u) == 0, "this UNet is class-conditional: pass labels_host");
-  }
-  const MultistepCoef ms{cx_host, c0_host, c1_host};
-  const LongBlock lg{R, W, m, r, canvas_out, recording_out};
-  return sample_impl(u, ae, noise, timesteps_host, a_t_host, nullptr, nullptr, n_steps, 0, pred_type, clip_sample, inv_scale_factor, 0, nullptr,
-                     nullptr, R * W, L, use_graph, graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class, &ms, nullptr, &lg);
+  return eegldm_sample_long_edit(u, ae, noise, nullptr, nullptr, timesteps_host, a_t_host, cx_host, c0_host, c1_host, nullptr, n_steps, pred_type,
+                                 clip_sample, inv_scale_factor, canvas_out, recording_out, R, W, L, m, r, use_graph, graph_used_host, labels_host,
+                                 guidance_scale, null_class);
 }
 
-// The same loop from a real recording (include/eegldm.h): the canvas form with the edit block.  known == NULL: eegldm_sample_long.
+// The same loop from a real recording (include/eegldm.h): the canvas form with the edit block.  known == NULL: the plain form.
 extern "C" int eegldm_sample_long_edit(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
                                        const int64_t* timesteps_host, const float* a_t_host, const float* cx_host, const float* c0_host,
                                        const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
@@ -426,22 +424,14 @@ extern "C" int eegldm_sample_long_edit(eegldm_unet* u, eegldm_aekl* ae, const fl
                                        int use_graph, int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
   EEG_CHECK(known || !mask, "a mask needs the known signal");
   EEG_CHECK(!known || a_next_host, "the run from an input needs a_next_host");
-  if (!known)
-    return eegldm_sample_long(u, ae, noise, timesteps_host, a_t_host, cx_host, c0_host, c1_host, n_steps, pred_type, clip_sample, inv_scale_factor,
-                              canvas_out, recording_out, R, W, L, m, r, use_graph, graph_used_host, labels_host, guidance_scale, null_class);
-  EEG_CHECK(u && cx_host && c0_host && c1_host, "null argument");
-  EEG_CHECK(n_steps >= 1 && R >= 1 && W >= 1, "bad sizes");
-  EEG_CHECK((long)R * W <= 0x3fffffffL, "R * W = %ld rows: too many", (long)R * W);
-  EEG_CHECK(c1_host[0] == 0.0f, "the first executed step has no history: c1[0] must be 0 (got %g)", (double)c1_host[0]);
-  if (labels_host) {
-    EEG_CHECK(unet_num_classes(u) > 0, "labels for a UNet built without classes");
-    EEG_CHECK(guidance_scale == guidance_scale, "guidance_scale is NaN");
-  } else {
-    EEG_CHECK(unet_num_classes(u) == 0, "this UNet is class-conditional: pass labels_host");
-  }
+  EEG_TRY(sample_preamble(u, true, cx_host, c0_host, c1_host, n_steps, R, W, known ? "the first executed step" : "step 0", labels_host,
+                          guidance_scale));
   const MultistepCoef ms{cx_host, c0_host, c1_host};
   const EditBlock ed{known, mask, a_next_host};
   const LongBlock lg{R, W, m, r, canvas_out, recording_out};
-  return sample_impl(u, ae, noise, timesteps_host, a_t_host, nullptr, nullptr, n_steps, 0, pred_type, clip_sample, inv_scale_factor, 0, nullptr,
-                     nullptr, R * W, L, use_graph, graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class, &ms, &ed, &lg);
+  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, nullptr, nullptr, R * W, L, use_graph,
+               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
+  q.ms = &ms; q.lg = &lg;
+  if (known) q.ed = &ed;
+  return sample_impl(q);
 }

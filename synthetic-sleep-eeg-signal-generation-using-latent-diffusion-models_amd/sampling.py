@@ -62,24 +62,51 @@ def _labels_host(unet, labels, B, guidance_scale, null_class):
     return lab, nc
 
 
-def _edit_args(autoencoder, scheduler, noise_shape, init, strength, mask, composite, init_latents):
-    """Checks the arguments of a run that starts from an input, on the host and before anything runs; -> None without init / init_latents,
-    else dict(tab = the truncated tables, composite = bool).  Shapes: noise (B, C, L); init (B, in_channels, L * down) windows for an LDM,
-    (B, C, L) for a pixel-space model; init_latents (B, C, L); mask (B, 1, L * down), 1 = keep."""
+def _fma32(a, b, c):
+    """float32 fma(a, b, c) on tensors (a may be a Python float holding a float32 value): the product of two float32 is exact in
+    float64, the sum is rounded there and once more to float32."""
+    a = a.double() if torch.is_tensor(a) else float(a)
+    return (a * b.double() + c.double()).float()
+
+
+def _renoise(z0, noise, a):
+    """k(a) = fma(sqrt(a), z0, sqrt(1 - a) * noise) with the library's roundings (eegldm_edit_start: the product, then a fused
+    multiply-add), a == 1: z0 itself.  A bfloat16 UNet turns a last-bit difference of its input into a bfloat16 ulp."""
+    a32 = np.float32(a)          # (numpy's float32 sqrt is correctly rounded, as the library's sqrtf; torch's scalar sqrt is not always)
+    if a32 >= 1.0:
+        return z0
+    ka, kb = float(np.sqrt(a32)), float(np.sqrt(np.float32(1.0) - a32))
+    return _fma32(ka, z0, noise * kb)
+
+
+# how the messages of a run from an input name its arguments: windows (ddim_sample) and recordings (sample_long)
+_EDIT_WORDS = dict(latents="init_latents", both="init (windows) or init_latents", composite="init (windows)")
+_LONG_EDIT_WORDS = dict(latents="init_canvas", both="init (the recording) or init_canvas (latents)",
+                        composite="init (the recording at window resolution)")
+
+
+def _edit_args(autoencoder, scheduler, shape, init, strength, mask, composite, latents, words=_EDIT_WORDS, mask_erode=0):
+    """Checks the arguments of a run that starts from an input, on the host and before anything runs; -> None without init / latents,
+    else dict(tab = the truncated tables, composite = bool).  shape = (B, C, L) of the latents the run works on -- windows, or the (R, C, Lc)
+    canvases of a long recording; init (B, in_channels, L * down) at window resolution for an LDM, (B, C, L) for a pixel-space model;
+    latents (init_latents / init_canvas, named by `words`) (B, C, L); mask (B, 1, L * down), 1 = keep."""
     from .schedulers import edit_start_index
     edit_start_index(1, strength)           # the range of strength, whatever else is given
-    if init is None and init_latents is None:
+    if int(mask_erode) != mask_erode or mask_erode < 0:
+        raise ValueError(f"mask_erode must be an integer >= 0 (got {mask_erode})")
+    name = words["latents"]
+    if init is None and latents is None:
         if mask is not None:
-            raise ValueError("mask needs init (or init_latents): the kept samples have to come from somewhere")
+            raise ValueError(f"mask needs init (or {name}): the kept samples have to come from somewhere")
         if composite:
             raise ValueError("composite needs init and mask")
         if float(strength) != 1.0:
-            raise ValueError("strength needs init (or init_latents)")
+            raise ValueError(f"strength needs init (or {name})")
         return None
-    if init is not None and init_latents is not None:
-        raise ValueError("pass init (windows) or init_latents, not both")
+    if init is not None and latents is not None:
+        raise ValueError(f"pass {words['both']}, not both")
     tab = scheduler_edit_tables(scheduler, strength)        # (refuses the ancestral scheduler)
-    B, Cc, L = (int(v) for v in noise_shape)
+    B, Cc, L = (int(v) for v in shape)
     down = autoencoder.down if autoencoder is not None else 1
     if init is not None:
         want = (B, autoencoder.in_channels, L * down) if autoencoder is not None else (B, Cc, L)
@@ -87,43 +114,52 @@ def _edit_args(autoencoder, scheduler, noise_shape, init, strength, mask, compos
             raise ValueError(f"init has shape {tuple(init.shape)}, expected {want}")
         if autoencoder is not None and autoencoder.in_channels != autoencoder.out_channels and mask is not None and composite is not False:
             raise ValueError("the composite needs an autoencoder with in_channels == out_channels")
-    elif tuple(init_latents.shape) != (B, Cc, L):
-        raise ValueError(f"init_latents has shape {tuple(init_latents.shape)}, expected {(B, Cc, L)}")
+    elif tuple(latents.shape) != (B, Cc, L):
+        raise ValueError(f"{name} has shape {tuple(latents.shape)}, expected {(B, Cc, L)}")
     if mask is not None and tuple(mask.shape) != (B, 1, L * down):
         raise ValueError(f"mask has shape {tuple(mask.shape)}, expected {(B, 1, L * down)}")
     if composite and (mask is None or init is None):
-        raise ValueError("composite needs mask and init (windows)")
+        raise ValueError(f"composite needs mask and {words['composite']}")
     return dict(tab=tab, composite=(mask is not None and init is not None) if composite is None else bool(composite))
 
 
-def _edit_inputs(unet, autoencoder, x, scale_factor, init, mask, init_latents, native=True):
-    """-> (z0 (B, C, L), window-resolution mask or None, mask at the sampler's resolution or None, init on the device or None).  native: z0 and
-    the pooled mask come from eegldm_edit_start / eegldm_edit_window; else from torch ops (the host loop's reference composition)."""
+def _encode_windows(unet, autoencoder, init_d, scale_factor, native):
+    """scale_factor * the posterior mean of the encoded windows (no reparameterisation draw)"""
+    z_mu, _sigma = autoencoder.encode(init_d)
+    if not native:
+        return z_mu * float(scale_factor)
+    z0 = torch.empty_like(z_mu)
+    check(lib.eegldm_edit_start(unet.ctx.h, ptr(z_mu), float(scale_factor), None, 1.0, ptr(z0), None, z0.numel()))
+    return z0
+
+
+def _edit_inputs(unet, autoencoder, x, init, mask, latents, encode, mask_erode=0, native=True):
+    """-> (z0 (B, C, L), the mask as given on the device or None, the keep-mask at the sampler's resolution or None, init on the device or
+    None), x (B, C, L) being the latents of the run: windows, or the canvases of a long recording.  encode(init on the device, native) -> z0
+    for an LDM (_encode_windows / encode_long).  The keep-mask is the min-pool over the mask eroded by mask_erode samples: latent position p
+    is kept only if all the samples [p down, (p + 1) down) are.  native: it comes from eegldm_edit_window; else from torch ops (the host
+    loops' reference composition)."""
     dev = unet.device
     B, Cc, L = x.shape
     down = autoencoder.down if autoencoder is not None else 1
     init_d = None if init is None else torch.as_tensor(init).to(dev, torch.float32).contiguous()
-    if init_latents is not None:
-        z0 = torch.as_tensor(init_latents).to(dev, torch.float32).contiguous()
+    if latents is not None:
+        z0 = torch.as_tensor(latents).to(dev, torch.float32).contiguous()
     elif autoencoder is None:
         z0 = init_d
     else:
-        z_mu, _sigma = autoencoder.encode(init_d)           # the posterior mean: no reparameterisation draw
-        if native:
-            z0 = torch.empty_like(z_mu)
-            check(lib.eegldm_edit_start(unet.ctx.h, ptr(z_mu), float(scale_factor), None, 1.0, ptr(z0), None, z0.numel()))
-        else:
-            z0 = z_mu * float(scale_factor)
+        z0 = encode(init_d, native)
     m_win = m_lat = None
     if mask is not None:
         m_win = torch.as_tensor(mask).to(dev, torch.float32).contiguous()
         if not bool(((m_win >= 0) & (m_win <= 1)).all()):
             raise ValueError("mask values must lie in [0, 1]")
+        m_er = erode_mask(m_win, mask_erode).contiguous()
         if native:
             m_lat = torch.empty(B, Cc, L, device=dev, dtype=torch.float32)
-            check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_win), B, L * down, down, Cc, ptr(m_lat), None, None, 0, None))
+            check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_er), B, L * down, down, Cc, ptr(m_lat), None, None, 0, None))
         else:
-            m_lat = (-torch.nn.functional.max_pool1d(-m_win, down, down)).expand(B, Cc, L).contiguous()
+            m_lat = (-torch.nn.functional.max_pool1d(-m_er, down, down)).expand(B, Cc, L).contiguous()
     return z0, m_win, m_lat, init_d
 
 
@@ -177,7 +213,8 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     i64, f32 = (lambda v: (C.c_int64 * len(v))(*v)), (lambda v: (C.c_float * len(v))(*v))
     tail = (ptr(lat), ptr(win), B, L, 1 if use_graph else 0, C.byref(used))
     if edit is not None:
-        z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, scale_factor, init, mask, init_latents)
+        z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_latents,
+                                                lambda w, native: _encode_windows(unet, autoencoder, w, scale_factor, native))
         nul = C.POINTER(C.c_float)()
         coef = (f32(tab["cx"]), f32(tab["c0"]), f32(tab["c1"])) if multistep else (nul, nul, nul)
         check(lib.eegldm_sample_edit(unet.h, ae_h, ptr(x), ptr(z0), ptr(m_lat), i64(ts), f32(a_t), nul if multistep else f32(tab["a_prev"]), *coef,
@@ -229,18 +266,9 @@ def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, 
     if edit is not None:
         tab = edit["tab"]
         nz = x
-        z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, scale_factor, init, mask, init_latents, native=False)
-
-        def renoise(a):
-            """sqrt(a) z0 + sqrt(1 - a) noise with the library's roundings (the product, then a fused multiply-add: the sum is formed in
-            float64, where the first product is exact): a bfloat16 UNet turns a last-bit difference of its input into a bfloat16 ulp."""
-            a = float(a)
-            if a >= 1.0:
-                return z0
-            a32 = np.float32(a)          # (numpy's float32 sqrt is correctly rounded, as the library's sqrtf; torch's scalar sqrt is not always)
-            ka, kb = float(np.sqrt(a32)), float(np.sqrt(np.float32(1.0) - a32))
-            return (z0.double() * ka + (nz * kb).double()).float()
-        x = renoise(tab["a_t"][0])
+        z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_latents,
+                                                lambda w, native: _encode_windows(unet, autoencoder, w, scale_factor, native), native=False)
+        x = _renoise(z0, nz, tab["a_t"][0])
         timesteps = tab["timesteps"]
         if isinstance(scheduler, DPMSolverMultistepScheduler):
             first = {"first_order": True}
@@ -252,7 +280,7 @@ def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, 
             out = out_u + w * (out - out_u)
         x, _ = scheduler.step(out, int(t), x, **(first if j == 0 else {}))
         if edit is not None and m_lat is not None:
-            x = m_lat * renoise(tab["a_next"][j]) + (1.0 - m_lat) * x
+            x = m_lat * _renoise(z0, nz, tab["a_next"][j]) + (1.0 - m_lat) * x
     comp = (lambda win: m_win * init_d + (1.0 - m_win) * win) if edit is not None and edit["composite"] else (lambda win: win)
     if autoencoder is None:      # pixel-space model (sample_trials_ddpm.py:99-104): the UNet output IS the window
         sample = comp(x)
@@ -422,42 +450,6 @@ def erode_mask(mask, erode):
     return -torch.nn.functional.max_pool1d(-m.to(torch.float32), 2 * e + 1, 1, e)        # (max_pool1d pads with -inf: +inf for the min)
 
 
-def _long_edit_args(autoencoder, scheduler, lay, R, Cc, init, init_canvas, strength, mask, composite, mask_erode):
-    """Checks the arguments of a long-recording run that starts from an input, on the host and before anything runs; -> None without init /
-    init_canvas, else dict(tab = the truncated tables, composite = bool).  Shapes: init (R, in_channels, down * Lc) for an LDM, (R, C, Lc)
-    for a pixel-space model; init_canvas (R, C, Lc); mask (R, 1, down * Lc), 1 = keep."""
-    from .schedulers import edit_start_index
-    edit_start_index(1, strength)           # the range of strength, whatever else is given
-    if int(mask_erode) != mask_erode or mask_erode < 0:
-        raise ValueError(f"mask_erode must be an integer >= 0 (got {mask_erode})")
-    if init is None and init_canvas is None:
-        if mask is not None:
-            raise ValueError("mask needs init (or init_canvas): the kept samples have to come from somewhere")
-        if composite:
-            raise ValueError("composite needs init and mask")
-        if float(strength) != 1.0:
-            raise ValueError("strength needs init (or init_canvas)")
-        return None
-    if init is not None and init_canvas is not None:
-        raise ValueError("pass init (the recording) or init_canvas (latents), not both")
-    tab = scheduler_edit_tables(scheduler, strength)
-    down = autoencoder.down if autoencoder is not None else 1
-    Lc = lay.canvas_len
-    if init is not None:
-        want = (R, autoencoder.in_channels, Lc * down) if autoencoder is not None else (R, Cc, Lc)
-        if tuple(init.shape) != want:
-            raise ValueError(f"init has shape {tuple(init.shape)}, expected {want}")
-        if autoencoder is not None and autoencoder.in_channels != autoencoder.out_channels and mask is not None and composite is not False:
-            raise ValueError("the composite needs an autoencoder with in_channels == out_channels")
-    elif tuple(init_canvas.shape) != (R, Cc, Lc):
-        raise ValueError(f"init_canvas has shape {tuple(init_canvas.shape)}, expected {(R, Cc, Lc)}")
-    if mask is not None and tuple(mask.shape) != (R, 1, Lc * down):
-        raise ValueError(f"mask has shape {tuple(mask.shape)}, expected {(R, 1, Lc * down)}")
-    if composite and (mask is None or init is None):
-        raise ValueError("composite needs mask and init (the recording at window resolution)")
-    return dict(tab=tab, composite=(mask is not None and init is not None) if composite is None else bool(composite))
-
-
 def _slices_of(cv, lay):
     """(R, C, Lc) -> (R * W, C, L) by torch slicing"""
     R, Cc, _ = cv.shape
@@ -497,34 +489,6 @@ def encode_long(autoencoder, recording, layout, scale_factor=1.0, native=True):
     return z0
 
 
-def _long_edit_inputs(unet, autoencoder, lay, x, scale_factor, init, init_canvas, mask, mask_erode, native=True):
-    """-> (z0 (R, C, Lc), the mask as given on the device or None, the canvas keep-mask or None, init on the device or None).  The canvas
-    mask is the min-pool of eegldm_edit_window (B = R, Lw = down * Lc) over the mask eroded by mask_erode samples: canvas position p is
-    kept only if all the samples [p down, (p + 1) down) are.  native=False: torch ops."""
-    dev = unet.device
-    R, Cc, Lc = x.shape
-    down = autoencoder.down if autoencoder is not None else 1
-    init_d = None if init is None else torch.as_tensor(init).to(dev, torch.float32).contiguous()
-    if init_canvas is not None:
-        z0 = torch.as_tensor(init_canvas).to(dev, torch.float32).contiguous()
-    elif autoencoder is None:
-        z0 = init_d
-    else:
-        z0 = encode_long(autoencoder, init_d, lay, scale_factor, native=native)
-    m_win = m_lat = None
-    if mask is not None:
-        m_win = torch.as_tensor(mask).to(dev, torch.float32).contiguous()
-        if not bool(((m_win >= 0) & (m_win <= 1)).all()):
-            raise ValueError("mask values must lie in [0, 1]")
-        m_er = erode_mask(m_win, mask_erode).contiguous()
-        if native:
-            m_lat = torch.empty(R, Cc, Lc, device=dev, dtype=torch.float32)
-            check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_er), R, Lc * down, down, Cc, ptr(m_lat), None, None, 0, None))
-        else:
-            m_lat = (-torch.nn.functional.max_pool1d(-m_er, down, down)).expand(R, Cc, Lc).contiguous()
-    return z0, m_win, m_lat, init_d
-
-
 @torch.no_grad()
 def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ramp=None, scale_factor=1.0, crop=36, labels=None,
                 guidance_scale=1.0, null_class=None, use_graph=None, info=None, init=None, init_canvas=None, strength=1.0, mask=None,
@@ -552,7 +516,8 @@ def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ram
     default is 0; no other default is proposed and NO value has been measured against anything.  Continuing a recording: init = the real
     samples followed by zeros, mask = 1 over the real samples and 0 beyond."""
     lay, R, labels = _long_args(unet, autoencoder, scheduler, noise.shape, n_windows, margin, ramp, crop, labels)
-    edit = _long_edit_args(autoencoder, scheduler, lay, R, int(noise.shape[1]), init, init_canvas, strength, mask, composite, mask_erode)
+    edit = _edit_args(autoencoder, scheduler, (R, int(noise.shape[1]), lay.canvas_len), init, strength, mask, composite, init_canvas,
+                      _LONG_EDIT_WORDS, mask_erode)
     from .models import UNetModel
     if not isinstance(unet, UNetModel):
         raise TypeError("sample_long runs the native loop: unet must be a UNetModel")
@@ -572,40 +537,27 @@ def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ram
     rec = torch.empty(R, out_c, lay.canvas_len * down, device=unet.device, dtype=torch.float32)
     used = C.c_int(0)
     i64, f32 = (lambda v: (C.c_int64 * len(v))(*v)), (lambda v: (C.c_float * len(v))(*v))
-    if edit is not None:
-        tab = edit["tab"]
-        z0, m_win, m_lat, init_d = _long_edit_inputs(unet, autoencoder, lay, x, scale_factor, init, init_canvas, mask, mask_erode)
-        check(lib.eegldm_sample_long_edit(unet.h, autoencoder.h if autoencoder is not None else None, ptr(x), ptr(z0), ptr(m_lat), i64(tab["timesteps"]),
-                                          f32(tab["a_t"]), f32(tab["cx"]), f32(tab["c0"]), f32(tab["c1"]), f32(tab["a_next"]), len(tab["timesteps"]),
-                                          PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor), ptr(canvas),
-                                          ptr(rec), R, W, L, lay.margin, lay.ramp, 1 if use_graph else 0, C.byref(used),
-                                          None if lab is None else i64(lab), float(guidance_scale), nc))
+    tab = edit["tab"] if edit is not None else dict(timesteps=ts, a_t=a_t, cx=cx, c0=c0, c1=c1)
+    head = (unet.h, autoencoder.h if autoencoder is not None else None, ptr(x))
+    coef = (f32(tab["cx"]), f32(tab["c0"]), f32(tab["c1"]))
+    tail = (len(tab["timesteps"]), PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor), ptr(canvas), ptr(rec),
+            R, W, L, lay.margin, lay.ramp, 1 if use_graph else 0, C.byref(used), None if lab is None else i64(lab), float(guidance_scale), nc)
+    if edit is None:
+        check(lib.eegldm_sample_long(*head, i64(tab["timesteps"]), f32(tab["a_t"]), *coef, *tail))
+    else:
+        z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_canvas,
+                                                lambda r, native: encode_long(autoencoder, r, lay, scale_factor, native=native), mask_erode)
+        check(lib.eegldm_sample_long_edit(*head, ptr(z0), ptr(m_lat), i64(tab["timesteps"]), f32(tab["a_t"]), *coef, f32(tab["a_next"]), *tail))
         if edit["composite"]:
             check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_win), R, lay.canvas_len * down, down, 0, None, ptr(init_d), ptr(rec), out_c, ptr(rec)))
-        unet._bump_tape()
-        if autoencoder is not None:
-            autoencoder._bump_tape()
-        if info is not None:
-            info["graph"], info["layout"], info["n_run"] = bool(used.value), lay, len(tab["timesteps"])
-        return (rec[:, :, crop:-crop] if crop else rec), canvas
-    check(lib.eegldm_sample_long(unet.h, autoencoder.h if autoencoder is not None else None, ptr(x), i64(ts), f32(a_t), f32(cx), f32(c0), f32(c1),
-                                 len(ts), PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor), ptr(canvas),
-                                 ptr(rec), R, W, L, lay.margin, lay.ramp, 1 if use_graph else 0, C.byref(used), None if lab is None else i64(lab),
-                                 float(guidance_scale), nc))
     unet._bump_tape()
     if autoencoder is not None:
         autoencoder._bump_tape()
     if info is not None:
-        info["graph"] = bool(used.value)
-        info["layout"] = lay
+        info["graph"], info["layout"] = bool(used.value), lay
+        if edit is not None:
+            info["n_run"] = len(tab["timesteps"])
     return (rec[:, :, crop:-crop] if crop else rec), canvas
-
-
-def _fma32(a, b, c):
-    """float32 fma(a, b, c) on tensors (a may be a Python float holding a float32 value): the product of two float32 is exact in
-    float64, the sum is rounded there and once more to float32."""
-    a = a.double() if torch.is_tensor(a) else float(a)
-    return (a * b.double() + c.double()).float()
 
 
 def _long_x0(o, x, a_t, prediction_type, clip_sample):
@@ -650,7 +602,8 @@ def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=
     measured against anything), composed from torch ops: the encode per window and its cross-fade, the noised start, the truncated
     tables, the blend m k + (1 - m) x after every step with the library's roundings (_fma32), the min-pooled mask and the composite."""
     lay, R, labels = _long_args(unet, autoencoder, scheduler, noise.shape, n_windows, margin, ramp, crop, labels)
-    edit = _long_edit_args(autoencoder, scheduler, lay, R, int(noise.shape[1]), init, init_canvas, strength, mask, composite, mask_erode)
+    edit = _edit_args(autoencoder, scheduler, (R, int(noise.shape[1]), lay.canvas_len), init, strength, mask, composite, init_canvas,
+                      _LONG_EDIT_WORDS, mask_erode)
     unet.eval()
     dev = unet.device
     x = noise.to(dev, torch.float32).contiguous().clone()
@@ -666,24 +619,19 @@ def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=
         tab = edit["tab"]
         ts, a_t, cx, c0, c1, a_next = (tab[k] for k in ("timesteps", "a_t", "cx", "c0", "c1", "a_next"))
         nz = x
-        z0, m_win, m_lat, init_d = _long_edit_inputs(unet, autoencoder, lay, x, scale_factor, init, init_canvas, mask, mask_erode, native=False)
-
-        def renoise(a):
-            """k(a) = fma(sqrt(a), z0, sqrt(1 - a) * noise), a == 1: z0 -- eegldm_edit_start's roundings"""
-            a32 = np.float32(a)
-            ka, kb = float(np.sqrt(a32)), float(np.sqrt(np.float32(1.0) - a32))
-            return _fma32(ka, z0, nz * kb) if kb != 0.0 else z0 * ka
+        z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_canvas,
+                                                lambda r, native: encode_long(autoencoder, r, lay, scale_factor, native=native), mask_erode,
+                                                native=False)
 
         def blend(mk, k, p):
             """m == 0: p, m == 1: k, else fma(m, k, (1 - m) * p) -- the library's edit_blend"""
             return torch.where(mk == 0, p, torch.where(mk == 1, k, _fma32(mk, k, (1.0 - mk) * p)))
-        x = renoise(a_t[0]).clone()
+        x = _renoise(z0, nz, a_t[0]).clone()
     tt = torch.empty(R * W, device=dev, dtype=torch.int64)
-    slices = lambda cv: torch.stack([cv[:, :, k * S:k * S + L] for k in range(W)], 1).reshape(R * W, Cc, L)
     hist = None
     for i, t in enumerate(ts):
         tt.fill_(t)
-        win = slices(x)
+        win = _slices_of(x, lay)
         out = unet(win, timesteps=tt, **kw).float()
         if lab is not None and w != 1.0:
             out_u = unet(win, timesteps=tt, y=null).float()
@@ -693,14 +641,14 @@ def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=
         x = _fma32(cx[i], x, inner)
         hist = x0
         if m_lat is not None:
-            x = blend(m_lat, renoise(a_next[i]), x)
+            x = blend(m_lat, _renoise(z0, nz, a_next[i]), x)
     if info is not None:
         info["graph"], info["layout"] = False, lay
     comp = (lambda rec: blend(m_win, init_d, rec)) if edit is not None and edit["composite"] else (lambda rec: rec)
     if autoencoder is None:
         rec = comp(x)
         return (rec[:, :, crop:-crop] if crop else rec), x
-    z = slices(x).contiguous()
+    z = _slices_of(x, lay).contiguous()
     if float(scale_factor) != 1.0:
         # 1 / scale_factor rounded to float32, minus one in float32: the native loop's value (see ddim_sample_hostloop)
         check(lib.eegldm_axpy(autoencoder.ctx.h, ptr(z), ptr(z), float(np.float32(1.0 / float(scale_factor)) - np.float32(1.0)), z.numel()))
