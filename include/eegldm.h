@@ -48,7 +48,8 @@ extern "C" {
  *    eegldm_edit_start, eegldm_edit_window, eegldm_sample_edit) and the weighted diffusion loss (eegldm_diffusion_loss, eegldm_loss_bins,
  *    eegldm_ldm_train_step_weighted) and global gradient-norm clipping (eegldm_grad_norm, eegldm_adam_step_clip, eegldm_grad_scale_by)
  *    and long recordings (eegldm_canvas_gather, eegldm_canvas_step, eegldm_canvas_compose, eegldm_sample_long) and their editing
- *    (eegldm_canvas_edit_step, eegldm_sample_long_edit). */
+ *    (eegldm_canvas_edit_step, eegldm_sample_long_edit) and resampled repair (eegldm_edit_jump, eegldm_sample_edit_resample,
+ *    eegldm_sample_long_edit_resample). */
 #define EEGLDM_ABI_VERSION 8
 
 /* Storage / operand type of activations and compute-copy weights (accumulation, statistics, master weights and optimizer state are
@@ -665,6 +666,40 @@ int eegldm_sample_long_edit(eegldm_unet*, eegldm_aekl* ae, const float* noise, c
                             const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample, float inv_scale_factor,
                             float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph, int* graph_used_host,
                             const int64_t* labels_host, float guidance_scale, int64_t null_class);
+
+/* Resampled repair (RePaint, Lugmayr et al. 2022): jumps back up the noise schedule with fresh noise; new symbols, ABI 8.
+ * eegldm_edit_jump: ONE launch that takes x from the noise level a step landed on back up to a_level,
+ *   p   = fma(jump_x, x, jump_n * eps)        jump_x = sqrt(rho), jump_n = sqrt(1 - rho), rho = a_level / a_landed (from the host)
+ *   out = mask == 0 ? p : mask == 1 ? k(a_level) : fma(mask, k(a_level), (1 - mask) * p)
+ * with k and the blend of eegldm_edit_step (the same device functions): the kept positions hold k(a_level) bit for bit after a jump as
+ * after a step.  fresh != NULL: eps = fresh (device, n floats).  fresh == NULL: eps[e] is DRAWN IN REGISTERS, word e & 3 of the Box-Muller
+ * quad of Philox(seed, offset + (e >> 2)) -- the value eegldm_randn(out, n, seed, offset) writes to out[e], bit for bit, a function of
+ * (seed, offset, e) alone: not of any pointer's alignment, of the 16-byte body / scalar edge split or of the grid.  mask == NULL: no blend,
+ * known / noise are not read.  out may be x itself; out2 (nullable) receives the same values (the null-class half of a guided batch).
+ * fp32, any 4-byte alignment per buffer (16-byte accesses where all buffers in use share an offset inside a 16-byte line), no atomics, no
+ * memset, one writer per element.  fresh / known / noise / mask may not overlap an output. */
+int eegldm_edit_jump(eegldm_ctx*, const float* x, float jump_x, float jump_n, const float* fresh, uint64_t seed, uint64_t offset,
+                     const float* known, const float* noise, const float* mask, float a_level, float* out, float* out2, long n);
+/* eegldm_sample_edit / eegldm_sample_long_edit with the resampling block.  All host arrays hold ONE ENTRY PER FORWARD (n_steps forwards:
+ * schedulers.resample_tables); jump_x_host / jump_n_host describe the jump in front of each forward, (0, 0) = none.  At the top of
+ * iteration i with jump_n_host[i] != 0 the loop makes one eegldm_edit_jump launch (x in place, out2 = the null-class half when guided,
+ * a_level = a_t_host[i], fresh = NULL, seed = noise_seed, offset = jump_index * ((n + 3) / 4), jump_index counting the call's jumps from
+ * 0); on the canvas the jump runs on the n = R C Lc canvas elements and an eegldm_canvas_gather rewrites the window rows.  The step
+ * behind a jump must not read the history: c1_host[i] == 0 there, and jump_n_host[0] == 0.  Needs known and mask.  jump_x_host ==
+ * jump_n_host == NULL: the predecessor export itself.  Everything else -- embedding table (one row per forward), eager launches or graph
+ * replay, decode -- is the predecessor's. */
+int eegldm_sample_edit_resample(eegldm_unet*, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                                const int64_t* timesteps_host, const float* a_t_host, const float* a_prev_host, const float* cx_host,
+                                const float* c0_host, const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
+                                float inv_scale_factor, const float* jump_x_host, const float* jump_n_host, uint64_t noise_seed,
+                                float* latents_out, float* windows_out, int B, int L, int use_graph, int* graph_used_host,
+                                const int64_t* labels_host, float guidance_scale, int64_t null_class);
+int eegldm_sample_long_edit_resample(eegldm_unet*, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                                     const int64_t* timesteps_host, const float* a_t_host, const float* cx_host, const float* c0_host,
+                                     const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
+                                     float inv_scale_factor, const float* jump_x_host, const float* jump_n_host, uint64_t noise_seed,
+                                     float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
+                                     int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class);
 
 /* ------------------------------------------------------------------ data-parallel collectives (RCCL over xGMI)
  * One communicator per process / GPU.  Stands where the reference gathers gradients with single-process nn.DataParallel

@@ -167,6 +167,13 @@ SIGNATURES = {
     "eegldm_sample_long_edit": [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f),
                                 C.POINTER(_f), _i, _i, _i, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_int64), _f,
                                 C.c_int64],
+    "eegldm_edit_jump": [_vp, _vp, _f, _f, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _f, _vp, _vp, _l],
+    "eegldm_sample_edit_resample": [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f),
+                                    C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _f, C.POINTER(_f), C.POINTER(_f), C.c_uint64, _vp, _vp, _i, _i, _i,
+                                    C.POINTER(_i), C.POINTER(C.c_int64), _f, C.c_int64],
+    "eegldm_sample_long_edit_resample": [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f),
+                                         C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _f, C.POINTER(_f), C.POINTER(_f), C.c_uint64, _vp, _vp, _i, _i,
+                                         _i, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_int64), _f, C.c_int64],
     "eegldm_disc_create": [_vp, _vp, C.POINTER(_vp)],
     "eegldm_disc_destroy": [_vp],
     "eegldm_disc_num_entries": [_vp],

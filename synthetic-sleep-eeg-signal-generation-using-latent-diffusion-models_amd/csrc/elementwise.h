@@ -40,4 +40,30 @@ inline int grid_vec(long n, long head, eegldm_ctx* ctx) {
   if (blocks < 1) blocks = 1;
   return (int)(blocks < cap ? blocks : cap);
 }
+
+// ------------------------------------------------------------------ Philox4x32-10 (perf-path RNG; parity runs pass noise in)
+__device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3, unsigned k0, unsigned k1) {
+  const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+  const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+  c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+}
+__device__ __forceinline__ void philox(unsigned long long seed, unsigned long long ctr, unsigned r[4]) {
+  unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0, c3 = 0;
+  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+  for (int i = 0; i < 10; i++) { philox_round(c0, c1, c2, c3, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+// the four N(0, 1) values of counter `ctr`: Box-Muller on the word pairs (0, 1) and (2, 3).  ONE function for randn_kernel and for the draw
+// inside edit_jump_kernel (sampler_steps.hip), so that value e of a stream is the same bits wherever it is formed.
+__device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned long long ctr, float z[4]) {
+  unsigned r[4]; philox(seed, ctr, r);
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const float u1 = ((float)r[2 * h] + 1.0f) * 2.3283064365386963e-10f;   // (0,1]
+    const float u2 = (float)r[2 * h + 1] * 2.3283064365386963e-10f;
+    const float rad = sqrtf(-2.0f * logf(u1));
+    z[2 * h] = rad * cosf(6.283185307179586f * u2); z[2 * h + 1] = rad * sinf(6.283185307179586f * u2);
+  }
+}
 }  // namespace

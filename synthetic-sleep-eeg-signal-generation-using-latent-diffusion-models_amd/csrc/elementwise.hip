@@ -545,31 +545,11 @@ __global__ __launch_bounds__(NT) void swap_kernel(float* __restrict__ a, float* 
   GRID_STRIDE(j, s.nedge) { const long i = EDGE_INDEX(s, j); const float av = a[i], bv = b[i]; a[i] = bv; b[i] = av; }
 }
 
-// ------------------------------------------------------------------ Philox4x32-10 (perf-path RNG; parity runs pass noise in)
-__device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3, unsigned k0, unsigned k1) {
-  const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-  const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-  c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-}
-__device__ __forceinline__ void philox(unsigned long long seed, unsigned long long ctr, unsigned r[4]) {
-  unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0, c3 = 0;
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-  for (int i = 0; i < 10; i++) { philox_round(c0, c1, c2, c3, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
+// ------------------------------------------------------------------ Philox4x32-10 (elementwise.h; perf-path RNG; parity runs pass noise in)
 __global__ void randn_kernel(float* __restrict__ out, long n, unsigned long long seed, unsigned long long offset) {
   const long nq = (n + 3) / 4;
   GRID_STRIDE(i, nq) {
-    unsigned r[4]; philox(seed, offset + (unsigned long long)i, r);
-    float z[4];
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const float u1 = ((float)r[2 * h] + 1.0f) * 2.3283064365386963e-10f;   // (0,1]
-      const float u2 = (float)r[2 * h + 1] * 2.3283064365386963e-10f;
-      const float rad = sqrtf(-2.0f * logf(u1));
-      z[2 * h] = rad * cosf(6.283185307179586f * u2); z[2 * h + 1] = rad * sinf(6.283185307179586f * u2);
-    }
+    float z[4]; philox_normal4(seed, offset + (unsigned long long)i, z);
 #pragma unroll
     for (int k = 0; k < 4; k++) if (i * 4 + k < n) out[i * 4 + k] = z[k];
   }

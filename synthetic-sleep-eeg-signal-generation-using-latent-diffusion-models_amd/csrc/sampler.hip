@@ -91,18 +91,24 @@ struct EditBlock { const float *known, *mask, *a_next; };
 // lg and ed together (eegldm_sample_long_edit): known / mask are canvas-shaped, the canvas starts as `known` noised to a_t[0] with `noise`,
 // and every step is one eegldm_canvas_edit_step launch (the canvas step and the blend; mask NULL: the canvas step alone).
 struct LongBlock { int R, W, m, r; float *canvas_out, *recording_out; };
+// rs (eegldm_sample_edit_resample / eegldm_sample_long_edit_resample; NULL otherwise; needs ed with a mask -- resample_preamble checks
+// that, both jump arrays and the entries behind a jump before the block is built): every host array holds one
+// entry per FORWARD, and in front of the forwards with jump_n[i] != 0 one eegldm_edit_jump launch takes x -- the canvas, then a gather --
+// back up to the level a_t[i] with noise drawn inside the kernel: Philox key `seed`, jump k of the call at offset k * ceil(elements / 4).
+// The hist buffers are not cleared: c1[i] == 0 behind a jump keeps the step from reading them.
+struct ResampleBlock { const float *jump_x, *jump_n; uint64_t seed; };
 // One call of the loop.  The exports fill the leading members in the order of their own argument lists and name the rest.
 struct SampleCall {
   eegldm_unet* u; eegldm_aekl* ae; const float* noise; const int64_t* timesteps; const float* a_t; int n_steps, pred_type, clip_sample;
   float inv_scale_factor; float *latents_out, *windows_out; int B, L, use_graph; int* graph_used; const int64_t* labels; float guidance_scale;
   int64_t null_class;
   const float *a_prev = nullptr, *beta_t = nullptr; int ancestral = 0; uint64_t noise_seed = 0;      // the DDIM / DDPM step
-  const MultistepCoef* ms = nullptr; const EditBlock* ed = nullptr; const LongBlock* lg = nullptr;
+  const MultistepCoef* ms = nullptr; const EditBlock* ed = nullptr; const LongBlock* lg = nullptr; const ResampleBlock* rs = nullptr;
 };
 static int sample_impl(const SampleCall& q) {
   eegldm_unet* const u = q.u; eegldm_aekl* const ae = q.ae;
   const int B = q.B, L = q.L;
-  const MultistepCoef* const ms = q.ms; const EditBlock* const ed = q.ed; const LongBlock* const lg = q.lg;
+  const MultistepCoef* const ms = q.ms; const EditBlock* const ed = q.ed; const LongBlock* const lg = q.lg; const ResampleBlock* const rs = q.rs;
   EEG_CHECK(u && q.noise && q.timesteps && q.a_t && (q.a_prev || ms), "null argument");
   EEG_CHECK(!q.ancestral || q.beta_t, "the ancestral (DDPM) step needs beta_t");
   EEG_CHECK(q.n_steps >= 1 && B >= 1 && L >= 1, "bad sizes");
@@ -254,7 +260,19 @@ static int sample_impl(const SampleCall& q) {
   }
 
   const size_t row0 = cond ? (size_t)q.labels[0] : 0;
+  uint64_t jump_index = 0;
   for (int i = 0; i < q.n_steps; i++) {
+    if (rs && rs->jump_n[i] != 0.0f) {
+      if (lg) {
+        EEG_TRY(eegldm_edit_jump(ctx, s.canvas, rs->jump_x[i], rs->jump_n[i], nullptr, rs->seed, jump_index * (uint64_t)((ncv + 3) / 4), ed->known,
+                                 q.noise, ed->mask, q.a_t[i], s.canvas, nullptr, ncv));
+        EEG_TRY(eegldm_canvas_gather(ctx, s.canvas, lg->R, C, lg->W, L, Sl, s.x, guided ? s.x + n : nullptr));
+      } else {
+        EEG_TRY(eegldm_edit_jump(ctx, s.x, rs->jump_x[i], rs->jump_n[i], nullptr, rs->seed, jump_index * (uint64_t)((n + 3) / 4), ed->known, q.noise,
+                                 ed->mask, q.a_t[i], s.x, guided ? s.x + n : nullptr, n));
+      }
+      jump_index++;
+    }
     const float* step_rows = table ? s.emb_table + (size_t)i * Kt * etot : nullptr;
     if (mode == 2) EEG_TRY(ew_emb_gather(ctx, step_rows, s.lab, Kt, etot, s.emb_rows, Bf));
     else if (table && graph_ok) HIP_TRY(hipMemcpyAsync(s.emb_row, step_rows + row0 * etot, sizeof(float) * (size_t)etot, hipMemcpyDeviceToDevice, run));
@@ -433,5 +451,70 @@ extern "C" int eegldm_sample_long_edit(eegldm_unet* u, eegldm_aekl* ae, const fl
                graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
   q.ms = &ms; q.lg = &lg;
   if (known) q.ed = &ed;
+  return sample_impl(q);
+}
+
+// What the resampling exports check ahead of the loop (include/eegldm.h): both jump arrays, no jump in front of the first forward, no
+// history read behind a jump, and the known signal with its mask.
+static int resample_preamble(const float* jump_x_host, const float* jump_n_host, const float* c1_host, int n_steps, const float* known,
+                             const float* mask) {
+  EEG_CHECK(jump_x_host && jump_n_host, "jump_x_host and jump_n_host must both be NULL or both be set");
+  EEG_CHECK(known && mask, "resampling needs the known signal and the mask");
+  EEG_CHECK(n_steps >= 1, "bad sizes");
+  EEG_CHECK(jump_n_host[0] == 0.0f, "no jump can stand in front of the first forward (jump_n[0] = %g)", (double)jump_n_host[0]);
+  for (int i = 0; i < n_steps; i++) {
+    EEG_CHECK(jump_x_host[i] == jump_x_host[i] && jump_n_host[i] == jump_n_host[i], "jump coefficient %d is NaN", i);
+    EEG_CHECK(jump_n_host[i] == 0.0f || !c1_host || c1_host[i] == 0.0f, "the step behind the jump at entry %d has no history: c1 must be 0 (got %g)", i,
+              (double)c1_host[i]);
+  }
+  return 0;
+}
+
+// Resampled repair (include/eegldm.h): eegldm_sample_edit with one entry per forward and a jump in front of some of them.
+extern "C" int eegldm_sample_edit_resample(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                                           const int64_t* timesteps_host, const float* a_t_host, const float* a_prev_host, const float* cx_host,
+                                           const float* c0_host, const float* c1_host, const float* a_next_host, int n_steps, int pred_type,
+                                           int clip_sample, float inv_scale_factor, const float* jump_x_host, const float* jump_n_host,
+                                           uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
+                                           int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
+  if (!jump_x_host && !jump_n_host)
+    return eegldm_sample_edit(u, ae, noise, known, mask, timesteps_host, a_t_host, a_prev_host, cx_host, c0_host, c1_host, a_next_host, n_steps,
+                              pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph, graph_used_host, labels_host,
+                              guidance_scale, null_class);
+  EEG_TRY(sample_preamble(u, cx_host != nullptr, cx_host, c0_host, c1_host, n_steps, 1, 1, "the first executed step", labels_host, guidance_scale));
+  EEG_TRY(resample_preamble(jump_x_host, jump_n_host, cx_host ? c1_host : nullptr, n_steps, known, mask));
+  EEG_CHECK(cx_host || a_prev_host, "the DDIM form needs a_prev_host");
+  EEG_CHECK(!cx_host || a_next_host, "the multistep form needs a_next_host");
+  const MultistepCoef ms{cx_host, c0_host, c1_host};
+  const EditBlock ed{known, mask, a_next_host};
+  const ResampleBlock rs{jump_x_host, jump_n_host, noise_seed};
+  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph,
+               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
+  if (cx_host) q.ms = &ms; else q.a_prev = a_prev_host;
+  q.ed = &ed; q.rs = &rs;
+  return sample_impl(q);
+}
+
+// The same on the canvas: eegldm_sample_long_edit with one entry per forward.
+extern "C" int eegldm_sample_long_edit_resample(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                                                const int64_t* timesteps_host, const float* a_t_host, const float* cx_host, const float* c0_host,
+                                                const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
+                                                float inv_scale_factor, const float* jump_x_host, const float* jump_n_host, uint64_t noise_seed,
+                                                float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
+                                                int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
+  if (!jump_x_host && !jump_n_host)
+    return eegldm_sample_long_edit(u, ae, noise, known, mask, timesteps_host, a_t_host, cx_host, c0_host, c1_host, a_next_host, n_steps, pred_type,
+                                   clip_sample, inv_scale_factor, canvas_out, recording_out, R, W, L, m, r, use_graph, graph_used_host, labels_host,
+                                   guidance_scale, null_class);
+  EEG_CHECK(a_next_host, "the run from an input needs a_next_host");
+  EEG_TRY(sample_preamble(u, true, cx_host, c0_host, c1_host, n_steps, R, W, "the first executed step", labels_host, guidance_scale));
+  EEG_TRY(resample_preamble(jump_x_host, jump_n_host, c1_host, n_steps, known, mask));
+  const MultistepCoef ms{cx_host, c0_host, c1_host};
+  const EditBlock ed{known, mask, a_next_host};
+  const LongBlock lg{R, W, m, r, canvas_out, recording_out};
+  const ResampleBlock rs{jump_x_host, jump_n_host, noise_seed};
+  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, nullptr, nullptr, R * W, L, use_graph,
+               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
+  q.ms = &ms; q.lg = &lg; q.ed = &ed; q.rs = &rs;
   return sample_impl(q);
 }

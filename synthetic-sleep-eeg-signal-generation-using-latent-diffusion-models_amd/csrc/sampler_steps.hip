@@ -215,6 +215,64 @@ __global__ __launch_bounds__(NT) void edit_start_kernel(const float* __restrict_
     if (xo) xo[i] = edit_renoise(z, noise[i], ka, kb);
   }
 }
+// ------------------------------------------------------------------ resampled repair: the jump back up the noise schedule (include/eegldm.h)
+// p = jx x + jn eps -- contraction off and the fma spelled out, as multistep_update -- then, with BLEND, the blend of the step towards the
+// known signal noised to the level the jump lands on, so the kept positions hold k(a_level) bit for bit after a jump as after a step.
+__device__ __forceinline__ float jump_update(float x, float eps, float jx, float jn) {
+#pragma clang fp contract(off)
+  return fmaf(jx, x, jn * eps);
+}
+// word e & 3 of the quad of counter e >> 2: the value eegldm_randn writes to out[e]
+__device__ __forceinline__ float jump_draw1(unsigned long long seed, unsigned long long offset, long e) {
+  float z[4]; philox_normal4(seed, offset + (unsigned long long)(e >> 2), z);
+  const int k = (int)(e & 3);
+  return k == 0 ? z[0] : (k == 1 ? z[1] : (k == 2 ? z[2] : z[3]));
+}
+// DRAW: eps[e] is drawn in registers -- a function of (seed, offset, e) alone, whatever the pointers' alignment, the body / edge split and
+// the grid; else eps = fresh.  A float4 of the body starts at element head + 4 i: with head & 3 == 0 it is one quad, otherwise the thread
+// evaluates the two quads its four elements straddle and takes words sh .. sh + 3 of the eight (sh is uniform: the selects are static).
+// out may be x itself (every element is read before it is written, by the same thread); out2 is optional.
+template <bool DRAW, bool BLEND>
+__global__ __launch_bounds__(NT) void edit_jump_kernel(const float* x, float jx, float jn, const float* __restrict__ fresh, unsigned long long seed,
+                                                       unsigned long long offset, const float* __restrict__ known, const float* __restrict__ noise,
+                                                       const float* __restrict__ mask, float ka, float kb, float* out, float* out2, long n,
+                                                       long head) {
+  const VecSplit s = vec_split(n, head);
+  const f32x4* x4 = (const f32x4*)(x + head); const f32x4* f4 = (const f32x4*)(fresh + head);
+  const f32x4* k4 = (const f32x4*)(known + head); const f32x4* n4 = (const f32x4*)(noise + head); const f32x4* m4 = (const f32x4*)(mask + head);
+  f32x4* q1 = (f32x4*)(out + head); f32x4* q2 = (f32x4*)(out2 + head);
+  const int sh = (int)(head & 3);
+  const unsigned long long quad0 = offset + (unsigned long long)(head >> 2);
+  GRID_STRIDE(i, s.n4) {
+    const f32x4 xv = x4[i];
+    f32x4 ev, pv;
+    if (DRAW) {
+      float za[4], zb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      philox_normal4(seed, quad0 + (unsigned long long)i, za);
+      if (sh != 0) philox_normal4(seed, quad0 + (unsigned long long)i + 1ull, zb);
+      if (sh == 0) { ev[0] = za[0]; ev[1] = za[1]; ev[2] = za[2]; ev[3] = za[3]; }
+      else if (sh == 1) { ev[0] = za[1]; ev[1] = za[2]; ev[2] = za[3]; ev[3] = zb[0]; }
+      else if (sh == 2) { ev[0] = za[2]; ev[1] = za[3]; ev[2] = zb[0]; ev[3] = zb[1]; }
+      else { ev[0] = za[3]; ev[1] = zb[0]; ev[2] = zb[1]; ev[3] = zb[2]; }
+    } else ev = f4[i];
+#pragma unroll
+    for (int k = 0; k < 4; k++) pv[k] = jump_update(xv[k], ev[k], jx, jn);
+    if (BLEND) {
+      const f32x4 kv = k4[i], nv = n4[i], mv = m4[i];
+#pragma unroll
+      for (int k = 0; k < 4; k++) pv[k] = edit_blend(mv[k], edit_renoise(kv[k], nv[k], ka, kb), pv[k]);
+    }
+    q1[i] = pv;
+    if (out2) q2[i] = pv;
+  }
+  GRID_STRIDE(j, s.nedge) {
+    const long i = EDGE_INDEX(s, j);
+    float p = jump_update(x[i], DRAW ? jump_draw1(seed, offset, i) : fresh[i], jx, jn);
+    if (BLEND) p = edit_blend(mask[i], edit_renoise(known[i], noise[i], ka, kb), p);
+    out[i] = p;
+    if (out2) out2[i] = p;
+  }
+}
 // Window side of an edit: (1) the keep-mask at the sampler's resolution, mask_lat[b][c][l] = min over the `down` window samples latent
 // position l covers (every one of the C channels receives the same row); (2) the composite out = blend(mask_win, input, decoded) over
 // Co channels.  Either half may be left out (mask_lat / out NULL).  One-off work of a sampling call: scalar accesses, any alignment.
@@ -600,6 +658,34 @@ extern "C" int eegldm_edit_start(eegldm_ctx* ctx, const float* z_mu, float scale
   const float a = x_start ? a_start : 1.0f;
   hipLaunchKernelGGL(edit_start_kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, z_mu, scale_factor, noise, sqrtf(a), sqrtf(1.0f - a),
                      z0, x_start, n, head);
+  LAUNCH_CHECK(); return 0;
+}
+// the jump of a resampled repair: one launch of edit_jump_kernel<draw in registers, blend>; the checks follow flat_step_launch
+extern "C" int eegldm_edit_jump(eegldm_ctx* ctx, const float* x, float jump_x, float jump_n, const float* fresh, uint64_t seed, uint64_t offset,
+                                const float* known, const float* noise, const float* mask, float a_level, float* out, float* out2, long n) {
+  EEG_CHECK(ctx && x && out, "null argument");
+  EEG_CHECK(n >= 0, "negative n (%ld)", n);
+  EEG_CHECK(jump_x == jump_x && jump_n == jump_n, "a coefficient is NaN");
+  EEG_CHECK(a_level > 0.0f && a_level <= 1.0f, "a_level %g outside (0, 1]", (double)a_level);
+  EEG_CHECK(!mask || (known && noise), "a mask needs the known signal and the noise");
+  // (out == x is the one aliasing the kernel is written for)
+  EEG_CHECK(out == x || !ov(out, n, x, n), "out may be x itself, not a shifted view of it");
+  EEG_CHECK(!ov(out2, n, out, n) && !ov(out2, n, x, n), "out2 aliases another buffer");
+  EEG_CHECK(!ov(fresh, n, out, n) && !ov(fresh, n, out2, n), "fresh aliases an output buffer");
+  if (mask)
+    for (const float* q : {known, noise, mask}) EEG_CHECK(!ov(q, n, out, n) && !ov(q, n, out2, n), "known / noise / mask alias an output buffer");
+  for (const void* q : {(const void*)x, (const void*)fresh, (const void*)out, (const void*)out2, (const void*)(mask ? known : nullptr),
+                        (const void*)(mask ? noise : nullptr), (const void*)mask})
+    EEG_CHECK(((uintptr_t)q & 3) == 0, "buffers must be 4-byte aligned");
+  if (n == 0) return 0;
+  long head = vec_head(n, {x, out});
+  for (const void* q : {(const void*)fresh, (const void*)out2, (const void*)(mask ? known : nullptr), (const void*)(mask ? noise : nullptr),
+                        (const void*)mask})
+    if (q && head < n && ((uintptr_t)q & 15) != ((uintptr_t)x & 15)) head = n;
+  auto kernel = fresh ? (mask ? edit_jump_kernel<false, true> : edit_jump_kernel<false, false>)
+                      : (mask ? edit_jump_kernel<true, true> : edit_jump_kernel<true, false>);
+  hipLaunchKernelGGL(kernel, dim3(grid_vec(n, head, ctx)), dim3(NT), 0, ctx->stream, x, jump_x, jump_n, fresh, (unsigned long long)seed,
+                     (unsigned long long)offset, known, noise, mask, sqrtf(a_level), sqrtf(1.0f - a_level), out, out2, n, head);
   LAUNCH_CHECK(); return 0;
 }
 extern "C" int eegldm_edit_window(eegldm_ctx* ctx, const float* mask_win, int B, int Lw, int down, int C, float* mask_lat, const float* input,

@@ -10,7 +10,9 @@ LATENT keep-mask by E samples beside every regenerated span (default 0; no value
 uses the mask as given.  --no_composite returns the decoded recording instead of input-where-kept.
 Writes edit_long_{seed}.npy ((R, 1, samples), crop off both ends), edit_long_{seed}_mask.npy (the mask used, same shape; all zeros when
 nothing was kept), edit_long_{seed}_labels.npy (class-conditional UNet only) and edit_long_{seed}_layout.json (sample_long.py's layout
-file plus input_samples / left_out / kept_windows: what tools/seam_report.py reads)."""
+file plus input_samples / left_out / kept_windows: what tools/seam_report.py reads).  --resamples R --jump_length J (defaults 1 and 1: the
+plain repair; needs something kept, i.e. a mask or an extension): RePaint's resampling as in edit_trials.py, fresh noise from the Philox key
+schedulers.RESAMPLE_KEY + --seed; with R > 1 the layout file gains {"resamples", "jump_length", "forwards"}."""
 import argparse
 import json
 import math
@@ -56,6 +58,8 @@ def parse_args(argv=None):
     p.add_argument("--use_ema", action="store_true", help="sample from best_model_ema.pth (a run trained with --ema_decay) instead of best_model.pth")
     p.add_argument("--sampler", default="dpmpp_2m", choices=["dpmpp_2m"], help="the canvas step is the multistep form; --solver_order 1 is DDIM")
     p.add_argument("--solver_order", type=int, default=2, choices=[1, 2])
+    p.add_argument("--resamples", type=int, default=1, help="RePaint resampling: visits of every jump point (1 = none); needs a mask or an extension")
+    p.add_argument("--jump_length", type=int, default=1, help="steps a jump goes back up, and the spacing of the jump points")
     return p.parse_args(argv)
 
 
@@ -64,6 +68,10 @@ def check_args(args):
         raise ValueError("--strength must lie in (0, 1]")
     if args.mask_erode < 0:
         raise ValueError("--mask_erode must be >= 0")
+    if args.resamples < 1 or args.jump_length < 1:
+        raise ValueError("--resamples and --jump_length must be >= 1")
+    if args.resamples > 1 and args.mask is None and not args.mask_span and not args.extend_minutes > 0:
+        raise ValueError("--resamples > 1 needs --mask, --mask_span or --extend_minutes")
     if not args.extend_minutes >= 0:
         raise ValueError("--extend_minutes must be >= 0")
     if args.hypnogram is not None and args.class_label is not None:
@@ -202,17 +210,20 @@ def main(args):
     sched = make_sampling_scheduler(args.num_inference_steps, prediction_type=args.prediction_type, device=local, sampler="dpmpp_2m",
                                     solver_order=args.solver_order)
     noise = randn(unet.ctx, (R, unet.in_channels, lay.canvas_len), seed=args.seed)
+    info = {}
     rec, _canvas = sample_long(unet, stage1, sched, noise, lay.n_windows, margin=lay.margin, ramp=lay.ramp, scale_factor=scale_factor, crop=CROP,
                                labels=labels, guidance_scale=args.guidance_scale if guided else 1.0, null_class=args.null_class if guided else None,
                                init=torch.from_numpy(init), strength=args.strength, mask=None if mk is None else torch.from_numpy(mk),
-                               composite=False if (args.no_composite or mk is None) else None, mask_erode=args.mask_erode)
+                               composite=False if (args.no_composite or mk is None) else None, mask_erode=args.mask_erode,
+                               resamples=args.resamples, jump_length=args.jump_length, seed=args.seed, info=info)
     np.save(os.path.join(out, f"edit_long_{args.seed}.npy"), rec.cpu().numpy())
     used_mask = np.zeros_like(init) if mk is None else mk
     np.save(os.path.join(out, f"edit_long_{args.seed}_mask.npy"), used_mask[:, :, CROP:-CROP])
     if labels is not None:
         np.save(os.path.join(out, f"edit_long_{args.seed}_labels.npy"), labels)
     with open(os.path.join(out, f"edit_long_{args.seed}_layout.json"), "w") as f:
-        json.dump(dict(layout_json(lay, down), input_samples=n, left_out=plan["left_out"], kept_windows=plan["kept_windows"]), f)
+        extra = dict(resamples=args.resamples, jump_length=args.jump_length, forwards=info["forwards"]) if args.resamples > 1 else {}
+        json.dump(dict(layout_json(lay, down), input_samples=n, left_out=plan["left_out"], kept_windows=plan["kept_windows"], **extra), f)
     return out
 
 

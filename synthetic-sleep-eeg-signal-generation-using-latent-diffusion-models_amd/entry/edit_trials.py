@@ -5,8 +5,13 @@ window i is noised with the N(0, 1) draw of seed --seed + i up to --strength of 
 ((3072,), (N, 3072) or (N, 1, 3072), values in [0, 1], 1 = keep) and / or --mask_span START:STOP (window samples START .. STOP - 1 are
 regenerated; may be repeated) select what is replaced; the kept samples come back bit for bit unless --no_composite.  Writes
 edit_{i}.npy of shape (1, 1, 3000) (crop [36:-36], as sample_{i}.npy) and, when a mask was used, edit_{i}_mask.npy: the keep-mask of
-the same shape.  Windows are batched and sharded over ranks (no collective)."""
+the same shape.  --resamples R --jump_length J (defaults 1 and 1: the plain repair; needs a mask): RePaint's resampling, R - 1 jumps of
+J steps back up the schedule at every J-th level, each with fresh noise from the Philox key schedulers.RESAMPLE_KEY + --seed + (index of
+the call's first window), so that no two calls -- batches or ranks -- share their jump noise (a window's result is reproducible for a given
+--batch and world size; its position inside the call decides which part of the stream it reads); the cost is the forward count, and with R > 1 edit_{i}_resample.json records {"resamples", "jump_length", "forwards"}.  J = 1 is a convention: no
+(R, J) has been measured on sleep data.  Windows are batched and sharded over ranks (no collective)."""
 import argparse
+import json
 import os
 
 import numpy as np
@@ -47,12 +52,18 @@ def parse_args(argv=None):
     p.add_argument("--use_ema", action="store_true", help="sample from best_model_ema.pth (a run trained with --ema_decay) instead of best_model.pth")
     p.add_argument("--sampler", default="ddim", choices=["ddim", "dpmpp_2m"])
     p.add_argument("--solver_order", type=int, default=2, choices=[1, 2], help="dpmpp_2m only")
+    p.add_argument("--resamples", type=int, default=1, help="RePaint resampling: visits of every jump point (1 = none); needs a mask")
+    p.add_argument("--jump_length", type=int, default=1, help="steps a jump goes back up, and the spacing of the jump points")
     return p.parse_args(argv)
 
 
 def check_args(args):
     if not 0.0 < args.strength <= 1.0:
         raise ValueError(f"--strength must lie in (0, 1], got {args.strength}")
+    if args.resamples < 1 or args.jump_length < 1:
+        raise ValueError("--resamples and --jump_length must be >= 1")
+    if args.resamples > 1 and args.mask is None and not args.mask_span:
+        raise ValueError("--resamples > 1 needs --mask or --mask_span")
     if args.pixel:
         if not args.config_file:
             raise ValueError("--pixel needs --config_file")
@@ -146,15 +157,20 @@ def main(args):
         for j, i in enumerate(idx):
             noise[j] = randn(unet.ctx, (lat, latent_len), seed=args.seed + i)
         m = None if keep is None else torch.from_numpy(keep[idx[0]:idx[-1] + 1])
+        info = {}
         windows, _ = sample(unet, stage1, sched, noise, scale_factor=scale_factor, labels=None if labels is None else labels[idx[0]:idx[-1] + 1],
                             guidance_scale=args.guidance_scale if guided else 1.0, null_class=args.null_class if guided else None,
                             init=torch.from_numpy(x_in[idx[0]:idx[-1] + 1]), strength=args.strength, mask=m,
-                            composite=False if args.no_composite else None)
+                            composite=False if args.no_composite else None, resamples=args.resamples, jump_length=args.jump_length,
+                            seed=args.seed + idx[0], info=info)
         arr = windows.cpu().numpy()
         for j, i in enumerate(idx):
             np.save(os.path.join(out, f"edit_{i}.npy"), arr[j:j + 1])
             if keep is not None:
                 np.save(os.path.join(out, f"edit_{i}_mask.npy"), keep[i:i + 1, :, 36:-36])
+            if args.resamples > 1:
+                with open(os.path.join(out, f"edit_{i}_resample.json"), "w") as f:
+                    json.dump(dict(resamples=args.resamples, jump_length=args.jump_length, forwards=info["forwards"]), f)
     return out
 
 

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from ._lib import lib, check, ptr, PRED
-from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, scheduler_edit_tables
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, RESAMPLE_KEY, scheduler_edit_tables, scheduler_resample_tables
 from .training import randn
 
 
@@ -123,6 +123,31 @@ def _edit_args(autoencoder, scheduler, shape, init, strength, mask, composite, l
     return dict(tab=tab, composite=(mask is not None and init is not None) if composite is None else bool(composite))
 
 
+def _resample_args(scheduler, edit, mask, resamples, jump_length):
+    """Checks resamples / jump_length on the host, before anything runs -> None for resamples == 1 (the calls made without the keywords),
+    else the tables of schedulers.resample_tables, one entry per forward."""
+    if int(resamples) != resamples or int(jump_length) != jump_length or resamples < 1 or jump_length < 1:
+        raise ValueError(f"resamples and jump_length must be integers >= 1 (got {resamples}, {jump_length})")
+    if resamples == 1:
+        return None
+    if edit is None or mask is None:
+        raise ValueError("resamples > 1 needs init (or latents) and mask: resampling reconciles a regenerated span with a kept one")
+    return scheduler_resample_tables(scheduler, edit["tab"], resamples, jump_length)
+
+
+def _blend(mk, k, p):
+    """m == 0: p, m == 1: k, else fma(m, k, (1 - m) * p) -- the library's edit_blend"""
+    return torch.where(mk == 0, p, torch.where(mk == 1, k, _fma32(mk, k, (1.0 - mk) * p)))
+
+
+def _jump(ctx, x, z0, nz, m_lat, rt, i, jump_index, seed):
+    """The jump in front of forward i of a resampled run, composed in torch with the library's roundings: eps from the Philox stream
+    RESAMPLE_KEY + seed at offset jump_index * ceil(n / 4), p = fma(jump_x, x, jump_n * eps), then the blend towards k(a_t[i])."""
+    eps = randn(ctx, tuple(x.shape), RESAMPLE_KEY + int(seed), jump_index * ((x.numel() + 3) // 4))
+    p = _fma32(rt["jump_x"][i], x, eps * rt["jump_n"][i])
+    return _blend(m_lat, _renoise(z0, nz, rt["a_t"][i]), p)
+
+
 def _encode_windows(unet, autoencoder, init_d, scale_factor, native):
     """scale_factor * the posterior mean of the encoded windows (no reparameterisation draw)"""
     z_mu, _sigma = autoencoder.encode(init_d)
@@ -165,7 +190,8 @@ def _edit_inputs(unet, autoencoder, x, init, mask, latents, encode, mask_erode=0
 
 @torch.no_grad()
 def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, use_graph=None, seed=0, info=None, labels=None,
-                guidance_scale=1.0, null_class=None, init=None, strength=1.0, mask=None, composite=None, init_latents=None):
+                guidance_scale=1.0, null_class=None, init=None, strength=1.0, mask=None, composite=None, init_latents=None, resamples=1,
+                jump_length=1):
     """noise (B, lat, Ll) on the device -> (windows (B, out, 3072 - 2*crop), final latents).  ONE native call
     (eegldm_sample): the scheduler loop, z / scale_factor and the decode run inside the library.  The UNet forward CAN be
     replayed from a hipGraph (use_graph=True or EEGLDM_SAMPLE_GRAPH=1) but that is no longer the default: measured on
@@ -183,8 +209,15 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     nothing else is drawn.  mask ((B, 1, window length), 1 = keep) regenerates only the samples marked 0: after every step the kept region
     is reset to z0 noised to that step's level (inside the step's kernel); a latent position is kept only if all the window samples it
     covers are.  composite (default: on with mask and init) returns mask * init + (1 - mask) * decoded windows, kept samples bit for bit.
-    The ancestral DDPMScheduler, mask without init and strength outside (0, 1] are refused."""
+    The ancestral DDPMScheduler, mask without init and strength outside (0, 1] are refused.
+    resamples = r > 1 (needs init and mask) is RePaint's resampling (eegldm_sample_edit_resample): at the levels l in range(0, n_run - j, j)
+    (l = steps still to run, j = jump_length) the run goes back up j levels in one jump, x <- sqrt(rho) x + sqrt(1 - rho) eps with FRESH
+    noise drawn inside the jump's kernel (Philox key schedulers.RESAMPLE_KEY + seed; the kept part stays k(a) of the call's one noise
+    tensor), and comes down again, r - 1 times per level: n_run + (r - 1) j len(range(0, n_run - j, j)) forwards in all, which is the cost.
+    The step behind a jump is first order.  jump_length = 1 is a convention; no (resamples, jump_length) has been measured on sleep data.
+    info also receives {"forwards": the number of forwards}."""
     edit = _edit_args(autoencoder, scheduler, noise.shape, init, strength, mask, composite, init_latents)
+    rt = _resample_args(scheduler, edit, mask, resamples, jump_length)
     unet.eval()
     x = noise.to(unet.device, torch.float32).contiguous()
     B, Cc, L = x.shape
@@ -193,7 +226,7 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     lab, nc = _labels_host(unet, labels, B, guidance_scale, null_class)
     multistep = isinstance(scheduler, DPMSolverMultistepScheduler)
     if edit is not None:
-        tab = edit["tab"]
+        tab = edit["tab"] if rt is None else rt
         ts, a_t = tab["timesteps"], tab["a_t"]
     elif multistep:
         ts, a_t, cx, c0, c1 = _multistep_tables(scheduler)
@@ -217,9 +250,13 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
                                                 lambda w, native: _encode_windows(unet, autoencoder, w, scale_factor, native))
         nul = C.POINTER(C.c_float)()
         coef = (f32(tab["cx"]), f32(tab["c0"]), f32(tab["c1"])) if multistep else (nul, nul, nul)
-        check(lib.eegldm_sample_edit(unet.h, ae_h, ptr(x), ptr(z0), ptr(m_lat), i64(ts), f32(a_t), nul if multistep else f32(tab["a_prev"]), *coef,
-                                     f32(tab["a_next"]), n, PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor),
-                                     *tail, None if lab is None else i64(lab), float(guidance_scale), nc))
+        front = (unet.h, ae_h, ptr(x), ptr(z0), ptr(m_lat), i64(ts), f32(a_t), nul if multistep else f32(tab["a_prev"]), *coef,
+                 f32(tab["a_next"]), n, PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor))
+        back = (*tail, None if lab is None else i64(lab), float(guidance_scale), nc)
+        if rt is None:
+            check(lib.eegldm_sample_edit(*front, *back))
+        else:
+            check(lib.eegldm_sample_edit_resample(*front, f32(rt["jump_x"]), f32(rt["jump_n"]), RESAMPLE_KEY + int(seed), *back))
         if edit["composite"]:
             check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_win), B, L * down, down, 0, None, ptr(init_d), ptr(win), out_c, ptr(win)))
     elif multistep:
@@ -237,7 +274,7 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     if autoencoder is not None:
         autoencoder._bump_tape()
     if info is not None:
-        info["graph"] = bool(used.value)
+        info["graph"], info["forwards"] = bool(used.value), n
     return (win[:, :, crop:-crop] if crop else win), lat
 
 
@@ -246,14 +283,17 @@ sample = ddim_sample      # the neutral name: the sampler is whatever `scheduler
 
 @torch.no_grad()
 def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, labels=None, guidance_scale=1.0, null_class=None,
-                         init=None, strength=1.0, mask=None, composite=None, init_latents=None):
+                         init=None, strength=1.0, mask=None, composite=None, init_latents=None, resamples=1, jump_length=1, seed=0):
     """The same loop driven from Python, one scheduler.step call per timestep (what round 1 shipped; kept as the
     reference composition the native sampler is tested against, and for schedulers the native loop does not know).
     Class-conditional: the UNet is called with the labels and, for guidance_scale != 1, a second time with null_class; the two
     outputs are mixed as out_u + w (out_c - out_u) ahead of scheduler.step.  init / strength / mask / composite / init_latents as in
     ddim_sample, composed from torch ops: the noised start, the blend m k + (1 - m) x after every scheduler.step, the min-pooled mask and
-    the composite."""
+    the composite.  resamples / jump_length / seed as in ddim_sample: the loop runs over the entries of schedulers.resample_tables; in front
+    of a forward with a jump it draws eps = training.randn(...) and forms the jump and its blend in torch (_jump), and the multistep
+    scheduler takes the step behind a jump with first_order=True."""
     edit = _edit_args(autoencoder, scheduler, noise.shape, init, strength, mask, composite, init_latents)
+    rt = _resample_args(scheduler, edit, mask, resamples, jump_length)
     unet.eval()
     x = noise.to(unet.device, torch.float32).contiguous()
     B = x.shape[0]
@@ -272,13 +312,20 @@ def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, 
         timesteps = tab["timesteps"]
         if isinstance(scheduler, DPMSolverMultistepScheduler):
             first = {"first_order": True}
+        if rt is not None:
+            tab, timesteps = rt, rt["timesteps"]
+    jumps = 0
     for j, t in enumerate(timesteps):
+        jumped = rt is not None and rt["jump_n"][j] != 0.0
+        if jumped:
+            x = _jump(unet.ctx, x, z0, nz, m_lat, rt, j, jumps, seed)
+            jumps += 1
         tt.fill_(int(t))
         out = unet(x, timesteps=tt, **kw)
         if lab is not None and w != 1.0:
             out_u = unet(x, timesteps=tt, y=null)
             out = out_u + w * (out - out_u)
-        x, _ = scheduler.step(out, int(t), x, **(first if j == 0 else {}))
+        x, _ = scheduler.step(out, int(t), x, **(first if j == 0 or jumped else {}))
         if edit is not None and m_lat is not None:
             x = m_lat * _renoise(z0, nz, tab["a_next"][j]) + (1.0 - m_lat) * x
     comp = (lambda win: m_win * init_d + (1.0 - m_win) * win) if edit is not None and edit["composite"] else (lambda win: win)
@@ -492,7 +539,7 @@ def encode_long(autoencoder, recording, layout, scale_factor=1.0, native=True):
 @torch.no_grad()
 def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ramp=None, scale_factor=1.0, crop=36, labels=None,
                 guidance_scale=1.0, null_class=None, use_graph=None, info=None, init=None, init_canvas=None, strength=1.0, mask=None,
-                composite=None, mask_erode=0):
+                composite=None, mask_erode=0, resamples=1, jump_length=1, seed=0):
     """noise (R, C, Lc) on the device -> (recording (R, out, down * Lc - 2 * crop), canvas (R, C, Lc)).  Overlapped-window sampling on one
     latent canvas (MultiDiffusion): the R * W overlapping slices of the canvases are the rows of ONE forward batch, and behind every
     forward ONE eegldm_canvas_step launch fuses the slices' data predictions with a partition-of-unity taper, takes the solver step on
@@ -514,10 +561,15 @@ def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ram
     the canvas keep-mask is taken from the mask with every kept region shrunk by e samples beside each regenerated span -- the encoder's
     receptive field contaminates the latents next to a regenerated or absent span -- while the composite uses the mask as given.  The
     default is 0; no other default is proposed and NO value has been measured against anything.  Continuing a recording: init = the real
-    samples followed by zeros, mask = 1 over the real samples and 0 beyond."""
+    samples followed by zeros, mask = 1 over the real samples and 0 beyond.
+    resamples / jump_length / seed: RePaint's resampling as in `sample` (eegldm_sample_long_edit_resample; needs init and mask): a jump is
+    ONE eegldm_edit_jump launch on the canvas, fresh noise from the Philox key schedulers.RESAMPLE_KEY + seed, and a gather.  The cost is
+    the forward count n_run + (r - 1) j len(range(0, n_run - j, j)); info also receives {"forwards"}.  jump_length = 1 is a convention; no
+    (resamples, jump_length) has been measured on sleep data."""
     lay, R, labels = _long_args(unet, autoencoder, scheduler, noise.shape, n_windows, margin, ramp, crop, labels)
     edit = _edit_args(autoencoder, scheduler, (R, int(noise.shape[1]), lay.canvas_len), init, strength, mask, composite, init_canvas,
                       _LONG_EDIT_WORDS, mask_erode)
+    rt = _resample_args(scheduler, edit, mask, resamples, jump_length)
     from .models import UNetModel
     if not isinstance(unet, UNetModel):
         raise TypeError("sample_long runs the native loop: unet must be a UNetModel")
@@ -537,26 +589,32 @@ def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ram
     rec = torch.empty(R, out_c, lay.canvas_len * down, device=unet.device, dtype=torch.float32)
     used = C.c_int(0)
     i64, f32 = (lambda v: (C.c_int64 * len(v))(*v)), (lambda v: (C.c_float * len(v))(*v))
-    tab = edit["tab"] if edit is not None else dict(timesteps=ts, a_t=a_t, cx=cx, c0=c0, c1=c1)
+    tab = (edit["tab"] if rt is None else rt) if edit is not None else dict(timesteps=ts, a_t=a_t, cx=cx, c0=c0, c1=c1)
     head = (unet.h, autoencoder.h if autoencoder is not None else None, ptr(x))
     coef = (f32(tab["cx"]), f32(tab["c0"]), f32(tab["c1"]))
-    tail = (len(tab["timesteps"]), PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor), ptr(canvas), ptr(rec),
+    sched = (len(tab["timesteps"]), PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor))
+    tail = (*sched, ptr(canvas), ptr(rec),
             R, W, L, lay.margin, lay.ramp, 1 if use_graph else 0, C.byref(used), None if lab is None else i64(lab), float(guidance_scale), nc)
     if edit is None:
         check(lib.eegldm_sample_long(*head, i64(tab["timesteps"]), f32(tab["a_t"]), *coef, *tail))
     else:
         z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_canvas,
                                                 lambda r, native: encode_long(autoencoder, r, lay, scale_factor, native=native), mask_erode)
-        check(lib.eegldm_sample_long_edit(*head, ptr(z0), ptr(m_lat), i64(tab["timesteps"]), f32(tab["a_t"]), *coef, f32(tab["a_next"]), *tail))
+        front = (*head, ptr(z0), ptr(m_lat), i64(tab["timesteps"]), f32(tab["a_t"]), *coef, f32(tab["a_next"]))
+        if rt is None:
+            check(lib.eegldm_sample_long_edit(*front, *tail))
+        else:
+            check(lib.eegldm_sample_long_edit_resample(*front, *sched, f32(rt["jump_x"]), f32(rt["jump_n"]), RESAMPLE_KEY + int(seed),
+                                                       *tail[len(sched):]))
         if edit["composite"]:
             check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_win), R, lay.canvas_len * down, down, 0, None, ptr(init_d), ptr(rec), out_c, ptr(rec)))
     unet._bump_tape()
     if autoencoder is not None:
         autoencoder._bump_tape()
     if info is not None:
-        info["graph"], info["layout"] = bool(used.value), lay
+        info["graph"], info["layout"], info["forwards"] = bool(used.value), lay, len(tab["timesteps"])
         if edit is not None:
-            info["n_run"] = len(tab["timesteps"])
+            info["n_run"] = len(edit["tab"]["timesteps"])
     return (rec[:, :, crop:-crop] if crop else rec), canvas
 
 
@@ -592,7 +650,7 @@ def _long_crossfade(rows, lay):
 @torch.no_grad()
 def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=None, ramp=None, scale_factor=1.0, crop=36, labels=None,
                          guidance_scale=1.0, null_class=None, use_graph=None, info=None, init=None, init_canvas=None, strength=1.0, mask=None,
-                         composite=None, mask_erode=0):
+                         composite=None, mask_erode=0, resamples=1, jump_length=1, seed=0):
     """The reference composition of sample_long in torch, none of the canvas kernels: slice the canvas, model(...) on all slices, the
     guidance mix, x0 from the scheduler's formulas, the taper of layout.weights (as a cross-fade of the two windows that carry weight),
     prev = cx x + c0 x0 + c1 hist on the canvas, then decode per window and cross-fade.  The float32 roundings are placed where the
@@ -600,10 +658,13 @@ def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=
     model(x, timesteps=, [y=]) with .device / .eval(); use_graph is accepted and ignored.
     init / init_canvas / strength / mask / composite / mask_erode as in sample_long (mask_erode defaults to 0; no other value has been
     measured against anything), composed from torch ops: the encode per window and its cross-fade, the noised start, the truncated
-    tables, the blend m k + (1 - m) x after every step with the library's roundings (_fma32), the min-pooled mask and the composite."""
+    tables, the blend m k + (1 - m) x after every step with the library's roundings (_fma32), the min-pooled mask and the composite.
+    resamples / jump_length / seed as in sample_long: the loop runs over the entries of schedulers.resample_tables (whose coefficients are
+    first order behind a jump) and forms each jump on the canvas in torch (_jump; the draw is training.randn on the scheduler's context)."""
     lay, R, labels = _long_args(unet, autoencoder, scheduler, noise.shape, n_windows, margin, ramp, crop, labels)
     edit = _edit_args(autoencoder, scheduler, (R, int(noise.shape[1]), lay.canvas_len), init, strength, mask, composite, init_canvas,
                       _LONG_EDIT_WORDS, mask_erode)
+    rt = _resample_args(scheduler, edit, mask, resamples, jump_length)
     unet.eval()
     dev = unet.device
     x = noise.to(dev, torch.float32).contiguous().clone()
@@ -616,20 +677,21 @@ def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=
     ts, a_t, cx, c0, c1 = _multistep_tables(scheduler)
     m_win = m_lat = init_d = None
     if edit is not None:
-        tab = edit["tab"]
+        tab = edit["tab"] if rt is None else rt
         ts, a_t, cx, c0, c1, a_next = (tab[k] for k in ("timesteps", "a_t", "cx", "c0", "c1", "a_next"))
         nz = x
         z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_canvas,
                                                 lambda r, native: encode_long(autoencoder, r, lay, scale_factor, native=native), mask_erode,
                                                 native=False)
-
-        def blend(mk, k, p):
-            """m == 0: p, m == 1: k, else fma(m, k, (1 - m) * p) -- the library's edit_blend"""
-            return torch.where(mk == 0, p, torch.where(mk == 1, k, _fma32(mk, k, (1.0 - mk) * p)))
+        blend = _blend
         x = _renoise(z0, nz, a_t[0]).clone()
     tt = torch.empty(R * W, device=dev, dtype=torch.int64)
     hist = None
+    jumps = 0
     for i, t in enumerate(ts):
+        if rt is not None and rt["jump_n"][i] != 0.0:
+            x = _jump(scheduler.ctx, x, z0, nz, m_lat, rt, i, jumps, seed)
+            jumps += 1
         tt.fill_(t)
         win = _slices_of(x, lay)
         out = unet(win, timesteps=tt, **kw).float()
@@ -643,7 +705,7 @@ def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=
         if m_lat is not None:
             x = blend(m_lat, _renoise(z0, nz, a_next[i]), x)
     if info is not None:
-        info["graph"], info["layout"] = False, lay
+        info["graph"], info["layout"], info["forwards"] = False, lay, len(ts)
     comp = (lambda rec: blend(m_win, init_d, rec)) if edit is not None and edit["composite"] else (lambda rec: rec)
     if autoencoder is None:
         rec = comp(x)

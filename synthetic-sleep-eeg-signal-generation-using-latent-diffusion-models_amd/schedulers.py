@@ -352,6 +352,87 @@ def scheduler_edit_tables(scheduler, strength):
                      f"not {type(scheduler).__name__}")
 
 
+# Philox key of the fresh noise of a resampled repair: the jumps of a call draw from key RESAMPLE_KEY + seed (jump k at offset
+# k * ceil(n / 4)), as the ancestral steps draw from 0x5EED + t / 0xD1D1 + t above.  The constant keeps the first jump's draw apart from a
+# start noise that a caller drew from key `seed` at offset 0 (entry/edit_trials.py --seed K: window i's start noise is key K + i).
+RESAMPLE_KEY = 0x7E9A1275
+
+
+def resample_forwards(n_run, resamples, jump_length):
+    """The number of forwards of a resampled run: n_run + (resamples - 1) * jump_length * len(range(0, n_run - jump_length, jump_length))."""
+    n, r, j = int(n_run), int(resamples), int(jump_length)
+    if r < 1 or j < 1:
+        raise ValueError(f"resamples and jump_length must be >= 1 (got {resamples}, {jump_length})")
+    if r == 1:
+        return n
+    if j >= n:
+        raise ValueError(f"jump_length {j} leaves no room for a jump in a run of {n} steps (needs jump_length < n_run)")
+    return n + (r - 1) * j * len(range(0, n - j, j))
+
+
+def resample_tables(tab, first_order, resamples, jump_length):
+    """The schedule of a resampled repair (RePaint, Lugmayr et al. 2022: the walk of its get_schedule_jump) as host arrays with ONE ENTRY
+    PER FORWARD.  tab: the dict of edit_tables / scheduler_edit_tables for the executed steps 0 .. n_run - 1; first_order: (cx1, c01), the
+    first-order coefficients of the same steps (None for the DDIM form).  -> the keys of tab, expanded, plus
+      step    the local step index s of each entry,
+      jump_x, jump_n   the jump IN FRONT OF the entry's forward, (0, 0) = none.
+    In levels (l = the number of steps still to run; n_run at the start, 0 on the final noise level): the jump points are
+    l in range(0, n_run - j, j), each with r - 1 jumps; the walk goes down one level per step, and on arriving at a jump point that has
+    jumps left it uses one up and goes back up j levels in ONE jump, x <- sqrt(rho) x + sqrt(1 - rho) eps with rho = a_t[s] / a_landed
+    (a_landed: the a_next of the entry before), then continues down.  Jump points are not re-armed.  The step behind a jump has no valid
+    history: its (cx, c0, c1) are (cx1[s], c01[s], 0); every other entry is tab's own.  jump_x / jump_n are formed in float64 and rounded
+    once to float32.  resamples == 1: tab's arrays, no jump.  ValueError for resamples < 1, jump_length < 1 and, with resamples > 1,
+    jump_length >= n_run (no room for a jump).  Pure Python; the device side knows nothing of the schedule but these arrays."""
+    import math
+    n_run = len(tab["timesteps"])
+    n_fwd = resample_forwards(n_run, resamples, jump_length)          # (the refusals)
+    r, j = int(resamples), int(jump_length)
+    multistep = "cx" in tab
+    if multistep and r > 1 and first_order is None:
+        raise ValueError("the multistep form needs the first-order coefficients (cx1, c01) of the executed steps")
+    left = {l: r - 1 for l in range(0, n_run - j, j)} if r > 1 else {}
+    steps, jumped = [], []
+    l, jump = n_run, False
+    while l >= 1:
+        steps.append(n_run - l)
+        jumped.append(jump)
+        l, jump = l - 1, False
+        if left.get(l, 0) > 0:
+            left[l] -= 1
+            l, jump = l + j, True
+    assert len(steps) == n_fwd
+    out = {k: v for k, v in tab.items() if not isinstance(v, (list, tuple))}
+    for k, v in tab.items():
+        if isinstance(v, (list, tuple)):
+            out[k] = v if r == 1 else [v[s] for s in steps]
+    f32 = lambda v: float(np.float32(v))
+    jx, jn = [0.0] * n_fwd, [0.0] * n_fwd
+    for i, s in enumerate(steps):
+        if not jumped[i]:
+            continue
+        rho = float(tab["a_t"][s]) / float(out["a_next"][i - 1])
+        if not 0.0 < rho < 1.0:
+            raise ValueError(f"a jump from a_next = {out['a_next'][i - 1]} up to a_t = {tab['a_t'][s]} does not add noise")
+        jx[i], jn[i] = f32(math.sqrt(rho)), f32(math.sqrt(1.0 - rho))
+        if multistep:
+            out["cx"][i], out["c0"][i], out["c1"][i] = first_order[0][s], first_order[1][s], 0.0
+    out["step"], out["jump_x"], out["jump_n"] = steps, jx, jn
+    return out
+
+
+def scheduler_resample_tables(scheduler, tab, resamples, jump_length):
+    """resample_tables for the truncated tables `tab` of `scheduler` (scheduler_edit_tables)."""
+    first = None
+    if isinstance(scheduler, DPMSolverMultistepScheduler) and int(resamples) > 1:
+        # the arrays set_timesteps keeps for step(first_order=True); an object that never ran set_timesteps gets them by the same call
+        fx, f0 = getattr(scheduler, "_cx1", None), getattr(scheduler, "_c01", None)
+        if fx is None or f0 is None:
+            fx, f0, _f1 = multistep_coefficients(scheduler.alphas_cumprod, scheduler.timesteps, scheduler.final_alpha_cumprod, 1,
+                                                 scheduler.lower_order_final)
+        first = (list(fx[tab["i0"]:]), list(f0[tab["i0"]:]))
+    return resample_tables(tab, first, resamples, jump_length)
+
+
 class DPMSolverMultistepScheduler(_Scheduler):
     """DPM-Solver++ (2M): a deterministic sampler that reuses the previous step's data prediction for a second-order update, one UNet
     forward per step like DDIM (multistep_coefficients has the formulas; solver_order=1 IS DDIM on the same grid).  `step` keeps the
