@@ -110,6 +110,34 @@ int eegldm_debug_reload_env(void);
  * threads per block, rows- (flat: chunks-) per-thread instantiation, chunk width in channels, XCD-aware block order (1 / 0).
  * The route-aware tests confirm from it that a case ran on the kernel it names.  No reference counterpart. */
 int eegldm_debug_gn_last_route(int backward, int* out6_host);
+/* developer aid: the kernels that served the calling thread's last eegldm_batchnorm_lrelu_fwd (backward = 0) / _bwd (1), as eight ints:
+ * statistics family (0 none: plain LeakyReLU, 1 eval, 2 scalar kernel + fp64 atomics, 3 4-wide partials + fold_finalize, 4 4-wide partials +
+ * fold into a sum area (forward: the ordered fold of the deterministic mode; backward: always), 5 from a producing conv's partials), apply family
+ * (0 scalar, 1 4-wide), blocks, rows per block, TX, TY of the statistics / reduce launch, deterministic mode (1 / 0), rows per block of the
+ * apply launch.  No reference counterpart. */
+int eegldm_debug_bn_last_route(int backward, int* out8_host);
+/* developer aid: BatchNorm statistics (and the running-statistics update) from per-block column partials parts_dev [nb][2 C] fp32 (interleaved
+ * sum, sum of squares) -- the fold that follows a conv whose epilogue left them.  No reference counterpart. */
+int eegldm_debug_bn_stats_from_parts(eegldm_ctx*, const float* parts_dev, int nb, float* stats, float* running_mean, float* running_var,
+                                     float* num_batches_tracked, long rows, int C);
+/* developer aids: the fused PatchDiscriminator tail (BatchNorm + LeakyReLU + final 3-tap conv to one channel; logits / dlogits fp32 [B][L], w3
+ * fp32 [3][C], gradients ACCUMULATED, dgamma = dbeta = dw3 = dbias = NULL: data gradient only) and the fused head backward (LeakyReLU + the
+ * 1 -> C0 conv; x [B * L] and w [3][C0] in the engine dtype, dw / db ACCUMULATED, dx fp32 [B][L] WRITTEN), as eegldm_disc_forward / _backward
+ * run them.  EEGLDM_ERR_UNSUPPORTED where the eligibility check of the executor says no (channel count, leading dimension, odd length).
+ * No reference counterpart. */
+int eegldm_debug_disc_tail_fwd(eegldm_ctx*, int dtype, const void* y, long ldy, const float* gamma, const float* beta, const float* stats,
+                               const float* w3, const float* bias, float slope, float* logits, int B, int L, int C);
+int eegldm_debug_disc_tail_bwd(eegldm_ctx*, int dtype, const void* y, long ldy, const float* gamma, const float* beta, const float* stats,
+                               const float* w3, float slope, const float* dlogits, void* dy, long lddy, float* dgamma, float* dbeta,
+                               float* dw3, float* dbias, int B, int L, int C);
+int eegldm_debug_disc_head_bwd(eegldm_ctx*, int dtype, const void* da, long ldda, const void* x, const void* w, const float* bias, float slope,
+                               float* dw, float* db, float* dx, int B, int L, int Lo, int C0, int stride);
+/* developer aid: eegldm_conv1d_fwd that also asks for the per-block column statistics of the UNROUNDED outputs (col_parts_dev [nparts][2 Cout]
+ * fp32, at most 16 MiB; *col_nparts_host = 0: the kernel that ran does not provide them).  No reference counterpart. */
+int eegldm_debug_conv1d_fwd_colstats(eegldm_ctx*, const void* x, long ldx, const void* w, const float* bias, void* y, long ldy,
+                                     int B, int Lin, int Cin, int Cout, int K, int stride, int pad_l, int pad_r,
+                                     const float* rowvec, long ld_rowvec, const void* resid, long ld_resid, int dtype,
+                                     float* col_parts_dev, int* col_nparts_host);
 /* EEGLDM_DETERMINISTIC=1 (environment variable, read like the developer switches; eegldm.set_deterministic() in the Python mirror):
  * bit-reproducible losses, parameter gradients and optimiser steps run to run.  Every order-dependent reduction -- fp32 atomics of
  * the bias / GroupNorm / thin-conv gradients and of the loss sums, fused column sums inside the weight-gradient GEMM, split-K without

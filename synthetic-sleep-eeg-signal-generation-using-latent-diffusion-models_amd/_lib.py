@@ -51,6 +51,12 @@ SIGNATURES = {
     "eegldm_prof_dump": [_vp, C.c_char_p],
     "eegldm_debug_reload_env": [],
     "eegldm_debug_gn_last_route": [_i, _vp],
+    "eegldm_debug_bn_last_route": [_i, _vp],
+    "eegldm_debug_bn_stats_from_parts": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _l, _i],
+    "eegldm_debug_disc_tail_fwd": [_vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i],
+    "eegldm_debug_disc_tail_bwd": [_vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _f, _vp, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i],
+    "eegldm_debug_disc_head_bwd": [_vp, _i, _vp, _l, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i],
+    "eegldm_debug_conv1d_fwd_colstats": [_vp, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _l, _i, _vp, _vp],
     "eegldm_ncl_to_nlc": [_vp, _vp, _vp, _l, _i, _i, _i, _i],
     "eegldm_nlc_to_ncl": [_vp, _vp, _l, _vp, _i, _i, _i, _i],
     "eegldm_pack_conv_weight": [_vp, _vp, _vp, _i, _i, _i],

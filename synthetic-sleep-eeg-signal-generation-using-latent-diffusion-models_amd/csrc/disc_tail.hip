@@ -519,3 +519,28 @@ int disc_head_bwd(eegldm_ctx* ctx, int dtype, const void* da, long ldda, const v
   }
   return 0;
 }
+
+// ---------------------------------------------------------------- developer exports: the fused kernels alone, behind their eligibility checks
+// (the route-aware tests run every template instantiation against float64; the model executors call the functions above directly)
+extern "C" int eegldm_debug_disc_tail_fwd(eegldm_ctx* ctx, int dtype, const void* y, long ldy, const float* gamma, const float* beta, const float* stats,
+                                          const float* w3, const float* bias, float slope, float* logits, int B, int L, int C) {
+  EEG_CHECK(ctx && y && gamma && beta && stats && w3 && logits && B > 0 && L > 0 && C > 0, "bad argument");
+  if (!disc_tail_ok(dtype, C, ldy)) EEG_FAIL(EEGLDM_ERR_UNSUPPORTED, "fused discriminator tail: C %d, ld %ld not eligible", C, ldy);
+  return disc_tail_fwd(ctx, dtype, y, ldy, gamma, beta, stats, w3, bias, slope, logits, B, L, C);
+}
+extern "C" int eegldm_debug_disc_tail_bwd(eegldm_ctx* ctx, int dtype, const void* y, long ldy, const float* gamma, const float* beta, const float* stats,
+                                          const float* w3, float slope, const float* dlogits, void* dy, long lddy, float* dgamma, float* dbeta,
+                                          float* dw3, float* dbias, int B, int L, int C) {
+  EEG_CHECK(ctx && y && gamma && beta && stats && w3 && dlogits && dy && B > 0 && L > 0 && C > 0, "bad argument");
+  EEG_CHECK((dgamma != nullptr) == (dbeta != nullptr) && (dgamma || (!dw3 && !dbias)), "parameter gradients: dgamma and dbeta together, dw3 / dbias only with them");
+  if (!disc_tail_ok(dtype, C, ldy) || !disc_tail_ok(dtype, C, lddy))
+    EEG_FAIL(EEGLDM_ERR_UNSUPPORTED, "fused discriminator tail: C %d, ld %ld / %ld not eligible", C, ldy, lddy);
+  return disc_tail_bwd(ctx, dtype, y, ldy, gamma, beta, stats, w3, slope, dlogits, dy, lddy, dgamma, dbeta, dw3, dbias, B, L, C);
+}
+extern "C" int eegldm_debug_disc_head_bwd(eegldm_ctx* ctx, int dtype, const void* da, long ldda, const void* x, const void* w, const float* bias, float slope,
+                                          float* dw, float* db, float* dx, int B, int L, int Lo, int C0, int stride) {
+  EEG_CHECK(ctx && da && x && w && B > 0 && L > 0 && Lo > 0 && C0 > 0, "bad argument");
+  EEG_CHECK(dw || !db, "db only together with dw");
+  if (!disc_head_ok(dtype, C0, ldda, stride, L, Lo)) EEG_FAIL(EEGLDM_ERR_UNSUPPORTED, "fused discriminator head: C0 %d, ld %ld, stride %d, L %d -> %d not eligible", C0, ldda, stride, L, Lo);
+  return disc_head_bwd(ctx, dtype, da, ldda, x, w, bias, slope, dw, db, dx, B, L, Lo, C0, stride);
+}

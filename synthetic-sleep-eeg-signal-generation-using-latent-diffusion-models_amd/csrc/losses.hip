@@ -16,20 +16,22 @@ inline int grid1d(long n, eegldm_ctx* ctx) {
 }
 
 // ------------------------------------------------------------------ BatchNorm statistics
-// sums[c][0..1] += sum x, sum x^2 over a chunk of rows (double atomics); grid (ceil(C/64), RSPLIT)
+// sums[c][0..1] += sum x, sum x^2 over a chunk of rows (double atomics); grid (ceil(C/64), RSPLIT).  The per-thread sums are fp64: the variance
+// is S2 / n - mean^2, so a relative error e of the sums reaches it as e (1 + mean^2 / var), and fp32 sums (e ~ 1e-7) showed in the 16-bit
+// outputs of a channel whose mean is 30 standard deviations away from zero (tests/test_gpu_batchnorm_rounding.py, profiles/bn_numerics.txt)
 template <typename T>
 __global__ __launch_bounds__(NT) void bn_stats_kernel(const T* __restrict__ x, long ldx, double* __restrict__ sums, long rows, int C, long rows_per_block) {
-  __shared__ float r1[4][64], r2[4][64];
+  __shared__ double r1[4][64], r2[4][64];
   const int c = blockIdx.x * 64 + (threadIdx.x & 63), ry = threadIdx.x >> 6;
   const long l0 = (long)blockIdx.y * rows_per_block, l1 = min(rows, l0 + rows_per_block);
-  float s1 = 0.f, s2 = 0.f;
-  if (c < C) for (long l = l0 + ry; l < l1; l += 4) { const float v = ld_f32(x + l * ldx + c); s1 += v; s2 += v * v; }
+  double s1 = 0.0, s2 = 0.0;
+  if (c < C) for (long l = l0 + ry; l < l1; l += 4) { const double v = (double)ld_f32(x + l * ldx + c); s1 += v; s2 = fma(v, v, s2); }
   r1[ry][threadIdx.x & 63] = s1; r2[ry][threadIdx.x & 63] = s2;
   __syncthreads();
   if (ry == 0 && c < C) {
     const int i = threadIdx.x;
-    atomicAdd(&sums[2 * c], (double)(r1[0][i] + r1[1][i] + r1[2][i] + r1[3][i]));
-    atomicAdd(&sums[2 * c + 1], (double)(r2[0][i] + r2[1][i] + r2[2][i] + r2[3][i]));
+    atomicAdd(&sums[2 * c], ((r1[0][i] + r1[1][i]) + r1[2][i]) + r1[3][i]);
+    atomicAdd(&sums[2 * c + 1], ((r2[0][i] + r2[1][i]) + r2[2][i]) + r2[3][i]);
   }
 }
 // stats[c] = (mean, rstd); running stats: momentum 0.1, unbiased variance (torch BatchNorm1d defaults)
@@ -63,7 +65,7 @@ __global__ __launch_bounds__(1024) void bn_fold_finalize_kernel(const float* __r
   const int col = threadIdx.x & 63, seg = threadIdx.x >> 6, i = blockIdx.x * 64 + col, n2c = 2 * C;
   double s = 0.0;
   if (i < n2c) {
-#pragma unroll 4
+#pragma unroll 16     // (16 blocks at C = 512: the loop is bound by load latency; sixteen loads in flight per trip keep the two-row partials of ls_bn_stats at the old cost)
     for (int r = seg; r < nparts; r += 16) s += (double)parts[(size_t)r * n2c + i];
   }
   red[seg][col] = s;
@@ -162,15 +164,44 @@ __device__ __forceinline__ BnMap bnmap(int C) {
   return m;
 }
 // MODE 0: sums x, x^2;  MODE 1: sums dz, dz*xhat (backward)
+// MODE 0 sums in fp64 all the way (see bn_stats_kernel): per thread in row order, across the row lanes of the block in lane order (plain LDS
+// slots, no atomics: the same bits in every run), and the block partial leaves as TWO fp32 rows, parts[b] = fp32(S) and parts[gridDim.x + b] =
+// fp32(S - parts[b]), which the fp64 folds add like any other rows (2 gridDim.x of them).  MODE 1 sums quantities without a common offset and
+// keeps fp32 partials.
 template <typename T, int MODE>
 __global__ __launch_bounds__(NT) void bn_reduce4_kernel(const T* __restrict__ x, long ldx, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         const float* __restrict__ stats, const T* __restrict__ dy, long lddy,
                                                         void* __restrict__ parts, long rows, int C, long rows_per_block, float slope) {
   __shared__ double red[2 * 1024];   // fp64 LDS atomics: order-independent sums, and faster than contended fp32 LDS atomics (see norm.hip)
   const BnMap m = bnmap(C);
+  const long l0 = (long)blockIdx.x * rows_per_block, l1 = min(rows, l0 + rows_per_block);
+  if (MODE == 0) {      // C <= 1024: TX = C / 4, one column per thread; slot [thread][channel of the column][sum, sum of squares]
+    double a1[4] = {0.0, 0.0, 0.0, 0.0}, a2[4] = {0.0, 0.0, 0.0, 0.0};
+    if (m.act) {
+      const int c = m.tx * 4;
+#pragma unroll 4
+      for (long l = l0 + m.ty; l < l1; l += m.TY) {
+        float v[4]; ldv4<T>(x + l * ldx + c, v);
+#pragma unroll
+        for (int j = 0; j < 4; j++) { const double dv = (double)v[j]; a1[j] += dv; a2[j] = fma(dv, dv, a2[j]); }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; j++) { red[threadIdx.x * 8 + 2 * j] = a1[j]; red[threadIdx.x * 8 + 2 * j + 1] = a2[j]; }
+    }
+    __syncthreads();
+    float* hi = (float*)parts + (size_t)blockIdx.x * 2 * C;
+    float* lo = (float*)parts + ((size_t)gridDim.x + blockIdx.x) * 2 * C;
+    for (int i = threadIdx.x; i < 2 * C; i += NT) {
+      const int c = i >> 1, slot = ((c >> 2) * 8) + 2 * (c & 3) + (i & 1);
+      double t = 0.0;
+      for (int ty = 0; ty < m.TY; ty++) t += red[ty * m.TX * 8 + slot];
+      const float h = (float)t;
+      hi[i] = h; lo[i] = (h - h == 0.f) ? (float)(t - (double)h) : 0.f;      // (a non-finite sum is carried by the first row alone)
+    }
+    return;
+  }
   for (int i = threadIdx.x; i < 2 * C; i += NT) red[i] = 0.0;
   __syncthreads();
-  const long l0 = (long)blockIdx.x * rows_per_block, l1 = min(rows, l0 + rows_per_block);
   if (m.act) {
     for (int col = m.tx; col < C / 4; col += m.TX) {
       const int c = col * 4;
@@ -402,6 +433,21 @@ inline void pick_rsplit(long rows, int C, eegldm_ctx* ctx, int* rsplit, long* rp
 
 // Sum areas in the context scratch: two alternating ones for the partials + fold path (the fold kernel of a call re-zeroes the area
 // the PREVIOUS call used -- all of that call's consumers precede it in stream order), a third, memset per call, for the atomic path.
+// last forward / backward route (eegldm_debug_bn_last_route: the route-aware tests confirm that a case ran on the kernels it names).
+// stats: 0 none (plain LeakyReLU), 1 eval, 2 scalar kernel + fp64 atomics, 3 4-wide partials + fold_finalize, 4 4-wide partials + ordered or
+// atomic fold into a sum area (the forward only in deterministic mode, the backward always), 5 from the partials of a producing conv;
+// apply: 0 scalar, 1 4-wide; blocks / rows per block / TX / TY of the statistics (backward: reduce) launch; det: deterministic mode;
+// apply_rpb: rows per block of the apply launch.  Host-side bookkeeping, one record per host thread, nothing the kernels read.
+struct BnRoute { int stats, apply, blocks, rpb, tx, ty, det, apply_rpb; };
+static thread_local BnRoute g_bn_route[2] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
+static void bn_note_stats(int bwd, int stats, long blocks, long rpb, int C, bool vec) {
+  BnRoute& r = g_bn_route[bwd];
+  const int ncols = C / 4, tx = vec ? (ncols < NT ? ncols : NT) : 64;
+  r.stats = stats; r.blocks = (int)blocks; r.rpb = (int)rpb; r.tx = stats >= 2 && stats <= 4 ? tx : 0; r.ty = stats >= 2 && stats <= 4 ? (vec ? NT / tx : 4) : 0;
+  r.det = eeg_deterministic() ? 1 : 0;
+}
+static void bn_note_apply(int bwd, int apply, long rpb) { g_bn_route[bwd].apply = apply; g_bn_route[bwd].apply_rpb = (int)rpb; g_bn_route[bwd].det = eeg_deterministic() ? 1 : 0; }
+
 static double* bn_area(eegldm_ctx* ctx, int i) { return (double*)((char*)ctx->scratch + (2u << 20) + (size_t)i * (256u << 10)); }
 // parts: [nb][nvals] fp32 partial sums -> sums[nvals] (fp64) in the current sum area; shared with the fused discriminator tail (disc_tail.hip)
 int ls_bn_fold(eegldm_ctx* ctx, const void* parts, int nb, int nvals, double** sums_out) {
@@ -426,21 +472,24 @@ int ls_bn_stats(eegldm_ctx* ctx, const void* x, long ldx, float* stats, float* r
     EEG_CHECK((size_t)C * 2 * sizeof(double) <= (256u << 10), "scratch too small");
     if (C % 4 == 0 && ldx % 4 == 0 && C <= 1024) {
       int nb; long rpb4; bn_split(rows, ctx, 8, &nb, &rpb4);
+      while ((size_t)2 * nb * 2 * C * sizeof(float) > (16u << 20)) { rpb4 *= 2; nb = (int)((rows + rpb4 - 1) / rpb4); }      // two fp32 rows per block in the 16 MiB partials area
       void* parts = (char*)ctx->scratch + (8u << 20);
       DISPATCH_T(dtype, hipLaunchKernelGGL((bn_reduce4_kernel<T, 0>), dim3(nb), dim3(NT), 0, ctx->stream, (const T*)x, ldx, nullptr, nullptr, nullptr,
                                            (const T*)nullptr, 0, parts, rows, C, rpb4, 0.f));
       LAUNCH_CHECK();
+      bn_note_stats(0, eeg_deterministic() ? 4 : 3, nb, rpb4, C, true);
       if (!eeg_deterministic()) {      // fold + finalise in one launch (the deterministic mode keeps its ordered fold)
-        hipLaunchKernelGGL(bn_fold_finalize_kernel, dim3((2 * C + 63) / 64), dim3(1024), 0, ctx->stream, (const float*)parts, nb, C, stats, rmean, rvar, nbt,
+        hipLaunchKernelGGL(bn_fold_finalize_kernel, dim3((2 * C + 63) / 64), dim3(1024), 0, ctx->stream, (const float*)parts, 2 * nb, C, stats, rmean, rvar, nbt,
                            (double)rows, 1e-5f, 0.1f, ctx->bn_running_repeats);
         LAUNCH_CHECK();
         return 0;
       }
-      EEG_TRY(bn_fold_launch(ctx, parts, nb, C, &sums));
+      EEG_TRY(bn_fold_launch(ctx, parts, 2 * nb, C, &sums));
     } else {
       HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * 2 * C, ctx->stream));
       int rs; long rpb; pick_rsplit(rows, C, ctx, &rs, &rpb);
       DISPATCH_T(dtype, hipLaunchKernelGGL((bn_stats_kernel<T>), dim3((C + 63) / 64, rs), dim3(NT), 0, ctx->stream, (const T*)x, ldx, sums, rows, C, rpb));
+      bn_note_stats(0, 2, rs, rpb, C, false);
     }
     LAUNCH_CHECK();
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, ctx->stream, sums, stats, rmean, rvar, nbt, C, (double)rows, 1e-5f, 0.1f,
@@ -450,11 +499,13 @@ int ls_bn_stats(eegldm_ctx* ctx, const void* x, long ldx, float* stats, float* r
     EEG_CHECK(rmean && rvar, "eval-mode BatchNorm needs running statistics");
     hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, ctx->stream, rmean, rvar, stats, C, 1e-5f);
     LAUNCH_CHECK();
+    bn_note_stats(0, 1, 0, 0, C, false);
   }
   return 0;
 }
 // statistics from the per-block column partials the producing conv left (conv_ws.hip ST kernels): parts[nb][2 C] interleaved (sum, sum of squares)
 int ls_bn_stats_from_parts(eegldm_ctx* ctx, const float* parts, int nb, float* stats, float* rmean, float* rvar, float* nbt, long rows, int C) {
+  bn_note_stats(0, 5, nb, 0, C, false);
   if (!eeg_deterministic()) {
     hipLaunchKernelGGL(bn_fold_finalize_kernel, dim3((2 * C + 63) / 64), dim3(1024), 0, ctx->stream, parts, nb, C, stats, rmean, rvar, nbt, (double)rows, 1e-5f, 0.1f,
                        ctx->bn_running_repeats);
@@ -475,7 +526,9 @@ int ls_bn_apply(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, co
     int nb; long rpb4; bn_split(rows, ctx, 16, &nb, &rpb4);
     DISPATCH_T(dtype, hipLaunchKernelGGL((bn_apply4_kernel<T, 0>), dim3(nb), dim3(NT), 0, ctx->stream, (const T*)x, ldx, gamma, beta, stats, (const T*)nullptr, 0,
                                          nullptr, (T*)y, ldy, nullptr, nullptr, rows, C, rpb4, slope));
+    bn_note_apply(0, 1, rpb4);
   } else {
+    bn_note_apply(0, 0, 0);
     DISPATCH_T(dtype, hipLaunchKernelGGL((bn_lrelu_apply_kernel<T>), dim3(grid1d(rows * C, ctx)), dim3(NT), 0, ctx->stream, (const T*)x, ldx, gamma, beta, stats, (T*)y, ldy, rows, C, slope));
   }
   LAUNCH_CHECK();
@@ -486,6 +539,7 @@ int ls_bn_apply(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, co
 int ls_bn_lrelu_fwd(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const float* beta, float* stats, float* rmean, float* rvar,
                     float* nbt, void* y, long ldy, long rows, int C, float slope, int training, int dtype) {
   if (gamma) EEG_TRY(ls_bn_stats(ctx, x, ldx, stats, rmean, rvar, nbt, rows, C, training, dtype));
+  else bn_note_stats(0, 0, 0, 0, C, false);
   return ls_bn_apply(ctx, x, ldx, gamma, beta, stats, y, ldy, rows, C, slope, dtype);
 }
 int ls_bn_lrelu_bwd(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const float* beta, const float* stats, const void* dy, long lddy,
@@ -498,19 +552,23 @@ int ls_bn_lrelu_bwd(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma
       DISPATCH_T(dtype, hipLaunchKernelGGL((bn_reduce4_kernel<T, 1>), dim3(nb), dim3(NT), 0, ctx->stream, (const T*)x, ldx, gamma, beta, stats,
                                            (const T*)dy, lddy, parts, rows, C, rpb4, slope));
       EEG_TRY(bn_fold_launch(ctx, parts, nb, C, &sums));
+      bn_note_stats(1, 4, nb, rpb4, C, true);
     } else {
       HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * 2 * C, ctx->stream));
       int rs; long rpb; pick_rsplit(rows, C, ctx, &rs, &rpb);
+      bn_note_stats(1, 2, rs, rpb, C, false);
       DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T>), dim3((C + 63) / 64, rs), dim3(NT), 0, ctx->stream, (const T*)x, ldx, gamma, beta, stats,
                                            (const T*)dy, lddy, sums, rows, C, rpb, slope));
     }
     LAUNCH_CHECK();
-  }
+  } else bn_note_stats(1, 0, 0, 0, C, false);
   if (C % 4 == 0 && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0) {
     int nb; long rpb4; bn_split(rows, ctx, 16, &nb, &rpb4);
+    bn_note_apply(1, 1, rpb4);
     DISPATCH_T(dtype, hipLaunchKernelGGL((bn_apply4_kernel<T, 1>), dim3(nb), dim3(NT), 0, ctx->stream, (const T*)x, ldx, gamma, beta, stats, (const T*)dy, lddy,
                                          sums, (T*)dx, lddx, dgamma, dbeta, rows, C, rpb4, slope));
   } else {
+    bn_note_apply(1, 0, 0);
     DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(grid1d(rows * C, ctx)), dim3(NT), 0, ctx->stream, (const T*)x, ldx, gamma, beta, stats,
                                          (const T*)dy, lddy, sums, (T*)dx, lddx, dgamma, dbeta, rows, C, slope));
   }
@@ -556,6 +614,18 @@ extern "C" int eegldm_batchnorm_lrelu_bwd(eegldm_ctx* ctx, const void* x, long l
   EEG_CHECK(ctx && x && dy && dx && rows > 0 && C > 0, "bad argument");
   EEG_CHECK(!gamma || (beta && stats && dgamma && dbeta), "BatchNorm backward needs gamma, beta, the forward statistics and both gradient buffers");
   return ls_bn_lrelu_bwd(ctx, x, ldx, gamma, beta, stats, dy, lddy, dx, lddx, dgamma, dbeta, rows, C, slope, dtype);
+}
+extern "C" int eegldm_debug_bn_last_route(int backward, int* out8_host) {
+  if (!out8_host || backward < 0 || backward > 1) return EEGLDM_ERR_INVALID;
+  const BnRoute& r = g_bn_route[backward];
+  out8_host[0] = r.stats; out8_host[1] = r.apply; out8_host[2] = r.blocks; out8_host[3] = r.rpb; out8_host[4] = r.tx; out8_host[5] = r.ty;
+  out8_host[6] = r.det; out8_host[7] = r.apply_rpb;
+  return 0;
+}
+extern "C" int eegldm_debug_bn_stats_from_parts(eegldm_ctx* ctx, const float* parts_dev, int nb, float* stats, float* running_mean, float* running_var,
+                                                float* num_batches_tracked, long rows, int C) {
+  EEG_CHECK(ctx && parts_dev && stats && nb > 0 && rows > 0 && C > 0, "bad argument");
+  return ls_bn_stats_from_parts(ctx, parts_dev, nb, stats, running_mean, running_var, num_batches_tracked, rows, C);
 }
 // z = mu + eps * sigma, sigma = exp(clamp(log_var, -30, 20) / 2); kl (nullable) += KL(N(mu, sigma) || N(0, 1)) summed over elements / B
 extern "C" int eegldm_kl_reparam_fwd(eegldm_ctx* ctx, const void* mu, const void* log_var, const float* eps, void* z, float* sigma, float* kl,

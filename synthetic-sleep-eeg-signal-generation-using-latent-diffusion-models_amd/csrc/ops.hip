@@ -47,7 +47,7 @@ int op_conv_fwd(eegldm_ctx* ctx, int dtype, const void* x, long ldx, const void*
     if (rc != 0) return rc < 0 ? rc : 0;
   }
   if (K == 3 && stride == 1 && pad_l == 1 && pad_r == 1) {      // HBM-bound wide-and-shallow layers: weights stay in registers (conv_ws.hip)
-    const int rc = conv_ws_try(ctx, dtype, x, ldx, w, Cin, Cout, 0, bias, rowvec, ld_rowvec, resid, ldr, y, ldy, B, Lin);
+    const int rc = conv_ws_try(ctx, dtype, x, ldx, w, Cin, Cout, 0, bias, rowvec, ld_rowvec, resid, ldr, y, ldy, B, Lin, col_parts, col_nparts);
     if (rc != 0) return rc < 0 ? rc : 0;
   }
   GemmArgs a = {};
@@ -342,6 +342,16 @@ extern "C" int eegldm_conv1d_fwd(eegldm_ctx* ctx, const void* x, long ldx, const
                                  const float* rowvec, long ld_rowvec, const void* resid, long ld_resid, int dtype) {
   EEG_CHECK(ctx && x && w && y, "null pointer");
   return op_conv_fwd(ctx, dtype, x, ldx, w, bias, y, ldy, B, Lin, Cin, Cout, K, stride, pad_l, pad_r, rowvec, ld_rowvec, resid, ld_resid);
+}
+// developer export: eegldm_conv1d_fwd that also asks the kernel for the per-block column statistics of its unrounded outputs
+// (col_parts_dev [nparts][2 Cout] fp32, interleaved sum / sum of squares; *col_nparts_host = 0: the kernel that ran does not provide them)
+extern "C" int eegldm_debug_conv1d_fwd_colstats(eegldm_ctx* ctx, const void* x, long ldx, const void* w, const float* bias, void* y, long ldy,
+                                                int B, int Lin, int Cin, int Cout, int K, int stride, int pad_l, int pad_r,
+                                                const float* rowvec, long ld_rowvec, const void* resid, long ld_resid, int dtype,
+                                                float* col_parts_dev, int* col_nparts_host) {
+  EEG_CHECK(ctx && x && w && y && col_parts_dev && col_nparts_host, "null pointer");
+  return op_conv_fwd(ctx, dtype, x, ldx, w, bias, y, ldy, B, Lin, Cin, Cout, K, stride, pad_l, pad_r, rowvec, ld_rowvec, resid, ld_resid, 0.f,
+                     col_parts_dev, col_nparts_host);
 }
 extern "C" int eegldm_conv1d_pack_kblocked(eegldm_ctx* ctx, const void* w, void* w_kblocked, int Cout, int Cin, int dtype) {
   return eegldm_conv1d_pack_kblocked_k(ctx, w, w_kblocked, Cout, Cin, 3, dtype);

@@ -527,3 +527,249 @@ def gn_bwd(x, G, gamma, beta, dy, eps=1e-6, silu=False, resample=0, dxr=None, to
         s = s + (gn_xr(xr, resample) * dxr).sum()
     s.backward()
     return xr.grad, gr.grad, br.grad
+
+
+# ---------------------------------------------------------------- BatchNorm1d + LeakyReLU and the fused discriminator tail / head
+# Row-major operands: x, y, dy, dx as (rows, C) (rows = B L of the NLC buffers); per-channel vectors as (C,).  The references are float64;
+# the bounds are those derived in the docstring of tests/test_gpu_batchnorm_rounding.py, evaluated from the reference alone.
+U64 = 2.0 ** -53
+
+
+_gam = gamma          # (the BatchNorm functions below take a parameter called gamma)
+
+
+def gamma64(n):
+    return (n + 4) * U64
+
+
+def bn_stats(x, eps, rmean=None, rvar=None, nbt=0.0, momentum=0.1, repeats=1):
+    """dict(mean, var (biased), rstd, rmean, rvar, nbt): per channel over all rows, and the running statistics after `repeats` momentum
+    updates with the unbiased variance (n - 1 >= 1 in the divisor, as torch's BatchNorm1d; one row: the biased value)"""
+    x = _f64(x)
+    n = x.shape[0]
+    mean = x.mean(0)
+    var = ((x - mean) ** 2).mean(0)
+    out = dict(mean=mean, var=var, rstd=1.0 / torch.sqrt(var + eps), n=n)
+    if rmean is not None:
+        rm, rv = _f64(rmean).clone(), _f64(rvar).clone()
+        ub = var * n / max(n - 1, 1)
+        for _ in range(repeats):
+            rm = (1 - momentum) * rm + momentum * mean
+            rv = (1 - momentum) * rv + momentum * ub
+        out.update(rmean=rm, rvar=rv, nbt=float(nbt) + repeats)
+    return out
+
+
+def bn_stats_from_sums(S1, S2, n, eps):
+    """the same from column sums (the from-parts fold: S1, S2 are the exact sums of the fp32 partials)"""
+    mean = _f64(S1) / n
+    var = torch.clamp(_f64(S2) / n - mean * mean, min=0.0)
+    return dict(mean=mean, var=var, rstd=1.0 / torch.sqrt(var + eps), n=n)
+
+
+def lrelu(z, slope):
+    return torch.where(z > 0, z, slope * z)
+
+
+def bn_z(x, gamma, beta, st):
+    xhat = (_f64(x) - st["mean"]) * st["rstd"]
+    return xhat, xhat * _f64(gamma) + _f64(beta)
+
+
+def bn_lrelu_fwd(x, gamma, beta, st, slope):
+    """y = lrelu(gamma (x - mean) rstd + beta); gamma None: plain LeakyReLU"""
+    if gamma is None:
+        return lrelu(_f64(x), slope)
+    return lrelu(bn_z(x, gamma, beta, st)[1], slope)
+
+
+def bn_lrelu_bwd(x, gamma, beta, st, dy, slope, mask=None):
+    """(dx, dgamma, dbeta, S1, S2) for an upstream gradient dy of the ACTIVATED output; the mask is z > 0 unless given"""
+    xhat, z = bn_z(x, gamma, beta, st)
+    m = (z > 0) if mask is None else mask
+    dz = torch.where(m, _f64(dy), slope * _f64(dy))
+    S1, S2 = dz.sum(0), (dz * xhat).sum(0)
+    n = x.shape[0]
+    dx = _f64(gamma) * st["rstd"] * (dz - S1 / n - xhat * (S2 / n))
+    return dx, S2, S1, S1, S2
+
+
+def bn_stat_bounds(x, st, n_p, block_round, eps):
+    """(e_mean absolute, e_rstd relative) of one-pass statistics about zero: per-thread fp32 sums of x and x^2 over at most n_p elements, fp64
+    across threads, one fp32 rounding of each block partial when block_round, fp64 fold, two casts"""
+    x = _f64(x)
+    u = U32 if block_round else 0.0
+    mean, var = st["mean"], st["var"]
+    e_mean = (_gam(n_p) + u) * x.abs().mean(0) + U32 * mean.abs()
+    e_var = (_gam(n_p + 2) + u) * (var + mean ** 2) + 2 * mean.abs() * e_mean
+    return e_mean, e_var / (2 * (var + eps)) + 4 * U32
+
+
+def bn_fwd_bound(x, gamma, beta, st, e_mean, e_rstd, slope):
+    """(z, y, d): the float64 pre-activation and output and the absolute bound d of the output (and of z: LeakyReLU is continuous with slope
+    <= 1): d = |gamma| (|xhat| e_rstd + rstd e_mean) + 3u |gamma| rstd (|x| + |mean|) + 4u |z| + u |y|"""
+    x = _f64(x); ga = _f64(gamma).abs()
+    xhat, z = bn_z(x, gamma, beta, st)
+    y = lrelu(z, slope)
+    d = ga * (xhat.abs() * e_rstd + st["rstd"] * e_mean) + 3 * U32 * ga * st["rstd"] * (x.abs() + st["mean"].abs()) + 4 * U32 * z.abs() + U32 * y.abs()
+    return z, y, d
+
+
+def bn_bwd_bounds(x, gamma, beta, st, e_mean, e_rstd, da, slope, d_z, da_mag=None, k_da=0, dgamma0=None, dbeta0=None):
+    """References and bounds of the backward of lrelu(bn(x)) for an upstream gradient da (float64 reference) that the kernel holds to within
+    k_da u da_mag (BatchNorm: da = dy exactly, k_da = 0; the fused tail recomputes da with three fp32 roundings).  d_z is the bound of the
+    kernel's own z; U = {|z| <= d_z} is the set where a correct kernel may take either LeakyReLU branch.  Returns a dict:
+      U, share            the set (with the elements whose z is NaN: a poisoned channel) and its share of the elements
+      dx, dx_alt, b_dx    reference with the mask z > 0, with the opposite mask ON U (same S1, S2), the bound (valid for either on U)
+      S1, S2, bS1, bS2    the column sums and their bounds (U widening included)
+      dbeta, dgamma, b_dbeta, b_dgamma   = S1 + dbeta0, S2 + dgamma0 and their bounds (the start value joins the sum of magnitudes)"""
+    x, da = _f64(x), _f64(da)
+    n = x.shape[0]
+    ga = _f64(gamma)
+    mean, rstd = st["mean"], st["rstd"]
+    xhat, z = bn_z(x, gamma, beta, st)
+    U = (z.abs() <= d_z) | torch.isnan(z)        # (a NaN z compares false both ways: `z > 0` and `z <= 0` pick different branches)
+    m = z > 0
+    mag = da.abs() if da_mag is None else _f64(da_mag)
+    dz = torch.where(m, da, slope * da)
+    dz_alt = torch.where(m ^ U, da, slope * da)
+    dzm = torch.where(m | U, mag, slope * mag)                   # bound of |dz'| whichever branch is taken on U
+    e_dz = k_da * U32 * dzm
+    wid = torch.where(U, (1 - slope) * mag, torch.zeros_like(mag))
+    dxh = xhat.abs() * e_rstd + rstd * e_mean + 2 * U32 * rstd * (x.abs() + mean.abs())
+    S1, S2 = dz.sum(0), (dz * xhat).sum(0)
+    bS1 = _gam(n + k_da) * dzm.sum(0) + wid.sum(0)
+    bS2 = _gam(n + k_da + 2) * (dzm * xhat.abs()).sum(0) + (dzm * dxh).sum(0) + (wid * xhat.abs()).sum(0)
+    db0 = torch.zeros_like(S1) if dbeta0 is None else _f64(dbeta0)
+    dg0 = torch.zeros_like(S2) if dgamma0 is None else _f64(dgamma0)
+    sc = (ga * rstd).abs()
+    k1, k2 = S1 / n, S2 / n
+
+    def dx_of(d):
+        return ga * rstd * (d - k1 - xhat * k2)
+
+    dx, dx_alt = dx_of(dz), dx_of(dz_alt)
+    dxa = torch.maximum(dx.abs(), dx_alt.abs())
+    b_dx = sc * (bS1 / n + xhat.abs() * bS2 / n + k2.abs() * dxh + e_dz) + (e_rstd + 3 * U32) * dxa + 6 * U32 * sc * (dzm + k1.abs() + (xhat * k2).abs())
+    return dict(U=U, share=float(U.double().mean()), xhat=xhat, z=z, dx=dx, dx_alt=dx_alt, b_dx=b_dx, S1=S1, S2=S2, bS1=bS1, bS2=bS2,
+                dbeta=S1 + db0, dgamma=S2 + dg0, b_dbeta=bS1 + _gam(n + k_da) * db0.abs(), b_dgamma=bS2 + _gam(n + k_da + 2) * dg0.abs(),
+                dzm=dzm, dz=dz)
+
+
+def _within(got, ref, d, fmt):
+    """element-wise: got inside [ref - d, ref + d] (16-bit outputs: inside [RNE(ref - d), RNE(ref + d)]); a NaN reference wants a NaN, an
+    infinite one the same infinity.  Returns (inside, |error| / allowed error)"""
+    got, ref, d = _f64(got), _f64(ref), _f64(d)
+    fin = torch.isfinite(ref) & torch.isfinite(d)
+    r = torch.where(fin, ref, torch.zeros_like(ref)); dd = torch.where(fin, d, torch.zeros_like(d))
+    if fmt == "f32":
+        inside = (got >= r - dd) & (got <= r + dd); allow = dd
+    else:
+        inside = (got >= rne(r - dd, fmt)) & (got <= rne(r + dd, fmt)); allow = 0.5 * ulp(r, fmt) + dd
+    nonfin = torch.where(torch.isnan(ref) | torch.isnan(d), torch.isnan(got), got == ref)
+    err = (got - r).abs()
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / allow)
+    ratio = torch.where(torch.isnan(ratio), torch.full_like(ratio, math.inf), ratio)
+    ok = torch.where(fin, inside, nonfin)
+    return ok, torch.where(fin, ratio, torch.where(nonfin, torch.zeros_like(ratio), torch.full_like(ratio, math.inf)))
+
+
+def check_abs(got, ref, d, fmt, route="", alt=None, report=True):
+    """check A with a derived absolute bound d per element.  alt = (ref2, mask): on `mask` an element also passes when it is within d of ref2
+    (the mask-uncertain set of a LeakyReLU backward).  Prints one [numerics] line; raises AssertionError with the worst element."""
+    got, ref, d = _f64(got), _f64(ref), _f64(d)
+    assert got.shape == ref.shape == d.shape, (got.shape, ref.shape, d.shape)
+    ok, ratio = _within(got, ref, d, fmt)
+    if alt is not None:
+        ok2, ratio2 = _within(got, alt[0], d, fmt)
+        ok = ok | (alt[1] & ok2); ratio = torch.where(alt[1], torch.minimum(ratio, ratio2), ratio)
+    nbad = int((~ok).sum())
+    i = int(torch.argmax(torch.nan_to_num(ratio, posinf=1e300)))
+    worst = float(ratio.reshape(-1)[i])
+    st = dict(route=route, fmt=fmt, n_elem=ref.numel(), n_red=0, bad_a=nbad, worst=worst)
+    if fmt != "f32":
+        mu, _cnt = mean_signed_ulp(got, ref, fmt)
+        st.update(mismatch=mismatch_share(got, ref, fmt), mean_ulp=mu)
+    if report:
+        print(format_report(st))
+    assert nbad == 0, (f"{route} [{fmt}]: check A: {nbad} of {ref.numel()} outside the bound (worst at flat index {i}: got {got.reshape(-1)[i].item()!r}, "
+                       f"ref {ref.reshape(-1)[i].item()!r}, bound {d.reshape(-1)[i].item():.4g}, {worst:.3g} x its bound)")
+    return st
+
+
+# fused tail: y (B, L, C); w3 (3, C) fp32 master weights; logits / dl (B, L)
+def _shift_rows(a, t):
+    """a[:, l + t] with zeros outside the sample (a: (B, L, ...))"""
+    out = torch.zeros_like(a)
+    L = a.shape[1]
+    if t == 0:
+        return a.clone()
+    if t > 0:
+        out[:, :L - t] = a[:, t:]
+    else:
+        out[:, -t:] = a[:, :L + t]
+    return out
+
+
+def tail_logits(y, gamma, beta, st, w3, bias, slope, a=None):
+    """logits[b, l] = bias + sum_t sum_c w3[t, c] a[b, l + t - 1, c], a = lrelu(bn(y)) (or the `a` given: the magnitudes of the bound)"""
+    y, w3 = _f64(y), _f64(w3)
+    if a is None:
+        a = bn_lrelu_fwd(y, gamma, beta, st, slope)
+    out = sum((_shift_rows(a, t - 1) * w3[t]).sum(-1) for t in range(3))
+    return out + (float(bias) if bias is not None else 0.0)
+
+
+def tail_da(dl, w3):
+    """da[b, l, c] = dl[b, l + 1] w0[c] + dl[b, l] w1[c] + dl[b, l - 1] w2[c]: the data gradient of the one-channel conv"""
+    dl, w3 = _f64(dl), _f64(w3)
+    return sum(_shift_rows(dl, 1 - t)[:, :, None] * w3[t] for t in range(3))
+
+
+def tail_bwd(y, gamma, beta, st, w3, slope, dl, mask=None):
+    """(dy, dgamma, dbeta, dw3, dbias); statistics over all B L rows"""
+    y = _f64(y); B, L, C = y.shape
+    a = bn_lrelu_fwd(y, gamma, beta, st, slope)
+    da = tail_da(dl, w3)
+    dx, dga, dbe, _s1, _s2 = bn_lrelu_bwd(y.reshape(B * L, C), gamma, beta, st, da.reshape(B * L, C), slope, None if mask is None else mask.reshape(B * L, C))
+    dw3 = torch.stack([(a * _shift_rows(_f64(dl), 1 - t)[:, :, None]).sum((0, 1)) for t in range(3)])
+    return dx.reshape(B, L, C), dga, dbe, dw3, _f64(dl).sum()
+
+
+# fused head: x (B, L) one input channel, w (3, C0), da (B, Lo, C0); pad 1
+def head_taps(x, stride, Lo):
+    """(3, B, Lo): x[b, s l + t - 1], zero outside the sample"""
+    x = _f64(x); B, L = x.shape
+    xp = torch.zeros(B, L + 2, dtype=torch.float64); xp[:, 1:L + 1] = x
+    return torch.stack([xp[:, t:t + stride * Lo:stride][:, :Lo] for t in range(3)])
+
+
+def head_z(x, w, bias, stride, Lo):
+    xt = head_taps(x, stride, Lo); w = _f64(w)
+    z = sum(xt[t][:, :, None] * w[t] for t in range(3))
+    mag = sum((xt[t][:, :, None] * w[t]).abs() for t in range(3))
+    if bias is not None:
+        z = z + _f64(bias)
+    return z, mag
+
+
+def head_bwd(da, x, w, bias, slope, stride, mask=None):
+    """(dw (3, C0), db (C0,), dx (B, L)) of a0 = lrelu(conv(x; w, stride, pad 1) + bias) for the gradient da of a0; mask recomputed from x"""
+    da, w = _f64(da), _f64(w)
+    B, Lo, C0 = da.shape; L = x.shape[1]
+    z, _mag = head_z(x, w, bias, stride, Lo)
+    m = (z > 0) if mask is None else mask
+    dy = torch.where(m, da, slope * da)
+    xt = head_taps(x, stride, Lo)
+    dw = torch.stack([(dy * xt[t][:, :, None]).sum((0, 1)) for t in range(3)])
+    q = torch.stack([(dy * w[t]).sum(-1) for t in range(3)])           # (3, B, Lo)
+    dxp = torch.zeros(B, L + 2 + stride, dtype=torch.float64)
+    for t in range(3):
+        dxp[:, t:t + stride * Lo:stride][:, :Lo] += q[t]
+    return dw, dy.sum((0, 1)), dxp[:, 1:L + 1]
+
+
+def col_stats(y_unrounded):
+    """(sum, sum of squares) per column of a (rows, N) float64 matrix"""
+    y = _f64(y_unrounded)
+    return y.sum(0), (y * y).sum(0)
