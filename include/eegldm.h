@@ -811,6 +811,53 @@ int eegldm_usleep_bind(eegldm_usleep*, float* params, float* buffers);
  * of compute_fid.py:380-381 is the bottleneck).  training != 0: BatchNorm on batch statistics + running-statistics update -- what the
  * reference script runs, since it never calls model.eval(). */
 int eegldm_usleep_forward(eegldm_usleep*, const float* x, float* y_pred, float* decoder_out, float* bottom, int B, int T, int training);
+/* ---- U-Sleep training (csrc/usleep_train.hip): fp32, additive (EEGLDM_ABI_VERSION stays 8).  Every reduction is written partials folded
+ * in a fixed order (no float atomics): a step repeats bit for bit.  Gradients ACCUMULATE (+=) into the flat buffer bound here, laid out as
+ * the parameter buffer of eegldm_usleep_bind. */
+int eegldm_usleep_bind_grads(eegldm_usleep*, float* grads);
+/* Training forward: BatchNorm on batch statistics (fp64 partial sums, ordered fold) + the running-statistics update of
+ * eegldm_usleep_forward(training = 1); writes y_pred (B, n_classes, T / input_size) and keeps the tape in the object's arena (per layer the
+ * ELU output z, mean / rstd, the normalised output; NOT x, which the first conv's weight gradient reads: keep it until the backward has run).
+ * Refused before any launch: unbound gradients, T < input_size, B * bottleneck length < 2
+ * (batch statistics over one value do not exist; torch raises too). */
+int eegldm_usleep_forward_train(eegldm_usleep*, const float* x, float* y_pred, int B, int T);
+/* Backward of the taped forward from dy_pred (B, n_classes, S): parameter gradients +=, dx (B, in_chans, T) written when not NULL.
+ * EEGLDM_ERR_INVALID, and nothing launched, when there is no tape or it is stale: ANY other forward on this object (eegldm_usleep_forward in
+ * either mode) reuses the arena and invalidates it. */
+int eegldm_usleep_backward(eegldm_usleep*, const float* dy_pred, float* dx /* nullable */);
+/* forward_train + weighted stage cross-entropy + backward.  labels (B, S) int64 on the device, any negative label is ignored; class_weight
+ * [n_classes] or NULL; loss = sum_i w[l_i] nll_i / sum_i w[l_i] (F.cross_entropy(weight=, ignore_index=-1), mean reduction; all ignored: loss
+ * and gradients 0).  Gradients are scaled by grad_scale, *loss_out (device) is not.  A label >= n_classes takes no part, and sets a device
+ * flag that eegldm_usleep_label_error reads (labels are device memory: the host cannot look at them without a synchronisation). */
+int eegldm_usleep_train_step(eegldm_usleep*, const float* x, const int64_t* labels, const float* class_weight /* nullable */, int B, int T,
+                             float grad_scale, float* loss_out, float* y_pred /* nullable */);
+/* Waits for the context's stream, *out = 1 when a train step since the last call met a label >= n_classes (the flag is cleared). */
+int eegldm_usleep_label_error(eegldm_usleep*, int* out);
+/* kernels launched by the last eegldm_usleep_train_step / _forward_train / _backward on this object */
+long eegldm_usleep_last_launches(const eegldm_usleep*);
+/* The loss alone: logits (B, n_classes, S) -> *loss_out, dlogits (nullable; scaled by grad_scale), label_flag (nullable device int). */
+int eegldm_usleep_stage_loss(eegldm_ctx*, const float* logits, const int64_t* labels, const float* class_weight /* nullable */, int B, int n_classes,
+                             int S, float grad_scale, float* loss_out, float* dlogits, int* label_flag);
+/* Primitives of the backward, exported for the tests (in the manner of eegldm_batchnorm_lrelu_*).
+ * conv_bwd: one conv1d 'same' layer (left pad (K - 1) / 2: an even K pads the extra zero on the right) over the forward's virtual input
+ * [a (B, Ca, La), nearest x2 when ups | b2 (B, Cb, Lb)], both cropped to L; dz (B, Cout, L).  dA (B, Ca, La) and dB2 (B, Cb, Lb) are WRITTEN
+ * (cropped-off positions 0; ups: dA[q] = dv[2q] + dv[2q + 1]), dw (Cout, Ca + Cb, K) and db += .  nsplit: splits of the B * L rows of the
+ * weight gradient (written partials + ordered fold when > 1), 0 = chosen from the shape.  Any output may be NULL (dw and db together). */
+int eegldm_usleep_conv_bwd(eegldm_ctx*, const float* a, int Ca, int La, int ups, const float* b2, int Cb, int Lb, int L, const float* w,
+                           const float* dz, int B, int Cout, int K, int nsplit, float* dA, float* dB2, float* dw, float* db);
+/* ELU + train-mode BatchNorm backward from the ELU output z (B, C, L) and the batch's mean / rstd [C]:
+ * dz = ELU'(z) * gamma * rstd * (dy - mean(dy) - zhat * mean(dy * zhat)), ELU'(z) = z > 0 ? 1 : z + 1; dgamma += sum dy * zhat, dbeta += sum dy
+ * (sums in fp64).  dz may alias dy. */
+int eegldm_usleep_elu_bn_bwd(eegldm_ctx*, const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma, float* dz,
+                             float* dgamma, float* dbeta, int B, int C, int L);
+/* MaxPool1d(2) over ConstantPad1d(1, 0) at odd L, backward: x (nrows, L), dpool (nrows, Lo), dx = (dskip ? dskip : 0) + gradient at the
+ * arg-max (equal values: the lower padded index; the pad's zero wins: dropped).  Exact. */
+int eegldm_usleep_maxpool_bwd(eegldm_ctx*, const float* x, const float* dpool, const float* dskip /* nullable */, float* dx, long nrows, int L);
+/* Classifier head + loss, forward and backward: x (B, C1, L) decoder output; weights / grads: {clf.0.weight, clf.0.bias, clf.3.weight, clf.3.bias,
+ * clf.5.weight, clf.5.bias} (grads +=); writes *loss_out, logits (B, n_classes, L / input_size) and dx (B, C1, L; 0 past S * input_size). */
+int eegldm_usleep_clf_loss(eegldm_ctx*, const float* x, const float* const* weights, float* const* grads, const int64_t* labels,
+                           const float* class_weight /* nullable */, int B, int C1, int L, int input_size, int n_classes, float grad_scale,
+                           float* loss_out, float* logits, float* dx, int* label_flag /* nullable */);
 /* First and second moments of a feature batch (N, D), accumulated in fp64 device buffers the caller zeroed: sum[D] += sum_n f[n],
  * outer[D][D] += sum_n f[n] f[n]^T.  mean = sum / N, covariance = (outer - N mean mean^T) / (N - 1) are the inputs of the Frechet
  * distance (compute_fid.py:412-414 = monai-generative FIDMetric: torch.mean, unbiased _cov, trace of the matrix square root). */

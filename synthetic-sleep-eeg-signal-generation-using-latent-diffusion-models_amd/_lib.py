@@ -203,6 +203,17 @@ SIGNATURES = {
     "eegldm_usleep_entry": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "eegldm_usleep_bind": [_vp, _vp, _vp],
     "eegldm_usleep_forward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i],
+    "eegldm_usleep_bind_grads": [_vp, _vp],
+    "eegldm_usleep_forward_train": [_vp, _vp, _vp, _i, _i],
+    "eegldm_usleep_backward": [_vp, _vp, _vp],
+    "eegldm_usleep_train_step": [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp],
+    "eegldm_usleep_label_error": [_vp, _vp],
+    "eegldm_usleep_last_launches": [_vp],
+    "eegldm_usleep_stage_loss": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp],
+    "eegldm_usleep_conv_bwd": [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "eegldm_usleep_elu_bn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i],
+    "eegldm_usleep_maxpool_bwd": [_vp, _vp, _vp, _vp, _vp, _l, _i],
+    "eegldm_usleep_clf_loss": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
     "eegldm_feature_moments": [_vp, _vp, _l, _i, _vp, _vp],
     "eegldm_knn_update": [_vp, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _l, _l, _vp, _vp],
     "eegldm_rows_sqnorm": [_vp, _vp, _l, _l, _i, _vp],
@@ -220,7 +231,7 @@ SIGNATURES = {
     "eegldm_timestep_embedding": [_vp, _vp, _vp, _i, _i],
     "eegldm_conv1d_fwd_gn": [_vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _l, _i, _i, _i, _i, _vp, _l, _vp, _l, _i],
 }
-for _n in ("eegldm_block_num_params", "eegldm_aekl_num_params", "eegldm_disc_num_params", "eegldm_disc_num_buffers", "eegldm_usleep_num_params", "eegldm_usleep_num_buffers"):
+for _n in ("eegldm_block_num_params", "eegldm_aekl_num_params", "eegldm_disc_num_params", "eegldm_disc_num_buffers", "eegldm_usleep_num_params", "eegldm_usleep_num_buffers", "eegldm_usleep_last_launches"):
     if hasattr(lib, _n):
         getattr(lib, _n).restype = C.c_long
 

@@ -1,5 +1,5 @@
 // U-Sleep feature extractor + feature statistics for the FID of /root/reference/src/compute_fid.py:341-419
-// (model: /root/reference/src/models/usleep.py:20-287).  Evaluation only: forward, fp32, (B, C, L) layout as the
+// (model: /root/reference/src/models/usleep.py:20-287).  This file: the forward (the training path is usleep_train.hip), fp32, (B, C, L) layout as the
 // reference holds it -- the channel counts are 2, 6, 9, 11, ... 214, 302 (nothing divides by 4 or 8) and the lengths run
 // 3000, 1500, 750, 375, 188, ... 3, 2, 1, so the contraction is a direct convolution over flattened (sample, position) rows, not an MFMA
 // GEMM: 6.7 MMAC per window through the encoder, HBM / launch bound.
@@ -19,21 +19,9 @@
 #include <string>
 #include <vector>
 
-#include "net.h"
+#include "usleep.h"
 
 namespace {
-constexpr int UT = 256;            // 4 waves: wave = channel group (4 output channels), lane = one of 64 flattened (sample, position) rows
-constexpr int UROWS = 64;
-constexpr int UCO = 16;            // output channels per block
-constexpr int UCI = 32;            // input channels per LDS weight stage
-constexpr int UKMAX = 16;
-
-struct ConvSrc {
-  const float* a; int Ca, La, ups;     // channels [0, Ca): a[b][ci][ups ? p / 2 : p], p < L
-  const float* b2; int Cb, Lb;         // channels [Ca, Ca + Cb): b2[b][ci - Ca][p]
-  int L;                               // common (cropped) length of the virtual input == output length
-};
-
 __device__ __forceinline__ float elu_f(float v) { return v > 0.f ? v : expm1f(v); }
 
 template <int KT>
@@ -89,8 +77,6 @@ __global__ __launch_bounds__(UT) void usleep_conv_kernel(ConvSrc s, const float*
     }
   }
 }
-
-struct BnDesc { long w, b, rm, rv, nbt, fold; int C; };
 
 // eval: fold[layer] = {gamma / sqrt(running_var + eps), beta - running_mean * that}
 __global__ void usleep_bn_fold_kernel(const BnDesc* __restrict__ tab, const float* __restrict__ params, const float* __restrict__ buffers,
@@ -175,21 +161,6 @@ __global__ __launch_bounds__(UT) void feat_accumulate_kernel(const float* __rest
   if (blockIdx.y == 0 && (threadIdx.x & 15) == 0) atomicAdd(&sum[i], s);
 }
 }  // namespace
-
-struct UConv { long w, b; int cin, cout, k; };
-struct eegldm_usleep {
-  eegldm_ctx* ctx = nullptr;
-  eegldm_usleep_cfg cfg;
-  std::vector<int> ch;
-  std::vector<Entry> entries; std::vector<int> kinds;     // reference state_dict order; kind 0 = parameter, 1 = buffer
-  long nparams = 0, nbuffers = 0, nfold = 0;
-  float* params = nullptr; float* buffers = nullptr;
-  std::vector<UConv> enc_c, pre_c, post_c; UConv bot_c, clf0, clf3, clf5;
-  std::vector<BnDesc> bns;                                  // order: encoder 0..d-1, bottom, decoder i: preskip, postskip
-  BnDesc* d_bns = nullptr; float* fold = nullptr; double* sums = nullptr;
-  Arena arena;
-  ~eegldm_usleep() { if (d_bns) (void)hipFree(d_bns); if (fold) (void)hipFree(fold); if (sums) (void)hipFree(sums); }
-};
 
 namespace {
 void add_param(eegldm_usleep* u, const std::string& name, long off, int ndim, int s0, int s1 = 0, int s2 = 0, int kind = 0) {
@@ -323,7 +294,7 @@ extern "C" int eegldm_usleep_forward(eegldm_usleep* u, const float* x, float* y_
   eegldm_ctx* ctx = u->ctx;
   const int d = u->cfg.depth, k = u->cfg.kernel_size, left = (k - 1) / 2;
   const std::vector<int>& ch = u->ch;
-  u->arena.reset();
+  u->arena.reset(); u->tape_valid = false;          // the arena held the tape of a training forward
   auto falloc = [&](long n) { return (float*)u->arena.alloc(sizeof(float) * (size_t)(n > 0 ? n : 1)); };
   if (!training) {
     hipLaunchKernelGGL(usleep_bn_fold_kernel, dim3((unsigned)u->bns.size()), dim3(64), 0, ctx->stream, u->d_bns, u->params, u->buffers, u->fold, 1e-5f);

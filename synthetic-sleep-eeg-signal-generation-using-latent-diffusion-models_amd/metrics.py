@@ -8,7 +8,8 @@ evaluation code uses:
   (multitaper, DPSS half-bandwidth 4, low-bias tapers, normalization "length").  The DPSS tapers (a few KB, once per window
   length) come from scipy on the host; everything per window runs in libeegldm (eegldm_psd_multitaper).
 * `band_powers`: integrates a PSD over the classical sleep-EEG bands.
-* `USleep(...)`, `fid_features(model, windows)`, `FIDMetric()(y_pred, y)`, `FeatureMoments`
+* `USleep(...)` (forward, `train_step`, `backward`, `predict`), `fid_features(model, windows)`, `FIDMetric()(y_pred, y)`, `FeatureMoments`
+* `balanced_class_weights(labels, n_classes)`, `stage_report(pred, true)`: class weights and the scores of a sleep stager (host numpy)
   -- the FID of /root/reference/src/compute_fid.py:341-419: the U-Sleep feature extractor (/root/reference/src/models/usleep.py:101-287,
   same constructor kwargs, state_dict keys and forward return value) runs in libeegldm (csrc/usleep.hip), the features' mean and
   covariance are accumulated on the device in fp64 (eegldm_feature_moments), and the 302 x 302 trace-of-square-root is host linear
@@ -122,7 +123,8 @@ def band_powers(psds, freqs, bands=None):
 # ---------------------------------------------------------------------------------------------------- FID on U-Sleep features
 class USleep:
     """Host-side mirror of /root/reference/src/models/usleep.py::USleep (constructor kwargs, `forward(x) -> (y_pred, x, bottom)`,
-    state_dict keys), forward only, executing on libeegldm.  `train()` / `eval()` select BatchNorm on batch or running statistics; a
+    state_dict keys), executing on libeegldm: the forward, and the training step of the stager (`train_step`, `forward_train` / `backward`,
+    `predict`; gradients in `flat_grad`).  `train()` / `eval()` select BatchNorm on batch or running statistics; a
     freshly constructed module is in TRAIN mode like any nn.Module -- /root/reference/src/compute_fid.py:357-386 never calls
     `.eval()`, so the reference's FID features are computed with batch statistics; `fid_features` below defaults to eval mode (the
     intended use of a trained stager) and takes `batch_stats=True` to reproduce the script literally."""
@@ -153,6 +155,8 @@ class USleep:
         self.flat = torch.zeros(int(lib.eegldm_usleep_num_params(h)), device=self.device)
         self.buffers = torch.zeros(int(lib.eegldm_usleep_num_buffers(h)), device=self.device)
         check(lib.eegldm_usleep_bind(h, ptr(self.flat), ptr(self.buffers)))
+        self.flat_grad = torch.zeros_like(self.flat)
+        check(lib.eegldm_usleep_bind_grads(h, ptr(self.flat_grad)))
         self.training = True
         self.load_state_dict(self._default_init())
 
@@ -233,6 +237,92 @@ class USleep:
             y = y[:, :, 0]
         return y, dec, bottom
 
+    # ---- training (csrc/usleep_train.hip): fp32 gradients in `flat_grad`, laid out as `flat`; eegldm.training.Adam / EMA / GradScaler
+    # work on this object as on the other models
+    def zero_grad(self):
+        self.flat_grad.zero_()
+
+    def sync_weights(self):
+        """fp32 model: the kernels read `flat` itself."""
+
+    def grad_dict(self):
+        return {k: self.flat_grad[o:o + n].reshape(shape) for k, (kind, o, n, shape) in self.entries.items() if kind == 0}
+
+    def _train_input(self, x):
+        x = x.to(self.device, torch.float32)
+        if x.dim() == 4:
+            x = x.permute(0, 2, 1, 3).flatten(start_dim=2)
+        if x.dim() != 3 or x.shape[1] != self.in_chans:
+            raise ValueError(f"USleep expects (B, {self.in_chans}, T) or (B, S, {self.in_chans}, T), got {tuple(x.shape)}")
+        B, _c, T = x.shape
+        check_train_shapes(B, T, self.depth, self.input_size)
+        return x.contiguous(), B, T
+
+    def forward_train(self, x):
+        """Training forward that keeps the tape for `backward`: logits (B, n_classes, S), S = T // input_size (never squeezed)."""
+        x, B, T = self._train_input(x)
+        y = torch.empty(B, self.n_classes, T // self.input_size, device=self.device)
+        check(lib.eegldm_usleep_forward_train(self.h, ptr(x), ptr(y), B, T))
+        self._tape, self._tape_x = (B, T), x          # the first conv's weight gradient reads the input: the device copy lives as long as the tape
+        return y
+
+    def backward(self, dy_pred, need_dx=False):
+        """Backward of the last `forward_train` from d(logits) (B, n_classes, S): accumulates into `flat_grad`, returns dx when asked.
+        Raises when there is no tape, or any other forward on this model (`forward`, `fid_features`, `predict`) ran in between."""
+        tape = getattr(self, "_tape", None)
+        dy = dy_pred.to(self.device, torch.float32).contiguous()
+        if tape is not None and tuple(dy.reshape(dy.shape[0], self.n_classes, -1).shape) != (tape[0], self.n_classes, tape[1] // self.input_size):
+            raise ValueError(f"dy_pred {tuple(dy.shape)} does not match the logits of the taped forward")
+        dx = torch.empty(tape[0], self.in_chans, tape[1], device=self.device) if (need_dx and tape is not None) else None
+        check(lib.eegldm_usleep_backward(self.h, ptr(dy), ptr(dx)))
+        return dx
+
+    def train_step(self, x, labels, class_weight=None, grad_scale=1.0, loss_out=None, y_pred=None):
+        """Training forward -> weighted stage cross-entropy (F.cross_entropy(weight=class_weight, ignore_index=any negative label), mean
+        reduction) -> backward, accumulating into `flat_grad`; returns the device scalar loss.  labels: (B,) or (B, S) integers.  Labels
+        given on the host are range-checked here; labels already on the device are checked by the loss kernel, which leaves an offending
+        window out and raises a flag that `label_error()` reads."""
+        x, B, T = self._train_input(x)
+        S = T // self.input_size
+        lab = check_stage_labels(labels, B, S, self.n_classes).to(self.device).contiguous()
+        cw = None
+        if class_weight is not None:
+            cw = torch.as_tensor(class_weight, dtype=torch.float32)
+            if tuple(cw.shape) != (self.n_classes,):
+                raise ValueError(f"class_weight must have shape ({self.n_classes},), got {tuple(cw.shape)}")
+            cw = cw.to(self.device).contiguous()
+        if loss_out is None:
+            loss_out = torch.zeros(1, device=self.device)
+        if y_pred is not None and (tuple(y_pred.shape) != (B, self.n_classes, S) or y_pred.dtype != torch.float32 or not y_pred.is_contiguous()):
+            raise ValueError(f"y_pred must be a contiguous float32 ({B}, {self.n_classes}, {S}) tensor")
+        check(lib.eegldm_usleep_train_step(self.h, ptr(x), ptr(lab), ptr(cw), B, T, float(grad_scale), ptr(loss_out), ptr(y_pred)))
+        self._tape, self._tape_x = (B, T), x
+        return loss_out
+
+    def label_error(self):
+        """True when a train step since the last call met a label >= n_classes in device labels (waits for the stream)."""
+        out = C.c_int(0)
+        check(lib.eegldm_usleep_label_error(self.h, C.byref(out)))
+        return bool(out.value)
+
+    def last_launches(self):
+        return int(lib.eegldm_usleep_last_launches(self.h))
+
+    def predict(self, windows, batch_size=256):
+        """Stages of single-channel windows (N, 1, T) as `fid_features` prepares them (36-sample pads of 3072-sample loader windows cropped,
+        the EEG channel duplicated when in_chans == 2), in eval mode: (stages (N,) int64, logits (N, n_classes)) on the device."""
+        was = self.training
+        self.eval()
+        try:
+            outs = []
+            for i in range(0, windows.shape[0], batch_size):
+                y, _d, _b = self.forward(_stager_input(self, windows[i:i + batch_size]))
+                outs.append(y.reshape(y.shape[0], self.n_classes, -1)[:, :, 0])
+        finally:
+            self.train(was)
+        logits = torch.cat(outs) if outs else torch.empty(0, self.n_classes, device=self.device)
+        return logits.argmax(1), logits
+
     __call__ = forward
 
     def __del__(self):
@@ -258,6 +348,88 @@ def fid_features(model, windows, batch_stats=False):
     finally:
         model.train(was)
     return bottom.squeeze(-1)
+
+
+def _stager_input(model, windows):
+    w = windows.to(model.device, torch.float32)
+    if w.dim() != 3 or w.shape[1] != 1:
+        raise ValueError(f"single-channel windows (B, 1, T) expected, got {tuple(w.shape)}")
+    if w.shape[-1] == 3072:
+        w = w[:, :, 36:-36]
+    return torch.cat([w, w], 1) if model.in_chans == 2 else w
+
+
+def usleep_bottleneck_length(T, depth):
+    for _ in range(depth):
+        T = (T + (2 if T % 2 else 0)) // 2
+    return T
+
+
+def check_train_shapes(B, T, depth, input_size):
+    """What a U-Sleep training step refuses, decided on the host before anything is launched."""
+    if B < 1:
+        raise ValueError("empty batch")
+    if T < input_size:
+        raise ValueError(f"T={T} is shorter than input_size={input_size} (the classifier's AvgPool1d window)")
+    Lb = usleep_bottleneck_length(T, depth)
+    if B * Lb < 2:
+        raise ValueError(f"train-mode BatchNorm needs more than one value per channel: B={B} x bottleneck length {Lb} (torch raises here too)")
+
+
+def check_stage_labels(labels, B, S, n_classes):
+    """labels (B,) or (B, S) integers -> (B, S) int64.  Host labels are range-checked (negative = ignored); device labels are left to the
+    loss kernel's flag, since looking at them here would wait for the device."""
+    lab = torch.as_tensor(labels)
+    if lab.is_floating_point() or lab.dtype == torch.bool:
+        raise ValueError(f"labels must be integers, got {lab.dtype}")
+    if lab.dim() == 1 and S == 1:
+        lab = lab.reshape(-1, 1)
+    if tuple(lab.shape) != (B, S):
+        raise ValueError(f"labels must have shape ({B}, {S}), got {tuple(lab.shape)}")
+    if not lab.is_cuda and lab.numel() and int(lab.max()) >= n_classes:
+        raise ValueError(f"label {int(lab.max())} is out of range for n_classes={n_classes}")
+    return lab.to(torch.int64)
+
+
+def balanced_class_weights(labels, n_classes):
+    """sklearn's class_weight='balanced': n / (n_classes * count_k) over the non-negative labels; an absent class gets 0."""
+    lab = np.asarray(torch.as_tensor(labels).cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)
+    lab = lab[lab >= 0]
+    if lab.size and int(lab.max()) >= n_classes:
+        raise ValueError(f"label {int(lab.max())} is out of range for n_classes={n_classes}")
+    count = np.bincount(lab.astype(np.int64), minlength=n_classes).astype(np.float64)
+    w = np.zeros(n_classes, dtype=np.float64)
+    w[count > 0] = lab.size / (n_classes * count[count > 0])
+    return w.astype(np.float32)
+
+
+def stage_report(pred, true, n_classes=5):
+    """Scores of a stager on the windows whose true label is non-negative (host numpy): confusion[t][p], accuracy, balanced accuracy (mean
+    recall over the classes that occur), per-class precision / recall / F1 (0 where undefined), Cohen's kappa (0 when chance agreement is 1)."""
+    p = np.asarray(torch.as_tensor(pred).cpu() if isinstance(pred, torch.Tensor) else pred).reshape(-1).astype(np.int64)
+    t = np.asarray(torch.as_tensor(true).cpu() if isinstance(true, torch.Tensor) else true).reshape(-1).astype(np.int64)
+    if p.shape != t.shape:
+        raise ValueError(f"pred {p.shape} and true {t.shape} differ in length")
+    keep = t >= 0
+    p, t = p[keep], t[keep]
+    if p.size and (int(t.max()) >= n_classes or int(p.max()) >= n_classes or int(p.min()) < 0):
+        raise ValueError(f"stage outside [0, {n_classes})")
+    cm = np.zeros((n_classes, n_classes), dtype=np.int64)
+    np.add.at(cm, (t, p), 1)
+    n = int(cm.sum())
+    tp = np.diag(cm).astype(np.float64); row = cm.sum(1).astype(np.float64); col = cm.sum(0).astype(np.float64)
+
+    def ratio(a, b):
+        return np.divide(a, b, out=np.zeros_like(a, dtype=np.float64), where=b > 0)
+
+    prec, rec = ratio(tp, col), ratio(tp, row)
+    f1 = ratio(2 * prec * rec, prec + rec)
+    acc = float(tp.sum() / n) if n else 0.0
+    bal = float(rec[row > 0].mean()) if n else 0.0
+    pe = float((row * col).sum() / (n * n)) if n else 0.0
+    kappa = (acc - pe) / (1.0 - pe) if n and pe < 1.0 else 0.0
+    return {"n": n, "confusion": cm.tolist(), "accuracy": acc, "balanced_accuracy": bal, "precision": prec.tolist(), "recall": rec.tolist(),
+            "f1": f1.tolist(), "kappa": float(kappa)}
 
 
 class FeatureMoments:

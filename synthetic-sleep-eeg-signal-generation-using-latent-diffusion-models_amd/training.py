@@ -464,6 +464,18 @@ def ldm_train_step(unet, scheduler, latents, noise, timesteps, loss_out=None, gr
     return loss_out
 
 
+def usleep_train_step(model, x, labels, class_weight=None, grad_scale=1.0, loss_out=None, grad_sync=None):
+    """One U-Sleep stager step (eegldm.metrics.USleep.train_step): training forward -> weighted stage cross-entropy -> backward, accumulating
+    into model.flat_grad; returns the device scalar loss.  grad_sync: an eegldm.distributed.OverlappedGradSync over model.flat_grad -- the
+    step has no gradient hook, so the whole buffer is reduced right after the call; the caller then only has to `grad_sync.wait()`."""
+    if grad_sync is not None:
+        grad_sync.begin()
+    loss = model.train_step(x, labels, class_weight=class_weight, grad_scale=grad_scale, loss_out=loss_out)
+    if grad_sync is not None:
+        grad_sync.finish()
+    return loss
+
+
 def dm_train_step(unet, scheduler, images, noise, timesteps, spectral_weight=0.0, spectral_loss=False, loss_out=None, grad_sync=None, grad_scale=1.0,
                   loss_weighting=None, snr_gamma=5.0, per_sample_out=None):
     """Pixel-space diffusion step of /root/reference/src/training/training_diffusion.py:141-151 (config_dm.yaml, BASELINE C5):
