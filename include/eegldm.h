@@ -49,7 +49,8 @@ extern "C" {
  *    eegldm_ldm_train_step_weighted) and global gradient-norm clipping (eegldm_grad_norm, eegldm_adam_step_clip, eegldm_grad_scale_by)
  *    and long recordings (eegldm_canvas_gather, eegldm_canvas_step, eegldm_canvas_compose, eegldm_sample_long) and their editing
  *    (eegldm_canvas_edit_step, eegldm_sample_long_edit) and resampled repair (eegldm_edit_jump, eegldm_sample_edit_resample,
- *    eegldm_sample_long_edit_resample). */
+ *    eegldm_sample_long_edit_resample) and context conditioning (eegldm_unet_create_ctx, eegldm_unet_set_context, eegldm_context_mask,
+ *    eegldm_add_noise_context, eegldm_context_window, eegldm_ldm_train_step_ctx, eegldm_sample_edit_ctx, eegldm_sample_long_edit_ctx). */
 #define EEGLDM_ABI_VERSION 8
 
 /* Storage / operand type of activations and compute-copy weights (accumulation, statistics, master weights and optimizer state are
@@ -728,6 +729,78 @@ int eegldm_sample_long_edit_resample(eegldm_unet*, eegldm_aekl* ae, const float*
                                      float inv_scale_factor, const float* jump_x_host, const float* jump_n_host, uint64_t noise_seed,
                                      float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
                                      int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class);
+
+/* ------------------------------------------------------------------ context conditioning: learned repair and continuation (additive; ABI 8)
+ * The Palette / inpainting-LDM form: the denoiser reads the kept signal and the keep-mask as extra input channels and is trained with
+ * masks drawn at random, so repair, continuation and plain generation are one model at one forward per step.  Masks: 1 = keep, 0 =
+ * regenerate (the convention of the edit entry points), one (L,) row per sample at the sampler's resolution.
+ *
+ * eegldm_unet_create_ctx: cfg->in_channels is the TOTAL input width; x has Cx = in_channels - context_channels channels, Cx == out_channels
+ * and context_channels >= 1 are required (num_classes 0: no classes).  Parameter layout and state-dict keys are those of a plain UNet with
+ * that in_channels (input_blocks.0.0.weight is [model_channels][in_channels][3]): the model is the reference UNetModel(in_channels) applied
+ * to cat([x, context], 1).
+ * eegldm_unet_set_context: context is device fp32 (rows, context_channels, L); the handle keeps the POINTER until it is cleared with NULL.
+ * A forward of B rows requires B % rows == 0 and row b reads context row b % rows (both halves of a guided 2B batch share one copy); with
+ * no context set a forward reads zeros.  The forward writes x into columns [0, Cx) and the context into columns [Cx, in_channels) of the
+ * first conv's channels-last input in one launch; everything behind the first conv is unchanged.
+ * THE CONTEXT GETS NO GRADIENT: eegldm_unet_backward on a context UNet accumulates every parameter gradient (the first conv's context
+ * columns included) and writes dx (nullable) for the Cx columns of x only.
+ * The unconditional / plain train steps (eegldm_ldm_train_step, _cond, _weighted) refuse a context UNet. */
+int eegldm_unet_create_ctx(eegldm_ctx*, const eegldm_unet_cfg* cfg, int num_classes, int context_channels, eegldm_unet** out);
+int eegldm_unet_set_context(eegldm_unet*, const float* context, int rows);
+/* The training masks.  Sample b takes the four words w0..w3 of Philox(seed, offset + b) -- advance offset by B per step, as for
+ * eegldm_label_dropout -- and u0 = (float)w0 * 2^-32 compared in fp32 as eegldm_label_dropout compares its word:
+ *   u0 < p_none                        the mask is all 0: no context (the unconditional case, and what classifier-free training needs)
+ *   else u0 < p_none + p_prefix        continuation: keep [0, s), regenerate [s, L), s = 1 + ((w1 * (L - 1)) >> 32); L == 1: all 0
+ *   else                               one span: len = span_min + ((w1 * (span_max - span_min + 1)) >> 32),
+ *                                      start = (w2 * (L - len + 1)) >> 32; regenerate [start, start + len), keep the rest
+ * (p_none + p_prefix is the fp32 sum; the ranges are 64-bit products of 32-bit words, so a numpy uint64 restatement is bit-exact).
+ * Refused before any launch: span_min < 1, span_max < span_min, span_max > L, a probability outside [0, 1], p_none + p_prefix > 1.
+ * mask: device fp32 (B, L), one launch, vector stores. */
+int eegldm_context_mask(eegldm_ctx*, float* mask, int B, int L, float p_none, float p_prefix, int span_min, int span_max, uint64_t seed,
+                        uint64_t offset);
+/* What a context train step feeds the UNet, in ONE launch: noisy = sqrt(a_t) x0 + sqrt(1 - a_t) noise (the bytes of eegldm_add_noise: one
+ * device function), context[:, :C] = m * ctx_src (ctx_src NULL: x0), context[:, C] = m; context is (B, C + 1, L), the others (B, C, L).
+ * mask (B, L) given: m is read from it and the draw's parameters are ignored.  mask == NULL: row b's mask is derived in registers from
+ * (seed, offset + b) exactly as eegldm_context_mask derives it -- no mask buffer is written or re-read, unless mask_out (nullable, (B, L))
+ * asks for a copy.  fp32, any 4-byte alignment per buffer: 16-byte accesses with a scalar head and tail wherever the buffers of a row
+ * share an offset inside a 16-byte line (always, when L % 4 == 0 and the bases do), else element by element.  No atomics, no memset, one
+ * writer per element.  No output may overlap an input or another output. */
+int eegldm_add_noise_context(eegldm_ctx*, const float* x0, const float* ctx_src, const float* noise, const int64_t* t, const float* acp,
+                             const float* mask, float p_none, float p_prefix, int span_min, int span_max, uint64_t seed, uint64_t offset,
+                             float* noisy, float* context, float* mask_out, int B, int C, int L);
+/* out = windows * upsample_nearest(mask, down): windows / out (B, Co, Lw), mask (B, Lw / down).  The masked input of the context encode: a
+ * latent next to a hole is computed by the encoder from the hole's true content, which is absent at repair time, so the LDM context is
+ * scale_factor * encode_mean(windows * upsample(mask)) in training and in sampling alike.  Exact (a multiply by the mask value). */
+int eegldm_context_window(eegldm_ctx*, const float* windows, const float* mask, int down, float* out, int B, int Co, int Lw);
+/* eegldm_ldm_train_step_weighted on a context UNet whose context_channels == out_channels + 1: eegldm_add_noise_context (ctx_latents
+ * nullable: the latents themselves; mask nullable: drawn from (mask_seed, mask_offset + b) with the draw's parameters; mask_out nullable),
+ * eegldm_unet_set_context, forward, eegldm_diffusion_loss over the WHOLE sample (the kept positions too), backward.  The context is
+ * cleared before returning.  Refuses a UNet built without context channels. */
+int eegldm_ldm_train_step_ctx(eegldm_unet*, const float* latents, const float* noise, const int64_t* t, const float* acp, int pred_type,
+                              int B, int L, float grad_scale, float* loss, const float* wtab, float* per_sample, const int64_t* labels,
+                              float p_uncond, int64_t null_class, uint64_t seed, uint64_t offset, const float* ctx_latents, const float* mask,
+                              float p_none, float p_prefix, int span_min, int span_max, uint64_t mask_seed, uint64_t mask_offset,
+                              float* mask_out);
+/* eegldm_sample_edit_resample / eegldm_sample_long_edit_resample with the context every forward reads: device (context_rows,
+ * context_channels, L) with B % context_rows == 0, or -- canvas form -- canvas-shaped (R, context_channels, Lc), gathered ONCE per call into
+ * window rows with eegldm_canvas_gather.  The loop copies the context into a buffer of its own, one row per forward row, and points the
+ * handle there: a captured graph outlives the call and never reads the caller's pointer.  context == NULL: the predecessor itself; every
+ * sampling export accepts a context UNet and then runs it on a zero context.  known == NULL with a context: the learned conditioning
+ * alone, without the replacement blend. */
+int eegldm_sample_edit_ctx(eegldm_unet*, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                           const int64_t* timesteps_host, const float* a_t_host, const float* a_prev_host, const float* cx_host,
+                           const float* c0_host, const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
+                           float inv_scale_factor, const float* jump_x_host, const float* jump_n_host, uint64_t noise_seed,
+                           float* latents_out, float* windows_out, int B, int L, int use_graph, int* graph_used_host,
+                           const int64_t* labels_host, float guidance_scale, int64_t null_class, const float* context, int context_rows);
+int eegldm_sample_long_edit_ctx(eegldm_unet*, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                                const int64_t* timesteps_host, const float* a_t_host, const float* cx_host, const float* c0_host,
+                                const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
+                                float inv_scale_factor, const float* jump_x_host, const float* jump_n_host, uint64_t noise_seed,
+                                float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
+                                int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class,
+                                const float* context, int context_rows);
 
 /* ------------------------------------------------------------------ data-parallel collectives (RCCL over xGMI)
  * One communicator per process / GPU.  Stands where the reference gathers gradients with single-process nn.DataParallel

@@ -180,6 +180,20 @@ SIGNATURES = {
     "eegldm_sample_long_edit_resample": [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f),
                                          C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _f, C.POINTER(_f), C.POINTER(_f), C.c_uint64, _vp, _vp, _i, _i,
                                          _i, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_int64), _f, C.c_int64],
+    # context conditioning (csrc/context.hip, unet.hip, sampler.hip)
+    "eegldm_unet_create_ctx": [_vp, _vp, _i, _i, C.POINTER(_vp)],
+    "eegldm_unet_set_context": [_vp, _vp, _i],
+    "eegldm_context_mask": [_vp, _vp, _i, _i, _f, _f, _i, _i, C.c_uint64, C.c_uint64],
+    "eegldm_add_noise_context": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _i, _i, _i],
+    "eegldm_context_window": [_vp, _vp, _vp, _i, _vp, _i, _i, _i],
+    "eegldm_ldm_train_step_ctx": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _f, C.c_int64, C.c_uint64, C.c_uint64,
+                                  _vp, _vp, _f, _f, _i, _i, C.c_uint64, C.c_uint64, _vp],
+    "eegldm_sample_edit_ctx": [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f),
+                               C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _f, C.POINTER(_f), C.POINTER(_f), C.c_uint64, _vp, _vp, _i, _i, _i,
+                               C.POINTER(_i), C.POINTER(C.c_int64), _f, C.c_int64, _vp, _i],
+    "eegldm_sample_long_edit_ctx": [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f),
+                                    C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _f, C.POINTER(_f), C.POINTER(_f), C.c_uint64, _vp, _vp, _i, _i,
+                                    _i, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_int64), _f, C.c_int64, _vp, _i],
     "eegldm_disc_create": [_vp, _vp, C.POINTER(_vp)],
     "eegldm_disc_destroy": [_vp],
     "eegldm_disc_num_entries": [_vp],

@@ -88,9 +88,10 @@ class FlatModule:
 # ---------------------------------------------------------------------------------------------------------------- UNet
 class _UNetFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, net, x, t, labels, _p):
-        out = net._forward_native(x, t, labels)         # (bumps net._tape_id)
+    def forward(ctx, net, x, t, labels, _p, context=None):
+        out = net._forward_native(x, t, labels, context)         # (bumps net._tape_id)
         ctx.net, ctx.tape, ctx.has_labels = net, net._tape_id, labels is not None
+        ctx.context = context                    # a context model's extra input: non-differentiable, kept for a re-forward
         ctx.save_for_backward(x, t, labels if labels is not None else t)
         return out
 
@@ -99,10 +100,10 @@ class _UNetFn(torch.autograd.Function):
         net = ctx.net
         x, t, labels = ctx.saved_tensors
         if net._tape_id != ctx.tape:             # another native call rewrote the tape since: rebuild this call's tape, with ITS labels
-            net._forward_native(x, t, labels if ctx.has_labels else None)
+            net._forward_native(x, t, labels if ctx.has_labels else None, ctx.context)
         net._adopt_grad()
         dx = net.backward(dy.contiguous(), need_dx=ctx.needs_input_grad[1])      # (bumps: the tape is consumed)
-        return None, dx, None, None, None
+        return None, dx, None, None, None, None
 
 
 # ---------------------------------------------------------------------------------------------------------------- AutoencoderKL

@@ -1,5 +1,5 @@
-// Launch geometry and the float4 body / scalar edge split shared by the streaming kernels of elementwise.hip and sampler_steps.hip.
-// Internal to those two translation units: everything here has internal linkage.
+// Launch geometry and the float4 body / scalar edge split shared by the streaming kernels of elementwise.hip, sampler_steps.hip and
+// context.hip.  Internal to those translation units: everything here has internal linkage.
 #pragma once
 #include <initializer_list>
 
@@ -40,6 +40,10 @@ inline int grid_vec(long n, long head, eegldm_ctx* ctx) {
   if (blocks < 1) blocks = 1;
   return (int)(blocks < cap ? blocks : cap);
 }
+
+// DDPMScheduler.add_noise on one element (sa = sqrt(a_t), sb = sqrt(1 - a_t)): ONE function for add_noise_kernel (sampler_steps.hip) and the
+// train step's fused add_noise_context_kernel (context.hip), so both round alike.  A plain expression, contracted the same way wherever it is inlined.
+__device__ __forceinline__ float add_noise_value(float x, float nz, float sa, float sb) { return sa * x + sb * nz; }
 
 // ------------------------------------------------------------------ Philox4x32-10 (perf-path RNG; parity runs pass noise in)
 __device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3, unsigned k0, unsigned k1) {

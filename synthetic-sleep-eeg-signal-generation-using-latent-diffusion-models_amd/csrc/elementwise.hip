@@ -47,6 +47,20 @@ __global__ __launch_bounds__(NT) void ncl_to_nlc_small_kernel(const float* __res
     for (int c = 0; c < C; c++) st_f32(dst + i * ld + c, src[(b * C + c) * L + l]);
   }
 }
+// The input rows of a context UNet (unet.hip): columns [0, Cx) from x (B, Cx, L), columns [Cx, Cx + Cc) from context row b % rows of
+// (rows, Cc, L), or zeros when there is no context.  The thread-per-position form of the kernel above: a context model's input is a few
+// channels wide (2 C + 1 for C latent or signal channels), so both sources are read coalesced along l and a thread writes its whole row.
+template <typename T>
+__global__ __launch_bounds__(NT) void ncl2_to_nlc_kernel(const float* __restrict__ x, int Cx, const float* __restrict__ cs, int Cc, int rows,
+                                                         T* __restrict__ dst, long ld, int L, long n) {
+  GRID_STRIDE(i, n) {
+    const long b = i / L; const int l = (int)(i - b * L);
+    T* d = dst + i * ld;
+    for (int c = 0; c < Cx; c++) st_f32(d + c, x[(b * Cx + c) * L + l]);
+    const long br = cs ? b % rows : 0;
+    for (int c = 0; c < Cc; c++) st_f32(d + Cx + c, cs ? cs[(br * Cc + c) * L + l] : 0.0f);
+  }
+}
 template <typename T>
 __global__ __launch_bounds__(NT) void nlc_to_ncl_small_kernel(const T* __restrict__ src, long ld, float* __restrict__ dst, int C, int L, long n) {
   GRID_STRIDE(i, n) {
@@ -659,6 +673,12 @@ __global__ void emb_gather_kernel(const float4* __restrict__ table, const int64_
 
 int ew_temb(eegldm_ctx* ctx, const int64_t* t, void* out, int B, int dim, int dtype) {
   DISPATCH_T(dtype, hipLaunchKernelGGL((temb_kernel<T>), dim3(grid1d((long)B * dim, ctx)), dim3(NT), 0, ctx->stream, t, (T*)out, B, dim));
+  LAUNCH_CHECK(); return 0;
+}
+int ew_ncl2_to_nlc(eegldm_ctx* ctx, const float* x, int Cx, const float* context, int Cc, int rows, void* dst, long ld, int B, int L, int dtype) {
+  const long n = (long)B * L;
+  DISPATCH_T(dtype, hipLaunchKernelGGL((ncl2_to_nlc_kernel<T>), dim3(grid1d(n, ctx)), dim3(NT), 0, ctx->stream, x, Cx, context, Cc, rows, (T*)dst, ld,
+                                       L, n));
   LAUNCH_CHECK(); return 0;
 }
 int ew_label_emb_add(eegldm_ctx* ctx, float* emb, long ld, const int64_t* y, const float* table, int B, int te, int K) {

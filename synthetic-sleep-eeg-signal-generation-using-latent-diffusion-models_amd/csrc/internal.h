@@ -22,6 +22,8 @@ int ew_film_silu_fwd(eegldm_ctx*, const void* hn, long ldh, const float* emb, lo
 int ew_film_silu_bwd(eegldm_ctx*, const void* hn, long ldh, const float* emb, long lde, const void* da, long ldda, void* dhn, long lddh,
                      float* demb, long ldde, int B, int L, int C, int dtype);
 int ew_copy_rows(eegldm_ctx*, void* dst, long ldd, const void* src, long lds, long rows, int C, int dtype);
+// input rows of a context UNet: dst[(b, l)][0 .. Cx) = x[b][:][l], dst[(b, l)][Cx .. Cx + Cc) = context[b % rows][:][l] (context NULL: zeros)
+int ew_ncl2_to_nlc(eegldm_ctx*, const float* x, int Cx, const float* context, int Cc, int rows, void* dst, long ld, int B, int L, int dtype);
 // class labels (unet.py:379-380,531-533): emb[b] += table[y_b] (fp32 rows of width te; labels outside [0, K) add nothing)
 int ew_label_emb_add(eegldm_ctx*, float* emb, long ld, const int64_t* y, const float* table, int B, int te, int K);
 // d table[c] += sum over b with y_b == c of demb[b], samples folded in index order (one thread per (class, column), no atomics)

@@ -135,6 +135,8 @@ int resample_backward(NetBase* u, const RsDesc& s, const RsTape& t, const View& 
 // accessors for the sampler (sampler.hip); the struct itself is private to unet.hip
 eegldm_ctx* unet_ctx(const eegldm_unet* u);
 int unet_in_channels(const eegldm_unet* u);
+int unet_x_channels(const eegldm_unet* u);            // in_channels minus the context channels: the channels of x and of the latents
+int unet_context_channels(const eegldm_unet* u);      // 0: a plain UNet
 int unet_emb_width(const eegldm_unet* u);
 long unet_embed_work_floats(const eegldm_unet* u);
 int unet_embed_table(eegldm_unet* u, const int64_t* tsteps_dev, const int64_t* labels_dev, int n, float* table, float* work);

@@ -35,6 +35,9 @@ struct SamplerState {
   // class labels: one per forward row ([labels | null_class x B] with guidance), on the device and the host copy they came from; the table
   // then has K rows per step (tab_t / tab_y: the (timestep, class) of each row) and emb_rows [rows][etot] receives each step's gathered rows
   int64_t* lab = nullptr; std::vector<int64_t> lab_host, tab_t, tab_y; int64_t* tab_y_dev = nullptr; float* emb_rows = nullptr;
+  // context UNets: the context of every forward row (one row per forward row, zeros without a context).  The handle points HERE for the
+  // duration of a call, never at the caller's buffer: a captured graph outlives the call and keeps reading this address
+  float* cx = nullptr;
 };
 std::map<GraphKey, SamplerState>& states() { static std::map<GraphKey, SamplerState> m; return m; }
 // guards the map AND serialises eegldm_sample: a call swaps ctx->stream for its duration, so two concurrent calls on contexts that
@@ -68,6 +71,7 @@ void sampler_release(const eegldm_unet* u) {
     if (s.lab) (void)hipFree(s.lab);
     if (s.tab_y_dev) (void)hipFree(s.tab_y_dev);
     if (s.emb_rows) (void)hipFree(s.emb_rows);
+    if (s.cx) (void)hipFree(s.cx);
     if (s.ev_in) (void)hipEventDestroy(s.ev_in);
     if (s.ev_out) (void)hipEventDestroy(s.ev_out);
     if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -97,6 +101,10 @@ struct LongBlock { int R, W, m, r; float *canvas_out, *recording_out; };
 // back up to the level a_t[i] with noise drawn inside the kernel: Philox key `seed`, jump k of the call at offset k * ceil(elements / 4).
 // The hist buffers are not cleared: c1[i] == 0 behind a jump keeps the step from reading them.
 struct ResampleBlock { const float *jump_x, *jump_n; uint64_t seed; };
+// context / context_rows (eegldm_sample_edit_ctx / eegldm_sample_long_edit_ctx on a UNet from eegldm_unet_create_ctx; NULL otherwise): device
+// (rows, context_channels, L) with B % rows == 0 -- sample b reads row b % rows -- or, with lg, canvas-shaped (R, context_channels, Lc), gathered
+// once into window rows.  The loop copies it into the state's own buffer (one row per forward row, both halves of a guided batch) and
+// points the handle there; a context UNet without a context runs on zeros.
 // One call of the loop.  The exports fill the leading members in the order of their own argument lists and name the rest.
 struct SampleCall {
   eegldm_unet* u; eegldm_aekl* ae; const float* noise; const int64_t* timesteps; const float* a_t; int n_steps, pred_type, clip_sample;
@@ -104,6 +112,7 @@ struct SampleCall {
   int64_t null_class;
   const float *a_prev = nullptr, *beta_t = nullptr; int ancestral = 0; uint64_t noise_seed = 0;      // the DDIM / DDPM step
   const MultistepCoef* ms = nullptr; const EditBlock* ed = nullptr; const LongBlock* lg = nullptr; const ResampleBlock* rs = nullptr;
+  const float* context = nullptr; int context_rows = 0;
 };
 static int sample_impl(const SampleCall& q) {
   eegldm_unet* const u = q.u; eegldm_aekl* const ae = q.ae;
@@ -118,8 +127,11 @@ static int sample_impl(const SampleCall& q) {
   EEG_CHECK(!ed || (ed->known && !q.ancestral), "editing needs the known signal and a deterministic step");
   EEG_CHECK(!ed || !ms || ed->a_next, "the multistep form needs a_next");
   eegldm_ctx* ctx = unet_ctx(u);
-  const int C = unet_in_channels(u);
-  EEG_CHECK(unet_out_channels(u) == C, "sampling needs in_channels == out_channels");
+  const int C = unet_x_channels(u), Cc = unet_context_channels(u);
+  EEG_CHECK(unet_out_channels(u) == C, "sampling needs x channels == out_channels");
+  EEG_CHECK(!q.context || Cc > 0, "a context for a UNet built without context channels");
+  EEG_CHECK(!q.context || (lg ? q.context_rows == lg->R : (q.context_rows >= 1 && B % q.context_rows == 0)),
+            "%d context rows: the canvas form needs one per recording, the others a divisor of B = %d", q.context_rows, B);
   EEG_CHECK(!ae || aekl_ctx(ae) == ctx, "the autoencoder and the UNet must share one context");
   const int K = unet_num_classes(u);
   const bool cond = q.labels != nullptr;
@@ -144,6 +156,8 @@ static int sample_impl(const SampleCall& q) {
     HIP_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
   }
   if (cond && !s.lab) HIP_TRY(hipMalloc(&s.lab, sizeof(int64_t) * Bf));
+  const long ncx = (long)B * Cc * L;                                 // context values of one half of the forward rows
+  if (Cc > 0 && !s.cx) HIP_TRY(hipMalloc(&s.cx, sizeof(float) * (size_t)Bf * Cc * L));
   if (ms && !lg && !s.hist) HIP_TRY(hipMalloc(&s.hist, sizeof(float) * nf));      // (nf: the state is shared like nz)
   const int Sl = lg ? L - (2 * lg->m + lg->r) : 0;                 // (checked by the first eegldm_canvas_gather / eegldm_canvas_step below)
   const long Lc = lg ? (long)(lg->W - 1) * Sl + L : 0, ncv = lg ? (long)lg->R * C * Lc : 0;
@@ -172,6 +186,17 @@ static int sample_impl(const SampleCall& q) {
   } else if (ed) EEG_TRY(eegldm_edit_start(ctx, ed->known, 1.0f, q.noise, q.a_t[0], nullptr, s.x, n));
   else HIP_TRY(hipMemcpyAsync(s.x, q.noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
   if (guided && !lg) HIP_TRY(hipMemcpyAsync(s.x + n, ed ? s.x : q.noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));     // the null-class half: same latents
+  struct ClearContext { eegldm_unet* u; ~ClearContext() { if (u) (void)eegldm_unet_set_context(u, nullptr, 0); } } clear_context{Cc > 0 ? u : nullptr};
+  if (Cc > 0) {
+    if (!q.context) HIP_TRY(hipMemsetAsync(s.cx, 0, sizeof(float) * (size_t)Bf * Cc * L, run));
+    else if (lg) EEG_TRY(eegldm_canvas_gather(ctx, q.context, lg->R, Cc, lg->W, L, Sl, s.cx, guided ? s.cx + ncx : nullptr));
+    else {
+      const long nrow = (long)q.context_rows * Cc * L;
+      for (long k = 0; k < (long)Bf / q.context_rows; k++)
+        HIP_TRY(hipMemcpyAsync(s.cx + k * nrow, q.context, sizeof(float) * nrow, hipMemcpyDeviceToDevice, run));
+    }
+    EEG_TRY(eegldm_unet_set_context(u, s.cx, Bf));
+  }
   if (cond) {
     HIP_TRY(hipStreamSynchronize(run));             // (the host arrays below are rewritten: an earlier call's copies from them must be done)
     s.lab_host.assign(q.labels, q.labels + B);
@@ -516,5 +541,67 @@ extern "C" int eegldm_sample_long_edit_resample(eegldm_unet* u, eegldm_aekl* ae,
   SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, nullptr, nullptr, R * W, L, use_graph,
                graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
   q.ms = &ms; q.lg = &lg; q.ed = &ed; q.rs = &rs;
+  return sample_impl(q);
+}
+
+// Learned repair (include/eegldm.h): the two exports above on a context UNet, with the context every forward reads.  context == NULL is the
+// predecessor itself (a context UNet then runs on zeros); jump_x_host == jump_n_host == NULL is the plain edit loop with a context.
+extern "C" int eegldm_sample_edit_ctx(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                                      const int64_t* timesteps_host, const float* a_t_host, const float* a_prev_host, const float* cx_host,
+                                      const float* c0_host, const float* c1_host, const float* a_next_host, int n_steps, int pred_type,
+                                      int clip_sample, float inv_scale_factor, const float* jump_x_host, const float* jump_n_host,
+                                      uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
+                                      int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class,
+                                      const float* context, int context_rows) {
+  if (!context)
+    return eegldm_sample_edit_resample(u, ae, noise, known, mask, timesteps_host, a_t_host, a_prev_host, cx_host, c0_host, c1_host, a_next_host,
+                                       n_steps, pred_type, clip_sample, inv_scale_factor, jump_x_host, jump_n_host, noise_seed, latents_out,
+                                       windows_out, B, L, use_graph, graph_used_host, labels_host, guidance_scale, null_class);
+  const bool jumps = jump_x_host || jump_n_host;
+  EEG_TRY(sample_preamble(u, cx_host != nullptr, cx_host, c0_host, c1_host, n_steps, 1, 1, "the first executed step", labels_host, guidance_scale));
+  if (jumps) EEG_TRY(resample_preamble(jump_x_host, jump_n_host, cx_host ? c1_host : nullptr, n_steps, known, mask));
+  EEG_CHECK(known || !mask, "a mask needs the known signal");
+  EEG_CHECK(cx_host || a_prev_host, "the DDIM form needs a_prev_host");
+  EEG_CHECK(!cx_host || !known || a_next_host, "the multistep form needs a_next_host");
+  const MultistepCoef ms{cx_host, c0_host, c1_host};
+  const EditBlock ed{known, mask, a_next_host};
+  const ResampleBlock rs{jump_x_host, jump_n_host, noise_seed};
+  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph,
+               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
+  if (cx_host) q.ms = &ms; else q.a_prev = a_prev_host;
+  if (known) q.ed = &ed;
+  if (jumps) q.rs = &rs;
+  q.context = context; q.context_rows = context_rows;
+  return sample_impl(q);
+}
+
+// The same on the canvas: context is canvas-shaped (R, context_channels, Lc), gathered once per call into window rows.
+extern "C" int eegldm_sample_long_edit_ctx(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                                           const int64_t* timesteps_host, const float* a_t_host, const float* cx_host, const float* c0_host,
+                                           const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
+                                           float inv_scale_factor, const float* jump_x_host, const float* jump_n_host, uint64_t noise_seed,
+                                           float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
+                                           int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class,
+                                           const float* context, int context_rows) {
+  if (!context)
+    return eegldm_sample_long_edit_resample(u, ae, noise, known, mask, timesteps_host, a_t_host, cx_host, c0_host, c1_host, a_next_host, n_steps,
+                                            pred_type, clip_sample, inv_scale_factor, jump_x_host, jump_n_host, noise_seed, canvas_out, recording_out,
+                                            R, W, L, m, r, use_graph, graph_used_host, labels_host, guidance_scale, null_class);
+  const bool jumps = jump_x_host || jump_n_host;
+  EEG_CHECK(known || !mask, "a mask needs the known signal");
+  EEG_CHECK(!known || a_next_host, "the run from an input needs a_next_host");
+  EEG_TRY(sample_preamble(u, true, cx_host, c0_host, c1_host, n_steps, R, W, known ? "the first executed step" : "step 0", labels_host,
+                          guidance_scale));
+  if (jumps) EEG_TRY(resample_preamble(jump_x_host, jump_n_host, c1_host, n_steps, known, mask));
+  const MultistepCoef ms{cx_host, c0_host, c1_host};
+  const EditBlock ed{known, mask, a_next_host};
+  const LongBlock lg{R, W, m, r, canvas_out, recording_out};
+  const ResampleBlock rs{jump_x_host, jump_n_host, noise_seed};
+  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, nullptr, nullptr, R * W, L, use_graph,
+               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
+  q.ms = &ms; q.lg = &lg;
+  if (known) q.ed = &ed;
+  if (jumps) q.rs = &rs;
+  q.context = context; q.context_rows = context_rows;
   return sample_impl(q);
 }

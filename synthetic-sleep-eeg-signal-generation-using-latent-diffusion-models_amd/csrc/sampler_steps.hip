@@ -31,7 +31,7 @@ __global__ void add_noise_kernel(const float* __restrict__ x, const float* __res
   GRID_STRIDE(i, n) {
     const float a = acp[t[i / per]];
     const float sa = sqrtf(a), sb = sqrtf(1.0f - a);
-    out[i] = velocity ? (sa * nz[i] - sb * x[i]) : (sa * x[i] + sb * nz[i]);
+    out[i] = velocity ? (sa * nz[i] - sb * x[i]) : add_noise_value(x[i], nz[i], sa, sb);
   }
 }
 __global__ void ddim_step_kernel(const float* __restrict__ mo, const float* __restrict__ x, float a_t, float a_prev, int pred,

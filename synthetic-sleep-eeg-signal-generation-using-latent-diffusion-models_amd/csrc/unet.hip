@@ -54,6 +54,9 @@ struct eegldm_unet : NetBase {
   // slice the grad hook reports early (its gradient is complete only after the embedding-MLP backward)
   int num_classes = 0; long off_label = -1;
   int64_t* labels = nullptr;     // tape: the labels the latest forward used (after any label dropout), a copy in the arena
+  // ---- context conditioning (eegldm_unet_create_ctx): the last context_channels input channels of the first conv come from `context`
+  // (device fp32 (context_rows, context_channels, L), the caller's until cleared; NULL reads zeros); forward row b reads row b % context_rows
+  int context_channels = 0; const float* context = nullptr; int context_rows = 0;
 };
 
 namespace {
@@ -231,7 +234,7 @@ int block_backward(eegldm_unet* u, const Block& b, View dout, const View& dx_des
 }  // namespace
 
 // ================================================================== C ABI
-static int unet_create(eegldm_ctx* ctx, const eegldm_unet_cfg* cfg, int num_classes, eegldm_unet** out) {
+static int unet_create(eegldm_ctx* ctx, const eegldm_unet_cfg* cfg, int num_classes, eegldm_unet** out, int context_channels = 0) {
   EEG_CHECK(ctx && cfg && out, "null argument");
   EEG_CHECK(cfg->num_heads >= 0 && cfg->num_heads <= 64 && cfg->num_heads_upsample <= 64, "bad num_heads");
   {      // every attention block: channels divisible by its head count, and head width a multiple of 8 (16-byte column views of the qkv rows)
@@ -248,7 +251,7 @@ static int unet_create(eegldm_ctx* ctx, const eegldm_unet_cfg* cfg, int num_clas
   EEG_CHECK(cfg->n_mult >= 1 && cfg->n_mult <= 8 && cfg->n_attn >= 0 && cfg->n_attn <= 8, "bad channel_mult / attention_resolutions");
   EEG_CHECK(cfg->dtype == EEGLDM_F32 || cfg->dtype == EEGLDM_BF16 || cfg->dtype == EEGLDM_F16, "bad dtype");
   eegldm_unet* u = new eegldm_unet();
-  u->ctx = ctx; u->cfg = *cfg; u->dtype = cfg->dtype; u->num_classes = num_classes;
+  u->ctx = ctx; u->cfg = *cfg; u->dtype = cfg->dtype; u->num_classes = num_classes; u->context_channels = context_channels;
   int rc = build_plan(u);
   if (rc) { delete u; return rc; }
   *out = u;
@@ -259,6 +262,26 @@ extern "C" int eegldm_unet_create_cond(eegldm_ctx* ctx, const eegldm_unet_cfg* c
   EEG_CHECK(num_classes >= 1 && num_classes <= (1 << 20), "num_classes=%d must be >= 1", num_classes);
   return unet_create(ctx, cfg, num_classes, out);
 }
+// A UNet whose input is [x | context]: cfg->in_channels is the TOTAL width, so the parameter layout and the state-dict keys are those of a
+// plain UNet with that in_channels; x has in_channels - context_channels == out_channels channels.
+extern "C" int eegldm_unet_create_ctx(eegldm_ctx* ctx, const eegldm_unet_cfg* cfg, int num_classes, int context_channels, eegldm_unet** out) {
+  EEG_CHECK(cfg, "null argument");
+  EEG_CHECK(num_classes >= 0 && num_classes <= (1 << 20), "num_classes=%d must be >= 0 (0: none)", num_classes);
+  EEG_CHECK(context_channels >= 1 && cfg->in_channels - context_channels == cfg->out_channels,
+            "context_channels=%d must be >= 1 and leave in_channels - context_channels = %d equal to out_channels = %d", context_channels,
+            cfg->in_channels - context_channels, cfg->out_channels);
+  return unet_create(ctx, cfg, num_classes, out, context_channels);
+}
+extern "C" int eegldm_unet_set_context(eegldm_unet* u, const float* context, int rows) {
+  EEG_CHECK(u, "null unet");
+  EEG_CHECK(u->context_channels > 0, "this UNet was built without context channels (eegldm_unet_create_ctx)");
+  EEG_CHECK(!context || rows >= 1, "context rows %d must be >= 1", rows);
+  EEG_CHECK(((uintptr_t)context & 3) == 0, "buffers must be 4-byte aligned");
+  u->context = context; u->context_rows = context ? rows : 0;
+  return 0;
+}
+int unet_context_channels(const eegldm_unet* u) { return u->context_channels; }
+int unet_x_channels(const eegldm_unet* u) { return u->cfg.in_channels - u->context_channels; }
 int unet_num_classes(const eegldm_unet* u) { return u->num_classes; }
 eegldm_ctx* unet_ctx(const eegldm_unet* u) { return u->ctx; }
 int unet_in_channels(const eegldm_unet* u) { return u->cfg.in_channels; }
@@ -333,6 +356,7 @@ static int unet_forward_impl(eegldm_unet* u, const float* x, const int64_t* tste
   EEG_CHECK(u && x && tsteps && y, "null argument");
   EEG_CHECK(u->params, "bind parameters first");
   EEG_CHECK(B > 0 && L > 0 && (L % (1 << (u->cfg.n_mult - 1))) == 0, "L=%d must be divisible by 2^(levels-1)", L);
+  EEG_CHECK(!u->context || B % u->context_rows == 0, "a forward of %d rows cannot share %d context rows (B %% rows != 0)", B, u->context_rows);
   eegldm_ctx* ctx = u->ctx; const int dt = u->dtype; const int mc = u->mc, te = u->te;
   u->arena.reset(); u->rt.clear(); u->at.clear(); u->st.clear(); u->in_out.clear(); u->cat.clear();
   u->B = B; u->L = L; u->have_tape = false; u->training = training != 0;
@@ -398,7 +422,10 @@ static int unet_forward_impl(eegldm_unet* u, const float* x, const int64_t* tste
 
   // ---- input path
   ALLOC_OR_FAIL(u->x0.p, u->alloc_act((long)B * L, u->cfg.in_channels)); u->x0.ld = u->cfg.in_channels; u->x0.C = u->cfg.in_channels;
-  EEG_TRY(eegldm_ncl_to_nlc(ctx, x, u->x0.p, u->x0.ld, B, u->cfg.in_channels, L, dt));
+  if (u->context_channels > 0) {      // [x | context] side by side in the channels-last rows, one launch; the first conv below reads them as one input
+    EEG_TRY(ew_ncl2_to_nlc(ctx, x, u->cfg.in_channels - u->context_channels, u->context, u->context_channels, u->context_rows, u->x0.p, u->x0.ld,
+                           B, L, dt));
+  } else EEG_TRY(eegldm_ncl_to_nlc(ctx, x, u->x0.p, u->x0.ld, B, u->cfg.in_channels, L, dt));
   EEG_TRY(op_conv_fwd(ctx, dt, u->x0.p, u->x0.ld, u->W(u->off_cin_w), u->P(u->off_cin_b), u->in_out[0].p, u->in_out[0].ld, B, L,
                       u->cfg.in_channels, mc, 3, 1, 1, 1, nullptr, 0, nullptr, 0));
   View h = u->in_out[0]; int Lc = L;
@@ -516,7 +543,7 @@ extern "C" int eegldm_unet_backward(eegldm_unet* u, const float* dy, float* dx_o
   if (dx_out) {
     void* dx0; ALLOC_OR_FAIL(dx0, u->alloc_act((long)B * L, cin));
     EEG_TRY(op_conv_dgrad(ctx, dt, dout.p, dout.ld, u->W(u->off_cin_w), dx0, cin, B, L, cin, mc, 3, 1, 1, 1, nullptr, 0));
-    EEG_TRY(eegldm_nlc_to_ncl(ctx, dx0, cin, dx_out, B, cin, L, dt));
+    EEG_TRY(eegldm_nlc_to_ncl(ctx, dx0, cin, dx_out, B, cin - u->context_channels, L, dt));      // the x columns only: the context gets no gradient
   }
   // ---- embedding MLP backward (fp32)
   const int E = u->etot, F = EEGLDM_F32;
@@ -541,23 +568,32 @@ extern "C" int eegldm_unet_backward(eegldm_unet* u, const float* dy, float* dx_o
   return 0;
 }
 
+// cx (eegldm_ldm_train_step_ctx; NULL otherwise): what the step's context is formed from, the arguments of eegldm_add_noise_context
+struct CtxArg { const float *src, *mask; float p_none, p_prefix; int span_min, span_max; uint64_t seed, offset; float* mask_out; };
 static int ldm_train_step(eegldm_unet* u, const float* latents, const float* noise, const int64_t* t, const float* acp,
                           int pred_type, int B, int L, float grad_scale, float* loss, const LabelArg& lab, bool weighted = false,
-                          const float* wtab = nullptr, float* per_sample = nullptr) {
+                          const float* wtab = nullptr, float* per_sample = nullptr, const CtxArg* cx = nullptr) {
   EEG_CHECK(u && latents && noise && t && acp && loss, "null argument");
   EEG_CHECK(pred_type == EEGLDM_PRED_EPSILON || pred_type == EEGLDM_PRED_V, "prediction type must be epsilon or v_prediction");
   eegldm_ctx* ctx = u->ctx;
-  const int C = u->cfg.in_channels;
-  EEG_CHECK(u->cfg.out_channels == C, "LDM training needs in_channels == out_channels");
-  const long n = (long)B * C * L;
+  const int C = u->cfg.in_channels - u->context_channels;
+  EEG_CHECK(cx || u->context_channels == 0, "this UNet takes a context (%d channels): use eegldm_ldm_train_step_ctx", u->context_channels);
+  EEG_CHECK(u->cfg.out_channels == C, "LDM training needs x channels == out_channels");
+  const long n = (long)B * C * L, nctx = cx ? (long)B * (C + 1) * L : 0;
   // small fp32 NCL staging buffers; they must outlive the arena reset inside forward, so they live in a side arena block
   static thread_local float* stage = nullptr; static thread_local size_t stage_cap = 0;
-  if (stage_cap < (size_t)n * 4) {
+  if (stage_cap < (size_t)(n * 4 + nctx)) {
     if (stage) hipFree(stage);
-    HIP_TRY(hipMalloc(&stage, sizeof(float) * n * 4)); stage_cap = (size_t)n * 4;
+    stage = nullptr; stage_cap = 0;
+    HIP_TRY(hipMalloc(&stage, sizeof(float) * (n * 4 + nctx))); stage_cap = (size_t)(n * 4 + nctx);
   }
-  float *noisy = stage, *pred = stage + n, *target = stage + 2 * n, *dpred = stage + 3 * n;
-  EEG_TRY(eegldm_add_noise(ctx, latents, noise, t, acp, noisy, B, (long)C * L));
+  float *noisy = stage, *pred = stage + n, *target = stage + 2 * n, *dpred = stage + 3 * n, *context = stage + 4 * n;
+  struct ClearContext { eegldm_unet* u; ~ClearContext() { if (u) { u->context = nullptr; u->context_rows = 0; } } } clear_context{cx ? u : nullptr};
+  if (cx) {      // noisy, [m * src | m]: one launch, the mask drawn in registers unless the caller gives one
+    EEG_TRY(eegldm_add_noise_context(ctx, latents, cx->src, noise, t, acp, cx->mask, cx->p_none, cx->p_prefix, cx->span_min, cx->span_max, cx->seed,
+                                     cx->offset, noisy, context, cx->mask_out, B, C, L));
+    u->context = context; u->context_rows = B;
+  } else EEG_TRY(eegldm_add_noise(ctx, latents, noise, t, acp, noisy, B, (long)C * L));
   EEG_TRY(unet_forward_impl(u, noisy, t, lab, pred, B, L, 1));
   if (weighted) {      // target in registers, per-sample weight and losses: no target pass, no memset, no atomics (loss kernel + one-block fold)
     EEG_TRY(eegldm_diffusion_loss(ctx, pred, latents, noise, t, acp, wtab, pred_type, B, (long)C * L, grad_scale, loss, per_sample, dpred));
@@ -601,4 +637,27 @@ extern "C" int eegldm_ldm_train_step_weighted(eegldm_unet* u, const float* laten
     lab.y = labels; lab.p_uncond = p_uncond; lab.null_class = null_class; lab.seed = seed; lab.offset = offset;
   }
   return ldm_train_step(u, latents, noise, t, acp, pred_type, B, L, grad_scale, loss, lab, true, wtab, per_sample);
+}
+// The weighted step on a context UNet (include/eegldm.h): eegldm_add_noise_context in place of eegldm_add_noise, the context set for the
+// forward and cleared before returning, the loss over the whole sample.
+extern "C" int eegldm_ldm_train_step_ctx(eegldm_unet* u, const float* latents, const float* noise, const int64_t* t, const float* acp, int pred_type,
+                                         int B, int L, float grad_scale, float* loss, const float* wtab, float* per_sample, const int64_t* labels,
+                                         float p_uncond, int64_t null_class, uint64_t seed, uint64_t offset, const float* ctx_latents,
+                                         const float* mask, float p_none, float p_prefix, int span_min, int span_max, uint64_t mask_seed,
+                                         uint64_t mask_offset, float* mask_out) {
+  EEG_CHECK(u, "null unet");
+  EEG_CHECK(u->context_channels > 0, "this UNet was built without context channels: use eegldm_ldm_train_step_weighted");
+  EEG_CHECK(u->context_channels == u->cfg.out_channels + 1, "the step forms a context of out_channels + 1 = %d channels, this UNet takes %d",
+            u->cfg.out_channels + 1, u->context_channels);
+  const CtxArg cx{ctx_latents, mask, p_none, p_prefix, span_min, span_max, mask_seed, mask_offset, mask_out};
+  LabelArg lab;
+  if (u->num_classes == 0) EEG_CHECK(!labels, "this UNet was built without classes: pass labels = NULL");
+  else {
+    EEG_CHECK(labels, "this UNet is class-conditional (%d classes): labels are required", u->num_classes);
+    EEG_CHECK(p_uncond >= 0.0f && p_uncond <= 1.0f, "p_uncond %g outside [0, 1]", (double)p_uncond);
+    EEG_CHECK(p_uncond == 0.0f || (null_class >= 0 && null_class < u->num_classes), "null_class %lld outside [0, %d)", (long long)null_class,
+              u->num_classes);
+    lab.y = labels; lab.p_uncond = p_uncond; lab.null_class = null_class; lab.seed = seed; lab.offset = offset;
+  }
+  return ldm_train_step(u, latents, noise, t, acp, pred_type, B, L, grad_scale, loss, lab, true, wtab, per_sample, &cx);
 }

@@ -250,6 +250,87 @@ def loss_weighting_resume(args, ck):
                          "or resume with the checkpoint's setting")
 
 
+def add_context_args(p):
+    p.add_argument("--context", action="store_true", help="train a context-conditioned UNet (learned repair / continuation): "
+                   "UNetModel(in_channels=2 C + 1, context_channels=C + 1) sees the kept signal and the keep-mask as extra input channels, "
+                   "with masks drawn at random on the device; adds the 'context' entry to checkpoint.pth")
+    p.add_argument("--ctx_p_none", type=float, default=None, help="share of samples trained without any context (default 0.1)")
+    p.add_argument("--ctx_p_prefix", type=float, default=None, help="share of samples trained as a continuation: keep a prefix (default 0.3)")
+    p.add_argument("--ctx_span_min", type=int, default=None, help="shortest regenerated span, in positions of the sampler's resolution "
+                   "(default L / 32: a convention, not measured on sleep data)")
+    p.add_argument("--ctx_span_max", type=int, default=None, help="longest regenerated span (default L / 2: a convention, not measured on sleep data)")
+
+
+_CONTEXT_FLAGS = (("p_none", "ctx_p_none"), ("p_prefix", "ctx_p_prefix"), ("span_min", "ctx_span_min"), ("span_max", "ctx_span_max"))
+
+
+def context_entry(args, channels, L=None):
+    """The 'context' entry of checkpoint.pth for the parsed flags -- {context_channels, p_none, p_prefix, span_min, span_max} with the
+    defaults filled in for sequences of L positions and checked (ValueError) -- or None without --context.  L None (before the data is
+    known): only what the flags themselves can get wrong is checked, and the spans of the result are placeholders."""
+    from ..training import context_draw_args
+    given = [flag for _k, flag in _CONTEXT_FLAGS if getattr(args, flag, None) is not None]
+    if not getattr(args, "context", False):
+        if given:
+            raise ValueError(f"--{given[0]} needs --context")
+        return None
+    spec = {k: getattr(args, flag) for k, flag in _CONTEXT_FLAGS if getattr(args, flag, None) is not None}
+    if L is None:
+        spec.setdefault("span_min", 1); spec.setdefault("span_max", max(1, spec["span_min"]))
+        L = max(1, spec["span_max"])
+    p_none, p_prefix, span_min, span_max = context_draw_args(spec, L)
+    return {"context_channels": int(channels) + 1, "p_none": p_none, "p_prefix": p_prefix, "span_min": span_min, "span_max": span_max}
+
+
+def context_resume(args, ck):
+    """checkpoint.pth against the command line, before the model is built: a checkpoint trained with --context restores the flag and every
+    draw parameter that was not given; a contradicting flag -- another value, or --context against a checkpoint without the entry -- is
+    refused (the first conv would not even have the checkpoint's shape)."""
+    saved = ck.get("context")
+    if saved is None:
+        if getattr(args, "context", False):
+            raise ValueError("checkpoint.pth was trained without --context: start a new run directory")
+        return
+    args.context = True
+    for k, flag in _CONTEXT_FLAGS:
+        mine = getattr(args, flag, None)
+        if mine is None:
+            setattr(args, flag, saved[k])
+        elif type(saved[k])(mine) != saved[k]:
+            raise ValueError(f"checkpoint.pth was trained with context {k} = {saved[k]}, the command line asks for {mine}: start a new run "
+                             "directory or resume with the checkpoint's setting")
+
+
+def context_of_checkpoint(ck, out_channels=None):
+    """How the scripts recognise a context model -> context_channels, or 0.  ck: what torch.load gave -- a checkpoint.pth (its 'context'
+    entry) or a bare state dict (input_blocks.0.0.weight has 2 * out + 1 input channels, out from out.2.weight unless given)."""
+    if isinstance(ck.get("context"), dict):
+        return int(ck["context"]["context_channels"])
+    sd = ck.get("diffusion", ck)
+    sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+    w = sd.get("input_blocks.0.0.weight")
+    if w is None or "out.2.weight" not in sd:
+        return 0
+    out = int(sd["out.2.weight"].shape[0]) if out_channels is None else int(out_channels)
+    return out + 1 if int(w.shape[1]) == 2 * out + 1 else 0
+
+
+def context_model_kwargs(up, weights, diffusion_path=None):
+    """For the sampling scripts: recognise a context model -- by the 'context' entry of {diffusion_path}/checkpoint.pth when there is one,
+    else by the first conv of the state dict `weights` -- and widen the UNet parameters `up` (in place) to in_channels = 2 C + 1.
+    -> the extra UNetModel keywords ({} for a plain model)."""
+    cc = 0
+    ck_path = os.path.join(diffusion_path, "checkpoint.pth") if diffusion_path else None
+    if ck_path and os.path.exists(ck_path):
+        cc = context_of_checkpoint(torch.load(ck_path, map_location="cpu"), up["out_channels"])
+    else:
+        cc = context_of_checkpoint(weights, up["out_channels"])
+    if not cc:
+        return {}
+    up["in_channels"] = int(up["out_channels"]) + cc
+    return {"context_channels": cc}
+
+
 def _positive_float(text):
     x = float(text)
     if not x > 0.0:
@@ -375,6 +456,7 @@ def ema_resume(ema, ck, rank=0):
 def rng_seed(base_seed, role, rank=0, world=1):
     """Distinct Philox key per (role, rank): base * 2^20 + role * 4096 + rank.  Roles: 1 timesteps, 2 posterior eps, 3 diffusion
     noise, 4 autoencoder eps, 5-7 validation draws, 8 training loader (crop / shuffle / synthetic windows), 9 validation loader,
-    10 label dropout of classifier-free guidance training (p_uncond).  (seed + role + rank collides across ranks: rank r's noise stream == rank r+1's eps stream.)"""
+    10 label dropout of classifier-free guidance training (p_uncond), 11 context masks of training (--context), 12 context masks of the
+    validation.  (seed + role + rank collides across ranks: rank r's noise stream == rank r+1's eps stream.)"""
     assert 0 <= rank < 4096 and 0 <= role < 256
     return (int(base_seed) << 20) + (int(role) << 12) + int(rank)

@@ -24,7 +24,7 @@ import torch
 from ..models import AutoencoderKL, UNetModel
 from ..sampling import long_layout, make_sampling_scheduler, sample_long, window_labels_from_hypnogram
 from ..training import randn
-from .common import load_config
+from .common import context_model_kwargs, load_config
 from .sample_long import CROP, SFREQ, WINDOW, layout_json, load_hypnogram
 
 
@@ -41,6 +41,8 @@ def parse_args(argv=None):
     p.add_argument("--mask_span", action="append", default=[], metavar="START:STOP", help="input samples to regenerate (repeatable)")
     p.add_argument("--mask_erode", type=int, default=0, help="shrink the latent keep-mask by this many samples beside every regenerated span")
     p.add_argument("--no_composite", action="store_true")
+    p.add_argument("--no_blend", action="store_true", help="a context model only (a checkpoint trained with --context, recognised by itself): use the "
+                   "learned conditioning alone instead of also resetting the kept canvas positions after every step")
     p.add_argument("--extend_minutes", type=float, default=0.0, help="continue the recording by at least this many minutes")
     p.add_argument("--margin", type=int, default=None, help="zero-weight positions at a window edge that has a neighbour (default 2 * 36 / down)")
     p.add_argument("--ramp", type=int, default=None, help="positions of the linear cross-fade (default 4 * 36 / down)")
@@ -202,20 +204,24 @@ def main(args):
         else:
             raise ValueError("a class-conditional UNet needs --hypnogram or --class_label")
     guided = labels is not None and args.null_class is not None
-    unet = UNetModel(**up, dtype=args.dtype, device=local)
     weights = os.path.join(args.diffusion_path, "best_model_ema.pth" if args.use_ema else "best_model.pth")
     if args.use_ema and not os.path.exists(weights):
         raise FileNotFoundError(f"--use_ema: {weights} not found (train with --ema_decay to have it written)")
-    unet.load_state_dict(torch.load(weights, map_location="cpu"))
+    sd = torch.load(weights, map_location="cpu")
+    # (a context model -- trained with --context -- is recognised by its checkpoint: in_channels = 2 C + 1, the context formed by the sampler)
+    ckw = context_model_kwargs(up, sd, args.diffusion_path)      # (widens up["in_channels"]: ahead of the constructor call)
+    unet = UNetModel(**up, dtype=args.dtype, device=local, **ckw)
+    unet.load_state_dict(sd)
     sched = make_sampling_scheduler(args.num_inference_steps, prediction_type=args.prediction_type, device=local, sampler="dpmpp_2m",
                                     solver_order=args.solver_order)
-    noise = randn(unet.ctx, (R, unet.in_channels, lay.canvas_len), seed=args.seed)
+    noise = randn(unet.ctx, (R, unet.x_channels, lay.canvas_len), seed=args.seed)
     info = {}
     rec, _canvas = sample_long(unet, stage1, sched, noise, lay.n_windows, margin=lay.margin, ramp=lay.ramp, scale_factor=scale_factor, crop=CROP,
                                labels=labels, guidance_scale=args.guidance_scale if guided else 1.0, null_class=args.null_class if guided else None,
                                init=torch.from_numpy(init), strength=args.strength, mask=None if mk is None else torch.from_numpy(mk),
                                composite=False if (args.no_composite or mk is None) else None, mask_erode=args.mask_erode,
-                               resamples=args.resamples, jump_length=args.jump_length, seed=args.seed, info=info)
+                               resamples=args.resamples, jump_length=args.jump_length, seed=args.seed, info=info,
+                               blend=not args.no_blend)
     np.save(os.path.join(out, f"edit_long_{args.seed}.npy"), rec.cpu().numpy())
     used_mask = np.zeros_like(init) if mk is None else mk
     np.save(os.path.join(out, f"edit_long_{args.seed}_mask.npy"), used_mask[:, :, CROP:-CROP])

@@ -9,7 +9,9 @@ the same shape.  --resamples R --jump_length J (defaults 1 and 1: the plain repa
 J steps back up the schedule at every J-th level, each with fresh noise from the Philox key schedulers.RESAMPLE_KEY + --seed + (index of
 the call's first window), so that no two calls -- batches or ranks -- share their jump noise (a window's result is reproducible for a given
 --batch and world size; its position inside the call decides which part of the stream it reads); the cost is the forward count, and with R > 1 edit_{i}_resample.json records {"resamples", "jump_length", "forwards"}.  J = 1 is a convention: no
-(R, J) has been measured on sleep data.  Windows are batched and sharded over ranks (no collective)."""
+(R, J) has been measured on sleep data.  A checkpoint trained with --context is recognised by its 'context' entry (a bare state dict: by
+its first conv) and the kept signal and the mask then also reach the model as its context, at no extra forward; --no_blend drops the
+replacement blend and leaves the learned conditioning alone.  Windows are batched and sharded over ranks (no collective)."""
 import argparse
 import json
 import os
@@ -21,7 +23,7 @@ from .. import distributed as D
 from ..models import AutoencoderKL, UNetModel
 from ..sampling import make_sampling_scheduler, sample
 from ..training import randn
-from .common import load_config
+from .common import context_model_kwargs, load_config
 
 WINDOW = 3072
 
@@ -54,6 +56,8 @@ def parse_args(argv=None):
     p.add_argument("--solver_order", type=int, default=2, choices=[1, 2], help="dpmpp_2m only")
     p.add_argument("--resamples", type=int, default=1, help="RePaint resampling: visits of every jump point (1 = none); needs a mask")
     p.add_argument("--jump_length", type=int, default=1, help="steps a jump goes back up, and the spacing of the jump points")
+    p.add_argument("--no_blend", action="store_true", help="a context model only (a checkpoint trained with --context, recognised by itself): use the "
+                   "learned conditioning alone instead of also resetting the kept latents after every step")
     return p.parse_args(argv)
 
 
@@ -142,15 +146,18 @@ def main(args):
         else:
             raise ValueError("a class-conditional UNet needs --class_label or --labels_file")
     guided = labels is not None and args.null_class is not None
-    unet = UNetModel(**up, dtype=args.dtype, device=local)
     weights = os.path.join(args.diffusion_path, "best_model_ema.pth" if args.use_ema else "best_model.pth")
     if args.use_ema and not os.path.exists(weights):
         raise FileNotFoundError(f"--use_ema: {weights} not found (train with --ema_decay to have it written)")
-    unet.load_state_dict(torch.load(weights, map_location="cpu"))
+    sd = torch.load(weights, map_location="cpu")
+    # (a context model -- trained with --context -- is recognised by its checkpoint: in_channels = 2 C + 1, the context formed by the sampler)
+    ckw = context_model_kwargs(up, sd, args.diffusion_path)      # (widens up["in_channels"]: ahead of the constructor call)
+    unet = UNetModel(**up, dtype=args.dtype, device=local, **ckw)
+    unet.load_state_dict(sd)
     sched = make_sampling_scheduler(args.num_inference_steps, prediction_type=args.prediction_type, device=local, sampler=args.sampler,
                                     solver_order=args.solver_order)
     lo, hi = D.shard_range(N, rank, world)
-    lat = unet.in_channels
+    lat = unet.x_channels
     for k in range(lo, hi, args.batch):
         idx = list(range(k, min(k + args.batch, hi)))
         noise = torch.empty(len(idx), lat, latent_len, device=unet.device)
@@ -162,7 +169,7 @@ def main(args):
                             guidance_scale=args.guidance_scale if guided else 1.0, null_class=args.null_class if guided else None,
                             init=torch.from_numpy(x_in[idx[0]:idx[-1] + 1]), strength=args.strength, mask=m,
                             composite=False if args.no_composite else None, resamples=args.resamples, jump_length=args.jump_length,
-                            seed=args.seed + idx[0], info=info)
+                            seed=args.seed + idx[0], info=info, blend=not args.no_blend)
         arr = windows.cpu().numpy()
         for j, i in enumerate(idx):
             np.save(os.path.join(out, f"edit_{i}.npy"), arr[j:j + 1])

@@ -18,7 +18,7 @@ import torch
 from ..models import AutoencoderKL, UNetModel
 from ..sampling import long_layout, make_sampling_scheduler, sample_long, window_labels_from_hypnogram
 from ..training import randn
-from .common import load_config
+from .common import context_model_kwargs, load_config
 
 WINDOW = 3072
 SFREQ = 100.0           # 3072 samples are the 30-s epoch plus the 36-sample border pad on both sides
@@ -128,14 +128,17 @@ def main(args):
         else:
             raise ValueError("a class-conditional UNet needs --hypnogram or --class_label")
     guided = labels is not None and args.null_class is not None
-    unet = UNetModel(**up, dtype=args.dtype, device=local)
     weights = os.path.join(args.diffusion_path, "best_model_ema.pth" if args.use_ema else "best_model.pth")
     if args.use_ema and not os.path.exists(weights):
         raise FileNotFoundError(f"--use_ema: {weights} not found (train with --ema_decay to have it written)")
-    unet.load_state_dict(torch.load(weights, map_location="cpu"))
+    sd = torch.load(weights, map_location="cpu")
+    # (a context model -- trained with --context -- is recognised by its checkpoint: in_channels = 2 C + 1, the context formed by the sampler)
+    ckw = context_model_kwargs(up, sd, args.diffusion_path)      # (widens up["in_channels"]: ahead of the constructor call)
+    unet = UNetModel(**up, dtype=args.dtype, device=local, **ckw)
+    unet.load_state_dict(sd)
     sched = make_sampling_scheduler(args.num_inference_steps, prediction_type=args.prediction_type, device=local, sampler="dpmpp_2m",
                                     solver_order=args.solver_order)
-    noise = randn(unet.ctx, (1, unet.in_channels, lay.canvas_len), seed=args.seed)
+    noise = randn(unet.ctx, (1, unet.x_channels, lay.canvas_len), seed=args.seed)
     rec, _canvas = sample_long(unet, stage1, sched, noise, lay.n_windows, margin=lay.margin, ramp=lay.ramp, scale_factor=scale_factor, crop=CROP,
                                labels=labels, guidance_scale=args.guidance_scale if guided else 1.0, null_class=args.null_class if guided else None)
     np.save(os.path.join(out, f"long_{args.seed}.npy"), rec.cpu().numpy())

@@ -11,7 +11,7 @@ import torch
 from .. import distributed as D
 from ..models import AutoencoderKL, UNetModel
 from ..sampling import make_sampling_scheduler, sample_seeds
-from .common import load_config
+from .common import context_model_kwargs, load_config
 
 
 def parse_args(argv=None):
@@ -63,11 +63,14 @@ def main(args):
         else:
             raise ValueError("a class-conditional UNet needs --class_label or --labels_file")
     guided = labels is not None and args.null_class is not None
-    unet = UNetModel(**up, dtype=args.dtype, device=local)
     weights = os.path.join(args.diffusion_path, "best_model_ema.pth" if args.use_ema else "best_model.pth")
     if args.use_ema and not os.path.exists(weights):
         raise FileNotFoundError(f"--use_ema: {weights} not found (train with --ema_decay to have it written)")
-    unet.load_state_dict(torch.load(weights, map_location="cpu"))
+    sd = torch.load(weights, map_location="cpu")
+    # (a context model -- trained with --context -- is recognised by its checkpoint: in_channels = 2 C + 1, the context formed by the sampler)
+    ckw = context_model_kwargs(up, sd, args.diffusion_path)      # (widens up["in_channels"]: ahead of the constructor call)
+    unet = UNetModel(**up, dtype=args.dtype, device=local, **ckw)
+    unet.load_state_dict(sd)
     scale_factor = float(torch.load(os.path.join(args.diffusion_path, "checkpoint.pth"), map_location="cpu")["scale_factor"])
     sched = make_sampling_scheduler(args.num_inference_steps, prediction_type=args.prediction_type, device=local, sampler=args.sampler,
                                     solver_order=args.solver_order)

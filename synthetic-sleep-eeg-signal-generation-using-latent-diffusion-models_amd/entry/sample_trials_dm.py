@@ -12,7 +12,7 @@ import torch
 from .. import distributed as D
 from ..models import UNetModel
 from ..sampling import make_sampling_scheduler, sample_seeds
-from .common import load_config
+from .common import context_model_kwargs, load_config
 
 
 def parse_args(argv=None):
@@ -37,11 +37,14 @@ def main(args):
     os.makedirs(out, exist_ok=True)
     up = dict(load_config(args.config_file)["model"]["params"]["unet_config"]["params"])
     up["in_channels"] = up["out_channels"] = 1                                   # sample_trials_ddpm.py:71-73
-    unet = UNetModel(**up, dtype=args.dtype, device=local)
     weights = os.path.join(args.diffusion_path, "best_model_ema.pth" if args.use_ema else "best_model.pth")
     if args.use_ema and not os.path.exists(weights):
         raise FileNotFoundError(f"--use_ema: {weights} not found (train with --ema_decay to have it written)")
-    unet.load_state_dict(torch.load(weights, map_location="cpu"))
+    sd = torch.load(weights, map_location="cpu")
+    # (a context model -- trained with --context -- is recognised by its checkpoint: in_channels = 2 C + 1, the context formed by the sampler)
+    ckw = context_model_kwargs(up, sd, args.diffusion_path)      # (widens up["in_channels"]: ahead of the constructor call)
+    unet = UNetModel(**up, dtype=args.dtype, device=local, **ckw)
+    unet.load_state_dict(sd)
     sched = make_sampling_scheduler(args.num_inference_steps, prediction_type=args.prediction_type, device=local, sampler=args.sampler,
                                     solver_order=args.solver_order)
     lo, hi = D.shard_range(args.stop_seed - args.start_seed, rank, world)

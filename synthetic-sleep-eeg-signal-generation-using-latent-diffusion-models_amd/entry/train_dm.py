@@ -13,7 +13,8 @@ from .. import distributed as D
 from ..models import UNetModel
 from ..schedulers import DDPMScheduler
 from ..training import EMA, Adam, GradScaler, NoiseLevelLoss, dm_train_step, randint, randn
-from .common import (WindowLoader, accum_factor, accum_plan, add_ema_args, add_grad_clip_args, add_loss_weighting_args, append_noise_level_record, cpu_state, ema_checkpoint_entry, ema_resume,
+from .common import (WindowLoader, accum_factor, accum_plan, add_context_args, add_ema_args, add_grad_clip_args, add_loss_weighting_args, append_noise_level_record, context_entry,
+                     context_resume, cpu_state, ema_checkpoint_entry, ema_resume,
                      format_clip_stats, format_noise_level_table, grad_clip_entry, grad_clip_resume, load_config, loss_weighting_resume, rng_seed, setup_run_dir, step_weighting)
 
 
@@ -31,6 +32,7 @@ def parse_args(argv=None):
     add_ema_args(p)
     add_loss_weighting_args(p)
     add_grad_clip_args(p)
+    add_context_args(p)
     return p.parse_args(argv)
 
 
@@ -43,9 +45,14 @@ def main(args):
     config = load_config(args.config_file)
     torch.manual_seed(config.train.seed)
     run_dir, resume = setup_run_dir(config, args)
+    if resume:                                 # (ahead of the model: a run trained with --context has another first conv)
+        context_resume(args, torch.load(os.path.join(run_dir, "checkpoint.pth"), map_location="cpu"))
+    context_entry(args, 1)            # the flags' own refusals, before any model exists (span_max <= L is checked once the data gives L)
     up = dict(config.model.params.unet_config.params)
     up["in_channels"] = up["out_channels"] = 1                                  # train_pure_ldm.py:113-115
-    unet = UNetModel(**up, dtype=args.dtype, device=local)
+    if args.context:                           # [x | m * x | m]: the pixel model's context is the masked window itself
+        up["in_channels"] = 3
+    unet = UNetModel(**up, dtype=args.dtype, device=local, **({"context_channels": 2} if args.context else {}))
     D.broadcast_flat(unet.flat); unet.sync_weights()
     sched = DDPMScheduler(num_train_timesteps=1000, schedule="linear_beta", beta_start=0.0015, beta_end=0.0195, device=local)
     ema = EMA(unet, decay=args.ema_decay, warmup=not args.ema_no_warmup) if args.ema_decay is not None else None      # after the broadcast
@@ -57,6 +64,7 @@ def main(args):
     train = WindowLoader(args.path_pre_processed, bs, args.synthetic_windows, seed=rng_seed(config.train.seed, 8, rank, world), drop_last=config.train.drop_last,
                          path_ids=args.path_train_ids, dataset=args.type_dataset, shard=(rank, world))
     s_t, s_noise = rng_seed(config.train.seed, 1, rank, world), rng_seed(config.train.seed, 3, rank, world)
+    s_mask, centry, cspec = rng_seed(config.train.seed, 11, rank, world), None, None
     dev, ctx = unet.device, unet.ctx
     loss = torch.zeros(1, device=dev)
     gsync = D.OverlappedGradSync(unet.flat_grad, ctx=unet.ctx, comm=D.make_comm(unet.ctx))   # no-op with one process; EEGLDM_NATIVE_COLLECTIVES=1: RCCL through the C ABI
@@ -95,8 +103,14 @@ def main(args):
                 opt.zero_grad()
             if train_levels is not None:
                 wkw["per_sample_out"] = torch.empty(B, device=dev)
+            ckw = {}
+            if args.context:               # the step draws the masks in registers: no mask buffer, no second pass
+                if centry is None:
+                    centry = context_entry(args, 1, x.shape[2])
+                    cspec = {k: centry[k] for k in ("p_none", "p_prefix", "span_min", "span_max")}
+                ckw = dict(context_mask=cspec, mask_seed=s_mask, mask_offset=gstep * B)
             dm_train_step(unet, sched, x, noise, t, spectral_weight=1e-6, spectral_loss=spectral, loss_out=loss, grad_sync=gsync if last else None,
-                          grad_scale=scaler.get_scale() / GA, **wkw)
+                          grad_scale=scaler.get_scale() / GA, **wkw, **ckw)
             if train_levels is not None:
                 train_levels.add(wkw["per_sample_out"], t, ctx=ctx)
             if last:                       # one all-reduce and one optimizer step per group; a short group counts its k micro-batches K / k
@@ -127,6 +141,8 @@ def main(args):
                 ck_out["loss_weighting"] = {"weighting": args.loss_weighting, "snr_gamma": float(args.snr_gamma)}
             if grad_clip_entry(args) is not None:
                 ck_out["grad_clip"] = grad_clip_entry(args)
+            if centry is not None:
+                ck_out["context"] = centry
             torch.save(ck_out, os.path.join(run_dir, "checkpoint.pth"))
         if args.max_steps and steps >= args.max_steps:
             break

@@ -11,8 +11,9 @@ import torch
 from .. import distributed as D
 from ..models import AutoencoderKL, UNetModel
 from ..schedulers import DDPMScheduler
-from ..training import EMA, Adam, GradScaler, NoiseLevelLoss, ldm_train_step, randint, randn
-from .common import (ParseListAction, WindowLoader, accum_factor, accum_plan, add_ema_args, add_grad_clip_args, add_loss_weighting_args, append_noise_level_record, cpu_state, ema_checkpoint_entry,
+from ..training import EMA, Adam, GradScaler, NoiseLevelLoss, context_mask, context_window, ldm_train_step, randint, randn
+from .common import (ParseListAction, WindowLoader, accum_factor, accum_plan, add_context_args, add_ema_args, add_grad_clip_args, add_loss_weighting_args, append_noise_level_record,
+                     context_entry, context_resume, cpu_state, ema_checkpoint_entry,
                      ema_resume, format_clip_stats, format_noise_level_table, grad_clip_entry, grad_clip_resume, load_config, loss_weighting_resume, rng_seed, setup_run_dir, step_weighting)
 
 
@@ -41,17 +42,28 @@ def parse_args(argv=None):
     add_ema_args(p)
     add_loss_weighting_args(p)
     add_grad_clip_args(p)
+    add_context_args(p)
     return p.parse_args(argv)
 
 
+def context_latents(unet, stage1, x, mask, scale_factor):
+    """The LDM's context source, in training and in sampling alike: scale_factor * the posterior mean of the MASKED window's encoding (a
+    second run of the frozen encoder), so that no latent next to a hole carries what the encoder saw inside it.  mask: (B, Ll), 1 = keep."""
+    from ..sampling import _encode_windows
+    return _encode_windows(unet, stage1, context_window(unet.ctx, x, mask, stage1.down), scale_factor, True)
+
+
 @torch.no_grad()
-def validate(unet, stage1, sched, loader, scale_factor, seeds, latent_channels, by_level=None):
+def validate(unet, stage1, sched, loader, scale_factor, seeds, latent_channels, by_level=None, context=None):
     """eval_ldm (training.py:455-497): mean epsilon-MSE over the validation windows, fixed noise stream (a class-conditional UNet is
     scored with each window's own label).  `seeds` = the three Philox
     keys (timesteps, posterior eps, diffusion noise), each from `rng_seed` with its own role.  Returns (sum of per-window losses,
     number of windows) so that data-parallel ranks can add their shards up.
     by_level (a NoiseLevelLoss): also receives every window's loss against the prediction type's OWN target (eegldm_diffusion_loss,
-    unweighted) -- the returned sum, the model-selection criterion, is unchanged."""
+    unweighted) -- the returned sum, the model-selection criterion, is unchanged.
+    context ((draw parameters, Philox key) for a context model): every window is scored under a mask drawn from that FIXED key at the
+    window's index in this rank's shard, so that every epoch scores the same masks.  Key and index are per rank, like the validation noise
+    (`seeds`): a run with another world size scores other masks."""
     from .._lib import lib, check, ptr
     unet.eval()
     tot, n, dev, ctx = 0.0, 0, unet.device, unet.ctx
@@ -66,7 +78,11 @@ def validate(unet, stage1, sched, loader, scale_factor, seeds, latent_channels, 
         eps = randn(ctx, (B, latent_channels, Ll), seed=s_eps, offset=seen * per)
         noise = randn(ctx, eps.shape, seed=s_noise, offset=seen * per)
         e = stage1.encode_stage_2_inputs(x, eps=eps, scale_factor=scale_factor)
-        pred = unet(sched.add_noise(original_samples=e, noise=noise, timesteps=t), timesteps=t, y=batch.get("label"))
+        ckw = {}
+        if context is not None:
+            m = context_mask(ctx, B, Ll, context[0], seed=context[1], offset=seen)
+            ckw["context"] = torch.cat([m[:, None, :] * context_latents(unet, stage1, x, m, scale_factor), m[:, None, :]], 1)
+        pred = unet(sched.add_noise(original_samples=e, noise=noise, timesteps=t), timesteps=t, y=batch.get("label"), **ckw)
         check(lib.eegldm_mse_loss(ctx.h, ptr(pred), ptr(noise), ptr(out), None, pred.numel(), 1.0))
         if by_level is not None:
             from .._lib import PRED
@@ -91,6 +107,9 @@ def main(args):
     config = load_config(args.config_file)
     torch.manual_seed(config.train.seed)
     run_dir, resume = setup_run_dir(config, args)
+    if resume:                                 # (ahead of the model: a run trained with --context has another first conv)
+        context_resume(args, torch.load(os.path.join(run_dir, "checkpoint.pth"), map_location="cpu"))
+    context_entry(args, args.latent_channels)      # the flags' own refusals, before any model exists (span_max <= L is checked once the data gives L)
     ae_cfg = dict(load_config(args.autoencoderkl_config_file_path).autoencoderkl.params)
     if args.num_channels is not None:
         ae_cfg["num_channels"] = args.num_channels
@@ -105,7 +124,9 @@ def main(args):
         up["num_classes"] = args.num_classes
     cond = up.get("num_classes") is not None                                  # UNetModel(**parameters) takes it from the yaml too
     null_class = args.null_class if args.null_class is not None else (int(up["num_classes"]) - 1 if cond and args.p_uncond > 0 else None)
-    unet = UNetModel(**up, dtype=args.dtype, device=local)
+    if args.context:
+        up["in_channels"] = 2 * args.latent_channels + 1
+    unet = UNetModel(**up, dtype=args.dtype, device=local, **({"context_channels": args.latent_channels + 1} if args.context else {}))
     D.broadcast_flat(unet.flat); unet.sync_weights(); D.broadcast_flat(stage1.flat); stage1.sync_weights()
     # train_ldm.py:199-200: monai-generative DDPMScheduler(beta_schedule="linear", 0.0015, 0.0195) = plain linspace of the betas
     # (alpha_bar[999] = 2.57e-5).  The sqrt-space "linear" of the reference's local models/ldm.py is a different table and is not
@@ -128,6 +149,9 @@ def main(args):
     s_lab = rng_seed(config.train.seed, 10, rank, world)
     dev, ctx = unet.device, unet.ctx
     first = next(iter(train))["eeg"].to(dev)
+    centry = context_entry(args, args.latent_channels, first.shape[2] // stage1.down)       # None without --context
+    cspec = None if centry is None else {k: centry[k] for k in ("p_none", "p_prefix", "span_min", "span_max")}
+    s_mask, v_context = rng_seed(config.train.seed, 11, rank, world), (None if centry is None else (cspec, rng_seed(config.train.seed, 12, rank, world)))
     z = stage1.encode_stage_2_inputs(first)
     # train_ldm.py:203-204 (unbiased std of one batch).  The reference is ONE process: one value for all replicas.  Here the loader is
     # rank-sharded, so every rank sees a different first batch -- rank 0's value is broadcast (and is the one checkpointed below)
@@ -178,6 +202,9 @@ def main(args):
             lab = dict(labels=batch["label"].to(dev), p_uncond=args.p_uncond, null_class=null_class, seed=s_lab, offset=gstep * B) if cond else {}
             if train_levels is not None:
                 wkw["per_sample_out"] = torch.empty(B, device=dev)
+            if centry is not None:         # draw the masks, mask the windows, encode them once more: the context the model will see at repair time
+                m = context_mask(ctx, B, e.shape[2], cspec, seed=s_mask, offset=gstep * B)
+                lab = dict(lab, context_mask=m, context_latents=context_latents(unet, stage1, x, m, scale_factor))
             ldm_train_step(unet, sched, e, noise, t, loss_out=loss, grad_scale=scaler.get_scale() / GA, grad_sync=gsync if last else None, **lab, **wkw)
             if train_levels is not None:
                 train_levels.add(wkw["per_sample_out"], t, ctx=ctx)
@@ -191,12 +218,12 @@ def main(args):
         cur = float(loss)
         lv, lv_ema = (NoiseLevelLoss(sched.num_train_timesteps, K), NoiseLevelLoss(sched.num_train_timesteps, K)) if K else (None, None)
         if do_eval and valid is not None:      # model selection on the validation split (training.py:356-380), epsilon MSE over its windows
-            v_sum, v_n = D.allreduce_sum_scalars(validate(unet, stage1, sched, valid, scale_factor, v_seeds, args.latent_channels, by_level=lv), like=loss)
+            v_sum, v_n = D.allreduce_sum_scalars(validate(unet, stage1, sched, valid, scale_factor, v_seeds, args.latent_channels, by_level=lv, context=v_context), like=loss)
             cur = v_sum / max(1.0, v_n)
         cur_ema = None                         # no validation split: no loss of the averaged weights exists
         if do_eval and valid is not None and ema is not None:      # the same windows and noise, scored with the averaged weights
             with ema.applied():
-                e_sum, e_n = D.allreduce_sum_scalars(validate(unet, stage1, sched, valid, scale_factor, v_seeds, args.latent_channels, by_level=lv_ema), like=loss)
+                e_sum, e_n = D.allreduce_sum_scalars(validate(unet, stage1, sched, valid, scale_factor, v_seeds, args.latent_channels, by_level=lv_ema, context=v_context), like=loss)
             cur_ema = e_sum / max(1.0, e_n)
         if K and do_eval:                      # every rank joins the sums; rank 0 prints and writes
             record = {"epoch": epoch + 1, "steps": gstep, "prediction_type": sched.prediction_type, "bins": K,
@@ -229,6 +256,8 @@ def main(args):
                     ck_out["loss_weighting"] = {"weighting": args.loss_weighting, "snr_gamma": float(args.snr_gamma)}
                 if grad_clip_entry(args) is not None:
                     ck_out["grad_clip"] = grad_clip_entry(args)
+                if centry is not None:
+                    ck_out["context"] = centry
                 torch.save(ck_out, os.path.join(run_dir, "checkpoint.pth"))
         if args.max_steps and steps >= args.max_steps:
             break

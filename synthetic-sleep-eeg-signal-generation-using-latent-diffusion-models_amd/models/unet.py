@@ -27,7 +27,7 @@ class UNetModel(FlatModule):
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions,
                  dropout=0, channel_mult=(1, 2, 4, 8), conv_resample=True, num_classes=None, num_heads=1,
                  num_head_channels=-1, num_heads_upsample=-1, use_scale_shift_norm=False, resblock_updown=False,
-                 n_embed=None, dtype="float32", device=0, ctx=None):
+                 n_embed=None, dtype="float32", device=0, ctx=None, context_channels=0):
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError("dropout must be in [0, 1)")
         self.dropout = float(dropout)
@@ -36,6 +36,15 @@ class UNetModel(FlatModule):
         if num_classes is not None and (int(num_classes) != num_classes or int(num_classes) < 1):
             raise ValueError(f"num_classes must be a positive integer, got {num_classes!r}")
         self.num_classes = None if num_classes is None else int(num_classes)
+        # context conditioning: the last context_channels of the in_channels input channels come from `context` (forward), the first
+        # in_channels - context_channels == out_channels from x; parameters and state_dict are a plain UNetModel(in_channels)'s
+        if int(context_channels) != context_channels or int(context_channels) < 0:
+            raise ValueError(f"context_channels must be a non-negative integer, got {context_channels!r}")
+        self.context_channels = int(context_channels)
+        if self.context_channels and in_channels - self.context_channels != out_channels:
+            raise ValueError(f"a context model needs in_channels - context_channels == out_channels, got {in_channels} - "
+                             f"{self.context_channels} != {out_channels}")
+        self.x_channels = in_channels - self.context_channels
         num_heads, num_head_channels, num_heads_upsample = int(num_heads), int(num_head_channels), int(num_heads_upsample)
         if num_heads < 1 or num_head_channels == 0:
             raise ValueError("num_heads >= 1 and num_head_channels = -1 or > 0 (unet.py:146-153)")
@@ -62,7 +71,9 @@ class UNetModel(FlatModule):
         cfg.resample_layers = 0 if self.resblock_updown else 1                          # Downsample / Upsample layers (unet.py:462-470,493-498)
         cfg.resample_pool_only = 0 if self.conv_resample else 1
         h = C.c_void_p()
-        if self.num_classes is None:
+        if self.context_channels:
+            check(lib.eegldm_unet_create_ctx(self.ctx.h, C.byref(cfg), self.num_classes or 0, self.context_channels, C.byref(h)))
+        elif self.num_classes is None:
             check(lib.eegldm_unet_create(self.ctx.h, C.byref(cfg), C.byref(h)))
         else:                       # label_emb = nn.Embedding(num_classes, 4 * model_channels) (unet.py:379-380)
             check(lib.eegldm_unet_create_cond(self.ctx.h, C.byref(cfg), self.num_classes, C.byref(h)))
@@ -165,10 +176,12 @@ class UNetModel(FlatModule):
         x = x.to(self.device, torch.float32).contiguous()
         t = timesteps.to(self.device, torch.int64).contiguous()
         if x.dim() != 3:
-            raise ValueError(f"UNetModel expects x of shape (B, {self.in_channels}, L), got {tuple(x.shape)}")
+            raise ValueError(f"UNetModel expects x of shape (B, {self.x_channels}, L), got {tuple(x.shape)}")
         B, Cc, L = x.shape
-        if Cc != self.in_channels:
-            raise ValueError(f"UNetModel was built with in_channels={self.in_channels}, got x with {Cc} channels")
+        if Cc != self.x_channels:
+            raise ValueError(f"UNetModel was built with in_channels={self.in_channels}"
+                             + (f" of which {self.context_channels} are context" if self.context_channels else "") + f", got x with {Cc} channels")
+        context = self.check_context(context, B, L)
         if tuple(t.shape) != (B,):
             raise ValueError(f"timesteps must have shape ({B},) to match the batch, got {tuple(t.shape)}")
         if B == 0:
@@ -188,8 +201,22 @@ class UNetModel(FlatModule):
             labels = self.check_labels(y)
         self._sync_if_stale()                            # a torch optimizer updated the flat parameter in place: refresh the compute copies
         if self.training and self._wants_graph(x):
-            return _UNetFn.apply(self, x, t, labels, self._flat_param())
-        return self._forward_native(x, t, labels)
+            return _UNetFn.apply(self, x, t, labels, self._flat_param(), context)
+        return self._forward_native(x, t, labels, context)
+
+    def check_context(self, context, B, L):
+        """The context of a forward of B rows as a contiguous device float32 (rows, context_channels, L) tensor with B % rows == 0 (row b
+        reads context row b % rows), or None: a context model then reads zeros.  Raises ValueError before anything is launched.  A model
+        built without context_channels ignores the argument, as it always did (the reference's forward takes and ignores it too); the
+        samplers and train steps, whose context keywords are new, refuse it there."""
+        if context is None or not self.context_channels:
+            return None
+        if not torch.is_tensor(context) or context.dim() != 3 or tuple(context.shape[1:]) != (self.context_channels, L):
+            raise ValueError(f"context must have shape (rows, {self.context_channels}, {L}), got "
+                             f"{tuple(context.shape) if torch.is_tensor(context) else type(context).__name__}")
+        if context.shape[0] < 1 or B % context.shape[0] != 0:
+            raise ValueError(f"{context.shape[0]} context rows cannot be shared by a batch of {B} (B % rows != 0)")
+        return context.detach().to(self.device, torch.float32).contiguous()
 
     def check_labels(self, y):
         """Class labels as a device int64 tensor; raises IndexError (as nn.Embedding does) before anything is launched when one lies
@@ -203,13 +230,19 @@ class UNetModel(FlatModule):
                 raise IndexError(f"class label {lo if lo < 0 else hi} is out of range for num_classes={self.num_classes}")
         return y.to(self.device, torch.int64).contiguous()
 
-    def _forward_native(self, x, t, labels=None):
+    def _forward_native(self, x, t, labels=None, context=None):
         B, _c, L = x.shape
         out = torch.empty(B, self.out_channels, L, device=self.device, dtype=torch.float32)
-        if self.num_classes is None:
-            check(lib.eegldm_unet_forward(self.h, ptr(x), ptr(t), ptr(out), B, L, 1 if self.training else 0))
-        else:
-            check(lib.eegldm_unet_forward_cond(self.h, ptr(x), ptr(t), ptr(labels), ptr(out), B, L, 1 if self.training else 0))
+        if context is not None:                          # the handle keeps the pointer: set for this forward, cleared behind it
+            check(lib.eegldm_unet_set_context(self.h, ptr(context), context.shape[0]))
+        try:
+            if self.num_classes is None:
+                check(lib.eegldm_unet_forward(self.h, ptr(x), ptr(t), ptr(out), B, L, 1 if self.training else 0))
+            else:
+                check(lib.eegldm_unet_forward_cond(self.h, ptr(x), ptr(t), ptr(labels), ptr(out), B, L, 1 if self.training else 0))
+        finally:
+            if context is not None:
+                check(lib.eegldm_unet_set_context(self.h, None, 0))
         self._bump_tape()                                # the executor's single tape now belongs to THIS call (eegldm.autograd)
         return out
 
@@ -217,7 +250,7 @@ class UNetModel(FlatModule):
 
     def backward(self, dy, need_dx=False):
         dy = dy.to(self.device, torch.float32).contiguous()
-        dx = torch.empty(dy.shape[0], self.in_channels, dy.shape[2], device=self.device) if need_dx else None
+        dx = torch.empty(dy.shape[0], self.x_channels, dy.shape[2], device=self.device) if need_dx else None      # (the context gets no gradient)
         check(lib.eegldm_unet_backward(self.h, ptr(dy), ptr(dx)))
         self._bump_tape()                                # consumed
         return dx

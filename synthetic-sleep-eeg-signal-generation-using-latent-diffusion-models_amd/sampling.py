@@ -10,7 +10,7 @@ import torch
 
 from ._lib import lib, check, ptr, PRED
 from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, RESAMPLE_KEY, scheduler_edit_tables, scheduler_resample_tables
-from .training import randn
+from .training import context_window, randn
 
 
 def _step_tables(scheduler):
@@ -188,10 +188,52 @@ def _edit_inputs(unet, autoencoder, x, init, mask, latents, encode, mask_erode=0
     return z0, m_win, m_lat, init_d
 
 
+def _context_args(unet, context, blend, resamples, rows, L):
+    """Host-side checks of the context keywords, behind those of the other arguments and before anything runs -> is `unet` a context
+    model.  context: (rows', context_channels, L) with rows % rows' == 0 -- for a long recording canvas-shaped, one row per recording."""
+    cc = getattr(unet, "context_channels", 0)
+    if not cc:
+        if context is not None:
+            raise ValueError("context needs a UNetModel built with context_channels")
+        if not blend:
+            raise ValueError("blend=False needs a context model: without the blend nothing but the start ties the result to the input")
+        return False
+    if not blend and resamples != 1:
+        raise ValueError("resamples > 1 needs blend=True: resampling reconciles the regenerated span with the replaced one")
+    if context is not None:
+        shape = tuple(context.shape) if torch.is_tensor(context) else None
+        if shape is None or len(shape) != 3 or shape[1:] != (cc, int(L)) or shape[0] < 1 or rows % shape[0] != 0:
+            raise ValueError(f"context has shape {shape}, expected (rows, {cc}, {int(L)}) with rows dividing {rows}")
+    return True
+
+
+def _form_context(unet, autoencoder, x, context, z0, m_lat, init_d, encode, native=True):
+    """The context of a run on a context model -> (rows, C + 1, L) on the device, or None (the model then reads zeros: plain generation).
+    As in training: with the keep-mask m at the sampler's resolution (the min-pooled mask) the context is [m * src | m], src being the
+    encoding of the MASKED input -- scale_factor * encode_mean(init * upsample(m)), so that no latent carries what the encoder saw inside
+    the span to regenerate -- or, for latents given directly and for a pixel-space model, the input itself."""
+    dev = unet.device
+    if context is not None:
+        return context.detach().to(dev, torch.float32).contiguous()
+    if m_lat is None:
+        return None
+    B, Cc, L = x.shape
+    if unet.context_channels != Cc + 1:
+        raise ValueError(f"the context of a repair has {Cc} + 1 channels (masked signal, mask), the model takes {unet.context_channels}")
+    m1 = m_lat[:, :1, :].contiguous()
+    if init_d is not None and autoencoder is not None:
+        down = autoencoder.down
+        masked = context_window(unet.ctx, init_d, m1[:, 0], down) if native else init_d * m1.repeat_interleave(down, dim=2)
+        src = encode(masked, native)
+    else:
+        src = z0
+    return torch.cat([m1 * src, m1], 1).contiguous()
+
+
 @torch.no_grad()
 def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, use_graph=None, seed=0, info=None, labels=None,
                 guidance_scale=1.0, null_class=None, init=None, strength=1.0, mask=None, composite=None, init_latents=None, resamples=1,
-                jump_length=1):
+                jump_length=1, context=None, blend=True):
     """noise (B, lat, Ll) on the device -> (windows (B, out, 3072 - 2*crop), final latents).  ONE native call
     (eegldm_sample): the scheduler loop, z / scale_factor and the decode run inside the library.  The UNet forward CAN be
     replayed from a hipGraph (use_graph=True or EEGLDM_SAMPLE_GRAPH=1) but that is no longer the default: measured on
@@ -215,14 +257,26 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     noise drawn inside the jump's kernel (Philox key schedulers.RESAMPLE_KEY + seed; the kept part stays k(a) of the call's one noise
     tensor), and comes down again, r - 1 times per level: n_run + (r - 1) j len(range(0, n_run - j, j)) forwards in all, which is the cost.
     The step behind a jump is first order.  jump_length = 1 is a convention; no (resamples, jump_length) has been measured on sleep data.
-    info also receives {"forwards": the number of forwards}."""
+    info also receives {"forwards": the number of forwards}.
+    A UNetModel built with context_channels (learned repair, eegldm_sample_edit_ctx): with init and mask the context is formed as in
+    training -- [m * src | m] with m the min-pooled mask and src = scale_factor * encode_mean(init * upsample(m)), the encoding of the
+    MASKED window (init_latents and pixel-space models: the input itself) -- and every forward reads it, at one forward per step.
+    blend=True (default) keeps the replacement blend as well, so kept latents still end as z0 and kept samples stay the input's bytes;
+    blend=False uses the learned conditioning alone (the run then starts from noise unless strength < 1, and composite defaults to off).
+    context= passes a (rows, context_channels, L) tensor directly (rows dividing B).  With neither init / mask nor context the context is
+    zero: plain generation.  Whether such a model repairs EEG more plausibly than replacement is not measured here."""
+    if composite is None and not blend:
+        composite = False                      # the learned conditioning alone: nothing is pasted back unless asked for
     edit = _edit_args(autoencoder, scheduler, noise.shape, init, strength, mask, composite, init_latents)
     rt = _resample_args(scheduler, edit, mask, resamples, jump_length)
+    ctx_model = _context_args(unet, context, blend, resamples, int(noise.shape[0]), int(noise.shape[2]))
+    if edit is None and context is not None:
+        edit = dict(tab=scheduler_edit_tables(scheduler, 1.0), composite=False)      # the edit loop with nothing known: a context and noise
     unet.eval()
     x = noise.to(unet.device, torch.float32).contiguous()
     B, Cc, L = x.shape
-    if Cc != unet.in_channels:
-        raise ValueError(f"noise has {Cc} channels, the UNet takes {unet.in_channels}")
+    if Cc != getattr(unet, "x_channels", unet.in_channels):
+        raise ValueError(f"noise has {Cc} channels, the UNet takes {getattr(unet, 'x_channels', unet.in_channels)}")
     lab, nc = _labels_host(unet, labels, B, guidance_scale, null_class)
     multistep = isinstance(scheduler, DPMSolverMultistepScheduler)
     if edit is not None:
@@ -246,14 +300,23 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     i64, f32 = (lambda v: (C.c_int64 * len(v))(*v)), (lambda v: (C.c_float * len(v))(*v))
     tail = (ptr(lat), ptr(win), B, L, 1 if use_graph else 0, C.byref(used))
     if edit is not None:
-        z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_latents,
-                                                lambda w, native: _encode_windows(unet, autoencoder, w, scale_factor, native))
+        z0 = m_win = m_lat = init_d = None
+        if init is not None or init_latents is not None:
+            z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_latents,
+                                                    lambda w, native: _encode_windows(unet, autoencoder, w, scale_factor, native))
         nul = C.POINTER(C.c_float)()
         coef = (f32(tab["cx"]), f32(tab["c0"]), f32(tab["c1"])) if multistep else (nul, nul, nul)
         front = (unet.h, ae_h, ptr(x), ptr(z0), ptr(m_lat), i64(ts), f32(a_t), nul if multistep else f32(tab["a_prev"]), *coef,
                  f32(tab["a_next"]), n, PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor))
         back = (*tail, None if lab is None else i64(lab), float(guidance_scale), nc)
-        if rt is None:
+        if ctx_model:
+            cx_t = _form_context(unet, autoencoder, x, context, z0, m_lat, init_d,
+                                 lambda w, native: _encode_windows(unet, autoencoder, w, scale_factor, native))
+            known = z0 if z0 is not None and (blend or float(strength) != 1.0) else None
+            front = (*front[:3], ptr(known), ptr(m_lat) if blend and known is not None else None, *front[5:])
+            jump = (nul, nul, 0) if rt is None else (f32(rt["jump_x"]), f32(rt["jump_n"]), RESAMPLE_KEY + int(seed))
+            check(lib.eegldm_sample_edit_ctx(*front, *jump, *back, ptr(cx_t), 0 if cx_t is None else cx_t.shape[0]))
+        elif rt is None:
             check(lib.eegldm_sample_edit(*front, *back))
         else:
             check(lib.eegldm_sample_edit_resample(*front, f32(rt["jump_x"]), f32(rt["jump_n"]), RESAMPLE_KEY + int(seed), *back))
@@ -283,7 +346,8 @@ sample = ddim_sample      # the neutral name: the sampler is whatever `scheduler
 
 @torch.no_grad()
 def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, labels=None, guidance_scale=1.0, null_class=None,
-                         init=None, strength=1.0, mask=None, composite=None, init_latents=None, resamples=1, jump_length=1, seed=0):
+                         init=None, strength=1.0, mask=None, composite=None, init_latents=None, resamples=1, jump_length=1, seed=0,
+                         context=None, blend=True):
     """The same loop driven from Python, one scheduler.step call per timestep (what round 1 shipped; kept as the
     reference composition the native sampler is tested against, and for schedulers the native loop does not know).
     Class-conditional: the UNet is called with the labels and, for guidance_scale != 1, a second time with null_class; the two
@@ -291,9 +355,15 @@ def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, 
     ddim_sample, composed from torch ops: the noised start, the blend m k + (1 - m) x after every scheduler.step, the min-pooled mask and
     the composite.  resamples / jump_length / seed as in ddim_sample: the loop runs over the entries of schedulers.resample_tables; in front
     of a forward with a jump it draws eps = training.randn(...) and forms the jump and its blend in torch (_jump), and the multistep
-    scheduler takes the step behind a jump with first_order=True."""
+    scheduler takes the step behind a jump with first_order=True.  context / blend as in ddim_sample: the reference composition of the
+    learned repair is model(x, timesteps=t, context=c) per step, the context formed from torch ops."""
+    if composite is None and not blend:
+        composite = False                      # the learned conditioning alone: nothing is pasted back unless asked for
     edit = _edit_args(autoencoder, scheduler, noise.shape, init, strength, mask, composite, init_latents)
     rt = _resample_args(scheduler, edit, mask, resamples, jump_length)
+    ctx_model = _context_args(unet, context, blend, resamples, int(noise.shape[0]), int(noise.shape[2]))
+    if edit is None and context is not None:
+        edit = dict(tab=scheduler_edit_tables(scheduler, 1.0), composite=False)
     unet.eval()
     x = noise.to(unet.device, torch.float32).contiguous()
     B = x.shape[0]
@@ -306,9 +376,20 @@ def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, 
     if edit is not None:
         tab = edit["tab"]
         nz = x
-        z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_latents,
-                                                lambda w, native: _encode_windows(unet, autoencoder, w, scale_factor, native), native=False)
-        x = _renoise(z0, nz, tab["a_t"][0])
+        z0 = m_win = m_lat = init_d = None
+        encode = lambda w, native: _encode_windows(unet, autoencoder, w, scale_factor, native)
+        if init is not None or init_latents is not None:
+            z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_latents, encode, native=False)
+        if ctx_model:
+            cx_t = _form_context(unet, autoencoder, x, context, z0, m_lat, init_d, encode, native=False)
+            if cx_t is not None:
+                kw["context"] = cx_t
+            if not blend:
+                m_lat = None
+                if float(strength) == 1.0:
+                    z0 = None
+        if z0 is not None:
+            x = _renoise(z0, nz, tab["a_t"][0])
         timesteps = tab["timesteps"]
         if isinstance(scheduler, DPMSolverMultistepScheduler):
             first = {"first_order": True}
@@ -323,7 +404,7 @@ def ddim_sample_hostloop(unet, autoencoder, scheduler, noise, scale_factor=1.0, 
         tt.fill_(int(t))
         out = unet(x, timesteps=tt, **kw)
         if lab is not None and w != 1.0:
-            out_u = unet(x, timesteps=tt, y=null)
+            out_u = unet(x, timesteps=tt, **dict(kw, y=null))
             out = out_u + w * (out - out_u)
         x, _ = scheduler.step(out, int(t), x, **(first if j == 0 or jumped else {}))
         if edit is not None and m_lat is not None:
@@ -367,7 +448,7 @@ def sample_seeds(unet, autoencoder, scheduler, seeds, latent_len=768, scale_fact
     """One window per seed (sample_trials.py:149-151 draws a fresh N(0,1) latent per seed), batched.
     autoencoder=None samples a pixel-space model: latent_len is then the window length (3072).  labels / guidance_scale / null_class:
     class-conditional sampling (ddim_sample)."""
-    lat = unet.in_channels
+    lat = getattr(unet, "x_channels", unet.in_channels)      # (a context model samples from zero context here: plain generation)
     noise = torch.empty(len(seeds), lat, latent_len, device=unet.device)
     for i, sd in enumerate(seeds):
         noise[i] = randn(unet.ctx, (lat, latent_len), seed=int(sd))
@@ -539,7 +620,7 @@ def encode_long(autoencoder, recording, layout, scale_factor=1.0, native=True):
 @torch.no_grad()
 def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ramp=None, scale_factor=1.0, crop=36, labels=None,
                 guidance_scale=1.0, null_class=None, use_graph=None, info=None, init=None, init_canvas=None, strength=1.0, mask=None,
-                composite=None, mask_erode=0, resamples=1, jump_length=1, seed=0):
+                composite=None, mask_erode=0, resamples=1, jump_length=1, seed=0, context=None, blend=True):
     """noise (R, C, Lc) on the device -> (recording (R, out, down * Lc - 2 * crop), canvas (R, C, Lc)).  Overlapped-window sampling on one
     latent canvas (MultiDiffusion): the R * W overlapping slices of the canvases are the rows of ONE forward batch, and behind every
     forward ONE eegldm_canvas_step launch fuses the slices' data predictions with a partition-of-unity taper, takes the solver step on
@@ -565,19 +646,29 @@ def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ram
     resamples / jump_length / seed: RePaint's resampling as in `sample` (eegldm_sample_long_edit_resample; needs init and mask): a jump is
     ONE eegldm_edit_jump launch on the canvas, fresh noise from the Philox key schedulers.RESAMPLE_KEY + seed, and a gather.  The cost is
     the forward count n_run + (r - 1) j len(range(0, n_run - j, j)); info also receives {"forwards"}.  jump_length = 1 is a convention; no
-    (resamples, jump_length) has been measured on sleep data."""
+    (resamples, jump_length) has been measured on sleep data.
+    context / blend: as in `sample`, on a UNetModel built with context_channels (eegldm_sample_long_edit_ctx).  The context is
+    canvas-shaped, (R, C + 1, Lc): with init and mask it is [m * src | m], m the canvas keep-mask and src = encode_long of the MASKED
+    recording (window by window); the native loop gathers it once per call into window rows."""
     lay, R, labels = _long_args(unet, autoencoder, scheduler, noise.shape, n_windows, margin, ramp, crop, labels)
+    if composite is None and not blend:
+        composite = False
     edit = _edit_args(autoencoder, scheduler, (R, int(noise.shape[1]), lay.canvas_len), init, strength, mask, composite, init_canvas,
                       _LONG_EDIT_WORDS, mask_erode)
     rt = _resample_args(scheduler, edit, mask, resamples, jump_length)
+    ctx_model = _context_args(unet, context, blend, resamples, R, lay.canvas_len)
+    if context is not None and int(context.shape[0]) != R:
+        raise ValueError(f"context has {int(context.shape[0])} rows, expected one canvas per recording ({R})")
+    if edit is None and context is not None:
+        edit = dict(tab=scheduler_edit_tables(scheduler, 1.0), composite=False)
     from .models import UNetModel
     if not isinstance(unet, UNetModel):
         raise TypeError("sample_long runs the native loop: unet must be a UNetModel")
     unet.eval()
     x = noise.to(unet.device, torch.float32).contiguous()
     Cc = x.shape[1]
-    if Cc != unet.in_channels:
-        raise ValueError(f"noise has {Cc} channels, the UNet takes {unet.in_channels}")
+    if Cc != unet.x_channels:
+        raise ValueError(f"noise has {Cc} channels, the UNet takes {unet.x_channels}")
     W, L = lay.n_windows, lay.window_len
     lab, nc = _labels_host(unet, labels, R * W, guidance_scale, null_class)
     ts, a_t, cx, c0, c1 = _multistep_tables(scheduler)
@@ -598,10 +689,19 @@ def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ram
     if edit is None:
         check(lib.eegldm_sample_long(*head, i64(tab["timesteps"]), f32(tab["a_t"]), *coef, *tail))
     else:
-        z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_canvas,
-                                                lambda r, native: encode_long(autoencoder, r, lay, scale_factor, native=native), mask_erode)
+        z0 = m_win = m_lat = init_d = None
+        encode = lambda r, native: encode_long(autoencoder, r, lay, scale_factor, native=native)
+        if init is not None or init_canvas is not None:
+            z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_canvas, encode, mask_erode)
         front = (*head, ptr(z0), ptr(m_lat), i64(tab["timesteps"]), f32(tab["a_t"]), *coef, f32(tab["a_next"]))
-        if rt is None:
+        if ctx_model:
+            cx_t = _form_context(unet, autoencoder, x, context, z0, m_lat, init_d, encode)
+            known = z0 if z0 is not None and (blend or float(strength) != 1.0) else None
+            front = (*head, ptr(known), ptr(m_lat) if blend and known is not None else None, *front[5:])
+            nul = C.POINTER(C.c_float)()
+            jump = (nul, nul, 0) if rt is None else (f32(rt["jump_x"]), f32(rt["jump_n"]), RESAMPLE_KEY + int(seed))
+            check(lib.eegldm_sample_long_edit_ctx(*front, *sched, *jump, *tail[len(sched):], ptr(cx_t), 0 if cx_t is None else R))
+        elif rt is None:
             check(lib.eegldm_sample_long_edit(*front, *tail))
         else:
             check(lib.eegldm_sample_long_edit_resample(*front, *sched, f32(rt["jump_x"]), f32(rt["jump_n"]), RESAMPLE_KEY + int(seed),
@@ -650,7 +750,7 @@ def _long_crossfade(rows, lay):
 @torch.no_grad()
 def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=None, ramp=None, scale_factor=1.0, crop=36, labels=None,
                          guidance_scale=1.0, null_class=None, use_graph=None, info=None, init=None, init_canvas=None, strength=1.0, mask=None,
-                         composite=None, mask_erode=0, resamples=1, jump_length=1, seed=0):
+                         composite=None, mask_erode=0, resamples=1, jump_length=1, seed=0, context=None, blend=True):
     """The reference composition of sample_long in torch, none of the canvas kernels: slice the canvas, model(...) on all slices, the
     guidance mix, x0 from the scheduler's formulas, the taper of layout.weights (as a cross-fade of the two windows that carry weight),
     prev = cx x + c0 x0 + c1 hist on the canvas, then decode per window and cross-fade.  The float32 roundings are placed where the
@@ -660,11 +760,19 @@ def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=
     measured against anything), composed from torch ops: the encode per window and its cross-fade, the noised start, the truncated
     tables, the blend m k + (1 - m) x after every step with the library's roundings (_fma32), the min-pooled mask and the composite.
     resamples / jump_length / seed as in sample_long: the loop runs over the entries of schedulers.resample_tables (whose coefficients are
-    first order behind a jump) and forms each jump on the canvas in torch (_jump; the draw is training.randn on the scheduler's context)."""
+    first order behind a jump) and forms each jump on the canvas in torch (_jump; the draw is training.randn on the scheduler's context).
+    context / blend as in sample_long: the canvas-shaped context is sliced like the canvas and model(win, timesteps=t, context=c) runs per step."""
     lay, R, labels = _long_args(unet, autoencoder, scheduler, noise.shape, n_windows, margin, ramp, crop, labels)
+    if composite is None and not blend:
+        composite = False
     edit = _edit_args(autoencoder, scheduler, (R, int(noise.shape[1]), lay.canvas_len), init, strength, mask, composite, init_canvas,
                       _LONG_EDIT_WORDS, mask_erode)
     rt = _resample_args(scheduler, edit, mask, resamples, jump_length)
+    ctx_model = _context_args(unet, context, blend, resamples, R, lay.canvas_len)
+    if context is not None and int(context.shape[0]) != R:
+        raise ValueError(f"context has {int(context.shape[0])} rows, expected one canvas per recording ({R})")
+    if edit is None and context is not None:
+        edit = dict(tab=scheduler_edit_tables(scheduler, 1.0), composite=False)
     unet.eval()
     dev = unet.device
     x = noise.to(dev, torch.float32).contiguous().clone()
@@ -680,11 +788,20 @@ def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=
         tab = edit["tab"] if rt is None else rt
         ts, a_t, cx, c0, c1, a_next = (tab[k] for k in ("timesteps", "a_t", "cx", "c0", "c1", "a_next"))
         nz = x
-        z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_canvas,
-                                                lambda r, native: encode_long(autoencoder, r, lay, scale_factor, native=native), mask_erode,
-                                                native=False)
-        blend = _blend
-        x = _renoise(z0, nz, a_t[0]).clone()
+        z0 = None
+        encode = lambda r, native: encode_long(autoencoder, r, lay, scale_factor, native=native)
+        if init is not None or init_canvas is not None:
+            z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_canvas, encode, mask_erode, native=False)
+        if ctx_model:
+            cx_t = _form_context(unet, autoencoder, x, context, z0, m_lat, init_d, encode, native=False)
+            if cx_t is not None:
+                kw["context"] = _slices_of(cx_t, lay).contiguous()
+            if not blend:
+                m_lat = None
+                if float(strength) == 1.0:
+                    z0 = None
+        if z0 is not None:
+            x = _renoise(z0, nz, a_t[0]).clone()
     tt = torch.empty(R * W, device=dev, dtype=torch.int64)
     hist = None
     jumps = 0
@@ -696,17 +813,17 @@ def sample_long_hostloop(unet, autoencoder, scheduler, noise, n_windows, margin=
         win = _slices_of(x, lay)
         out = unet(win, timesteps=tt, **kw).float()
         if lab is not None and w != 1.0:
-            out_u = unet(win, timesteps=tt, y=null).float()
+            out_u = unet(win, timesteps=tt, **dict(kw, y=null)).float()
             out = _fma32(w, out - out_u, out_u)
         x0 = _long_crossfade(_long_x0(out, win, a_t[i], scheduler.prediction_type, scheduler.clip_sample).reshape(R, W, Cc, L), lay)
         inner = _fma32(c0[i], x0, hist * c1[i]) if c1[i] != 0.0 else x0 * c0[i]
         x = _fma32(cx[i], x, inner)
         hist = x0
         if m_lat is not None:
-            x = blend(m_lat, _renoise(z0, nz, a_next[i]), x)
+            x = _blend(m_lat, _renoise(z0, nz, a_next[i]), x)
     if info is not None:
         info["graph"], info["layout"], info["forwards"] = False, lay, len(ts)
-    comp = (lambda rec: blend(m_win, init_d, rec)) if edit is not None and edit["composite"] else (lambda rec: rec)
+    comp = (lambda rec: _blend(m_win, init_d, rec)) if edit is not None and edit["composite"] else (lambda rec: rec)
     if autoencoder is None:
         rec = comp(x)
         return (rec[:, :, crop:-crop] if crop else rec), x

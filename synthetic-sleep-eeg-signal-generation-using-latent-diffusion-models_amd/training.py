@@ -409,8 +409,102 @@ def _weighting_args(scheduler, loss_weighting, snr_gamma, per_sample_out, B, dev
     return True, wtab
 
 
+CONTEXT_DRAW_DEFAULTS = {"p_none": 0.1, "p_prefix": 0.3}
+
+
+def context_draw_args(spec, L):
+    """The draw of the training masks as (p_none, p_prefix, span_min, span_max), checked as the library checks it -- a ValueError before the
+    device is touched.  spec: a dict with any of p_none (0.1), p_prefix (0.3), span_min (max(1, L // 32)), span_max (max(span_min, L // 2));
+    the span defaults are conventions, not values measured on sleep data."""
+    unknown = set(spec) - {"p_none", "p_prefix", "span_min", "span_max"}
+    if unknown:
+        raise ValueError(f"unknown context_mask entries {sorted(unknown)}")
+    L = int(L)
+    p_none = float(spec.get("p_none", CONTEXT_DRAW_DEFAULTS["p_none"])); p_prefix = float(spec.get("p_prefix", CONTEXT_DRAW_DEFAULTS["p_prefix"]))
+    span_min = spec.get("span_min"); span_max = spec.get("span_max")
+    span_min = max(1, L // 32) if span_min is None else int(span_min)
+    span_max = max(span_min, L // 2) if span_max is None else int(span_max)
+    if not (0.0 <= p_none <= 1.0 and 0.0 <= p_prefix <= 1.0):
+        raise ValueError(f"p_none={p_none} and p_prefix={p_prefix} must lie in [0, 1]")
+    if float(torch.tensor(p_none, dtype=torch.float32) + torch.tensor(p_prefix, dtype=torch.float32)) > 1.0:      # the library's fp32 sum
+        raise ValueError(f"p_none + p_prefix = {p_none + p_prefix} exceeds 1")
+    if L < 1 or not 1 <= span_min <= span_max <= L:
+        raise ValueError(f"the span range [{span_min}, {span_max}] must satisfy 1 <= span_min <= span_max <= L = {L}")
+    return p_none, p_prefix, span_min, span_max
+
+
+def _context_step_args(unet, context_mask, context_latents, mask_out, x, what):
+    """-> (mask tensor or None, source tensor or None, draw tuple, mask_out) for eegldm_add_noise_context / eegldm_ldm_train_step_ctx;
+    every refusal is a ValueError before the device is touched."""
+    B, Cx, L = x.shape
+    cc = getattr(unet, "context_channels", 0)
+    if not cc:
+        raise ValueError(f"context_mask needs a UNetModel built with context_channels ({what})")
+    if cc != Cx + 1:
+        raise ValueError(f"the step forms a context of {Cx} + 1 channels (masked signal, mask), the model takes {cc}")
+    dev = unet.device
+    def dev_f32(v, shape, name):
+        if not torch.is_tensor(v) or tuple(v.shape) != shape:
+            raise ValueError(f"{name} must be a tensor of shape {shape}, got {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}")
+        return v.detach().to(dev, torch.float32).contiguous()
+    mask, draw = None, (0.0, 0.0, 1, 1)
+    if torch.is_tensor(context_mask):
+        mask = dev_f32(context_mask, (B, L), "context_mask")
+    elif isinstance(context_mask, dict):
+        draw = context_draw_args(context_mask, L)
+    else:
+        raise ValueError("context_mask must be a (B, L) tensor (1 = keep, 0 = regenerate) or a dict of draw parameters")
+    src = None if context_latents is None else dev_f32(context_latents, (B, Cx, L), "context_latents")
+    if mask_out is not None:
+        if (not torch.is_tensor(mask_out) or mask_out.dtype != torch.float32 or tuple(mask_out.shape) != (B, L) or not mask_out.is_contiguous()
+                or not mask_out.is_cuda or mask_out.device != torch.device(dev)):
+            raise ValueError(f"mask_out must be a contiguous float32 tensor of shape {(B, L)} on the model's device {dev}")
+    return mask, src, draw, mask_out
+
+
+def context_mask(ctx, B, L, spec=None, seed=0, offset=0, device=None):
+    """(B, L) training masks (1 = keep, 0 = regenerate) from eegldm_context_mask: sample b from Philox(seed, offset + b); advance offset by B
+    per step.  spec: see context_draw_args."""
+    p_none, p_prefix, span_min, span_max = context_draw_args(spec or {}, L)
+    if int(B) < 1:
+        raise ValueError(f"B={B} must be >= 1")
+    out = torch.empty(int(B), int(L), device=device or torch.device("cuda", ctx.device), dtype=torch.float32)
+    check(lib.eegldm_context_mask(ctx.h, ptr(out), int(B), int(L), p_none, p_prefix, span_min, span_max, int(seed), int(offset)))
+    return out
+
+
+def context_window(ctx, windows, mask, down):
+    """windows * upsample_nearest(mask, down) (eegldm_context_window): windows (B, Co, Lw), mask (B, Lw // down).  The masked input of the
+    context encode, in training and in sampling alike."""
+    down = int(down)
+    if windows.dim() != 3 or mask.dim() != 2 or down < 1 or windows.shape[2] % down or tuple(mask.shape) != (windows.shape[0], windows.shape[2] // down):
+        raise ValueError(f"windows {tuple(windows.shape)} and mask {tuple(mask.shape)} do not fit down={down}: mask must be (B, Lw / down)")
+    dev = torch.device("cuda", ctx.device)
+    w = windows.detach().to(dev, torch.float32).contiguous(); m = mask.detach().to(dev, torch.float32).contiguous()
+    out = torch.empty_like(w)
+    check(lib.eegldm_context_window(ctx.h, ptr(w), ptr(m), down, ptr(out), w.shape[0], w.shape[1], w.shape[2]))
+    return out
+
+
+def add_noise_context(unet, scheduler, x0, noise, timesteps, context_mask, context_latents=None, mask_seed=0, mask_offset=0, mask_out=None):
+    """-> (noisy, context): eegldm_add_noise_context, one launch.  context = [m * (context_latents or x0) | m], (B, C + 1, L)."""
+    return _add_noise_context(unet, scheduler, x0, noise, timesteps, _context_step_args(unet, context_mask, context_latents, mask_out, x0, "add_noise_context"),
+                              mask_seed, mask_offset)
+
+
+def _add_noise_context(unet, scheduler, x0, noise, timesteps, checked, mask_seed, mask_offset):
+    """add_noise_context behind the checks: checked = what _context_step_args returned"""
+    mask, src, draw, mask_out = checked
+    B, Cx, L = x0.shape
+    noisy = torch.empty_like(x0); context = torch.empty(B, Cx + 1, L, device=x0.device, dtype=torch.float32)
+    check(lib.eegldm_add_noise_context(unet.ctx.h, ptr(x0), ptr(src), ptr(noise), ptr(timesteps), ptr(scheduler._acp_dev), ptr(mask), draw[0], draw[1],
+                                       draw[2], draw[3], int(mask_seed), int(mask_offset), ptr(noisy), ptr(context), ptr(mask_out), B, Cx, L))
+    return noisy, context
+
+
 def ldm_train_step(unet, scheduler, latents, noise, timesteps, loss_out=None, grad_scale=1.0, grad_sync=None, labels=None, p_uncond=0.0,
-                   null_class=None, seed=0, offset=0, loss_weighting=None, snr_gamma=5.0, per_sample_out=None):
+                   null_class=None, seed=0, offset=0, loss_weighting=None, snr_gamma=5.0, per_sample_out=None, context_mask=None,
+                   context_latents=None, mask_seed=0, mask_offset=0, mask_out=None):
     """add_noise -> UNet forward -> MSE against noise (epsilon) or velocity (v_prediction) -> backward.
     Accumulates into unet.flat_grad; returns the device scalar loss tensor.  grad_sync: an
     eegldm.distributed.OverlappedGradSync -- the tail of the gradient buffer is all-reduced while the input blocks'
@@ -420,8 +514,22 @@ def ldm_train_step(unet, scheduler, latents, noise, timesteps, loss_out=None, gr
     -- advance `offset` by B per step; the backward uses the replaced labels.
     loss_weighting: None (default) = the plain MSE through the exports above.  "none" / "min_snr" / a (T,) table (schedulers.loss_weights,
     snr_gamma) = the weighted step (eegldm_ldm_train_step_weighted): sample b counts wtab[t_b] in the loss and its gradient, and
-    per_sample_out (a (B,) float32 device tensor) receives the UNWEIGHTED per-sample losses (for NoiseLevelLoss)."""
+    per_sample_out (a (B,) float32 device tensor) receives the UNWEIGHTED per-sample losses (for NoiseLevelLoss).
+    context_mask (a UNetModel built with context_channels = C + 1; required there, refused elsewhere): a (B, L) keep-mask (1 = keep, 0 =
+    regenerate) or a dict of draw parameters (context_draw_args) -- the masks are then drawn on the device from Philox(mask_seed,
+    mask_offset + b), advance mask_offset by B per step.  The model sees [m * context_latents | m] as its context (context_latents None:
+    the latents themselves; the LDM passes the encoding of the MASKED window) and the loss runs over the whole sample
+    (eegldm_ldm_train_step_ctx; weights as loss_weighting says, None = all ones).  mask_out ((B, L) float32 device tensor): the masks used."""
     B, _C, L = latents.shape
+    ctx_model = bool(getattr(unet, "context_channels", 0))
+    if ctx_model != (context_mask is not None):
+        raise ValueError("context_mask must be given if and only if the UNet was built with context_channels")
+    if ctx_model:
+        cmask, csrc, cdraw, mask_out = _context_step_args(unet, context_mask, context_latents, mask_out, latents, "ldm_train_step")
+        if loss_weighting is None:
+            loss_weighting = "none"
+    elif context_latents is not None or mask_out is not None:
+        raise ValueError("context_latents / mask_out need context_mask")
     weighted, wtab = _weighting_args(scheduler, loss_weighting, snr_gamma, per_sample_out, B, unet.device)
     if loss_out is None:
         loss_out = torch.zeros(1, device=unet.device)
@@ -443,7 +551,13 @@ def ldm_train_step(unet, scheduler, latents, noise, timesteps, loss_out=None, gr
         grad_sync.begin()
         set_grad_hook(unet, grad_sync.on_ready)
     try:
-        if weighted:
+        if ctx_model:
+            check(lib.eegldm_ldm_train_step_ctx(unet.h, ptr(latents), ptr(noise), ptr(timesteps), ptr(scheduler._acp_dev),
+                                                PRED[scheduler.prediction_type], B, L, grad_scale, ptr(loss_out), ptr(wtab),
+                                                ptr(per_sample_out), ptr(lab) if cond else None, float(p_uncond) if cond else 0.0,
+                                                nc if cond else 0, int(seed), int(offset), ptr(csrc), ptr(cmask), cdraw[0], cdraw[1], cdraw[2],
+                                                cdraw[3], int(mask_seed), int(mask_offset), ptr(mask_out)))
+        elif weighted:
             check(lib.eegldm_ldm_train_step_weighted(unet.h, ptr(latents), ptr(noise), ptr(timesteps), ptr(scheduler._acp_dev),
                                                      PRED[scheduler.prediction_type], B, L, grad_scale, ptr(loss_out), ptr(wtab),
                                                      ptr(per_sample_out), ptr(lab) if cond else None, float(p_uncond) if cond else 0.0,
@@ -477,7 +591,8 @@ def usleep_train_step(model, x, labels, class_weight=None, grad_scale=1.0, loss_
 
 
 def dm_train_step(unet, scheduler, images, noise, timesteps, spectral_weight=0.0, spectral_loss=False, loss_out=None, grad_sync=None, grad_scale=1.0,
-                  loss_weighting=None, snr_gamma=5.0, per_sample_out=None):
+                  loss_weighting=None, snr_gamma=5.0, per_sample_out=None, context_mask=None, context_latents=None, mask_seed=0, mask_offset=0,
+                  mask_out=None):
     """Pixel-space diffusion step of /root/reference/src/training/training_diffusion.py:141-151 (config_dm.yaml, BASELINE C5):
     epsilon prediction directly on the (B,1,3072) windows, loss = mse(noise_pred, noise) [+ spectral_weight *
     JukeboxLoss(sum)(noise_pred, noise)].  Composed from the same native calls as the latent step: add_noise, UNet forward,
@@ -485,7 +600,16 @@ def dm_train_step(unet, scheduler, images, noise, timesteps, spectral_weight=0.0
     grad_scale: the GradScaler's loss scale (training_diffusion.py:37,149-151 -- `scaler.scale(loss).backward()`): it multiplies d pred, i.e.
     every gradient of the backward; the reported loss stays unscaled and the optimizer step divides the scale out again (GradScaler.step).
     loss_weighting / snr_gamma / per_sample_out: as in ldm_train_step -- eegldm_diffusion_loss (target of the scheduler's prediction type) in
-    place of eegldm_mse_loss; the spectral term still accumulates into d pred afterwards, unweighted."""
+    place of eegldm_mse_loss; the spectral term still accumulates into d pred afterwards, unweighted.
+    context_mask / context_latents / mask_seed / mask_offset / mask_out: as in ldm_train_step, on a UNetModel built with context_channels --
+    eegldm_add_noise_context in place of add_noise, then unet(noisy, timesteps=t, context=c); the loss still runs over the whole window."""
+    ctx_model = bool(getattr(unet, "context_channels", 0))
+    if ctx_model != (context_mask is not None):
+        raise ValueError("context_mask must be given if and only if the UNet was built with context_channels")
+    if not ctx_model and (context_latents is not None or mask_out is not None):
+        raise ValueError("context_latents / mask_out need context_mask")
+    if ctx_model:                              # (the refusals, ahead of everything else)
+        checked = _context_step_args(unet, context_mask, context_latents, mask_out, images, "dm_train_step")
     weighted, wtab = _weighting_args(scheduler, loss_weighting, snr_gamma, per_sample_out, images.shape[0], unet.device)
     dev = unet.device
     if loss_out is None:
@@ -493,8 +617,13 @@ def dm_train_step(unet, scheduler, images, noise, timesteps, spectral_weight=0.0
     unet.train()
     x = images.to(dev, torch.float32).contiguous(); nz = noise.to(dev, torch.float32).contiguous()
     B, Cc, L = x.shape
-    noisy = scheduler.add_noise(original_samples=x, noise=nz, timesteps=timesteps)
-    pred = unet(noisy, timesteps=timesteps)
+    if ctx_model:
+        t = timesteps.to(dev, torch.int64).contiguous()
+        noisy, context = _add_noise_context(unet, scheduler, x, nz, t, checked, mask_seed, mask_offset)
+        pred = unet(noisy, timesteps=t, context=context)
+    else:
+        noisy = scheduler.add_noise(original_samples=x, noise=nz, timesteps=timesteps)
+        pred = unet(noisy, timesteps=timesteps)
     dpred = torch.empty_like(pred)
     if weighted:
         t = timesteps.to(dev, torch.int64).contiguous()
