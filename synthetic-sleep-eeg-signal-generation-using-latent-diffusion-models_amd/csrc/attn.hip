@@ -75,6 +75,8 @@ struct ChainArgs {
   // fuse_kv == 2 (round 5): a THIRD pass dV = P^T dO behind it -- the probabilities are fetched again (73 KB per sample, L2) at the end of
   // the dK pass and overwrite the dS tile, tiles = rows of dO (= A1); the result goes to dV
   int fuse_kv; const bf16_t* Q3; long ldq3, sQ3; bf16_t* dK; bf16_t* dV;
+  // forward, optional: residual rows [B][T][ldr] added to the product-2 accumulators in fp32 ahead of the store (out = R + P V); null: out = P V
+  const bf16_t* R; long ldr, sR;
 };
 #define ATTN_STAMP(k) do { if (p.stamps && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.stamps[k] = __builtin_readcyclecounter(); } while (0)
 
@@ -144,6 +146,8 @@ __global__ __launch_bounds__(64 * NCW * NQ) void attn_chain_kernel(const ChainAr
   const long ld0 = p.ldb2, ld1 = fuse_kv ? p.ldq3 : p.ldb2, ld2 = p.lda1;
   bf16_t* const dst0 = p.O; bf16_t* const dst1 = fuse_kv ? p.dK : p.O; bf16_t* const dst2 = fuse_v ? p.dV : p.O;
   const long sO = p.sO, ldo = p.ldo;
+  const bf16_t* const res = (MODE == 0 && p.R) ? p.R + (long)b * p.sR : nullptr;      // (forward only; read at the output store)
+  const long ldres = p.ldr;
   // (sources / destinations are switched at pass boundaries through two-way selects only: a three-way `pass == 0 ? a : pass == 1 ? b : c`
   //  became a lookup table on the stack -- 160 bytes of scratch per lane in every instantiation)
   auto issue_tile = [&](const bf16_t* src, const long ld, int uu, int buf) __attribute__((always_inline)) {
@@ -421,8 +425,14 @@ __global__ __launch_bounds__(64 * NCW * NQ) void attn_chain_kernel(const ChainAr
       for (int i = 0; i < 2; i++)
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-          uint2 o; o.x = pack16x2<T16>(o2[c][i][j][0], o2[c][i][j][1]); o.y = pack16x2<T16>(o2[c][i][j][2], o2[c][i][j][3]);
-          *(uint2*)(p.O + (long)b * p.sO + (long)(m0 + mr + i * 16 + lm) * p.ldo + c * 256 + wc * 64 + j * 16 + q * 4) = o;
+          const long row = m0 + mr + i * 16 + lm; const int col = c * 256 + wc * 64 + j * 16 + q * 4;
+          float r0 = o2[c][i][j][0], r1 = o2[c][i][j][1], r2 = o2[c][i][j][2], r3 = o2[c][i][j][3];
+          if (MODE == 0 && res) {
+            const uint2 xr = *(const uint2*)(res + row * ldres + col);
+            r0 += w16_lo<T16>(xr.x); r1 += w16_hi<T16>(xr.x); r2 += w16_lo<T16>(xr.y); r3 += w16_hi<T16>(xr.y);
+          }
+          uint2 o; o.x = pack16x2<T16>(r0, r1); o.y = pack16x2<T16>(r2, r3);
+          *(uint2*)(p.O + (long)b * p.sO + row * p.ldo + col) = o;
         }
     ATTN_STAMP(3);
     return;
@@ -500,8 +510,14 @@ __global__ __launch_bounds__(64 * NCW * NQ) void attn_chain_kernel(const ChainAr
       for (int i = 0; i < RF2; i++)
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-          uint2 o; o.x = pack16x2<T16>(acc2[i][j][0], acc2[i][j][1]); o.y = pack16x2<T16>(acc2[i][j][2], acc2[i][j][3]);
-          *(uint2*)(cdst + (long)b * sO + (long)(m0 + mq2 + i * 16 + lm) * ldo + nc * 256 + wc2 * 64 + j * 16 + q * 4) = o;
+          const long row = m0 + mq2 + i * 16 + lm; const int col = nc * 256 + wc2 * 64 + j * 16 + q * 4;
+          float r0 = acc2[i][j][0], r1 = acc2[i][j][1], r2 = acc2[i][j][2], r3 = acc2[i][j][3];
+          if (MODE == 0 && res) {
+            const uint2 xr = *(const uint2*)(res + row * ldres + col);
+            r0 += w16_lo<T16>(xr.x); r1 += w16_hi<T16>(xr.x); r2 += w16_lo<T16>(xr.y); r3 += w16_hi<T16>(xr.y);
+          }
+          uint2 o; o.x = pack16x2<T16>(r0, r1); o.y = pack16x2<T16>(r2, r3);
+          *(uint2*)(cdst + (long)b * sO + row * ldo + col) = o;
         }
       stores_pending = true;
     }
@@ -565,8 +581,9 @@ bool attn_chain_ok(int dtype, int T, int C, long ldq, long ldo) {
 
 // forward: probs written, out = softmax(alpha q k^T) v
 template <typename T16>
-static int chain_fwd_t(eegldm_ctx* ctx, const void* qkv, long ldq, void* out, long ldo, void* probs, int B, int T, int C) {
+static int chain_fwd_t(eegldm_ctx* ctx, const void* qkv, long ldq, void* out, long ldo, void* probs, int B, int T, int C, const void* resid, long ldr) {
   ChainArgs a = {};
+  a.R = (const bf16_t*)resid; a.ldr = ldr; a.sR = (long)T * ldr;
   const bf16_t* q = (const bf16_t*)qkv;
   a.A1 = q; a.lda1 = ldq; a.sA1 = (long)T * ldq; a.B1 = q + C; a.ldb1 = ldq; a.sB1 = (long)T * ldq; a.B2 = q + 2 * C; a.ldb2 = ldq; a.sB2 = (long)T * ldq;
   a.P = (bf16_t*)probs; a.sP = (long)T * T; a.O = (bf16_t*)out; a.ldo = ldo; a.sO = (long)T * ldo; a.T = T; a.C = C; a.alpha = 1.0f / sqrtf((float)C);
@@ -605,8 +622,11 @@ static int chain_bwd_t(eegldm_ctx* ctx, const void* qkv, long ldq, const void* p
   }
 }
 
-int attn_chain_fwd(eegldm_ctx* ctx, const void* qkv, long ldq, void* out, long ldo, void* probs, int B, int T, int C, int dtype) {
-  return dtype == EEGLDM_F16 ? chain_fwd_t<f16_t>(ctx, qkv, ldq, out, ldo, probs, B, T, C) : chain_fwd_t<bf16_t>(ctx, qkv, ldq, out, ldo, probs, B, T, C);
+int attn_chain_fwd(eegldm_ctx* ctx, const void* qkv, long ldq, void* out, long ldo, void* probs, int B, int T, int C, int dtype,
+                   const void* resid, long ldr) {
+  EEG_CHECK(!resid || (ldr % 4 == 0 && (size_t)resid % 8 == 0), "attention residual rows must be 8-byte aligned");
+  return dtype == EEGLDM_F16 ? chain_fwd_t<f16_t>(ctx, qkv, ldq, out, ldo, probs, B, T, C, resid, ldr)
+                             : chain_fwd_t<bf16_t>(ctx, qkv, ldq, out, ldo, probs, B, T, C, resid, ldr);
 }
 int attn_chain_bwd(eegldm_ctx* ctx, const void* qkv, long ldq, const void* probs, const void* dout, long lddo, void* dq, long lddq,
                    void* dS, int B, int T, int C, int fuse_kv, int dtype) {

@@ -57,7 +57,11 @@ struct AttnDesc { int c; long n_w, n_b, qkv_w, qkv_b, pr_w, pr_b; int heads = 1;
 struct RsDesc { int c = 0, up = 0, conv = 0; long w = -1, b = -1; };
 struct RsTape { View x, xu; int B, Lin, Lout; };
 struct ResTape { View x, a1, xr, h1, a2, hn; float *st1, *st2; int B, Lin, Lout; unsigned long long drop_off = 0; bool dropped = false; };
-struct AttnTape { View x, xn, qkv, o; void* probs; float* st; int B, T; };
+struct AttnTape { View x, xn, qkv, o; void* probs; float* st; int B, T; int fold = -1; };      // fold >= 0: index into NetBase::folds, qkv holds V' and o is not allocated
+// proj_out folded into the V projection (attn_fold.hip): per foldable block (16-bit storage, one head, C % 256 == 0) an effective
+// qkv weight [3C][C] = [Wq ; Wk ; round(Wp Wv)] at element e_off of NetBase::wE (its data-gradient copy at the same offset of wET), an fp32
+// effective bias [bq | bk | Wp bv + bp] at b_off of bE, and an fp32 gradient scratch [3C][C] + [3C] at g_off of gE
+struct AttnFold { AttnDesc a; long e_off, b_off, g_off; };
 
 struct NetBase {
   eegldm_ctx* ctx = nullptr;
@@ -103,6 +107,17 @@ struct NetBase {
   float2* fuse_alloc(size_t slots) { if (fuse_used + slots > fuse_cap) return nullptr; float2* a = fuse_stats + fuse_used; fuse_used += slots; return a; }
   float2* fuse_stats = nullptr; size_t fuse_cap = 0, fuse_used = 0;     // float2 slots; every slot of a used area is written by its producer
   std::vector<ResTape> rt; std::vector<AttnTape> at;
+  // folded AttentionBlocks: the creators list their blocks in attn_list, bind() allocates, sync_weights() -- and nothing else -- refreshes wE / wET / bE.
+  // A backward sends the qkv weight gradient of a folded block to its scratch (zeroed there) and lists the block in fold_pending;
+  // flush_attn_folds() back-transforms everything listed into the real gradient slots (+=) once the launches that complete it are out.
+  std::vector<AttnDesc> attn_list; std::vector<AttnFold> folds; std::vector<int> fold_pending;
+  void* wE = nullptr; void* wET = nullptr; void* d_kbe = nullptr; int n_kbe = 0; long kbe_chunks = 0;
+  float* bE = nullptr; float* gE = nullptr;
+  int find_fold(const AttnDesc& a) const { for (size_t i = 0; i < folds.size(); i++) if (folds[i].a.qkv_w == a.qkv_w) return (int)i; return -1; }
+  bool fold_usable() const { return !folds.empty() && (size_t)params % 16 == 0 && (size_t)grads % 16 == 0; }      // (the fold kernels move float4s)
+  const void* WE(const AttnFold& f) const { return (const char*)wE + (size_t)f.e_off * 2; }
+  int refresh_attn_folds();
+  int flush_attn_folds();
 
   const void* W(long off) const { return (const char*)wT + (size_t)off * dtype_size(dtype); }
   const float* P(long off) const { return params + off; }
@@ -129,6 +144,7 @@ int res_forward(NetBase* u, const ResDesc& r, const View& x, int B, int Lin, con
 int res_backward(NetBase* u, const ResDesc& r, const ResTape& t, const View& dout, const View& dx, float* demb_all,
                  const View* extra = nullptr, int* extra_done = nullptr);
 int attn_forward(NetBase* u, const AttnDesc& a, const View& x, int B, int T, const View& out);
+// (a folded block's weight gradients are complete only after NetBase::flush_attn_folds(), which the caller runs behind op_wgrad_flush in the deferred mode)
 int attn_backward(NetBase* u, const AttnDesc& a, const AttnTape& t, const View& dout, const View& dx);
 int resample_forward(NetBase* u, const RsDesc& s, const View& x, int B, int Lin, const View& out, RsTape* tape);
 int resample_backward(NetBase* u, const RsDesc& s, const RsTape& t, const View& dout, const View& dx);

@@ -60,7 +60,82 @@ int NetBase::bind(float* p, float* g) {
       }
     }
   }
+  // proj_out folded into the V projection (net.h AttnFold): buffers for every 16-bit single-head block the fused attention kernel can serve
+  if (dtype != EEGLDM_F32 && folds.empty()) {
+    long eo = 0, bo = 0, go = 0;
+    for (const AttnDesc& a : attn_list) {
+      if (a.heads != 1 || a.c % 256 != 0 || a.qkv_w % 8 != 0 || a.pr_w % 8 != 0 || a.qkv_b % 4 != 0) continue;
+      AttnFold f; f.a = a; f.e_off = eo; f.b_off = bo; f.g_off = go;
+      eo += (long)3 * a.c * a.c; bo += 3 * a.c; go += (long)3 * a.c * a.c + 3 * a.c;
+      folds.push_back(f);
+    }
+    if (!folds.empty()) {
+      HIP_TRY(hipMalloc(&wE, (size_t)eo * 2));
+      HIP_TRY(hipMalloc(&bE, (size_t)bo * sizeof(float)));
+      HIP_TRY(hipMalloc(&gE, (size_t)go * sizeof(float)));
+      if (!no_kblk) {      // the data gradient of the qkv conv finds its [Cout / 32][Cin][32] copy under the effective weight's address, like qkv.weight's under W()
+        std::vector<KbDesc> tab; long chunks = 0;
+        for (const AttnFold& f : folds) {
+          KbDesc d; d.off = f.e_off; d.chunk0 = chunks; d.cout = 3 * f.a.c; d.cin = f.a.c;
+          chunks += (long)3 * f.a.c * f.a.c / 8; tab.push_back(d);
+        }
+        HIP_TRY(hipMalloc(&wET, (size_t)eo * 2));
+        HIP_TRY(hipMalloc(&d_kbe, tab.size() * sizeof(KbDesc)));
+        HIP_TRY(hipMemcpy(d_kbe, tab.data(), tab.size() * sizeof(KbDesc), hipMemcpyHostToDevice));
+        n_kbe = (int)tab.size(); kbe_chunks = chunks;
+        for (const AttnFold& f : folds) ctx->kblk_t[WE(f)] = (const char*)wET + (size_t)f.e_off * 2;
+      }
+    }
+  }
   return sync_weights();
+}
+// effective qkv weights and biases of the folded AttentionBlocks from the CURRENT parameters: one batched product launch per channel count
+int NetBase::refresh_attn_folds() {
+  std::vector<char> done(folds.size(), 0);
+  for (size_t i = 0; i < folds.size(); i++) {
+    if (done[i]) continue;
+    const int C = folds[i].a.c;
+    std::vector<FoldGemm> gs; std::vector<FoldMisc> ms;
+    for (size_t j = i; j < folds.size(); j++) {
+      if (done[j] || folds[j].a.c != C) continue;
+      done[j] = 1;
+      const AttnFold& f = folds[j]; const AttnDesc& a = f.a;
+      char* e = (char*)wE + (size_t)f.e_off * 2;
+      FoldGemm g = {}; g.A = P(a.pr_w); g.B = P(a.qkv_w) + (long)2 * C * C; g.out16 = e + (size_t)2 * C * C * 2;      // Wvp = Wp Wv
+      gs.push_back(g);
+      FoldMisc m = {}; m.w16 = W(a.qkv_w); m.e16 = e; m.bqkv = P(a.qkv_b); m.wp = P(a.pr_w); m.bp = P(a.pr_b); m.be = bE + f.b_off;
+      ms.push_back(m);
+    }
+    EEG_TRY(fold_misc_launch(ctx, ms.data(), (int)ms.size(), C, 0));
+    EEG_TRY(fold_gemm_launch(ctx, gs.data(), (int)gs.size(), C, dtype));
+  }
+  return kblk_pack_t(ctx, wE, wET, (const KbDesc*)d_kbe, n_kbe, kbe_chunks);
+}
+// gradients with respect to the effective weights (scratch) -> the real slots, added: one batched launch pair per channel count, fixed
+// summation order and no atomics (bit-reproducible).  Runs behind the launches that complete the scratch and ahead of the gradient hook.
+int NetBase::flush_attn_folds() {
+  std::vector<int> pend; pend.swap(fold_pending);
+  std::vector<char> done(pend.size(), 0);
+  for (size_t i = 0; i < pend.size(); i++) {
+    if (done[i]) continue;
+    const int C = folds[pend[i]].a.c;
+    std::vector<FoldGemm> gs; std::vector<FoldMisc> ms;
+    for (size_t j = i; j < pend.size(); j++) {
+      if (done[j] || folds[pend[j]].a.c != C) continue;
+      done[j] = 1;
+      const AttnFold& f = folds[pend[j]]; const AttnDesc& a = f.a;
+      const float* gw = gE + f.g_off; const float* gb = gw + (long)3 * C * C; const float* gv = gw + (long)2 * C * C;
+      FoldGemm g1 = {}; g1.A = P(a.pr_w); g1.ta = 1; g1.B = gv; g1.acc = G(a.qkv_w) + (long)2 * C * C;                    // dWv += Wp^T dWvp
+      FoldGemm g2 = {}; g2.A = gv; g2.B = P(a.qkv_w) + (long)2 * C * C; g2.tb = 1; g2.u = gb + 2 * C; g2.v = P(a.qkv_b) + 2 * C;
+      g2.acc = G(a.pr_w);                                                                                                 // dWp += dWvp Wv^T + dbv' bv^T
+      gs.push_back(g1); gs.push_back(g2);
+      FoldMisc m = {}; m.wp = P(a.pr_w); m.g = gw; m.gb = gb; m.dwqkv = G(a.qkv_w); m.dbqkv = G(a.qkv_b); m.dbp = G(a.pr_b);
+      ms.push_back(m);
+    }
+    EEG_TRY(fold_misc_launch(ctx, ms.data(), (int)ms.size(), C, 1));
+    EEG_TRY(fold_gemm_launch(ctx, gs.data(), (int)gs.size(), C, dtype));
+  }
+  return 0;
 }
 int NetBase::flush_gn_folds() {
   for (const GnFold& f : gn_pending) EEG_TRY(op_gn_slot_reduce_deferred(ctx, f.dgamma, f.dbeta, f.C, f.region));
@@ -86,6 +161,12 @@ void NetBase::release_kblk() {      // the two copies are independent: a model m
     }
     (void)hipFree(wKT); (void)hipFree(d_kbt); wKT = nullptr; d_kbt = nullptr; n_kbt = 0;
   }
+  if (wE) {      // the effective qkv weights of the folded AttentionBlocks and their data-gradient copies
+    if (wET) for (const AttnFold& f : folds) ctx->kblk_t.erase(WE(f));
+    (void)hipFree(wE); (void)hipFree(bE); (void)hipFree(gE); wE = nullptr; bE = nullptr; gE = nullptr;
+    if (wET) { (void)hipFree(wET); (void)hipFree(d_kbe); wET = nullptr; d_kbe = nullptr; n_kbe = 0; }
+    folds.clear(); fold_pending.clear();
+  }
 }
 int NetBase::sync_weights() {
   EEG_CHECK(params, "bind parameters first");
@@ -96,7 +177,8 @@ int NetBase::sync_weights() {
     constexpr size_t ONE = (size_t)3 * 128 * 128 * 2;
     EEG_TRY(s2ws_pack(ctx, W(s2_offs[i]), (char*)wS2 + (2 * i) * ONE, (char*)wS2 + (2 * i + 1) * ONE, 128, 64));
   }
-  return kblk_pack_t(ctx, wT, wKT, (const KbDesc*)d_kbt, n_kbt, kbt_chunks);
+  EEG_TRY(kblk_pack_t(ctx, wT, wKT, (const KbDesc*)d_kbt, n_kbt, kbt_chunks));
+  return folds.empty() ? 0 : refresh_attn_folds();
 }
 int entry_query(const NetBase* u, int i, char* name, int cap, long* offset, long* numel, int* ndim, int shape[3]) {
   EEG_CHECK(u && i >= 0 && i < (int)u->entries.size(), "entry index %d out of range", i);
@@ -326,9 +408,24 @@ int attn_forward(NetBase* u, const AttnDesc& a, const View& x, int B, int T, con
     if (rcq < 0) return rcq;
     if (rcq == 1) u->fused_used = true;
   }
+  // proj_out folded into the V projection (net.h AttnFold): the qkv conv takes the effective weight and bias, the attention kernel writes
+  // out = x + P V' and there is no proj_out launch.  Training and the normal eval forward only: the few-row eval route keeps its own fusion,
+  // and a shape the fused attention kernel does not serve keeps the composition (whose last GEMM has no batched residual operand).
+  EEG_ENV_VAR(bool, no_fold, getenv("EEGLDM_NO_ATTN_FOLD") != nullptr);
+  if (!no_fold && !u->eval_fuse && a.heads == 1 && u->fold_usable() && attn_chain_ok(dt, T, C, 3 * C, out.ld) &&
+      x.ld % 4 == 0 && (size_t)x.p % 8 == 0 && (size_t)out.p % 8 == 0)
+    t.fold = u->find_fold(a);
+  const AttnFold* f = t.fold >= 0 ? &u->folds[t.fold] : nullptr;
   if (rcq != 1) {
     EEG_TRY(eegldm_groupnorm_fwd(ctx, x.p, x.ld, u->P(a.n_w), u->P(a.n_b), t.xn.p, C, t.st, B, T, C, AG, GN_EPS, 0, 0, nullptr, 0, dt));
-    EEG_TRY(op_conv_fwd(ctx, dt, t.xn.p, C, u->W(a.qkv_w), u->P(a.qkv_b), t.qkv.p, 3 * C, B, T, C, 3 * C, 1, 1, 0, 0, nullptr, 0, nullptr, 0));
+    EEG_TRY(op_conv_fwd(ctx, dt, t.xn.p, C, f ? u->WE(*f) : u->W(a.qkv_w), f ? u->bE + f->b_off : u->P(a.qkv_b), t.qkv.p, 3 * C, B, T, C, 3 * C, 1, 1, 0, 0,
+                        nullptr, 0, nullptr, 0));
+  }
+  if (f) {      // out = x + P V': no `o`, no projection (the fused kernel needs no logits scratch)
+    ALLOC_OR_FAIL(t.probs, u->alloc_act((long)B * T, T));
+    EEG_TRY(op_attention_fwd(ctx, dt, t.qkv.p, 3 * C, out.p, out.ld, t.probs, nullptr, B, T, C, x.p, x.ld));
+    u->at.push_back(t);
+    return 0;
   }
   // heads (QKVAttentionLegacy, unet.py:107-125): head h owns columns [3 h ch, 3 (h + 1) ch) = [q | k | v] of the qkv rows and columns
   // [h ch, (h + 1) ch) of the output; one launch sequence per head on column views (the probabilities of all heads stay on the tape)
@@ -363,9 +460,16 @@ int attn_backward(NetBase* u, const AttnDesc& a, const AttnTape& t, const View& 
   void* dqkv_keep = nullptr;      // deferred weight gradients: the qkv conv's dY operand must outlive this block
   if (ctx->defer_wgrad && u->param_grads) ALLOC_OR_FAIL(dqkv_keep, u->alloc_act((long)B * T, 3 * C));
   Arena::Mark mk = u->arena.mark();
-  EEG_TRY(op_conv_wgrad(ctx, dt, t.o.p, C, dout.p, dout.ld, u->G(a.pr_w), u->G(a.pr_b), B, T, C, C, 1, 1, 0, 0));
-  void* d_o; ALLOC_OR_FAIL(d_o, u->alloc_act((long)B * T, C));
-  EEG_TRY(op_conv_dgrad(ctx, dt, dout.p, dout.ld, u->W(a.pr_w), d_o, C, B, T, C, C, 1, 1, 0, 0, nullptr, 0));
+  // folded block (net.h AttnFold): d_o = dout, the tape's qkv holds V' and there is no proj_out gradient here; the one weight gradient is
+  // with respect to the effective weight and bias: it goes to this block's scratch, zeroed here, and NetBase::flush_attn_folds() adds its
+  // back-transform into the real slots -- right away, or behind the grouped flush that completes it in the deferred mode
+  const AttnFold* f = t.fold >= 0 ? &u->folds[t.fold] : nullptr;
+  View d_o = dout;
+  if (!f || (size_t)dout.p % 16 != 0) { ALLOC_OR_FAIL(d_o.p, u->alloc_act((long)B * T, C)); d_o.ld = C; }      // (the fused backward kernel fetches 16-byte chunks of its rows)
+  if (!f) {
+    EEG_TRY(op_conv_wgrad(ctx, dt, t.o.p, C, dout.p, dout.ld, u->G(a.pr_w), u->G(a.pr_b), B, T, C, C, 1, 1, 0, 0));
+    EEG_TRY(op_conv_dgrad(ctx, dt, dout.p, dout.ld, u->W(a.pr_w), d_o.p, C, B, T, C, C, 1, 1, 0, 0, nullptr, 0));
+  } else if (d_o.p != dout.p) EEG_TRY(ew_copy_rows(ctx, d_o.p, C, dout.p, dout.ld, (long)B * T, C, dt));
   void* dqkv = dqkv_keep;
   if (!dqkv) ALLOC_OR_FAIL(dqkv, u->alloc_act((long)B * T, 3 * C));
   float* dprobs; ALLOC_OR_FAIL(dprobs, (float*)u->arena.alloc(sizeof(float) * (size_t)B * T * T));
@@ -374,11 +478,18 @@ int attn_backward(NetBase* u, const AttnDesc& a, const AttnTape& t, const View& 
     const int H = a.heads, ch = C / H; const size_t es = dtype_size(dt);
     for (int h = 0; h < H; h++)
       EEG_TRY(op_attention_bwd(ctx, dt, (const char*)t.qkv.p + (size_t)h * 3 * ch * es, 3 * C, (const char*)t.probs + (size_t)h * B * T * T * es,
-                               (const char*)d_o + (size_t)h * ch * es, C, (char*)dqkv + (size_t)h * 3 * ch * es, 3 * C, dprobs, dlogits, B, T, ch));
+                               (const char*)d_o.p + (size_t)h * ch * es, d_o.ld, (char*)dqkv + (size_t)h * 3 * ch * es, 3 * C, dprobs, dlogits, B, T, ch));
   }
-  EEG_TRY(op_conv_wgrad(ctx, dt, t.xn.p, C, dqkv, 3 * C, u->G(a.qkv_w), u->G(a.qkv_b), B, T, C, 3 * C, 1, 1, 0, 0));
+  if (!f) EEG_TRY(op_conv_wgrad(ctx, dt, t.xn.p, C, dqkv, 3 * C, u->G(a.qkv_w), u->G(a.qkv_b), B, T, C, 3 * C, 1, 1, 0, 0));
+  else if (u->param_grads) {
+    float* gw = u->gE + f->g_off;
+    HIP_TRY(hipMemsetAsync(gw, 0, sizeof(float) * ((size_t)3 * C * C + 3 * C), ctx->stream));
+    EEG_TRY(op_conv_wgrad(ctx, dt, t.xn.p, C, dqkv, 3 * C, gw, gw + (long)3 * C * C, B, T, C, 3 * C, 1, 1, 0, 0));
+    u->fold_pending.push_back(t.fold);
+    if (!ctx->defer_wgrad) EEG_TRY(u->flush_attn_folds());
+  }
   void* dxn; ALLOC_OR_FAIL(dxn, u->alloc_act((long)B * T, C));
-  EEG_TRY(op_conv_dgrad(ctx, dt, dqkv, 3 * C, u->W(a.qkv_w), dxn, C, B, T, C, 3 * C, 1, 1, 0, 0, nullptr, 0));
+  EEG_TRY(op_conv_dgrad(ctx, dt, dqkv, 3 * C, f ? u->WE(*f) : u->W(a.qkv_w), dxn, C, B, T, C, 3 * C, 1, 1, 0, 0, nullptr, 0));
   // (dgamma / dbeta slot fold: batched with all the others in the grouped mode, else right here)
   int gn_deferred = 0;
   EEG_TRY(op_groupnorm_bwd(ctx, t.x.p, t.x.ld, u->P(a.n_w), u->P(a.n_b), t.st, dxn, C, dx.p, dx.ld, u->G(a.n_w), u->G(a.n_b),

@@ -273,8 +273,9 @@ int op_linear_wgrad(eegldm_ctx* ctx, int dtype, const void* x, long ldx, const v
 
 // ------------------------------------------------------------------ attention (unet.py:107-125)
 int op_attention_fwd(eegldm_ctx* ctx, int dtype, const void* qkv, long ldq, void* out, long ldo, void* probs, float* logits,
-                     int B, int T, int C) {
-  if (attn_chain_ok(dtype, T, C, ldq, ldo)) return attn_chain_fwd(ctx, qkv, ldq, out, ldo, probs, B, T, C, dtype);
+                     int B, int T, int C, const void* resid, long ldr) {
+  if (attn_chain_ok(dtype, T, C, ldq, ldo)) return attn_chain_fwd(ctx, qkv, ldq, out, ldo, probs, B, T, C, dtype, resid, ldr);
+  EEG_CHECK(!resid, "the residual operand of the attention output needs the fused kernel");
   const size_t es = dtype_size(dtype);
   const char* q = (const char*)qkv; const char* k = q + (size_t)C * es; const char* v = q + (size_t)2 * C * es;
   GemmArgs a = {};

@@ -165,6 +165,7 @@ int build_plan(eegldm_unet* u) {
         u->add_entry(p + "qkv.weight", a.qkv_w, 3, 3 * a.c, a.c, 1); u->add_entry(p + "qkv.bias", a.qkv_b, 1, 3 * a.c);
         a.pr_w = take((long)a.c * a.c); a.pr_b = take(a.c);
         u->add_entry(p + "proj_out.weight", a.pr_w, 3, a.c, a.c, 1); u->add_entry(p + "proj_out.bias", a.pr_b, 1, a.c);
+        u->attn_list.push_back(a);
       }
       blk.layers.push_back(L);
     }
@@ -481,6 +482,7 @@ extern "C" int eegldm_unet_backward(eegldm_unet* u, const float* dy, float* dx_o
   const int cin = u->cfg.in_channels, cout = u->cfg.out_channels;
   const int n_in = (int)u->in_blocks.size(), n_out = (int)u->out_blocks.size();
   u->have_tape = false;   // the tape is consumed
+  u->fold_pending.clear();
   // Weight gradients of the GEMM-path convs are RECORDED during the backward chain and launched grouped by shape (ops.hip:
   // op_wgrad_flush) when their slice of the gradient buffer is due: at the all-reduce hook (out / output_blocks / middle_block) and
   // at the end.  EEGLDM_NO_GROUPED_WGRAD=1 restores one launch per layer on the side stream.
@@ -529,6 +531,7 @@ extern "C" int eegldm_unet_backward(eegldm_unet* u, const float* dy, float* dx_o
   // across ranks while the input blocks' backward runs
   EEG_TRY(u->flush_gn_folds());   // the last middle ResBlock's deferred dgamma / dbeta fold
   if (u->grad_hook) { EEG_TRY(op_wgrad_flush(ctx)); EEG_TRY(op_gn_fold_flush(ctx)); }     // the hook promises final gradients for this slice: launch what is pending for it
+  if (u->grad_hook) EEG_TRY(u->flush_attn_folds());      // ... and back-transform the folded AttentionBlocks' qkv gradients that flush completed (net.h AttnFold)
   if (u->grad_hook) u->grad_hook(u->grad_hook_user, u->off_mid_begin, u->nparams - u->off_mid_begin);
   // ---- input blocks, reversed: gradient of block i's output = consumer's dx + skip gradient
   for (int i = n_in - 1; i >= 1; i--) {
@@ -564,6 +567,7 @@ extern "C" int eegldm_unet_backward(eegldm_unet* u, const float* dy, float* dx_o
   EEG_TRY(ew_colsum(ctx, dh1, te, nullptr, 0, u->G(u->off_te0_b), 1, B, te, F));
   EEG_TRY(op_linear_wgrad(ctx, F, u->e0, mc, dh1, te, u->G(u->off_te0_w), mc, B, te, mc));
   EEG_TRY(op_wgrad_flush(ctx));      // the remaining (input-block) weight gradients, grouped by shape
+  EEG_TRY(u->flush_attn_folds());    // the folded AttentionBlocks whose qkv gradient that flush completed: back-transformed into the real slots
   EEG_TRY(op_gn_fold_flush(ctx));    // and the remaining GroupNorm dgamma / dbeta folds
   return 0;
 }
