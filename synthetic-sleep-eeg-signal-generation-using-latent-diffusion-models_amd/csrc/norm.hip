@@ -10,6 +10,7 @@
 #include "common.h"
 #include "internal.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -397,6 +398,13 @@ __device__ __forceinline__ ResMap resmap(int CC, int C, int cpg, int xcd) {
 __device__ __forceinline__ int res_row(int k, int ty, int TY, bool pair) {
   return pair ? 2 * ((k >> 1) * TY + ty) + (k & 1) : k * TY + ty;
 }
+// Full-slab backward, between pass 1 and pass 2: the packed rows pass through an empty asm statement, so that pass 2 unpacks them again.
+// Without it hipcc carries xhat of pass 1 over the barriers in place of the packed rows -- twice the registers -- and spills.  No
+// instruction is emitted and no value changes.
+// compiler-only fence (no instruction): the loads above it stay in front of the loads below it in the in-order memory queue
+__device__ __forceinline__ void gn_issue_order() { asm volatile("" ::: "memory"); }
+__device__ __forceinline__ void keep_packed(uint2& r) { asm volatile("" : "+v"(r.x), "+v"(r.y)); }
+__device__ __forceinline__ void keep_packed(float4& r) { asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w)); }
 
 #ifdef EEG_STAGE_TIMING
 __device__ unsigned long long gn_tlog[4096 * 8];
@@ -756,6 +764,170 @@ __global__ __launch_bounds__(NTH) GN_BWD_ATTR void gn_bwd_resident_kernel(const 
   }
 }
 
+// FULL-SLAB form of the backward (1024 threads, every thread active, RPT * TY == L), bit-identical to gn_bwd_resident_kernel: same partial
+// sums in the same order, same fp64 accumulators, same mapping.  What differs is what the memory queue sees ("Counting vmcnt"):
+//   * no `l < L` / `m.act` predicate; the resampling mode (RS) and the presence of the addends and of the column sums (FL: bit 0 dxr, 1 dxr2,
+//     2 colsum_ps) are compile-time, so no unrolled loop contains a branch and hipcc keeps count of the outstanding loads and stores
+//     (`slots` stays a run-time test: it guards eight atomics of the ty == 0 threads in front of pass 2, not a loop);
+//   * (mean, rstd), gamma and beta are loaded FIRST, in front of the rows: pass 1 (VALU-bound: exp + rcp per element) starts on row 0 while
+//     rows 1.. are still in flight (vmcnt counts down) -- loaded behind the rows, their first use waited for the whole slab;
+//   * pass 2 stores free-running: the predicated kernel waits vmcnt(1) / vmcnt(0) in every row = for the previous row's store to be acknowledged;
+//   * every tensor is addressed as (wave-uniform base + k * row-lane stride) + ONE per-thread offset: twelve per-row offsets per tensor in
+//     VGPRs are what pushed the addend variants over 128 registers.
+// The gradient rows are fetched packed at every RS (RS 2: both rows of the pair) and converted in pass 1; a lone first addend is fetched
+// packed under the barrier rounds at RS 0 / 1.  What stays a load inside pass 2 -- a further 12-row register array (24 at RS 2) does not
+// fit 128 VGPRs -- is the first addend at RS 2 and BOTH addends where there are two (seven of the LDM UNet's launches per step: the skip gradient);
+// in straight-line code hipcc issues those loads rows ahead of their use and waits with a count.
+template <typename T, int RS> struct GnDyRow {      // dy-resolution row(s) of the thread's row k = k * TY + ty (TY is even: resident_full_slab)
+  unsigned stride, off;                              // bytes: per k (wave-uniform), per thread
+  __device__ __forceinline__ GnDyRow(int ty, int TY, unsigned ldb, unsigned cb) {
+    stride = (RS == 0 ? (unsigned)TY : RS == 1 ? (unsigned)TY >> 1 : 2u * (unsigned)TY) * ldb;
+    off = (RS == 0 ? (unsigned)ty : RS == 1 ? (unsigned)ty >> 1 : 2u * (unsigned)ty) * ldb + cb;
+  }
+  __device__ __forceinline__ typename Vec<T, 4>::type ld(const char* base, int k, unsigned second) const {
+    return *(const typename Vec<T, 4>::type*)(base + (size_t)k * stride + (off + second));
+  }
+};
+// effective gradient of one row from its packed row(s): the arithmetic of load_dy_eff32
+template <typename T, int RS>
+__device__ __forceinline__ void gn_dy_eff(const typename Vec<T, 4>::type& a, const typename Vec<T, 4>::type& a2, float d[4]) {
+  unpack4<T>(a, d);
+  if constexpr (RS == 1) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) d[j] *= 0.5f;
+  } else if constexpr (RS == 2) {
+    float e[4]; unpack4<T>(a2, e);
+#pragma unroll
+    for (int j = 0; j < 4; j++) d[j] += e[j];
+  }
+}
+template <typename T, int RPT, int RS, bool SILU, int FL>
+__global__ __launch_bounds__(NTB) void gn_bwd_resident_full_kernel(const T* __restrict__ x, long ldx, const float* __restrict__ gamma,
+                                                                   const float* __restrict__ beta, const float* __restrict__ stats,
+                                                                   const T* __restrict__ dy, long lddy, T* __restrict__ dx, long lddx,
+                                                                   const T* __restrict__ dxr, long lddxr, float* __restrict__ slots,
+                                                                   float* __restrict__ colsum_ps, long ldps, int L, int C, int G, int CC,
+                                                                   const T* __restrict__ dxr2, long lddxr2, int xcd, int nslot) {
+  typedef typename Vec<T, 4>::type V4;
+  constexpr bool HAS_DXR = (FL & 1) != 0, HAS_DXR2 = (FL & 2) != 0, HAS_CS = (FL & 4) != 0;
+  constexpr int NDY = RS == 2 ? 2 : 1;      // packed gradient rows per row
+  __shared__ double redg[2 * RES_MAXG];
+  __shared__ double redc[3 * RES_MAXC];
+  const int cpg = C / G;
+  const ResMap m = resmap<NTB>(CC, C, cpg, xcd);
+  const int b = m.b;
+  const float* st = stats + ((long)b * G + m.c / cpg) * 2;
+  const float mean = st[0], rstd = st[1];
+  float ga[4], be[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) { ga[j] = gamma[m.c + j]; be[j] = beta[m.c + j]; }
+  gn_issue_order();
+  V4 raw[RPT], dr[NDY * RPT];
+  float d[RPT][4];
+  const unsigned cb = (unsigned)m.c * (unsigned)sizeof(T);
+  const unsigned ldxb = (unsigned)ldx * (unsigned)sizeof(T), lddyb = (unsigned)lddy * (unsigned)sizeof(T);
+  const char* xs = (const char*)(x + (long)b * L * ldx);
+  const char* dys = (const char*)(dy + (long)b * dy_rows(L, RS) * lddy);
+  const GnDyRow<T, 0> rx(m.ty, m.TY, ldxb, cb);
+  const GnDyRow<T, RS> rdy(m.ty, m.TY, lddyb, cb);
+#pragma unroll
+  for (int k = 0; k < RPT; k++) {
+    raw[k] = rx.ld(xs, k, 0);
+    dr[NDY * k] = rdy.ld(dys, k, 0);
+    if constexpr (RS == 2) dr[2 * k + 1] = rdy.ld(dys, k, lddyb);
+    gn_issue_order();      // rows land in the order pass 1 consumes them (hipcc's scheduler moved row 0 to the back of the queue)
+  }
+  for (int i = threadIdx.x; i < 2 * RES_MAXG + 3 * RES_MAXC; i += NTB) { if (i < 2 * RES_MAXG) redg[i] = 0.0; else redc[i - 2 * RES_MAXG] = 0.0; }
+  __syncthreads();
+  {
+    float dg[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
+    const float nmr = -mean * rstd;
+#pragma unroll
+    for (int k = 0; k < RPT; k++) {
+      float v[4]; unpack4<T>(raw[k], v);
+      gn_dy_eff<T, RS>(dr[NDY * k], dr[NDY * k + NDY - 1], d[k]);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const float xh = fmaf(v[j], rstd, nmr);
+        float dz = d[k][j];
+        if constexpr (SILU) dz *= silu_grad_f(fmaf(ga[j], xh, be[j]));
+        d[k][j] = dz;
+        dg[j] = fmaf(dz, xh, dg[j]); db[j] += dz;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) { atomicAdd(&redc[m.tx * 4 + j], (double)dg[j]); atomicAdd(&redc[RES_MAXC + m.tx * 4 + j], (double)db[j]); }
+  }
+#pragma unroll
+  for (int k = 0; k < RPT; k++) keep_packed(raw[k]);
+  // the first addend's rows, packed: their round trip runs under the two barrier rounds (as in the predicated kernel)
+  constexpr bool ER_BATCH = HAS_DXR && !HAS_DXR2 && RS != 2;
+  V4 er[ER_BATCH ? RPT : 1];
+  const char* dxrs = HAS_DXR ? (const char*)(dxr + (long)b * dy_rows(L, RS) * lddxr) : nullptr;
+  const unsigned lddxrb = (unsigned)lddxr * (unsigned)sizeof(T);
+  const GnDyRow<T, RS> rer(m.ty, m.TY, lddxrb, cb);
+  if constexpr (ER_BATCH) {
+#pragma unroll
+    for (int k = 0; k < RPT; k++) er[k] = rer.ld(dxrs, k, 0);
+  }
+  __syncthreads();
+  if (m.ty == 0) {
+    double p1 = 0.0, p2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) { p1 += (double)ga[j] * redc[RES_MAXC + m.tx * 4 + j]; p2 += (double)ga[j] * redc[m.tx * 4 + j]; }
+    atomicAdd(&redg[2 * m.gl], p1); atomicAdd(&redg[2 * m.gl + 1], p2);
+  }
+  __syncthreads();
+  const double inv_n = gn_inv_n<T>(cpg, L);
+  const float m1 = (float)(redg[2 * m.gl] * inv_n), m2 = (float)(redg[2 * m.gl + 1] * inv_n);
+  if (slots && m.ty == 0) {
+    float* sl = slots + (size_t)(b % nslot) * 2 * C;
+#pragma unroll
+    for (int j = 0; j < 4; j++) { atomicAdd(&sl[m.c + j], (float)redc[m.tx * 4 + j]); atomicAdd(&sl[C + m.c + j], (float)redc[RES_MAXC + m.tx * 4 + j]); }
+  }
+  const float rm1 = rstd * m1, rm2 = rstd * m2;
+  float gr[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) gr[j] = ga[j] * rstd;
+  float cs[4] = {0.f, 0.f, 0.f, 0.f};
+  char* dxs = (char*)(dx + (long)b * L * lddx);
+  const char* dxr2s = HAS_DXR2 ? (const char*)(dxr2 + (long)b * L * lddxr2) : nullptr;
+  const GnDyRow<T, 0> rdx(m.ty, m.TY, (unsigned)lddx * (unsigned)sizeof(T), cb), rdx2(m.ty, m.TY, (unsigned)lddxr2 * (unsigned)sizeof(T), cb);
+#pragma unroll
+  for (int k = 0; k < RPT; k++) {
+    float v[4], o[4]; unpack4<T>(raw[k], v);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const float xh = fmaf(v[j], rstd, -mean * rstd);
+      o[j] = fmaf(d[k][j], gr[j], fmaf(xh, -rm2, -rm1));
+    }
+    if constexpr (HAS_DXR) {
+      float e[4];
+      if constexpr (ER_BATCH) gn_dy_eff<T, RS>(er[k], er[k], e);
+      else gn_dy_eff<T, RS>(rer.ld(dxrs, k, 0), rer.ld(dxrs, k, lddxrb), e);
+#pragma unroll
+      for (int j = 0; j < 4; j++) o[j] += e[j];
+    }
+    if constexpr (HAS_DXR2) {
+      float e[4]; unpack4<T>(rdx2.ld(dxr2s, k, 0), e);
+#pragma unroll
+      for (int j = 0; j < 4; j++) o[j] += e[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) cs[j] += o[j];
+    store4<T>((T*)(dxs + (size_t)k * rdx.stride + rdx.off), o);
+  }
+  if constexpr (HAS_CS) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) atomicAdd(&redc[2 * RES_MAXC + m.tx * 4 + j], (double)cs[j]);
+    __syncthreads();
+    if (m.ty == 0) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) colsum_ps[(long)b * ldps + m.c + j] = (float)redc[2 * RES_MAXC + m.tx * 4 + j];
+    }
+  }
+}
+
 // ------------------------------------------------------------------ pipelined form of the one-pass backward (round 4; bf16, resample 0)
 // gn_bwd_resident_kernel is a chain per workgroup -- load the slab, pass 1, two barrier rounds, pass 2, store -- and with one 1024-thread
 // workgroup per CU nothing overlaps the chain: HBM idles while the VALU runs and the other way round (in the LDM step 47 us per 50 MB
@@ -989,6 +1161,20 @@ int resident_chunk(int L, int C, int G, int resample_pair, int rpt_max, int* rpt
   return best;
 }
 
+// full slab of the 1024-thread resident kernels: the chunk's columns divide the block, and the instantiation's rows per thread times the
+// row lanes are exactly L -- every thread is active and no row needs the `l < L` predicate (pair mode: rows 2 * ((k / 2) * TY + ty) + k % 2
+// cover [0, RPT * TY) as well, RPT being even; an even TY lets the backward address the half-resolution rows l / 2 as k * TY / 2 + ty / 2)
+bool resident_full_slab(int L, int cc, int rpt_inst) {
+  const int tx = cc / 4;
+  return tx >= 1 && NTB % tx == 0 && (NTB / tx) % 2 == 0 && rpt_inst % 2 == 0 && (long)rpt_inst * (NTB / tx) == L;
+}
+
+// f(std::integral_constant<int, v>) for the run-time v in [0, N): turns a small run-time index into a template argument
+template <int N, typename F> void gn_static_switch(int v, F&& f) {
+  if (v == N - 1) f(std::integral_constant<int, N - 1>());
+  else if constexpr (N > 1) gn_static_switch<N - 1>(v, f);
+}
+
 int grid_for(long total_threads, eegldm_ctx* ctx) {
   long blocks = (total_threads + NT - 1) / NT;
   long cap = (long)ctx->num_cu * 16;
@@ -1206,7 +1392,17 @@ int gn_bwd_t(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const
 #define GN_BWD_RES(R) do { if (resample == 0 && raw0) GN_BWD_RES1(R, true); else GN_BWD_RES1(R, false); } while (0)
       constexpr int RLO = sizeof(T) == 2 ? 6 : 4, RHI = sizeof(T) == 2 ? 12 : 8;
       gn_note(1, 2, 1, nth, rpt <= RLO ? RLO : RHI, cc, xcd);
-      if (rpt <= RLO) GN_BWD_RES(RLO); else GN_BWD_RES(RHI);
+      // same route, same geometry; a full slab runs the straight-line body, instantiated for what this launch has (EEGLDM_GN_NO_STREAM=1: never)
+      EEG_ENV_VAR(bool, no_stream, getenv("EEGLDM_GN_NO_STREAM") != nullptr);
+      if (!no_stream && nth == NTB && resident_full_slab(L, cc, rpt <= RLO ? RLO : RHI)) {
+        const int sel = (dxr ? 1 : 0) | (dxr2 ? 2 : 0) | (colsum_ps ? 4 : 0) | (silu ? 8 : 0) | (rpt <= RLO ? 0 : 16) | ((resample == 1 ? 1 : resample == 2 ? 2 : 0) << 5);
+        gn_static_switch<96>(sel, [&](auto s) {
+          constexpr int S = decltype(s)::value;
+          hipLaunchKernelGGL((gn_bwd_resident_full_kernel<T, (S & 16) ? RHI : RLO, (S / 32), (S & 8) != 0, (S & 7)>), grid, dim3(NTB), 0, ctx->stream,
+                             (const T*)x, ldx, gamma, beta, stats, (const T*)dy, lddy, (T*)dx, lddx, (const T*)dxr, lddxr, slots, colsum_ps, ldps,
+                             L, C, G, cc, (const T*)dxr2, lddxr2, xcd, nslot);
+        });
+      } else if (rpt <= RLO) GN_BWD_RES(RLO); else GN_BWD_RES(RHI);
 #undef GN_BWD_RES
 #undef GN_BWD_RES1
 #undef GN_BWD_RES2
