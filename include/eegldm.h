@@ -117,6 +117,14 @@ int eegldm_debug_gn_last_route(int backward, int* out6_host);
  * (0 scalar, 1 4-wide), blocks, rows per block, TX, TY of the statistics / reduce launch, deterministic mode (1 / 0), rows per block of the
  * apply launch.  No reference counterpart. */
 int eegldm_debug_bn_last_route(int backward, int* out8_host);
+/* developer aid: the thin-channel direct kernel (csrc/direct_conv.hip) that served the calling thread's last forward / data-gradient launch
+ * (which = 0) or weight-gradient launch (which = 1), as eight ints: family (which = 0: 1 row, 2 in1_seg, 3 thin_in_reg, 4 thin_in with LDS
+ * weights, 5 thin_out_run, 6 thin_out, 7 rowdot, 8 point; which = 1: 1 tinyv + fold, 2 tiny, 3 in1out, 4 wt, 5 generic; 0: none yet), the
+ * template channel counts CI and CO (row, tinyv: both; thin_in_reg: CI; wt: CI = 1 for the wide-Cout instantiation, 0 for wide Cin; else 0),
+ * data-gradient mode (1 / 0), grid blocks, rows per block and grid-stride pass (rounded up, so blocks * rows_per_block < rows proves that the
+ * grid-stride loop wrapped), block partials written for a fold (0: the blocks add atomically), deterministic mode (1 / 0).  Convs that the
+ * MFMA GEMM family serves leave the record untouched.  No reference counterpart. */
+int eegldm_debug_dconv_last_route(int which, int* out8_host);
 /* developer aid: BatchNorm statistics (and the running-statistics update) from per-block column partials parts_dev [nb][2 C] fp32 (interleaved
  * sum, sum of squares) -- the fold that follows a conv whose epilogue left them.  No reference counterpart. */
 int eegldm_debug_bn_stats_from_parts(eegldm_ctx*, const float* parts_dev, int nb, float* stats, float* running_mean, float* running_var,

@@ -241,7 +241,8 @@ __global__ __launch_bounds__(NT) void dconv_in1_seg_kernel(const DArgs a) {
 #pragma unroll
   for (int t = 0; t < 3; t++) toff[t] = t < a.K ? (dg ? a.K - 1 - t : t) : 0;
   const T* xin = (const T*)a.in + (long)b * a.Li * a.ldin;
-  for (int i = threadIdx.x; i < SEG * 2 + 8; i += NT) { const int v = v0 + i; xs[i] = (i < nin && v >= 0 && v < a.Li) ? ld_f32(xin + (long)v * a.ldin) : 0.f; }   // (zeros behind the segment: a K < 3 conv multiplies them by zero weights)
+  for (int i = threadIdx.x; i < SEG * 2 + 8; i += NT) { const int v = v0 + i; xs[i] = (i < nin && v >= 0 && v < a.Li) ? ld_f32(xin + (long)v * a.ldin) : 0.f; }
+  const bool k1 = a.K > 1, k2 = a.K > 2;       // a tap beyond K contributes a selected 0, never x * 0 (inf * 0 = NaN)
   float w[3][G], bias[G];
 #pragma unroll
   for (int t = 0; t < 3; t++)
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(NT) void dconv_in1_seg_kernel(const DArgs a) {
   const T* res = a.resid ? (const T*)a.resid + ((long)b * a.Lo + l0) * a.ldr + o0 : nullptr;
 #pragma unroll 4
   for (int l = ty; l < nseg; l += rpb) {
-    const float x0 = xs[l * sm + toff[0]], x1 = xs[l * sm + toff[1]], x2 = xs[l * sm + toff[2]];
+    const float x0 = xs[l * sm + toff[0]], x1 = k1 ? xs[l * sm + toff[1]] : 0.f, x2 = k2 ? xs[l * sm + toff[2]] : 0.f;
     float acc[G];
 #pragma unroll
     for (int k = 0; k < G; k++) acc[k] = fmaf(x2, w[2][k], fmaf(x1, w[1][k], fmaf(x0, w[0][k], bias[k])));
@@ -428,13 +429,13 @@ __global__ __launch_bounds__(NT) void dconv_wgrad_in1out_kernel(const T* __restr
 #pragma unroll 8
   for (int v = v_lo + rl; v < v_hi; v += rpb) {
     const RowVec<T, G> xv = *(const RowVec<T, G>*)(xb + (long)v * ldx);
-    float d[3];
+    float d[3]; bool ok[3];      // ok: the tap pairs this x row with a dy row of the sample; outside it x is a selected 0, not x * 0 (inf * 0 = NaN)
 #pragma unroll
-    for (int t = 0; t < 3; t++) d[t] = t < K ? dys[v - t + pad_l + 2] : 0.f;
+    for (int t = 0; t < 3; t++) { const int l = v - t + pad_l; ok[t] = t < K && l >= 0 && l < Lo; d[t] = t < K ? dys[l + 2] : 0.f; }
 #pragma unroll
     for (int k = 0; k < G; k++) { const float xf = ld_f32(&xv.v[k]);
 #pragma unroll
-      for (int t = 0; t < 3; t++) acc[t][k] = fmaf(xf, d[t], acc[t][k]); }
+      for (int t = 0; t < 3; t++) acc[t][k] = fmaf(ok[t] ? xf : 0.f, d[t], acc[t][k]); }
   }
 #pragma unroll
   for (int t = 0; t < 3; t++)
@@ -467,7 +468,7 @@ __global__ __launch_bounds__(NT) void dconv_wgrad_wt_kernel(const T* __restrict_
 #pragma unroll
       for (int k = 0; k < G; k++) acc[t][j][k] = 0.f;
   const int rows = B * Lo;                    // (the launcher keeps B * Lo < 2^31: 32-bit index arithmetic in the row loop)
-  // loads are unconditional (clamped row, zero factor for taps outside the sample): predicated loads are waited for one by one
+  // loads are unconditional (clamped row, a selected zero for taps outside the sample): predicated loads are waited for one by one
 #pragma unroll 2
   for (int r = blockIdx.x * rpb + rl; r < rows; r += gridDim.x * rpb) {
     const int b = (int)((unsigned)r / (unsigned)Lo), lo = r - b * Lo;
@@ -495,12 +496,12 @@ __global__ __launch_bounds__(NT) void dconv_wgrad_wt_kernel(const T* __restrict_
           }
         }
     } else {
-      RowVec<T, G> xvv[3]; float f[3];
+      RowVec<T, G> xvv[3]; bool f[3];
 #pragma unroll
       for (int t = 0; t < 3; t++) {
         const int v = lo * stride + t - pad_l;
         const bool ok = t < K && v >= 0 && v < Li;
-        f[t] = ok ? 1.f : 0.f;
+        f[t] = ok;
         xvv[t] = *(const RowVec<T, G>*)(x + ((long)b * Li + (ok ? v : 0)) * ldx + lane * G);
       }
       float d[2];
@@ -509,7 +510,7 @@ __global__ __launch_bounds__(NT) void dconv_wgrad_wt_kernel(const T* __restrict_
 #pragma unroll
       for (int t = 0; t < 3; t++)
 #pragma unroll
-        for (int k = 0; k < G; k++) { const float xv = ld_f32(&xvv[t].v[k]) * f[t];
+        for (int k = 0; k < G; k++) { const float xv = f[t] ? ld_f32(&xvv[t].v[k]) : 0.f;      // selected, not x * 0: the clamped row may hold inf / NaN
 #pragma unroll
           for (int j = 0; j < 2; j++) acc[t][j][k] = fmaf(d[j], xv, acc[t][j][k]); }
     }
@@ -724,7 +725,33 @@ inline int grid_cap(long blocks, eegldm_ctx* ctx) {
   if (blocks < 1) blocks = 1;
   return (int)(blocks < cap ? blocks : cap);
 }
+
+// last route of dconv_run (slot 0) / dconv_wgrad (slot 1) (eegldm_debug_dconv_last_route: the route-aware tests confirm that a case ran
+// on the kernel it names).  family, slot 0: 1 row, 2 in1_seg, 3 thin_in_reg, 4 thin_in (LDS weights), 5 thin_out_run, 6 thin_out, 7 rowdot,
+// 8 point; slot 1: 1 tinyv (+ tiny_fold or the ordered fold), 2 tiny, 3 in1out, 4 wt, 5 generic; 0: nothing launched yet.
+// ci / co: the template channel counts (row, tinyv: both; thin_in_reg: ci; wt: ci = 1 for WIDE_OUT, 0 for wide Cin; 0 where the kernel has
+// none); dgrad: data-gradient mode; blocks: grid blocks (in1_seg / in1out: both grid dimensions multiplied); rpb: output rows (weight
+// gradient: reduction rows) one block covers per grid-stride pass, rounded UP where threads own (row, channel group) pairs, so that
+// blocks * rpb < rows proves a wrap; parts: block partials written for a fold, 0 = the blocks add atomically; det: deterministic mode.
+// Host-side bookkeeping, one record per host thread, nothing the kernels read.
+struct DconvRoute { int family, ci, co, dgrad, blocks, rpb, parts, det; };
+thread_local DconvRoute g_dconv_route[2] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
+enum { DR_ROW = 1, DR_IN1_SEG, DR_THIN_IN_REG, DR_THIN_IN, DR_THIN_OUT_RUN, DR_THIN_OUT, DR_ROWDOT, DR_POINT };
+enum { DW_TINYV = 1, DW_TINY, DW_IN1OUT, DW_WT, DW_GENERIC };
+inline void dconv_note(int slot, int family, int ci, int co, int dgrad, long blocks, long rpb, long parts) {
+  DconvRoute& r = g_dconv_route[slot];
+  r.family = family; r.ci = ci; r.co = co; r.dgrad = dgrad; r.blocks = (int)blocks; r.rpb = (int)rpb; r.parts = (int)parts;
+  r.det = eeg_deterministic() ? 1 : 0;
+}
 }  // namespace
+
+extern "C" int eegldm_debug_dconv_last_route(int which, int* out8_host) {
+  if (!out8_host || which < 0 || which > 1) return EEGLDM_ERR_INVALID;
+  const DconvRoute& r = g_dconv_route[which];
+  out8_host[0] = r.family; out8_host[1] = r.ci; out8_host[2] = r.co; out8_host[3] = r.dgrad; out8_host[4] = r.blocks; out8_host[5] = r.rpb;
+  out8_host[6] = r.parts; out8_host[7] = r.det;
+  return 0;
+}
 
 // is this conv handled by the direct kernels (vs the MFMA implicit GEMM)?
 bool conv_is_thin(int Cin, int Cout, int dtype) {
@@ -764,6 +791,7 @@ int dconv_run(eegldm_ctx* ctx, int dtype, bool dgrad, const void* in, long ldin,
 #undef DROW_CO
 #undef DROW
     LAUNCH_CHECK();
+    dconv_note(0, DR_ROW, ci, co, a.dgrad, g.x, NT, 0);
     return 0;
   }
   {
@@ -782,6 +810,7 @@ int dconv_run(eegldm_ctx* ctx, int dtype, bool dgrad, const void* in, long ldin,
         else if (dtype == EEGLDM_F16) hipLaunchKernelGGL((dconv_in1_seg_kernel<f16_t, SEG>), gs, dim3(NT), 0, ctx->stream, a);
         else hipLaunchKernelGGL((dconv_in1_seg_kernel<bf16_t, SEG>), gs, dim3(NT), 0, ctx->stream, a);
         LAUNCH_CHECK();
+        dconv_note(0, DR_IN1_SEG, 0, 0, a.dgrad, (long)gs.x * gs.y, SEG, 0);
         return 0;
       }
       if (reg_ok && a.Ci <= 4 && gpr <= NT && NT % gpr == 0 && rows < (1L << 30)) {
@@ -791,6 +820,7 @@ int dconv_run(eegldm_ctx* ctx, int dtype, bool dgrad, const void* in, long ldin,
 #undef DTI_T
 #undef DTI
         LAUNCH_CHECK();
+        dconv_note(0, DR_THIN_IN_REG, a.Ci == 1 ? 1 : (a.Ci == 2 ? 2 : 4), 0, a.dgrad, g.x, NT / gpr, 0);
         return 0;
       }
       const size_t sh = ((size_t)K * a.Ci * a.Co + a.Co) * sizeof(float);
@@ -798,6 +828,7 @@ int dconv_run(eegldm_ctx* ctx, int dtype, bool dgrad, const void* in, long ldin,
       else if (dtype == EEGLDM_F16) hipLaunchKernelGGL((dconv_thin_in_kernel<f16_t>), g, dim3(NT), sh, ctx->stream, a);
       else hipLaunchKernelGGL((dconv_thin_in_kernel<bf16_t>), g, dim3(NT), sh, ctx->stream, a);
       LAUNCH_CHECK();
+      dconv_note(0, DR_THIN_IN, 0, 0, a.dgrad, g.x, (NT + gpr - 1) / gpr, 0);
       return 0;
     }
     const int lpr = a.Ci / G;
@@ -812,6 +843,7 @@ int dconv_run(eegldm_ctx* ctx, int dtype, bool dgrad, const void* in, long ldin,
         else if (dtype == EEGLDM_F16) hipLaunchKernelGGL((dconv_thin_out_run_kernel<f16_t, RUN>), gr, dim3(NT), 0, ctx->stream, a);
         else hipLaunchKernelGGL((dconv_thin_out_run_kernel<bf16_t, RUN>), gr, dim3(NT), 0, ctx->stream, a);
         LAUNCH_CHECK();
+        dconv_note(0, DR_THIN_OUT_RUN, 0, 0, a.dgrad, gr.x, (long)rpb * RUN, 0);
         return 0;
       }
       const dim3 g(grid_cap((rows + rpb - 1) / rpb, ctx));
@@ -820,6 +852,7 @@ int dconv_run(eegldm_ctx* ctx, int dtype, bool dgrad, const void* in, long ldin,
       else if (dtype == EEGLDM_F16) hipLaunchKernelGGL((dconv_thin_out_kernel<f16_t>), g, dim3(NT), sh, ctx->stream, a);
       else hipLaunchKernelGGL((dconv_thin_out_kernel<bf16_t>), g, dim3(NT), sh, ctx->stream, a);
       LAUNCH_CHECK();
+      dconv_note(0, DR_THIN_OUT, 0, 0, a.dgrad, g.x, rpb, 0);
       return 0;
     }
   }
@@ -834,6 +867,8 @@ int dconv_run(eegldm_ctx* ctx, int dtype, bool dgrad, const void* in, long ldin,
     else hipLaunchKernelGGL((dconv_point_kernel<bf16_t>), dim3(grid_cap((rows * a.Co + NT - 1) / NT, ctx)), dim3(NT), 0, ctx->stream, a);
   }
   LAUNCH_CHECK();
+  if (rowdot) dconv_note(0, DR_ROWDOT, 0, 0, a.dgrad, grid_cap((rows + 3) / 4, ctx), 4, 0);
+  else dconv_note(0, DR_POINT, 0, 0, a.dgrad, grid_cap((rows * a.Co + NT - 1) / NT, ctx), (NT + a.Co - 1) / a.Co, 0);
   return 0;
 }
 
@@ -870,6 +905,7 @@ int dconv_wgrad(eegldm_ctx* ctx, int dtype, const void* x, long ldx, const void*
         LAUNCH_CHECK();
       }
       if (bias_done && dbias) *bias_done = 1;
+      dconv_note(1, DW_TINYV, Cin, Cout, 0, blocks, NT, blocks);
       return 0;
     }
     const int tb = eeg_deterministic() ? 1 : blocks;      // one atomic per element and block: a single block is a single writer
@@ -883,6 +919,7 @@ int dconv_wgrad(eegldm_ctx* ctx, int dtype, const void* x, long ldx, const void*
       hipLaunchKernelGGL((dconv_wgrad_tiny_kernel<bf16_t>), dim3(tb), dim3(NT), 0, ctx->stream, (const bf16_t*)x, ldx, (const bf16_t*)dy, lddy,
                          dw, B, Lout, Lin, Cout, Cin, K, stride, pad_l);
     LAUNCH_CHECK();
+    dconv_note(1, DW_TINY, 0, 0, 0, tb, NT, 0);
     return 0;
   }
   {
@@ -903,6 +940,7 @@ int dconv_wgrad(eegldm_ctx* ctx, int dtype, const void* x, long ldx, const void*
         float* parts1 = (float*)((char*)ctx->scratch + (8u << 20));
         hipLaunchKernelGGL((dconv_wgrad_in1out_kernel<bf16_t>), dim3(B, nsegs), dim3(NT), 0, ctx->stream, (const bf16_t*)x, ldx, (const bf16_t*)dy, lddy, parts1, Lout, Cin, K, pad_l, segr);
         LAUNCH_CHECK();
+        dconv_note(1, DW_IN1OUT, 0, 0, 0, (long)B * nsegs, segr, (long)B * nsegs);
         return ew_fold_partials(ctx, parts1, B * nsegs, (int)((long)K * Cin), dw);
       }
       long nb = (rows + rpb - 1) / rpb; const long capb = (long)ctx->num_cu * 4; if (nb > capb) nb = capb;   // 48 KB of LDS per block: 3 per CU
@@ -916,6 +954,7 @@ int dconv_wgrad(eegldm_ctx* ctx, int dtype, const void* x, long ldx, const void*
       else { if (wide_out) DWT(bf16_t, true); else DWT(bf16_t, false); }
 #undef DWT
       LAUNCH_CHECK();
+      dconv_note(1, DW_WT, wide_out ? 1 : 0, 0, 0, nb, rpb, parts ? nb : 0);
       if (parts) EEG_TRY(ew_fold_partials(ctx, parts, (int)nb, (int)E, dw));
       return 0;
     }
@@ -935,5 +974,6 @@ int dconv_wgrad(eegldm_ctx* ctx, int dtype, const void* x, long ldx, const void*
     hipLaunchKernelGGL((dconv_wgrad_kernel<bf16_t>), dim3((unsigned)blocks), dim3(NT), 0, ctx->stream, (const bf16_t*)x, ldx,
                        (const bf16_t*)dy, lddy, dw, B, Lout, Lin, Cout, Cin, K, stride, pad_l, rpc);
   LAUNCH_CHECK();
+  dconv_note(1, DW_GENERIC, 0, 0, 0, blocks, rpc, 0);
   return 0;
 }

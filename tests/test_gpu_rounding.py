@@ -74,7 +74,7 @@ def _poison(t, spots):
 #   expected: None (thin) or (kernel, M-override or None)
 FWD_CASES = [
     ("thin direct k3", (2, 64, 3, 32, 3, 1, 1, 1), (0, 1, 2), "bs", {}, None, None),
-    ("thin direct k3 stride2 (conv_out shape)", (2, 64, 32, 1, 3, 2, 1, 1), (0, 1, 2), "b", {}, None, None),
+    ("thin direct k3 stride2 32->1 (thin_out kernel)", (2, 64, 32, 1, 3, 2, 1, 1), (0, 1, 2), "b", {}, None, None),
     ("conv_skinny 3-tap", (2, 96, 64, 192, 3, 1, 1, 1), (1, 2), "brs", {}, None, "conv_skinny"),
     ("conv_skinny 1x1", (2, 96, 64, 192, 1, 1, 0, 0), (1, 2), "brs", {}, None, "conv_skinny"),
     ("conv_ws Cin128 M16512 (smallest accepted)", (86, 192, 128, 256, 3, 1, 1, 1), (1, 2), "brs", {}, None, "conv_ws"),
