@@ -967,6 +967,29 @@ int eegldm_rows_standardize(eegldm_ctx*, const float* x, long ldx, long N, int D
 int eegldm_knn_rescore(eegldm_ctx*, const float* q, long ldq, const float* x, long ldx, int Nq, int D, int k, long index_base, long Nc,
                        const int64_t* best_i, float* out_d2);
 
+/* ---- kernel matrix times a thin matrix (MMD^2, KID, permutation two-sample test, MMD witness; csrc/kmm.hip).  fp32 in, float64 out;
+ * additive, ABI 8.
+ *   R[i][p] = sum_j k(a_i, b_j) V[j][p]     0 <= i < Na, 0 <= j < Nb, 0 <= p < P;  pairs with j - i == diag_off are left out
+ *   kind 0 (poly): k = (gamma <a, b> + coef0)^degree, degree 1..4 by repeated multiplication (KID: degree 3, gamma 1 / D, coef0 1)
+ *   kind 1 (rbf):  k = (1 / S) sum_s exp(-betas_host[s] d2), d2 = max(0, asq[i] + bsq[j] - 2 <a, b>), S = n_betas in 1..8, beta = 1 / (2 sigma^2);
+ *                  asq / bsq are the caller's eegldm_rows_sqnorm outputs and are taken as given (poly ignores them: NULL is fine).
+ * The Na x Nb kernel matrix never exists: a workgroup evaluates it in 128 x 128 tiles (f32-input MFMA: the dot product of a pair is one fmaf
+ * chain in ascending k whatever the pair's place), applies k in fp32, and multiplies each tile at once by its 128 x P slice of V (fmaf chains
+ * of 32 rows of B, each from zero in ascending j); the chains' results are added in float64.  out [Na][ldo] float64 is stored, or added onto when accumulate != 0, so B
+ * can be streamed in chunks (diag_off then counts from the chunk's first row).  EEGLDM_KMM_NO_DIAG leaves no pair out; left-out pairs and
+ * rows past Nb are removed by selection, so a NaN or inf there never reaches a sum.  Elsewhere non-finite values propagate as in K @ V under
+ * IEEE rules: a NaN row of B makes every R[i][p] NaN, also where V[j][p] == 0.
+ * lda / ldb / ldv / ldo are row strides in elements (>= D, D, P, P).  1 <= P <= 64, D >= 1, Na >= 1, Nb >= 0 (Nb == 0: zeros, or out left as
+ * it is when accumulating); a, asq, b, bsq, v need 4-byte alignment only, out 8.  Every refusal leaves out untouched.  B's tiles are cut into
+ * at most 32 slabs by a rule that depends on Nb alone; slab partials are summed from zero in index order, then stored or added onto out: no
+ * atomics, no memset, a result repeats bit for bit, a row of R does not depend on Na and a column not on P.  Workspace: slabs x rows x P
+ * float64 in the context's split-K buffer (main stream), at most 64 MiB: row blocks run in groups beyond that, which changes no bit. */
+#define EEGLDM_KMM_NO_DIAG  (-0x7fffffffffffffffL - 1)
+int eegldm_kernel_matmul(eegldm_ctx*, const float* a, long lda, const float* asq, const float* b, long ldb, const float* bsq,
+                         const float* v, long ldv, int Na, int Nb, int D, int P,
+                         int kind /* 0 poly, 1 rbf */, int degree, float gamma, float coef0, const float* betas_host, int n_betas,
+                         long diag_off, int accumulate, double* out, long ldo);
+
 #ifdef __cplusplus
 }
 #endif

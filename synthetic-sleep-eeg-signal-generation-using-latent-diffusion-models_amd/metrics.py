@@ -827,3 +827,237 @@ def memorisation_audit(synthetic, train_chunks, holdout, space="signal", k=1, la
     out.update({"space": space, "metric": "1 - pearson r" if space == "signal" else "squared euclidean distance of U-Sleep features",
                 "k": k, "lags": [int(l) for l in crops], "n_train": int(base)})
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- kernel two-sample statistics
+# MMD^2 (Gretton et al. 2012), KID (Binkowski et al. 2018: the unbiased MMD^2 under the cubic kernel (<a, b> / D + 1)^3), a permutation
+# p-value and the MMD witness function, all as float64 algebra on R = K(A, B) V (csrc/kmm.hip, eegldm_kernel_matmul): the kernel matrix
+# never exists, the weights V are indicator columns.  The functions that turn R into statistics take R as input and run anywhere;
+# everything that refuses an argument does so before the device is touched.
+KMM_NO_DIAG = -(1 << 63)
+KMM_MAX_COLS, KMM_MAX_SIGMAS = 64, 8
+KMM_KERNELS = ("poly", "rbf")
+
+
+def rbf_betas(sigmas):
+    """beta = 1 / (2 sigma^2) as the fp32 values the kernel multiplies by."""
+    s = np.asarray(sigmas, np.float64).reshape(-1)
+    if not 1 <= s.size <= KMM_MAX_SIGMAS:
+        raise ValueError(f"sigmas must hold 1..{KMM_MAX_SIGMAS} bandwidths, got {s.size}")
+    if not np.all(s > 0):                  # a NaN fails too
+        raise ValueError(f"sigmas must be positive, got {s.tolist()}")
+    return (1.0 / (2.0 * s * s)).astype(np.float32)
+
+
+def _check_kernel(kernel, degree, sigmas):
+    if kernel not in KMM_KERNELS:
+        raise ValueError(f"kernel must be one of {KMM_KERNELS}, got {kernel!r}")
+    if kernel == "poly" and (int(degree) != degree or not 1 <= int(degree) <= 4):
+        raise ValueError(f"degree must be an integer in 1..4, got {degree!r}")
+    if kernel == "rbf" and sigmas is not None:
+        rbf_betas(sigmas)
+
+
+def _check_two_sets(x, y, names=("x", "y"), min_rows=2):
+    x, y = _rows2d(x, names[0]), _rows2d(y, names[1])
+    _check_dim(x, y, " / ".join(names))
+    if x.shape[1] < 1:
+        raise ValueError("rows without features")
+    for t, n in zip((x, y), names):
+        if t.shape[0] < min_rows:
+            raise ValueError(f"{n}: at least {min_rows} rows are needed, got {t.shape[0]}")
+    return x, y
+
+
+def median_bandwidth(x, y, max_rows=1024, seed=0, ctx=None):
+    """Median pairwise Euclidean distance of a seeded subsample of the pooled rows (torch on the device): the usual scale of an rbf kernel."""
+    x, y = _check_two_sets(x, y, min_rows=1)
+    if int(max_rows) < 2:
+        raise ValueError("max_rows must be >= 2")
+    ctx = ctx or default_context(0)
+    dev = torch.device("cuda", ctx.device)
+    n, m = int(x.shape[0]), int(y.shape[0])
+    pick = np.sort(np.random.default_rng(seed).choice(n + m, min(n + m, int(max_rows)), replace=False))
+    z = torch.cat([x[torch.from_numpy(pick[pick < n])].to(dev, torch.float32), y[torch.from_numpy(pick[pick >= n] - n)].to(dev, torch.float32)], 0)
+    if z.shape[0] < 2:
+        raise ValueError("a bandwidth needs at least two rows")
+    d = torch.cdist(z.double(), z.double())
+    iu = torch.triu_indices(z.shape[0], z.shape[0], 1, device=dev)
+    return float(d[iu[0], iu[1]].median())
+
+
+def _default_sigmas(kernel, sigmas, x, y, ctx):
+    if kernel != "rbf" or sigmas is not None:
+        return sigmas
+    med = median_bandwidth(x, y, ctx=ctx)
+    if not med > 0.0:
+        raise ValueError("the median pairwise distance is zero: give sigmas")
+    return (0.5 * med, med, 2.0 * med)
+
+
+def kernel_matmul(a, b, v, kernel="poly", degree=3, gamma=None, coef0=1.0, sigmas=None, diag_off=None, chunk=65536, ctx=None):
+    """R = K(a, b) v as (Na, P) float64 on the device, any P (columns go to the device 64 at a time), b and v streamed `chunk` rows at a
+    time.  poly: k = (gamma <a, b> + coef0)^degree, gamma None = 1 / D; rbf: the mean over `sigmas` of exp(-|a - b|^2 / (2 sigma^2)),
+    sigmas None = (0.5, 1, 2) x `median_bandwidth(a, b)`.  `diag_off=d` leaves the pairs with j - i == d out (0: a set against itself
+    without its diagonal)."""
+    a, b = _check_two_sets(a, b, ("a", "b"), min_rows=0)
+    v = _rows2d(v, "v")
+    if v.shape[0] != b.shape[0]:
+        raise ValueError(f"v has {v.shape[0]} rows, b has {b.shape[0]}")
+    if a.shape[0] < 1 or v.shape[1] < 1:
+        raise ValueError(f"empty problem: a {tuple(a.shape)}, v {tuple(v.shape)}")
+    _check_kernel(kernel, degree, sigmas)
+    if int(chunk) < 1:
+        raise ValueError("chunk must be >= 1")
+    chunk = int(chunk)
+    ctx = ctx or default_context(0)
+    dev = torch.device("cuda", ctx.device)
+    sigmas = _default_sigmas(kernel, sigmas, a, b, ctx)
+    na, nb, d, ptot = int(a.shape[0]), int(b.shape[0]), int(a.shape[1]), int(v.shape[1])
+    rbf = kernel == "rbf"
+    betas = rbf_betas(sigmas) if rbf else np.zeros(1, np.float32)
+    betas_c = (C.c_float * len(betas))(*betas.tolist())
+    g = 1.0 / d if gamma is None else float(gamma)
+    ad = _dev_rows(a, dev)
+    asq = rows_sqnorm(ad, ctx) if rbf else None
+    out = torch.zeros(na, ptot, dtype=torch.float64, device=dev)
+    for s in range(0, nb, chunk):
+        bd, vd = _dev_rows(b[s:s + chunk], dev), _dev_rows(v[s:s + chunk], dev)
+        bsq = rows_sqnorm(bd, ctx) if rbf else None
+        off = KMM_NO_DIAG if diag_off is None else int(diag_off) - s
+        for c in range(0, ptot, KMM_MAX_COLS):
+            vc, oc = vd[:, c:c + KMM_MAX_COLS], out[:, c:c + KMM_MAX_COLS]
+            check(lib.eegldm_kernel_matmul(ctx.h, ptr(ad), _ld(ad), ptr(asq), ptr(bd), _ld(bd), ptr(bsq), ptr(vc), _ld(vd), na, int(bd.shape[0]), d,
+                                           int(vc.shape[1]), 1 if rbf else 0, int(degree), g, float(coef0), betas_c, len(betas), off,
+                                           1 if s else 0, ptr(oc), ptot))
+    return out
+
+
+def subset_indicators(n, size, count, rng):
+    """(n, count) fp32 0/1 columns, each with `size` ones drawn without replacement from `rng`."""
+    if not 1 <= int(size) <= int(n):
+        raise ValueError(f"a subset of {size} rows out of {n}")
+    out = np.zeros((int(n), int(count)), np.float32)
+    for c in range(int(count)):
+        out[rng.choice(int(n), int(size), replace=False), c] = 1.0
+    return out
+
+
+def permutation_indicators(n, m, n_perm, seed=0):
+    """(n + m, n_perm + 2) fp32: column 0 marks the first n pooled rows (the observed split), columns 1..n_perm the first n entries of
+    seeded permutations of the pool, the last column is all ones."""
+    if int(n_perm) < 1:
+        raise ValueError(f"n_perm must be >= 1, got {n_perm}")
+    if n < 2 or m < 2:
+        raise ValueError("at least 2 rows per set are needed")
+    rng = np.random.default_rng(seed)
+    out = np.zeros((n + m, int(n_perm) + 2), np.float32)
+    out[:n, 0] = 1.0
+    for c in range(1, int(n_perm) + 1):
+        out[rng.permutation(n + m)[:n], c] = 1.0
+    out[:, -1] = 1.0
+    return out
+
+
+def mmd2_from_sums(sxx, syy, sxy, n, m, unbiased=True):
+    """sxx / syy: the sums of k over the pairs inside each set (unbiased: without the diagonal; biased: with it), sxy: over all cross pairs."""
+    kxx = float(sxx) / (n * (n - 1) if unbiased else n * n)
+    kyy = float(syy) / (m * (m - 1) if unbiased else m * m)
+    kxy = float(sxy) / (n * m)
+    return {"mmd2": kxx + kyy - 2.0 * kxy, "kxx": kxx, "kyy": kyy, "kxy": kxy, "n": int(n), "m": int(m)}
+
+
+def kid_from_r(ind_x, ind_y, r_xx, r_yy, r_xy):
+    """Per-subset unbiased MMD^2 from r_xx = K°(x, x) ind_x, r_yy = K°(y, y) ind_y, r_xy = K(x, y) ind_y (K°: zero diagonal)."""
+    ax, ay = np.asarray(ind_x, np.float64), np.asarray(ind_y, np.float64)
+    kx, ky = ax.sum(0), ay.sum(0)
+    sxx = (ax * np.asarray(r_xx, np.float64)).sum(0); syy = (ay * np.asarray(r_yy, np.float64)).sum(0)
+    sxy = (ax * np.asarray(r_xy, np.float64)).sum(0)
+    return sxx / (kx * (kx - 1)) + syy / (ky * (ky - 1)) - 2.0 * sxy / (kx * ky)
+
+
+def permutation_stats_from_r(ind, r, n, m):
+    """Unbiased MMD^2 of every split in `ind` (`permutation_indicators`) from r = K°(z, z) ind, z = [x; y]: with a a column and 1 the last,
+    a^T K° a = sum a_i r_i, a^T K° b = a^T K° 1 - a^T K° a, b^T K° b = 1^T K° 1 - 2 a^T K° 1 + a^T K° a -> (n_perm + 1,), observed first."""
+    a, r = np.asarray(ind, np.float64)[:, :-1], np.asarray(r, np.float64)
+    aka = (a * r[:, :-1]).sum(0)
+    ak1 = (a * r[:, -1:]).sum(0)
+    k11 = r[:, -1].sum()
+    akb = ak1 - aka
+    bkb = k11 - 2.0 * ak1 + aka
+    return aka / (n * (n - 1)) + bkb / (m * (m - 1)) - 2.0 * akb / (n * m)
+
+
+def permutation_p_value(observed, null):
+    """(1 + #{null >= observed}) / (1 + n_perm): never 0, valid at any n_perm (Phipson & Smyth 2010)."""
+    null = np.asarray(null, np.float64).reshape(-1)
+    return (1.0 + float(np.sum(null >= observed))) / (1.0 + null.size)
+
+
+def mmd2(x, y, kernel="poly", degree=3, gamma=None, coef0=1.0, sigmas=None, unbiased=True, chunk=65536, ctx=None):
+    """MMD^2 between the row sets -> {"mmd2", "kxx", "kyy", "kxy", "n", "m"}.  unbiased: the within-set means leave the diagonal out in the
+    kernel (`diag_off`); it is never summed and subtracted."""
+    x, y = _check_two_sets(x, y)
+    _check_kernel(kernel, degree, sigmas)
+    ctx = ctx or default_context(0)
+    sigmas = _default_sigmas(kernel, sigmas, x, y, ctx)
+    kw = dict(kernel=kernel, degree=degree, gamma=gamma, coef0=coef0, sigmas=sigmas, chunk=chunk, ctx=ctx)
+    n, m = int(x.shape[0]), int(y.shape[0])
+    ones_n, ones_m = torch.ones(n, 1), torch.ones(m, 1)
+    d = 0 if unbiased else None
+    sxx = kernel_matmul(x, x, ones_n, diag_off=d, **kw).sum().item()
+    syy = kernel_matmul(y, y, ones_m, diag_off=d, **kw).sum().item()
+    sxy = kernel_matmul(x, y, ones_m, **kw).sum().item()
+    return mmd2_from_sums(sxx, syy, sxy, n, m, unbiased)
+
+
+def kid(real, fake, subsets=100, subset_size=1000, seed=0, chunk=65536, ctx=None):
+    """Kernel inception distance: mean and standard deviation of the unbiased cubic-kernel MMD^2 over `subsets` seeded subsets of
+    min(subset_size, n, m) rows of each set -> {"kid_mean", "kid_std", "per_subset", "subset_size"}."""
+    x, y = _check_two_sets(real, fake, ("real", "fake"))
+    if int(subsets) < 1 or int(subset_size) < 2:
+        raise ValueError(f"subsets must be >= 1 and subset_size >= 2, got {subsets} and {subset_size}")
+    size = min(int(subset_size), int(x.shape[0]), int(y.shape[0]))
+    rng = np.random.default_rng(seed)
+    ix, iy = subset_indicators(x.shape[0], size, subsets, rng), subset_indicators(y.shape[0], size, subsets, rng)
+    kw = dict(kernel="poly", degree=3, gamma=None, coef0=1.0, chunk=chunk, ctx=ctx)
+    r_xx = kernel_matmul(x, x, torch.from_numpy(ix), diag_off=0, **kw).cpu().numpy()
+    r_yy = kernel_matmul(y, y, torch.from_numpy(iy), diag_off=0, **kw).cpu().numpy()
+    r_xy = kernel_matmul(x, y, torch.from_numpy(iy), **kw).cpu().numpy()
+    per = kid_from_r(ix, iy, r_xx, r_yy, r_xy)
+    return {"kid_mean": float(per.mean()), "kid_std": float(per.std()), "per_subset": per.tolist(), "subset_size": size}
+
+
+def mmd_permutation_test(x, y, n_perm=1000, seed=0, kernel="poly", degree=3, gamma=None, coef0=1.0, sigmas=None, chunk=65536, ctx=None):
+    """Kernel two-sample test: the unbiased MMD^2 of (x, y) against its values under `n_perm` seeded relabellings of the pooled rows
+    -> {"mmd2", "p_value", "null", "n_perm"}.  A large p-value is not evidence that the sets are equal."""
+    x, y = _check_two_sets(x, y)
+    _check_kernel(kernel, degree, sigmas)
+    n, m = int(x.shape[0]), int(y.shape[0])
+    ind = permutation_indicators(n, m, n_perm, seed)
+    ctx = ctx or default_context(0)
+    sigmas = _default_sigmas(kernel, sigmas, x, y, ctx)
+    z = torch.cat([x.to(torch.float32).cpu(), y.to(torch.float32).cpu()], 0) if not (x.is_cuda and y.is_cuda) else torch.cat([x.float(), y.float()], 0)
+    r = kernel_matmul(z, z, torch.from_numpy(ind), kernel=kernel, degree=degree, gamma=gamma, coef0=coef0, sigmas=sigmas, diag_off=0,
+                      chunk=chunk, ctx=ctx).cpu().numpy()
+    stats = permutation_stats_from_r(ind, r, n, m)
+    return {"mmd2": float(stats[0]), "p_value": permutation_p_value(stats[0], stats[1:]), "null": stats[1:].tolist(), "n_perm": int(n_perm)}
+
+
+def witness_from_r(r_x, r_y, n, m):
+    return np.asarray(r_x, np.float64).reshape(-1) / n - np.asarray(r_y, np.float64).reshape(-1) / m
+
+
+def mmd_witness(points, x, y, kernel="poly", degree=3, gamma=None, coef0=1.0, sigmas=None, chunk=65536, ctx=None):
+    """MMD witness function at `points`: mean_j k(p, x_j) - mean_j k(p, y_j) as (N,) float64 numpy; negative where a point looks more like
+    y than like x."""
+    x, y = _check_two_sets(x, y)
+    p, _x = _check_two_sets(points, x, ("points", "x"), min_rows=1)
+    _check_kernel(kernel, degree, sigmas)
+    ctx = ctx or default_context(0)
+    sigmas = _default_sigmas(kernel, sigmas, x, y, ctx)
+    kw = dict(kernel=kernel, degree=degree, gamma=gamma, coef0=coef0, sigmas=sigmas, chunk=chunk, ctx=ctx)
+    n, m = int(x.shape[0]), int(y.shape[0])
+    r_x = kernel_matmul(p, x, torch.ones(n, 1), **kw).cpu().numpy()
+    r_y = kernel_matmul(p, y, torch.ones(m, 1), **kw).cpu().numpy()
+    return witness_from_r(r_x, r_y, n, m)
