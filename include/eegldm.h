@@ -990,6 +990,30 @@ int eegldm_kernel_matmul(eegldm_ctx*, const float* a, long lda, const float* asq
                          int kind /* 0 poly, 1 rbf */, int degree, float gamma, float coef0, const float* betas_host, int n_betas,
                          long diag_off, int accumulate, double* out, long ldo);
 
+/* ---- sleep micro-structure primitives (spindle and slow-wave detectors of eegldm.metrics; csrc/events.hip).  fp32; additive, ABI 8.
+ * eegldm_fir_same: zero-phase FIR over B rows of L samples, y[b][n] = sum_{k = 0..M-1} taps[k] xe[b][n + k - c], c = (M - 1) / 2, M odd in
+ * 1..2049, L in 1..4096; taps is a DEVICE array of M floats.  xe is the row extended by zeros (edge 0) or by whole-sample reflection that does
+ * not repeat the end sample (edge 1: xe[-i] = x[i], xe[L-1+i] = x[L-1-i]; needs c <= L - 1).  mode 1 is the RMS envelope: every sample
+ * enters as x * x (one fp32 rounding) and sqrtf(max(sum, 0)) is stored; a NaN or infinite sum stays non-finite.  Every output is ONE fmaf chain in ascending k
+ * from +0 over its own support: its bits do not depend on B, on the launch geometry or on where in a row the same samples sit, and a
+ * non-finite sample makes non-finite exactly the outputs whose support [n - c, n + c] holds it.  ldx / ldy are row strides in floats (>= L);
+ * x, taps, y need 4-byte alignment only; x == y is refused; B == 0 is a no-op.  A refusal leaves y untouched. */
+int eegldm_fir_same(eegldm_ctx*, const float* x, long ldx, const float* taps, int M, float* y, long ldy, long B, int L,
+                    int edge /* 0 zeros, 1 reflect */, int mode /* 0 plain, 1 rms */);
+/* eegldm_threshold_events: per row, the runs of s above thr[b] after closing, with features.  All comparisons are exact fp32 comparisons.
+ *  1. active[n] = s[b][n] > thr[b] (a NaN on either side and a tie are inactive);
+ *  2. a maximal inactive stretch strictly between two active samples and at most merge_gap long becomes active (never one that touches a row end);
+ *  3. events are the maximal runs [start, stop) of the closed set with min_len <= stop - start <= max_len, without those that touch a row end
+ *     when drop_edge != 0; they are numbered by start, the first max_events (E, 1..64) are stored, the others only counted;
+ *  counts [B][2] = (events kept, raw runs before closing and gating); ev_i [B][E][6] = (start, length, argmax, n_up, n_raw, flags): argmax the
+ *  first index of the maximum of s over the run under `>` from s[start], n_up the number of n in [start + 1, stop) with aux[n-1] < 0 &&
+ *  aux[n] >= 0, n_raw the raw runs merged, flags bit 0 / 1 = the run touches the left / right end; ev_f [B][E][4] = (peak, sum, aux_max, aux_min):
+ *  sum the fp32 sum of s over the run in ascending order from +0 (a NaN inside a closed gap makes it NaN), aux_max / aux_min by `>` / `<`
+ *  from aux[start].  aux == NULL: n_up, aux_max, aux_min are 0.  Unused table slots are left untouched.  L in 1..4096, lds_ / ldaux >= L.
+ *  One wave per row; no atomics, no memset, one writer per element: a result repeats bit for bit. */
+int eegldm_threshold_events(eegldm_ctx*, const float* s, long lds_, const float* aux, long ldaux, const float* thr, long B, int L,
+                            int min_len, int max_len, int merge_gap, int drop_edge, int max_events, int* counts, int* ev_i, float* ev_f);
+
 #ifdef __cplusplus
 }
 #endif

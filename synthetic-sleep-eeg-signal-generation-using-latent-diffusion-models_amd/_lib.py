@@ -235,6 +235,8 @@ SIGNATURES = {
     "eegldm_rows_standardize": [_vp, _vp, _l, _l, _i, _vp, _l],
     "eegldm_knn_rescore": [_vp, _vp, _l, _vp, _l, _i, _i, _i, _l, _l, _vp, _vp],
     "eegldm_kernel_matmul": [_vp, _vp, _l, _vp, _vp, _l, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _f, _f, C.POINTER(_f), _i, _l, _i, _vp, _l],
+    "eegldm_fir_same": [_vp, _vp, _l, _vp, _i, _vp, _l, _l, _i, _i, _i],
+    "eegldm_threshold_events": [_vp, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "eegldm_resblock_create": [_vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)],
     "eegldm_attnblock_create": [_vp, _i, _i, _i, C.POINTER(_vp)],
     "eegldm_block_destroy": [_vp],

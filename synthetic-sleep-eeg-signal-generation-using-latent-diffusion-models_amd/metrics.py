@@ -1061,3 +1061,338 @@ def mmd_witness(points, x, y, kernel="poly", degree=3, gamma=None, coef0=1.0, si
     r_x = kernel_matmul(p, x, torch.ones(n, 1), **kw).cpu().numpy()
     r_y = kernel_matmul(p, y, torch.ones(m, 1), **kw).cpu().numpy()
     return witness_from_r(r_x, r_y, n, m)
+
+
+# ---------------------------------------------------------------------------------------------------- sleep micro-structure
+# Spindles (band-pass, RMS envelope, threshold, duration gate) and slow waves (low-pass, zero-crossing half-waves, duration and amplitude
+# gate) on two device primitives (csrc/events.hip): eegldm_fir_same, a zero-phase FIR filter over rows of windows, and
+# eegldm_threshold_events, the runs of a row above a threshold with per-event features.  Everything that is not a pass over the windows is
+# float64 numpy in functions that take tables as input; everything that refuses an argument does so before the device is touched.
+# THE DETECTOR DEFAULTS ARE THE LITERATURE'S FOR SCALP EEG; NOBODY HAS VALIDATED THEM ON THIS PROJECT'S 18-Hz-LOW-PASSED DATA.
+FIR_MAX_TAPS, FIR_MAX_LEN, EVENTS_MAX = 2049, 4096, 64
+FIR_EDGES = {"zero": 0, "reflect": 1}
+EVENT_INT_FIELDS = ("start", "length", "argmax", "n_up", "n_raw", "flags")
+EVENT_FLOAT_FIELDS = ("peak", "sum", "aux_max", "aux_min")
+SUMMARY_FEATURES = ("duration_s", "amplitude", "freq_hz")
+
+
+def fir_length(sfreq, trans_hz):
+    """Taps of a Hamming-windowed sinc with transition width trans_hz: the smallest odd integer >= 3.3 sfreq / trans_hz."""
+    if not (sfreq > 0 and trans_hz > 0):                     # a NaN fails too
+        raise ValueError(f"sfreq and trans_hz must be positive, got {sfreq} and {trans_hz}")
+    m = int(np.ceil(3.3 * float(sfreq) / float(trans_hz)))
+    return m + 1 - m % 2
+
+
+def fir_design(sfreq, lo=None, hi=None, trans_hz=2.0):
+    """(M,) float64 taps of a zero-phase (symmetric, odd-length) windowed-sinc filter with a Hamming window: low-pass (hi), high-pass (lo) or
+    band-pass (lo, hi), cut-offs in Hz at the half-amplitude points, scaled to unit gain at DC (low-pass), at the band centre (band-pass) or
+    at Nyquist (high-pass): scipy.signal.firwin(M, ..., window="hamming", fs=sfreq) in plain numpy."""
+    m = fir_length(sfreq, trans_hz)
+    nyq = 0.5 * float(sfreq)
+    if lo is None and hi is None:
+        raise ValueError("give lo (high-pass), hi (low-pass) or both (band-pass)")
+    for name, f in (("lo", lo), ("hi", hi)):
+        if f is not None and not 0.0 < float(f) < nyq:
+            raise ValueError(f"{name} = {f} Hz must lie strictly between 0 and sfreq / 2 = {nyq}")
+    if lo is not None and hi is not None and not float(lo) < float(hi):
+        raise ValueError(f"band ({lo}, {hi}) Hz: lo must be below hi")
+    if m > FIR_MAX_TAPS:
+        raise ValueError(f"trans_hz = {trans_hz} at sfreq = {sfreq} needs {m} taps, eegldm_fir_same takes at most {FIR_MAX_TAPS}")
+    left = 0.0 if lo is None else float(lo) / nyq
+    right = 1.0 if hi is None else float(hi) / nyq
+    k = np.arange(m, dtype=np.float64) - 0.5 * (m - 1)
+    h = (right * np.sinc(right * k) - left * np.sinc(left * k)) * np.hamming(m)
+    centre = 0.0 if left == 0.0 else (1.0 if right == 1.0 else 0.5 * (left + right))
+    return h / np.sum(h * np.cos(np.pi * k * centre))
+
+
+def _check_taps(taps, length, edge):
+    t = np.asarray(taps, np.float64).reshape(-1)
+    if edge not in FIR_EDGES:
+        raise ValueError(f"edge must be one of {tuple(FIR_EDGES)}, got {edge!r}")
+    if not 1 <= t.size <= FIR_MAX_TAPS or t.size % 2 == 0:
+        raise ValueError(f"an odd number of taps in 1..{FIR_MAX_TAPS} is needed, got {t.size}")
+    with np.errstate(over="ignore"):
+        finite = np.all(np.isfinite(t.astype(np.float32)))          # as uploaded: a float64 tap beyond fp32's range is an inf on the device
+    if not finite:
+        raise ValueError("non-finite taps (as fp32)")
+    if not 1 <= int(length) <= FIR_MAX_LEN:
+        raise ValueError(f"windows of 1..{FIR_MAX_LEN} samples are taken, got {length}")
+    if edge == "reflect" and (t.size - 1) // 2 > int(length) - 1:
+        raise ValueError(f"reflect needs (M - 1) / 2 <= L - 1, got {t.size} taps for windows of {length} samples")
+    return t
+
+
+def _rows_any_length(w, name):
+    """(N, L) or (N, 1, L) -> (N, L), nothing cropped."""
+    if not torch.is_tensor(w):
+        w = torch.as_tensor(np.asarray(w))
+    if w.dim() == 3 and w.shape[1] == 1:
+        w = w[:, 0]
+    if w.dim() != 2:
+        raise ValueError(f"{name}: windows (N, L) or (N, 1, L) expected, got shape {tuple(w.shape)}")
+    return w
+
+
+def fir_filter(windows, taps, edge="zero", rms=False, ctx=None):
+    """Zero-phase FIR over every window: (N, L) fp32 on the device.  y[n] = sum_k taps[k] xe[n + k - (M - 1) / 2], xe the window extended by
+    zeros ("zero") or by whole-sample reflection ("reflect"); rms=True squares every sample on the way in and returns sqrt(max(sum, 0)): with
+    box taps 1 / W the moving RMS.  Windows (N, L) or (N, 1, L), L <= 4096, are filtered as they are (no pad is cropped)."""
+    w = _rows_any_length(windows, "windows")
+    t = _check_taps(taps, w.shape[1], edge)
+    ctx = ctx or default_context(0)
+    dev = torch.device("cuda", ctx.device)
+    x = _dev_rows(w, dev)
+    out = torch.empty(x.shape[0], x.shape[1], device=dev)
+    if x.shape[0]:
+        td = torch.from_numpy(t.astype(np.float32)).to(dev)
+        check(lib.eegldm_fir_same(ctx.h, ptr(x), _ld(x), ptr(td), int(t.size), ptr(out), int(x.shape[1]), int(x.shape[0]), int(x.shape[1]),
+                                  FIR_EDGES[edge], 1 if rms else 0))
+    return out
+
+
+def rms_box(rms_s, sfreq):
+    """Box taps of the moving RMS: W = round(rms_s sfreq) samples, made odd by adding one, gain 1 / W."""
+    w = int(round(float(rms_s) * float(sfreq)))
+    if w < 1:
+        raise ValueError(f"rms_s = {rms_s} s is shorter than a sample at sfreq = {sfreq}")
+    w += 1 - w % 2
+    return np.full(w, 1.0 / w)
+
+
+def band_envelope(windows, lo, hi, sfreq=100.0, rms_s=0.2, trans_hz=2.0, ctx=None):
+    """(band, env): the windows band-passed to (lo, hi) Hz and the moving RMS of that over rms_s seconds, both (N, L) fp32 on the device,
+    edges by reflection.  The loader's 3072-sample windows lose their zero pads first."""
+    w = _windows2d(windows, "windows")
+    taps, box = fir_design(sfreq, lo, hi, trans_hz), rms_box(rms_s, sfreq)
+    _check_taps(taps, w.shape[1], "reflect"); _check_taps(box, w.shape[1], "reflect")
+    band = fir_filter(w, taps, "reflect", ctx=ctx)
+    return band, fir_filter(band, box, "reflect", rms=True, ctx=ctx)
+
+
+def _check_events_args(length, min_len, max_len, merge_gap, max_events):
+    if not 1 <= int(length) <= FIR_MAX_LEN:
+        raise ValueError(f"rows of 1..{FIR_MAX_LEN} samples are taken, got {length}")
+    if int(max_events) != max_events or not 1 <= int(max_events) <= EVENTS_MAX:
+        raise ValueError(f"max_events must be an integer in 1..{EVENTS_MAX}, got {max_events!r}")
+    if int(min_len) < 1 or int(max_len) < int(min_len) or int(merge_gap) < 0:
+        raise ValueError(f"need 1 <= min_len <= max_len and merge_gap >= 0, got {min_len}, {max_len}, {merge_gap}")
+
+
+def threshold_events(s, thr, aux=None, min_len=1, max_len=None, merge_gap=0, drop_edge=False, max_events=32, ctx=None):
+    """Runs of every row of s (N, L) above thr (a float or (N,)) after closing gaps of at most merge_gap samples, kept when min_len <= length
+    <= max_len (and, with drop_edge, when they touch no row end), with features (eegldm_threshold_events; include/eegldm.h has the
+    definition).  Returns numpy tables: n_events (N,) all kept events, n_raw_runs (N,), stored (N, E) bool, and per stored event (N, E)
+    start, length, argmax, n_up, n_raw, flags (int32), peak, sum, aux_max, aux_min (fp32); slots past the stored events are zero."""
+    s = _rows_any_length(s, "s")
+    n, length = int(s.shape[0]), int(s.shape[1])
+    max_len = length if max_len is None else max_len
+    _check_events_args(length, min_len, max_len, merge_gap, max_events)
+    if aux is not None:
+        aux = _rows_any_length(aux, "aux")
+        if tuple(aux.shape) != tuple(s.shape):
+            raise ValueError(f"aux {tuple(aux.shape)} does not match s {tuple(s.shape)}")
+    thr_a = np.asarray(thr.detach().cpu().numpy() if torch.is_tensor(thr) else thr, np.float32)
+    if thr_a.ndim == 0:
+        thr_a = np.full(n, thr_a, np.float32)
+    if thr_a.shape != (n,):
+        raise ValueError(f"thr must be a float or ({n},), got shape {thr_a.shape}")
+    e = int(max_events)
+    ctx = ctx or default_context(0)
+    dev = torch.device("cuda", ctx.device)
+    sd = _dev_rows(s, dev)
+    ad = None if aux is None else _dev_rows(aux, dev)
+    counts = torch.zeros(n, 2, dtype=torch.int32, device=dev)
+    ev_i = torch.zeros(n, e, 6, dtype=torch.int32, device=dev)
+    ev_f = torch.zeros(n, e, 4, dtype=torch.float32, device=dev)
+    if n:
+        td = torch.from_numpy(thr_a).to(dev)
+        check(lib.eegldm_threshold_events(ctx.h, ptr(sd), _ld(sd), ptr(ad), _ld(ad) if ad is not None else 0, ptr(td), n, length, int(min_len),
+                                          int(max_len), int(merge_gap), 1 if drop_edge else 0, e, ptr(counts), ptr(ev_i), ptr(ev_f)))
+    return events_from_tables(counts.cpu().numpy(), ev_i.cpu().numpy(), ev_f.cpu().numpy())
+
+
+def events_from_tables(counts, ev_i, ev_f):
+    """The export's three tables as a dict of named numpy tables (see `threshold_events`)."""
+    counts, ev_i, ev_f = np.asarray(counts), np.asarray(ev_i), np.asarray(ev_f)
+    e = ev_i.shape[1]
+    out = {"n_events": counts[:, 0].copy(), "n_raw_runs": counts[:, 1].copy(),
+           "stored": np.arange(e)[None, :] < np.minimum(counts[:, :1], e)}
+    for k, name in enumerate(EVENT_INT_FIELDS):
+        out[name] = ev_i[:, :, k].copy()
+    for k, name in enumerate(EVENT_FLOAT_FIELDS):
+        out[name] = ev_f[:, :, k].copy()
+    return out
+
+
+def event_table(ev, sfreq=100.0):
+    """One row per stored event, in window order then start order: window, the export's fields, duration_s and mid_s (the run's midpoint);
+    `truncated` counts the windows that had more events than slots."""
+    win, slot = np.nonzero(ev["stored"])
+    t = {"window": win.astype(np.int64)}
+    for name in EVENT_INT_FIELDS + EVENT_FLOAT_FIELDS:
+        t[name] = ev[name][win, slot]
+    t["duration_s"] = t["length"].astype(np.float64) / float(sfreq)
+    t["mid_s"] = (t["start"].astype(np.float64) + 0.5 * t["length"]) / float(sfreq)
+    t["sfreq"] = float(sfreq)
+    t["n_windows"] = int(ev["stored"].shape[0])
+    t["truncated"] = int(np.sum(ev["n_events"] > ev["stored"].shape[1]))
+    return t
+
+
+def _seconds_to_samples(sfreq, **kw):
+    out = {}
+    for k, v in kw.items():
+        if not (v >= 0):
+            raise ValueError(f"{k} = {v} s must be non-negative")
+        out[k] = int(round(float(v) * float(sfreq)))
+    return out
+
+
+def envelope_threshold(real_windows, factor=1.5, band=(11.0, 16.0), batch_size=4096, **band_kw):
+    """ONE absolute threshold for the spindle detector: mean + factor * std (float64, population) of the band envelope over every sample of the
+    REAL set.  It is taken from the real set and applied to both sets: a per-window threshold invents events in windows that have none.
+    `band` defaults to `detect_spindles`' band; band_kw are `band_envelope`'s other keywords (sfreq, rms_s, trans_hz; lo / hi override band)."""
+    if len(band) != 2:
+        raise ValueError(f"band must be (lo, hi), got {band!r}")
+    lo, hi = band_kw.pop("lo", band[0]), band_kw.pop("hi", band[1])
+    w = _windows2d(real_windows, "real_windows")
+    if w.shape[0] < 1:
+        raise ValueError("no real windows")
+    if not np.isfinite(factor):
+        raise ValueError(f"factor must be finite, got {factor}")
+    n, s1, s2 = 0, 0.0, 0.0
+    for i in range(0, w.shape[0], int(batch_size)):
+        env = band_envelope(w[i:i + int(batch_size)], lo, hi, **band_kw)[1].double()
+        n += env.numel(); s1 += float(env.sum()); s2 += float((env * env).sum())
+    mean = s1 / n
+    return mean + float(factor) * float(np.sqrt(max(s2 / n - mean * mean, 0.0)))
+
+
+def detect_spindles(windows, thr, sfreq=100.0, band=(11.0, 16.0), rms_s=0.2, min_s=0.5, max_s=3.0, merge_s=0.1, drop_edge=True, trans_hz=2.0,
+                    max_events=32, ctx=None):
+    """Sleep spindles by the classical amplitude criterion: band-pass to `band`, moving RMS over rms_s, runs of the envelope above the absolute
+    threshold `thr` (see `envelope_threshold`), gaps up to merge_s closed, duration in [min_s, max_s].  Returns `event_table` plus freq_hz =
+    upward zero crossings of the band signal per second of the run (n_up * sfreq / length) and amplitude = peak-to-peak of the band signal."""
+    if len(band) != 2:
+        raise ValueError(f"band must be (lo, hi), got {band!r}")
+    n = _seconds_to_samples(sfreq, min_s=min_s, max_s=max_s, merge_s=merge_s)
+    w = _windows2d(windows, "windows")
+    _check_events_args(w.shape[1], max(n["min_s"], 1), n["max_s"], n["merge_s"], max_events)
+    bd, env = band_envelope(w, band[0], band[1], sfreq, rms_s, trans_hz, ctx=ctx)
+    ev = threshold_events(env, thr, aux=bd, min_len=max(n["min_s"], 1), max_len=n["max_s"], merge_gap=n["merge_s"], drop_edge=drop_edge,
+                          max_events=max_events, ctx=ctx)
+    t = event_table(ev, sfreq)
+    t["freq_hz"] = t["n_up"].astype(np.float64) * float(sfreq) / np.maximum(t["length"], 1)
+    t["amplitude"] = t["aux_max"].astype(np.float64) - t["aux_min"].astype(np.float64)
+    return t
+
+
+def detect_half_waves(windows, polarity=-1, sfreq=100.0, lowpass_hz=4.0, highpass_hz=None, min_s=0.3, max_s=1.0, min_amp=None, trans_hz=2.0,
+                      max_events=64, ctx=None):
+    """Half-waves of one polarity of the low-passed window (the building block of slow-wave detection): runs of polarity * filtered above 0
+    with duration in [min_s, max_s].  The row mean is removed when there is no high-pass; the sign costs nothing, the taps are negated.
+    `min_amp` gates the stored peak afterwards.  Returns `event_table` plus amplitude = the half-wave's peak magnitude and polarity."""
+    if polarity not in (-1, 1):
+        raise ValueError(f"polarity must be -1 or 1, got {polarity!r}")
+    n = _seconds_to_samples(sfreq, min_s=min_s, max_s=max_s)
+    w = _windows2d(windows, "windows")
+    taps = fir_design(sfreq, highpass_hz, lowpass_hz, trans_hz) * float(polarity)
+    _check_taps(taps, w.shape[1], "reflect")
+    _check_events_args(w.shape[1], max(n["min_s"], 1), n["max_s"], 0, max_events)
+    if min_amp is not None and not min_amp >= 0:
+        raise ValueError(f"min_amp must be non-negative, got {min_amp}")
+    ctx = ctx or default_context(0)
+    x = w.to(torch.device("cuda", ctx.device), torch.float32)
+    if highpass_hz is None:
+        x = x - x.mean(1, keepdim=True)
+    sig = fir_filter(x, taps, "reflect", ctx=ctx)
+    ev = threshold_events(sig, 0.0, min_len=max(n["min_s"], 1), max_len=n["max_s"], merge_gap=0, drop_edge=False, max_events=max_events, ctx=ctx)
+    t = event_table(ev, sfreq)
+    t["amplitude"] = t["peak"].astype(np.float64)
+    t["polarity"] = int(polarity)
+    if min_amp is not None:
+        keep = t["amplitude"] >= float(min_amp)
+        t = {k: (v[keep] if isinstance(v, np.ndarray) else v) for k, v in t.items()}
+    return t
+
+
+def pair_half_waves(neg, pos):
+    """Attach to each negative half-wave the positive one of the same window that starts where it ends (the negative-to-positive zero crossing);
+    negative half-waves without one are left out.  Returns one row per pair: window, start, neg_length, pos_length, neg_peak, pos_peak,
+    amplitude (peak to peak) and duration_s (both halves): the criteria of Massimini et al. 2004."""
+    if neg["sfreq"] != pos["sfreq"] or neg["n_windows"] != pos["n_windows"]:
+        raise ValueError("the two tables come from different sets")
+    where = {(int(w), int(s)): i for i, (w, s) in enumerate(zip(pos["window"], pos["start"]))}
+    pairs = [(i, where[(int(w), int(s + n))]) for i, (w, s, n) in enumerate(zip(neg["window"], neg["start"], neg["length"])) if (int(w), int(s + n)) in where]
+    i = np.asarray([p[0] for p in pairs], np.int64); j = np.asarray([p[1] for p in pairs], np.int64)
+    t = {"window": neg["window"][i], "start": neg["start"][i], "neg_length": neg["length"][i], "pos_length": pos["length"][j],
+         "neg_peak": neg["peak"][i].astype(np.float64), "pos_peak": pos["peak"][j].astype(np.float64)}
+    t["amplitude"] = t["neg_peak"] + t["pos_peak"]
+    t["duration_s"] = (t["neg_length"] + t["pos_length"]).astype(np.float64) / neg["sfreq"]
+    t["mid_s"] = (t["start"] + t["neg_length"]).astype(np.float64) / neg["sfreq"]
+    t["sfreq"], t["n_windows"] = neg["sfreq"], neg["n_windows"]
+    return t
+
+
+def _feature_stats(v):
+    v = np.asarray(v, np.float64)
+    if v.size == 0:
+        return {"n": 0, "mean": None, "sd": None, "q25": None, "median": None, "q75": None}
+    q = np.quantile(v, [0.25, 0.5, 0.75])
+    return {"n": int(v.size), "mean": float(v.mean()), "sd": float(v.std()), "q25": float(q[0]), "median": float(q[1]), "q75": float(q[2])}
+
+
+def event_summary(table, n_windows, window_s, labels=None):
+    """Density (events per minute of signal) and the mean, population sd and quartiles of duration_s, amplitude and freq_hz (those the table
+    has) over the events of `table`.  With labels (n_windows,) the same per stage under "per_stage", keyed by the stage code."""
+    n_windows = int(n_windows)
+    if n_windows < 1 or not window_s > 0:
+        raise ValueError(f"n_windows and window_s must be positive, got {n_windows} and {window_s}")
+    win = np.asarray(table["window"], np.int64)
+    if win.size and (win.min() < 0 or win.max() >= n_windows):
+        raise ValueError(f"the table names window {int(win.max())}, n_windows is {n_windows}")
+
+    def block(pick, nw):
+        out = {"n_windows": int(nw), "n_events": int(pick.sum()), "density_per_min": float(pick.sum()) / (nw * float(window_s) / 60.0) if nw else None}
+        for f in SUMMARY_FEATURES:
+            if f in table:
+                out[f] = _feature_stats(np.asarray(table[f])[pick])
+        return out
+
+    res = block(np.ones(win.size, bool), n_windows)
+    if labels is not None:
+        lab = np.asarray(labels).reshape(-1)
+        if lab.size != n_windows:
+            raise ValueError(f"{lab.size} labels for {n_windows} windows")
+        res["per_stage"] = {str(int(c)): block(lab[win] == c, int(np.sum(lab == c))) for c in np.unique(lab)}
+    return res
+
+
+def ks_statistic(a, b):
+    """Two-sample Kolmogorov-Smirnov statistic sup |F_a - F_b| from the sorted samples (float64)."""
+    a, b = np.sort(np.asarray(a, np.float64)), np.sort(np.asarray(b, np.float64))
+    z = np.concatenate([a, b])
+    return float(np.max(np.abs(np.searchsorted(a, z, side="right") / a.size - np.searchsorted(b, z, side="right") / b.size)))
+
+
+def wasserstein_1d(a, b):
+    """1-D Wasserstein-1 distance, the integral of |F_a - F_b| (float64)."""
+    a, b = np.sort(np.asarray(a, np.float64)), np.sort(np.asarray(b, np.float64))
+    z = np.sort(np.concatenate([a, b]))
+    fa, fb = np.searchsorted(a, z[:-1], side="right") / a.size, np.searchsorted(b, z[:-1], side="right") / b.size
+    return float(np.sum(np.abs(fa - fb) * np.diff(z)))
+
+
+def compare_events(real, fake):
+    """Per feature (duration_s, amplitude, freq_hz, where both tables have it): the two-sample KS statistic and the 1-D Wasserstein distance of
+    the real against the synthetic events, with the sample sizes; None where a side has no events."""
+    out = {}
+    for f in SUMMARY_FEATURES:
+        if f in real and f in fake:
+            a, b = np.asarray(real[f], np.float64), np.asarray(fake[f], np.float64)
+            ok = a.size > 0 and b.size > 0
+            out[f] = {"n_real": int(a.size), "n_synthetic": int(b.size), "ks": ks_statistic(a, b) if ok else None,
+                      "wasserstein": wasserstein_1d(a, b) if ok else None}
+    return out
