@@ -125,6 +125,13 @@ int eegldm_debug_bn_last_route(int backward, int* out8_host);
  * grid-stride loop wrapped), block partials written for a fold (0: the blocks add atomically), deterministic mode (1 / 0).  Convs that the
  * MFMA GEMM family serves leave the record untouched.  No reference counterpart. */
 int eegldm_debug_dconv_last_route(int which, int* out8_host);
+/* developer aid: what served the last eegldm_aekl_forward (ints 0-4) and the last eegldm_aekl_backward / _backward_ex (ints 5-9) on this handle,
+ * five ints each: whole-network program ran (1: csrc/aekl_thin.hip, one workgroup per window; 0: the layer-by-layer path), micro-ops of its
+ * forward and of its backward program, floats per LDS tensor (`maxt`) -- all three 0 on the layer-by-layer path --, and 1 when the
+ * configuration was accepted for the whole-network route but its program did not fit the LDS, so that the layer-by-layer path was taken
+ * instead.  All zero before the first call.  The route-aware tests confirm from it that a case ran on the kernels it names.
+ * No reference counterpart. */
+int eegldm_debug_aekl_last_route(const eegldm_aekl*, int* out10_host);
 /* developer aid: BatchNorm statistics (and the running-statistics update) from per-block column partials parts_dev [nb][2 C] fp32 (interleaved
  * sum, sum of squares) -- the fold that follows a conv whose epilogue left them.  No reference counterpart. */
 int eegldm_debug_bn_stats_from_parts(eegldm_ctx*, const float* parts_dev, int nb, float* stats, float* running_mean, float* running_var,

@@ -53,6 +53,7 @@ SIGNATURES = {
     "eegldm_debug_gn_last_route": [_i, _vp],
     "eegldm_debug_bn_last_route": [_i, _vp],
     "eegldm_debug_dconv_last_route": [_i, _vp],
+    "eegldm_debug_aekl_last_route": [_vp, _vp],
     "eegldm_debug_bn_stats_from_parts": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _l, _i],
     "eegldm_debug_disc_tail_fwd": [_vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i],
     "eegldm_debug_disc_tail_bwd": [_vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _f, _vp, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i],

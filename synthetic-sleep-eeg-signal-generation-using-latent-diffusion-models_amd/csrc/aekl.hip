@@ -212,6 +212,8 @@ struct eegldm_aekl : SeqNet {
   // whole-network path for thin configurations (aekl_thin.hip): program compiled per window length
   ThinProgram thin; int thin_L = -1; bool thin_tape = false; float* thin_eps = nullptr;
   int thin_fail_L = -1;          // length for which the whole-network program did not fit (LDS footprint): use the general path
+  // what served the last forward ([0]) / backward ([1]) on this handle (eegldm_debug_aekl_last_route): host-side bookkeeping only
+  struct Route { int thin, nfwd, nbwd, maxt, lds_fail; } route[2] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
   ~eegldm_aekl() { thin_free(&thin); }
 };
 
@@ -587,8 +589,10 @@ extern "C" int eegldm_aekl_forward(eegldm_aekl* a, const float* x, const float* 
     if (kl && !a->ctx->loss_prezeroed) HIP_TRY(hipMemsetAsync(kl, 0, sizeof(float), a->ctx->stream));
     EEG_TRY(thin_forward(a->ctx, p, a->params, x, a->thin_eps, recon, z_mu, z_sigma, kl, B));
     a->have_tape = true; a->thin_tape = true;
+    a->route[0] = {1, (int)p.fwd.size(), (int)p.bwd.size(), p.maxt, 0};
     return 0;
   }
+  a->route[0] = {0, 0, 0, 0, a->thin_fail_L == L ? 1 : 0};
   View zv;
   EEG_TRY(aekl_encode_impl(a, x, eps, B, L, &zv, kl));
   EEG_TRY(aekl_export_latents(a, zv, nullptr, z_mu, z_sigma));
@@ -608,6 +612,7 @@ extern "C" int eegldm_aekl_backward_ex(eegldm_aekl* a, const float* d_recon, con
   EEG_CHECK(a->have_tape, "call eegldm_aekl_forward first");
   EEG_CHECK(a->grads, "no gradient buffer bound");
   a->have_tape = false;
+  a->route[1] = a->route[0];     // the backward pass follows the forward pass's tape
   if (a->thin_tape) {
     a->thin_tape = false;
     return thin_backward(a->ctx, a->thin, a->params, a->grads, d_recon, a->thin_eps, kl_weight / (float)a->B, dx, a->B, d_mu, d_sigma);
@@ -630,6 +635,16 @@ extern "C" int eegldm_aekl_backward_ex(eegldm_aekl* a, const float* d_recon, con
   View dx0;
   EEG_TRY(a->backward_seq(a->enc, a->tape_enc, B, dh, &dx0, dx != nullptr));
   if (dx) EEG_TRY(eegldm_nlc_to_ncl(ctx, dx0.p, dx0.ld, dx, B, a->cfg.in_channels, L, dt));
+  return 0;
+}
+
+extern "C" int eegldm_debug_aekl_last_route(const eegldm_aekl* a, int* out10_host) {
+  EEG_CHECK(a && out10_host, "null argument");
+  for (int d = 0; d < 2; d++) {
+    const eegldm_aekl::Route& r = a->route[d];
+    int* o = out10_host + 5 * d;
+    o[0] = r.thin; o[1] = r.nfwd; o[2] = r.nbwd; o[3] = r.maxt; o[4] = r.lds_fail;
+  }
   return 0;
 }
 

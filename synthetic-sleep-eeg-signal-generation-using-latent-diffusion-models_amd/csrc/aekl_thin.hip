@@ -187,18 +187,31 @@ template <int C>
 __device__ void f_gn_t(const ThinOp& o, const float* P, const Bufs& B, float* __restrict__ stats) {
   const float* X = B.b[o.src]; float* Y = B.b[o.dst];
   const int n = C * o.Lin, nq = n >> 2;
-  // one pass: sums of (x - K) and (x - K)^2 with K = the tensor's first element (removes the cancellation of E[x^2] - mean^2)
-  const float K = X[0];
-  float sq[2] = {0.f, 0.f};
-  for (int q = threadIdx.x; q < nq; q += NT) {
-    const float4 x = *(const float4*)(X + (q << 2));
-    const float a = x.x - K, b = x.y - K, c = x.z - K, d = x.w - K;
-    sq[0] += (a + b) + (c + d);
-    sq[1] = fmaf(a, a, fmaf(b, b, fmaf(c, c, fmaf(d, d, sq[1]))));
+  // Sums of (x - K) and (x - K)^2 about a shift K: var = m2 - m1 * m1 with m1 = mean - K loses (1 + m1^2 / var) epsilons.  The first pass
+  // takes K = the tensor's first element; when that element turns out to lie more than GN_RESHIFT standard deviations from the mean -- a
+  // window that opens with an artefact spike -- a second pass over the LDS-resident tensor repeats the sums about K = the first pass's
+  // mean, which lies within the data.  Without it, a 3072-sample window whose first two samples carry a spike of 200 standard deviations
+  // came out 5e-5 (outputs) and 2e-4 to 7e-4 (gradients) of the tensors' scale away from float64, 50 to 220 x what fp32 arithmetic in another
+  // order gives (tests/test_gpu_aekl_thin_rounding.py, outlier_first_element_full_window).  The branch is uniform: every thread reads the
+  // same two sums.
+  constexpr float GN_RESHIFT = 2.0f;
+  float K = X[0], m1 = 0.f, m2 = 0.f, var = 0.f;
+#pragma unroll 1
+  for (int pass = 0; pass < 2; pass++) {
+    float sq[2] = {0.f, 0.f};
+    for (int q = threadIdx.x; q < nq; q += NT) {
+      const float4 x = *(const float4*)(X + (q << 2));
+      const float a = x.x - K, b = x.y - K, c = x.z - K, d = x.w - K;
+      sq[0] += (a + b) + (c + d);
+      sq[1] = fmaf(a, a, fmaf(b, b, fmaf(c, c, fmaf(d, d, sq[1]))));
+    }
+    block_reduce<2>(sq, B.red);
+    m1 = B.red[RED_ROWS * 2] / (float)n; m2 = B.red[RED_ROWS * 2 + 1] / (float)n;      // (read before the first barrier of a second reduction)
+    var = fmaxf(m2 - m1 * m1, 0.f);
+    if (pass == 1 || !(m1 * m1 > GN_RESHIFT * GN_RESHIFT * var)) break;
+    K += m1;
   }
-  block_reduce<2>(sq, B.red);
-  const float m1 = B.red[RED_ROWS * 2] / (float)n, m2 = B.red[RED_ROWS * 2 + 1] / (float)n;
-  const float mean = K + m1, rstd = rsqrtf(fmaxf(m2 - m1 * m1, 0.f) + GN_EPS_T);
+  const float mean = K + m1, rstd = rsqrtf(var + GN_EPS_T);
   if (threadIdx.x == 0) { stats[2 * o.stat] = mean; stats[2 * o.stat + 1] = rstd; }
   gn_apply_t<C>(o, P, X, Y, mean, rstd);
 }
