@@ -219,22 +219,6 @@ __device__ __forceinline__ void load_dy_eff_c(const T* dy, long lddy, int b, int
     for (int k = 0; k < V; k++) d[k] += e[k];
   }
 }
-template <typename T, int V>
-__device__ __forceinline__ void load_dy_eff(const T* dy, long lddy, int b, int l, int L, int c, int resample, float d[V]) {
-  if (resample == 0) {
-    loadv<T, V>(dy + ((long)b * L + l) * lddy + c, d);
-  } else if (resample == 1) {
-    loadv<T, V>(dy + ((long)b * (L / 2) + (l >> 1)) * lddy + c, d);
-#pragma unroll
-    for (int k = 0; k < V; k++) d[k] *= 0.5f;
-  } else {
-    float e[V];
-    loadv<T, V>(dy + ((long)b * 2 * L + 2 * l) * lddy + c, d);
-    loadv<T, V>(dy + ((long)b * 2 * L + 2 * l + 1) * lddy + c, e);
-#pragma unroll
-    for (int k = 0; k < V; k++) d[k] += e[k];
-  }
-}
 
 // grid (LSPLIT, B): group sums S1 = sum dz*gamma, S2 = sum dz*gamma*xhat -> gsums double [B][G][2];
 // dgamma[c] += sum dz*xhat, dbeta[c] += sum dz (fp32 atomics)
@@ -554,13 +538,8 @@ __global__ __launch_bounds__(NTH) void gn_fwd_resident_kernel(const T* __restric
 // the per-sample column sums of the written dx -- the block owns (sample, channels) over all of L, so no atomics.
 // RAW0: resample == 0 specialisation that fetches the gradient rows packed, in the same predicated block as the x rows (the
 // conversion in place makes hipcc wait for every load separately: 12 serialised HBM latencies, 19 k of the block's 57 k cycles)
-#ifdef EEG_GN_W4      // developer build (tools/debug/gn_hazard.sh): at most 128 VGPRs, whatever else the build flags do
-#define GN_BWD_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
-#else
-#define GN_BWD_ATTR
-#endif
 template <typename T, int RPT, bool RAW0, bool SILU, int NTH>
-__global__ __launch_bounds__(NTH) GN_BWD_ATTR void gn_bwd_resident_kernel(const T* __restrict__ x, long ldx, const float* __restrict__ gamma,
+__global__ __launch_bounds__(NTH) void gn_bwd_resident_kernel(const T* __restrict__ x, long ldx, const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, const float* __restrict__ stats,
                                                               const T* __restrict__ dy, long lddy, T* __restrict__ dx, long lddx,
                                                               const T* __restrict__ dxr, long lddxr, float* __restrict__ slots,
@@ -571,9 +550,6 @@ __global__ __launch_bounds__(NTH) GN_BWD_ATTR void gn_bwd_resident_kernel(const 
   // difference in the group sums flips bf16 roundings of dx and the flips compound through the remaining layers
   __shared__ double redg[2 * RES_MAXG];
   __shared__ double redc[3 * RES_MAXC];
-#ifdef EEG_GN_BWD_NO_LDS_ATOMICS
-  __shared__ float gn_part[NTH * 8];
-#endif
   GN_TSTAMP(0);
   const int cpg = C / G;
   const ResMap m = resmap<NTH>(CC, C, cpg, xcd);
@@ -633,46 +609,9 @@ __global__ __launch_bounds__(NTH) GN_BWD_ATTR void gn_bwd_resident_kernel(const 
         }
       }
     }
-#ifdef EEG_GN_BWD_NO_LDS_ATOMICS
-    // developer build (tools/debug/gn_hazard.sh): no LDS atomics anywhere in this kernel -- per-thread partials to LDS, one writer per sum
-#pragma unroll
-    for (int j = 0; j < 4; j++) { gn_part[(m.ty * m.TX + m.tx) * 8 + j] = dg[j]; gn_part[(m.ty * m.TX + m.tx) * 8 + 4 + j] = db[j]; }
-#ifdef EEG_GN_HAZ_VERIFY      // (1) does a thread read back what it just wrote?
-    {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      bool mism = false;
-#pragma unroll
-      for (int j = 0; j < 4; j++) mism = mism || ((volatile float*)gn_part)[(m.ty * m.TX + m.tx) * 8 + j] != dg[j] || ((volatile float*)gn_part)[(m.ty * m.TX + m.tx) * 8 + 4 + j] != db[j];
-      if (mism) printf("HAZ1 own write not read back: block %d thread %d\n", (int)blockIdx.x, (int)threadIdx.x);
-    }
-#endif
-#else
 #pragma unroll
     for (int j = 0; j < 4; j++) { atomicAdd(&redc[m.tx * 4 + j], (double)dg[j]); atomicAdd(&redc[RES_MAXC + m.tx * 4 + j], (double)db[j]); }
-#endif
   }
-#ifdef EEG_GN_BWD_NO_LDS_ATOMICS
-  __syncthreads();
-  if (m.act && m.ty == 0) {
-    double sg[4] = {0.0, 0.0, 0.0, 0.0}, sb[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int r = 0; r < m.TY; r++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) { sg[j] += (double)gn_part[(r * m.TX + m.tx) * 8 + j]; sb[j] += (double)gn_part[(r * m.TX + m.tx) * 8 + 4 + j]; }
-#pragma unroll
-    for (int j = 0; j < 4; j++) { redc[m.tx * 4 + j] = sg[j]; redc[RES_MAXC + m.tx * 4 + j] = sb[j]; }
-#ifdef EEG_GN_HAZ_VERIFY      // (2) do the partials still read the same a little later?  (3) were they all written: own row 0 equals the registers
-    __builtin_amdgcn_s_sleep(64);
-    double sg2[4] = {0.0, 0.0, 0.0, 0.0}, sb2[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int r = 0; r < m.TY; r++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) { sg2[j] += (double)((volatile float*)gn_part)[(r * m.TX + m.tx) * 8 + j]; sb2[j] += (double)((volatile float*)gn_part)[(r * m.TX + m.tx) * 8 + 4 + j]; }
-    bool diff = false;
-#pragma unroll
-    for (int j = 0; j < 4; j++) diff = diff || sg2[j] != sg[j] || sb2[j] != sb[j];
-    if (diff) printf("HAZ2 partials changed after the barrier: block %d column %d (TY %d): %.9g -> %.9g\n", (int)blockIdx.x, m.tx, m.TY, sg[0], sg2[0]);
-#endif
-  }
-#endif
   // the residual-path addend(s) of dx are fetched HERE, packed and unconditionally (clamped row), so their round trip runs under the
   // two barriers and the group-sum phase: loaded inside pass 2 they were twelve load-wait-use chains per thread (the first GroupNorm of
   // every ResBlock has such an addend: those launches took ~70 us against 45 us without)
@@ -686,20 +625,12 @@ __global__ __launch_bounds__(NTH) GN_BWD_ATTR void gn_bwd_resident_kernel(const 
     }
   }
   __syncthreads();
-#ifdef EEG_GN_BWD_NO_LDS_ATOMICS
-  if (m.act && m.ty == 0 && (m.tx * 4) % cpg == 0) {       // one writer per group: its channels' sums in channel order
-    double p1 = 0.0, p2 = 0.0;
-    for (int i = 0; i < cpg; i++) { const double g = (double)gamma[m.c + i]; p1 += g * redc[RES_MAXC + m.tx * 4 + i]; p2 += g * redc[m.tx * 4 + i]; }
-    redg[2 * m.gl] = p1; redg[2 * m.gl + 1] = p2;
-  }
-#else
   if (m.act && m.ty == 0) {
     double p1 = 0.0, p2 = 0.0;
 #pragma unroll
     for (int j = 0; j < 4; j++) { p1 += (double)ga[j] * redc[RES_MAXC + m.tx * 4 + j]; p2 += (double)ga[j] * redc[m.tx * 4 + j]; }
     atomicAdd(&redg[2 * m.gl], p1); atomicAdd(&redg[2 * m.gl + 1], p2);
   }
-#endif
   GN_TSTAMP(3);
   __syncthreads();
   GN_TSTAMP(4);
@@ -1175,10 +1106,13 @@ template <int N, typename F> void gn_static_switch(int v, F&& f) {
   else if constexpr (N > 1) gn_static_switch<N - 1>(v, f);
 }
 
-int grid_for(long total_threads, eegldm_ctx* ctx) {
-  long blocks = (total_threads + NT - 1) / NT;
-  long cap = (long)ctx->num_cu * 16;
-  return (int)(blocks < cap ? (blocks < 1 ? 1 : blocks) : cap);
+// f(GnType<T>()) with T the storage type that `dtype` names: turns the run-time dtype into a template argument
+template <typename T> struct GnType { typedef T type; };
+template <typename F> int gn_dtype_switch(int dtype, F&& f) {
+  if (dtype == EEGLDM_F32) return f(GnType<float>());
+  if (dtype == EEGLDM_BF16) return f(GnType<bf16_t>());
+  if (dtype == EEGLDM_F16) return f(GnType<f16_t>());
+  EEG_FAIL(EEGLDM_ERR_UNSUPPORTED, "dtype %d", dtype);
 }
 
 // row-chunk split of one sample: `per_cu` blocks per CU in total, at least `min_rows` rows per block.
@@ -1192,44 +1126,112 @@ int pick_lsplit(int B, int L, int C, eegldm_ctx* ctx, int* rows_per_block, int p
   return (L + rpb - 1) / rpb;
 }
 
+// ------------------------------------------------------------------ the resident route, forward and backward: one pick
+// {chunk width, rows per thread, threads per block, XCD-aware block order}; cc == 0: not this route (EEGLDM_GN_NO_RESIDENT=1: never)
+struct GnResPick { int cc, rpt, nth, xcd; };
+inline int gn_block_threads(int asked) { return (asked == 512 || asked == 256) ? asked : 1024; }      // EEGLDM_GN_FWD_NTH / _BWD_NTH
+// esize: bytes per element; pair: the avgpool forward (both rows of a pooling pair in one thread); rpt_max: rows per thread the kernel's
+// registers hold; blocks_per_cu: the launch must fit that many 1024-thread blocks per CU (callers: what was measured); nth: threads per
+// block asked for; few_slab_narrow: the forward's narrowing of launches that leave most of the chip idle
+GnResPick gn_resident_pick(const eegldm_ctx* ctx, int B, int L, int C, int G, int esize, bool pair, int rpt_max, long blocks_per_cu, int nth,
+                           bool few_slab_narrow) {
+  EEG_ENV_VAR(bool, off, getenv("EEGLDM_GN_NO_RESIDENT") != nullptr);
+  GnResPick p = {0, 0, nth, 0};
+  if (off) return p;
+  p.cc = resident_chunk(L, C, G, pair, rpt_max, &p.rpt, nth);
+  // a launch that leaves most of the chip idle (sampling one window per call: 1-8 slabs) is a latency chain, not a bandwidth problem:
+  // 16-channel slabs on 256 threads are 4x as many, shorter blocks (DDIM-50 at B = 1: 71.5 -> 64.5 ms).  The fp64 group sums make
+  // the statistics independent of the slab shape, so the outputs do not change.
+  if (few_slab_narrow && p.cc && nth == 1024 && (long)(C / p.cc) * B <= ctx->num_cu / 4) {
+    int rpt2 = 0; const int cc2 = resident_chunk(L, C, G, pair, rpt_max, &rpt2, 256);
+    if (cc2 && cc2 * esize >= 32) p = GnResPick{cc2, rpt2, 256, 0};
+  }
+  // rows of at least a 128-byte line; 32-byte rows (16-channel slabs) are fine under the XCD-aware order, which needs B % 8 == 0:
+  // L = 3072 runs one-pass (pixel-space step 22.84 -> 22.64 ms)
+  const bool can_xcd = B % 8 == 0;
+  const int min_row = (p.nth == 1024 && !can_xcd) ? 128 : 32;
+  if (p.cc && (p.cc * esize < min_row || (long)(C / p.cc) * B > blocks_per_cu * ctx->num_cu * (1024 / p.nth))) p.cc = 0;
+  p.xcd = (p.cc && (p.nth < 1024 || p.cc * esize < 128) && can_xcd) ? 1 : 0;
+  return p;
+}
+
+// ------------------------------------------------------------------ the dgamma / dbeta slot plan of a backward launch
+// Every backward kernel adds its per-channel partials into one of `nslot` rows of 2 C floats, and a fold behind the launch adds the rows
+// into dgamma / dbeta and zeroes them again.  Where the rows are, and who folds them:
+//   shared     the slot area of the context scratch; folded right behind the launch (gn_slot_reduce_kernel)
+//   deferred   a caller that can run the 7-us fold elsewhere (side stream) offers `slots_deferred`: the rows go to the region it names and
+//              it calls op_gn_slot_reduce_deferred itself (*slots_deferred = 1)
+//   batched    (the UNet backward with grouped weight gradients) the launch gets a region of gn_slot_arena of its OWN and is folded
+//              together with all the others by op_gn_fold_flush -- 49 folds of 7 us become one launch (*slots_deferred = 2: nothing left
+//              for the caller to fold)
+//   private    deterministic mode: det_slots zeroed rows with one writer each (a sample; a block of the split route), folded right behind
+//              the launch in row order
+struct GnSlots { float* slots = nullptr; int nslot = GN_NSLOT; bool fold64 = false, defer = false, batched = false; };
+float* gn_deferred_slots(eegldm_ctx* ctx, int region) { return (float*)((char*)ctx->scratch + gn_slot_region(region)); }
+
+// can_defer: the resident and pipelined routes.  The split and flat routes never defer and never batch, and their deterministic fold stays
+// the in-order fp32 one of gn_slot_reduce_kernel over the private rows (the other two fold in fp64, ew_fold_partials_det)
+int gn_slots_begin(eegldm_ctx* ctx, float* dgamma, float* dbeta, int C, int det_slots, const int* slots_deferred, int defer_region,
+                   bool can_defer, GnSlots* out) {
+  GnSlots s;
+  *out = s;
+  if (!dgamma) return 0;
+  const bool det = eeg_deterministic();
+  s.fold64 = det && can_defer;
+  s.defer = can_defer && slots_deferred && !det;
+  s.batched = s.defer && ctx->defer_wgrad && C <= 1024 && ctx->gn_fold_count < GN_FOLD_MAX;
+  if (det) {
+    s.nslot = det_slots;
+    EEG_TRY(eeg_det_buffer(ctx, (size_t)s.nslot * 2 * C * sizeof(float), &s.slots));
+    HIP_TRY(hipMemsetAsync(s.slots, 0, (size_t)s.nslot * 2 * C * sizeof(float), ctx->stream));
+  } else if (s.batched) {
+    if (!ctx->gn_slot_arena) {
+      HIP_TRY(hipMalloc(&ctx->gn_slot_arena, (size_t)GN_FOLD_MAX * GN_REGION_FLOATS * sizeof(float)));
+      HIP_TRY(hipMemsetAsync(ctx->gn_slot_arena, 0, (size_t)GN_FOLD_MAX * GN_REGION_FLOATS * sizeof(float), ctx->stream));
+    }
+    s.slots = ctx->gn_slot_arena + (size_t)ctx->gn_fold_count * GN_REGION_FLOATS;
+    ctx->gn_fold_pending.push_back({s.slots, dgamma, dbeta, C});
+    ctx->gn_fold_count++;
+  } else {
+    s.slots = s.defer ? gn_deferred_slots(ctx, defer_region) : (float*)((char*)ctx->scratch + GN_SLOT_OFFSET);
+  }
+  *out = s;
+  return 0;
+}
+// behind the launch.  n_gsums: the split route's group sums at the head of the scratch, zeroed again by the same fold (also without dgamma)
+int gn_slots_end(eegldm_ctx* ctx, const GnSlots& s, float* dgamma, float* dbeta, int C, int* slots_deferred, int n_gsums = 0) {
+  if (s.fold64) {
+    EEG_TRY(ew_fold_partials_det(ctx, s.slots, s.nslot, 2 * C, 0, C, dgamma)); EEG_TRY(ew_fold_partials_det(ctx, s.slots, s.nslot, 2 * C, C, C, dbeta));
+  } else if ((s.slots && !s.defer) || n_gsums) {
+    const int n = 2 * C > n_gsums ? 2 * C : n_gsums;
+    hipLaunchKernelGGL(gn_slot_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, s.slots, dgamma, dbeta, C, (double*)ctx->scratch, n_gsums, s.nslot);
+    LAUNCH_CHECK();
+  }
+  if (s.defer) *slots_deferred = s.batched ? 2 : 1;
+  return 0;
+}
+
 template <typename T, int V>
 int gn_fwd_t(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const float* beta, void* y, long ldy,
              float* stats, int B, int L, int C, int G, float eps, int silu, int resample, void* xr, long ldxr) {
   if constexpr (V == 4) {
-    EEG_ENV_VAR(bool, off, getenv("EEGLDM_GN_NO_RESIDENT") != nullptr);
-    // 12 rows per thread (56 VGPRs: two 1024-thread blocks per CU) measured faster than 24 (one block per CU): 24 vs 35 us
-    constexpr int fwd_rpt_max = 12;
     // threads per block: 1024 = one (sample, 64-channel) slab per block; 512 / 256 = narrower slabs (32 / 16 channels), 2 / 4x as many
     // independent blocks per CU whose load / reduce / store phases interleave (EEGLDM_GN_FWD_NTH; narrow slabs use the XCD-aware order)
     EEG_ENV_VAR(int, fwd_nth, getenv("EEGLDM_GN_FWD_NTH") ? atoi(getenv("EEGLDM_GN_FWD_NTH")) : 1024);
-    int nth = (fwd_nth == 512 || fwd_nth == 256) ? fwd_nth : 1024;
-    int rpt = 0; int cc = off ? 0 : resident_chunk(L, C, G, resample == 1, fwd_rpt_max, &rpt, nth);
-    // a launch that leaves most of the chip idle (sampling one window per call: 1-8 slabs) is a latency chain, not a bandwidth problem:
-    // 16-channel slabs on 256 threads are 4x as many, shorter blocks (DDIM-50 at B = 1: 71.5 -> 64.5 ms).  The fp64 group sums make
-    // the statistics independent of the slab shape, so the outputs do not change.
     EEG_ENV_VAR(bool, no_few, getenv("EEGLDM_GN_NO_FEW_SLAB_NARROW") != nullptr);
-    if (!no_few && cc && nth == 1024 && (long)(C / cc) * B <= ctx->num_cu / 4) {
-      int rpt2 = 0; const int cc2 = resident_chunk(L, C, G, resample == 1, fwd_rpt_max, &rpt2, 256);
-      if (cc2 && cc2 * (int)sizeof(T) >= 32) { nth = 256; cc = cc2; rpt = rpt2; }
-    }
-    // measured (tools/debug/gn_bench.py): wins while the rows are at least a 128-byte line and the blocks fit two rounds
+    // 12 rows per thread (56 VGPRs: two 1024-thread blocks per CU) measured faster than 24 (one block per CU): 24 vs 35 us.
+    // 4 blocks per CU, measured (tools/debug/gn_bench.py): wins while the rows are at least a 128-byte line and the blocks fit two rounds
     // (1024 blocks = the 100 MB concat tensors of the up path: 47-48 us one-pass vs 51 us split)
-    constexpr long fwd_bpc = 4;
-    constexpr bool no_xcd = false;
-    constexpr int narrow_min = 32;    // 32-byte rows (16-channel slabs) are fine under the XCD-aware order: L = 3072 runs one-pass (pixel-space step 22.84 -> 22.64 ms); 128 = round-2 behaviour
-    const bool can_xcd = !no_xcd && B % 8 == 0;
-    const int min_row = nth == 1024 ? (can_xcd ? narrow_min : 128) : 32;
-    if (cc && (cc * (int)sizeof(T) < min_row || (long)(C / cc) * B > fwd_bpc * ctx->num_cu * (1024 / nth))) cc = 0;
-    if (cc) {
-      const int xcd = ((nth < 1024 || cc * (int)sizeof(T) < 128) && can_xcd) ? 1 : 0;
-      const dim3 grid((unsigned)((long)(C / cc) * B));
-#define GN_FWD_RES1(R, N) hipLaunchKernelGGL((gn_fwd_resident_kernel<T, R, N>), grid, dim3(N), 0, ctx->stream, (const T*)x, ldx, gamma, beta, \
-                                         (T*)y, ldy, (T*)xr, ldxr, stats, L, C, G, eps, silu, resample, cc, xcd)
-#define GN_FWD_RES(R) do { if (nth == 1024) GN_FWD_RES1(R, 1024); else if (nth == 512) GN_FWD_RES1(R, 512); else GN_FWD_RES1(R, 256); } while (0)
-      gn_note(0, 2, 1, nth, rpt <= 6 ? 6 : 12, cc, xcd);
-      if (rpt <= 6) GN_FWD_RES(6); else GN_FWD_RES(12);      // resident_chunk never returns more than fwd_rpt_max rows per thread
-#undef GN_FWD_RES
-#undef GN_FWD_RES1
+    const GnResPick p = gn_resident_pick(ctx, B, L, C, G, (int)sizeof(T), resample == 1, 12, 4, gn_block_threads(fwd_nth), !no_few);
+    if (p.cc) {
+      const dim3 grid((unsigned)((long)(C / p.cc) * B));
+      const int r12 = p.rpt <= 6 ? 0 : 1;      // resident_chunk never returns more than 12 rows per thread
+      gn_note(0, 2, 1, p.nth, r12 ? 12 : 6, p.cc, p.xcd);
+      gn_static_switch<6>(r12 | (p.nth == 1024 ? 0 : p.nth == 512 ? 2 : 4), [&](auto s) {
+        constexpr int S = decltype(s)::value, R = (S & 1) ? 12 : 6, N = 1024 >> (S >> 1);
+        hipLaunchKernelGGL((gn_fwd_resident_kernel<T, R, N>), grid, dim3(N), 0, ctx->stream, (const T*)x, ldx, gamma, beta,
+                           (T*)y, ldy, (T*)xr, ldxr, stats, L, C, G, eps, silu, resample, p.cc, p.xcd);
+      });
       LAUNCH_CHECK();
       return 0;
     }
@@ -1258,29 +1260,25 @@ int gn_bwd_t(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const
   if (dxr2_done) *dxr2_done = 0;
   if (slots_deferred) *slots_deferred = 0;
   if (!dxr2_done || lddxr2 % 4 != 0) dxr2 = nullptr;      // only a caller that can fall back may hand over a second addend
+  GnSlots sl;
   if constexpr (V == 4) {
-    EEG_ENV_VAR(bool, off, getenv("EEGLDM_GN_NO_RESIDENT") != nullptr);
     EEG_ENV_VAR(int, bwd_nth, getenv("EEGLDM_GN_BWD_NTH") ? atoi(getenv("EEGLDM_GN_BWD_NTH")) : 1024);      // see gn_fwd_t
     // 256-thread blocks (EEGLDM_GN_BWD_NTH=256) measure 42-44 vs 47-49 us on the 50 MB tensors at L <= 384 (tools/debug/gn_nth.py); at step
     // level they gain nothing (19.76 vs 19.67 ms), so the default stays at 1024 threads.
-    // HAZARD: until round 4 these blocks returned wrong sums (~1e-3, bf16 rounding flips over whole slabs) whenever they
-    // shared a CU with the fused 3-tap weight-gradient GEMM (LDS-DMA build) of another stream -- 1024-thread blocks own a CU and never
-    // share it.  Round-4 diagnosis (tools/debug/gn_hazard.sh, gn_hazard_diag.py): the errors sit in EVEN channels only = the low lane of
-    // the v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32 instructions hipcc's SLP vectoriser makes of the per-channel math; LDS atomics,
-    // LDS stomping and late DMA are not involved (the sums are wrong with the atomics replaced by single-writer stores; right with
-    // the packed instructions gone).  The library is now built with -fno-slp-vectorize -fno-vectorize (Makefile), which removes the error
+    // HAZARD (the logs of the diagnosis are profiles/r04_hazard_*.txt): until round 4 these blocks returned wrong sums
+    // (~1e-3, bf16 rounding flips over whole slabs) whenever they shared a CU with the fused 3-tap weight-gradient GEMM (LDS-DMA build) of
+    // another stream -- 1024-thread blocks own a CU and never share it.  The errors sat in EVEN channels only = the low lane of the
+    // v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32 instructions hipcc's SLP vectoriser makes of the per-channel math; LDS atomics, LDS stomping
+    // and late DMA were not involved.  The library is built with -fno-slp-vectorize -fno-vectorize (Makefile), which removes the error
     // (0 of 108 noisy runs against 27 of 27).  The fence below stays as a second line: narrow blocks are refused whenever anything of this
     // library can run beside them -- the opt-in side stream, or a second live context in this process (g_eeg_live_ctx, api.hip).
     // EEGLDM_GN_NARROW_UNFENCED=1 (developer / regression switch): narrow blocks even beside a second context -- the configuration that
     // returned wrong sums until the library was built without packed-fp32 instructions (tests/test_gpu_concurrency.py runs it)
     EEG_ENV_VAR(bool, unfenced, getenv("EEGLDM_GN_NARROW_UNFENCED") != nullptr);
-#ifdef EEG_GN_NO_FENCE      // developer build (tools/debug/gn_hazard.sh)
-    const int nth = (bwd_nth == 512 || bwd_nth == 256) ? bwd_nth : 1024;
-#else
-    const int nth = ((bwd_nth == 512 || bwd_nth == 256) && (unfenced || (!ctx->side_on && g_eeg_live_ctx <= 1))) ? bwd_nth : 1024;
-#endif
+    const int nth = (unfenced || (!ctx->side_on && g_eeg_live_ctx <= 1)) ? gn_block_threads(bwd_nth) : 1024;
     if constexpr (sizeof(T) == 2) {
       // pipelined persistent form (gn_bwd_pipe_kernel): slabs of exactly 6 rows x 4 channels per thread, L * CC = 24 576, CC a power of two
+      EEG_ENV_VAR(bool, off, getenv("EEGLDM_GN_NO_RESIDENT") != nullptr);
       EEG_ENV_VAR(bool, no_pipe, getenv("EEGLDM_GN_NO_PIPE") != nullptr);
       constexpr int pipe_min_row = 64;
       EEG_ENV_VAR(int, pipe_min_slabs, getenv("EEGLDM_GN_PIPE_MIN_SLABS") ? atoi(getenv("EEGLDM_GN_PIPE_MIN_SLABS")) : 2);
@@ -1298,28 +1296,7 @@ int gn_bwd_t(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const
         const int nchunk = C / pcc, per_xcd = ctx->num_cu / 8;
         int nslot = per_xcd / nchunk; if (nslot > B / 8) nslot = B / 8; if (nslot > pipe_max_slot) nslot = pipe_max_slot;
         if (nslot >= 1 && (long)nchunk * B >= (long)pipe_min_slabs * 8 * nslot * nchunk) {
-          float* slots = nullptr;
-          constexpr bool no_defer_p = false;
-          const bool det = eeg_deterministic() && dgamma;      // a slot per sample (one writer each), folded right behind the launch in sample order
-          const bool defer = slots_deferred && dgamma && !no_defer_p && !det;
-          int ndg = GN_NSLOT;
-          if (dgamma) slots = (float*)((char*)ctx->scratch + (defer ? gn_slot_region(defer_region) : GN_SLOT_OFFSET));
-          if (det) {
-            ndg = B;
-            EEG_TRY(eeg_det_buffer(ctx, (size_t)ndg * 2 * C * sizeof(float), &slots));
-            HIP_TRY(hipMemsetAsync(slots, 0, (size_t)ndg * 2 * C * sizeof(float), ctx->stream));
-          }
-          constexpr bool no_batch_p = false;
-          const bool batched = defer && ctx->defer_wgrad && !no_batch_p && C <= 1024 && ctx->gn_fold_count < GN_FOLD_MAX;
-          if (batched) {
-            if (!ctx->gn_slot_arena) {
-              HIP_TRY(hipMalloc(&ctx->gn_slot_arena, (size_t)GN_FOLD_MAX * GN_REGION_FLOATS * sizeof(float)));
-              HIP_TRY(hipMemsetAsync(ctx->gn_slot_arena, 0, (size_t)GN_FOLD_MAX * GN_REGION_FLOATS * sizeof(float), ctx->stream));
-            }
-            slots = ctx->gn_slot_arena + (size_t)ctx->gn_fold_count * GN_REGION_FLOATS;
-            ctx->gn_fold_pending.push_back({slots, dgamma, dbeta, C});
-            ctx->gn_fold_count++;
-          }
+          EEG_TRY(gn_slots_begin(ctx, dgamma, dbeta, C, B, slots_deferred, defer_region, true, &sl));
           static DevOnce attr_once;
           if (attr_once.need(ctx->device)) {
             HIP_TRY(hipFuncSetAttribute((const void*)gn_bwd_pipe_kernel<true, true, T>, hipFuncAttributeMaxDynamicSharedMemorySize, PIPE_LDS));
@@ -1330,91 +1307,48 @@ int gn_bwd_t(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const
           const dim3 grid((unsigned)(8 * nslot * nchunk));
           gn_note(1, 3, 1, NTB, PIPE_RPT, pcc, 1);
 #define GN_BWD_PIPE(SL, ER) hipLaunchKernelGGL((gn_bwd_pipe_kernel<SL, ER, T>), grid, dim3(NTB), PIPE_LDS, ctx->stream, (const bf16_t*)x, ldx, gamma, beta, stats, \
-                                           (const bf16_t*)dy, lddy, (bf16_t*)dx, lddx, (const bf16_t*)dxr, lddxr, slots, colsum_ps, ldps, B, L, C, G, pcc, ndg)
+                                           (const bf16_t*)dy, lddy, (bf16_t*)dx, lddx, (const bf16_t*)dxr, lddxr, sl.slots, colsum_ps, ldps, B, L, C, G, pcc, sl.nslot)
           if (silu) { if (dxr) GN_BWD_PIPE(true, true); else GN_BWD_PIPE(true, false); }
           else { if (dxr) GN_BWD_PIPE(false, true); else GN_BWD_PIPE(false, false); }
 #undef GN_BWD_PIPE
           LAUNCH_CHECK();
-          if (det) {
-            EEG_TRY(ew_fold_partials_det(ctx, slots, ndg, 2 * C, 0, C, dgamma)); EEG_TRY(ew_fold_partials_det(ctx, slots, ndg, 2 * C, C, C, dbeta));
-          } else if (slots && !defer) {
-            hipLaunchKernelGGL(gn_slot_reduce_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, ctx->stream, slots, dgamma, dbeta, C, (double*)ctx->scratch, 0, ndg);
-            LAUNCH_CHECK();
-          }
-          if (defer) *slots_deferred = batched ? 2 : 1;
+          EEG_TRY(gn_slots_end(ctx, sl, dgamma, dbeta, C, slots_deferred));
           if (colsum_done && colsum_ps) *colsum_done = 1;
           return 0;
         }
       }
     }
-    int rpt = 0; int cc = off ? 0 : resident_chunk(L, C, G, 0, sizeof(T) == 2 ? 12 : 8, &rpt, nth);
-    // measured (tools/debug/gn_bench.py): the one-pass kernel wins while its blocks fit two rounds of one block per CU
+    // 8 blocks per CU, measured (tools/debug/gn_bench.py): the one-pass kernel wins while its blocks fit two rounds of one block per CU
     // (1024 blocks: 112 us one-pass vs 117-120 us split on the 100 MB tensors; 2048 blocks of 96-channel chunks lose)
-    constexpr long bwd_bpc = 8;
-    constexpr int bwd_minrow = 128, narrow_min = 32;
-    constexpr bool no_xcd = false;
-    const bool can_xcd = !no_xcd && B % 8 == 0;
-    const int min_row = nth == 1024 ? (can_xcd && narrow_min < bwd_minrow ? narrow_min : bwd_minrow) : 32;
-    if (cc && (cc * (int)sizeof(T) < min_row || (long)(C / cc) * B > bwd_bpc * ctx->num_cu * (1024 / nth))) cc = 0;
-    if (cc) {
-      const int xcd = ((nth < 1024 || cc * (int)sizeof(T) < 128) && can_xcd) ? 1 : 0;
-      const dim3 grid((unsigned)((long)(C / cc) * B));
-      // a caller that can run the 7-us fold of the dgamma / dbeta partial slots elsewhere (side stream) gets them in the second slot
-      // region and calls op_gn_slot_reduce_deferred itself
-      constexpr bool no_defer = false;
-      const bool det = eeg_deterministic() && dgamma;      // see the pipelined launch above
-      const bool defer = slots_deferred && dgamma && !no_defer && !det;
-      float* slots = dgamma ? (float*)((char*)ctx->scratch + (defer ? gn_slot_region(defer_region) : GN_SLOT_OFFSET)) : nullptr;
-      int nslot = GN_NSLOT;
-      if (det) {
-        nslot = B;
-        EEG_TRY(eeg_det_buffer(ctx, (size_t)nslot * 2 * C * sizeof(float), &slots));
-        HIP_TRY(hipMemsetAsync(slots, 0, (size_t)nslot * 2 * C * sizeof(float), ctx->stream));
-      }
-      // batched mode (the UNet backward with grouped weight gradients): this launch gets its OWN slot region and is folded together with
-      // all the others by op_gn_fold_flush -- 49 folds of 7 us become one launch
-      constexpr bool no_batch = false;
-      const bool batched = defer && ctx->defer_wgrad && !no_batch && C <= 1024 && ctx->gn_fold_count < GN_FOLD_MAX;
-      if (batched) {
-        if (!ctx->gn_slot_arena) {
-          HIP_TRY(hipMalloc(&ctx->gn_slot_arena, (size_t)GN_FOLD_MAX * GN_REGION_FLOATS * sizeof(float)));
-          HIP_TRY(hipMemsetAsync(ctx->gn_slot_arena, 0, (size_t)GN_FOLD_MAX * GN_REGION_FLOATS * sizeof(float), ctx->stream));
-        }
-        slots = ctx->gn_slot_arena + (size_t)ctx->gn_fold_count * GN_REGION_FLOATS;
-        ctx->gn_fold_pending.push_back({slots, dgamma, dbeta, C});
-        ctx->gn_fold_count++;
-      }
-#define GN_BWD_RES3(R, RAW, SL, N) hipLaunchKernelGGL((gn_bwd_resident_kernel<T, R, RAW, SL, N>), grid, dim3(N), 0, ctx->stream, (const T*)x, ldx, gamma, beta, stats, \
-                                         (const T*)dy, lddy, (T*)dx, lddx, (const T*)dxr, lddxr, slots, colsum_ps, ldps, L, C, G, silu, resample, cc, (const T*)dxr2, lddxr2, xcd, nslot)
-#define GN_BWD_RES2(R, RAW, SL) do { if (nth == 1024) GN_BWD_RES3(R, RAW, SL, 1024); else if (nth == 512) GN_BWD_RES3(R, RAW, SL, 512); else GN_BWD_RES3(R, RAW, SL, 256); } while (0)
-      constexpr bool raw0 = true;
-#define GN_BWD_RES1(R, RAW) do { if (silu) GN_BWD_RES2(R, RAW, true); else GN_BWD_RES2(R, RAW, false); } while (0)
-#define GN_BWD_RES(R) do { if (resample == 0 && raw0) GN_BWD_RES1(R, true); else GN_BWD_RES1(R, false); } while (0)
-      constexpr int RLO = sizeof(T) == 2 ? 6 : 4, RHI = sizeof(T) == 2 ? 12 : 8;
-      gn_note(1, 2, 1, nth, rpt <= RLO ? RLO : RHI, cc, xcd);
+    constexpr int RLO = sizeof(T) == 2 ? 6 : 4, RHI = sizeof(T) == 2 ? 12 : 8;
+    const GnResPick p = gn_resident_pick(ctx, B, L, C, G, (int)sizeof(T), false, RHI, 8, nth, false);
+    if (p.cc) {
+      const dim3 grid((unsigned)((long)(C / p.cc) * B));
+      EEG_TRY(gn_slots_begin(ctx, dgamma, dbeta, C, B, slots_deferred, defer_region, true, &sl));
+      const int rhi = p.rpt <= RLO ? 0 : 1;
+      gn_note(1, 2, 1, p.nth, rhi ? RHI : RLO, p.cc, p.xcd);
       // same route, same geometry; a full slab runs the straight-line body, instantiated for what this launch has (EEGLDM_GN_NO_STREAM=1: never)
       EEG_ENV_VAR(bool, no_stream, getenv("EEGLDM_GN_NO_STREAM") != nullptr);
-      if (!no_stream && nth == NTB && resident_full_slab(L, cc, rpt <= RLO ? RLO : RHI)) {
-        const int sel = (dxr ? 1 : 0) | (dxr2 ? 2 : 0) | (colsum_ps ? 4 : 0) | (silu ? 8 : 0) | (rpt <= RLO ? 0 : 16) | ((resample == 1 ? 1 : resample == 2 ? 2 : 0) << 5);
+      if (!no_stream && p.nth == NTB && resident_full_slab(L, p.cc, rhi ? RHI : RLO)) {
+        const int sel = (dxr ? 1 : 0) | (dxr2 ? 2 : 0) | (colsum_ps ? 4 : 0) | (silu ? 8 : 0) | (rhi ? 16 : 0) | ((resample == 1 ? 1 : resample == 2 ? 2 : 0) << 5);
         gn_static_switch<96>(sel, [&](auto s) {
           constexpr int S = decltype(s)::value;
           hipLaunchKernelGGL((gn_bwd_resident_full_kernel<T, (S & 16) ? RHI : RLO, (S / 32), (S & 8) != 0, (S & 7)>), grid, dim3(NTB), 0, ctx->stream,
-                             (const T*)x, ldx, gamma, beta, stats, (const T*)dy, lddy, (T*)dx, lddx, (const T*)dxr, lddxr, slots, colsum_ps, ldps,
-                             L, C, G, cc, (const T*)dxr2, lddxr2, xcd, nslot);
+                             (const T*)x, ldx, gamma, beta, stats, (const T*)dy, lddy, (T*)dx, lddx, (const T*)dxr, lddxr, sl.slots, colsum_ps, ldps,
+                             L, C, G, p.cc, (const T*)dxr2, lddxr2, p.xcd, sl.nslot);
         });
-      } else if (rpt <= RLO) GN_BWD_RES(RLO); else GN_BWD_RES(RHI);
-#undef GN_BWD_RES
-#undef GN_BWD_RES1
-#undef GN_BWD_RES2
-#undef GN_BWD_RES3
-      LAUNCH_CHECK();
-      if (det) {
-        EEG_TRY(ew_fold_partials_det(ctx, slots, nslot, 2 * C, 0, C, dgamma)); EEG_TRY(ew_fold_partials_det(ctx, slots, nslot, 2 * C, C, C, dbeta));
-      } else if (slots && !defer) {
-        hipLaunchKernelGGL(gn_slot_reduce_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, ctx->stream, slots, dgamma, dbeta, C, (double*)ctx->scratch, 0, nslot);
-        LAUNCH_CHECK();
+      } else {
+        // bit 0 rows per thread, 1 RAW0 (resample == 0: the gradient rows fetched packed), 2 SiLU, 3.. threads per block (1024, 512, 256)
+        const int sel = rhi | (resample == 0 ? 2 : 0) | (silu ? 4 : 0) | ((p.nth == 1024 ? 0 : p.nth == 512 ? 1 : 2) << 3);
+        gn_static_switch<24>(sel, [&](auto s) {
+          constexpr int S = decltype(s)::value, N = 1024 >> (S >> 3);
+          hipLaunchKernelGGL((gn_bwd_resident_kernel<T, (S & 1) ? RHI : RLO, (S & 2) != 0, (S & 4) != 0, N>), grid, dim3(N), 0, ctx->stream,
+                             (const T*)x, ldx, gamma, beta, stats, (const T*)dy, lddy, (T*)dx, lddx, (const T*)dxr, lddxr, sl.slots, colsum_ps, ldps,
+                             L, C, G, silu, resample, p.cc, (const T*)dxr2, lddxr2, p.xcd, sl.nslot);
+        });
       }
-      if (defer) *slots_deferred = batched ? 2 : 1;       // 2: nothing left for the caller to fold
+      LAUNCH_CHECK();
+      EEG_TRY(gn_slots_end(ctx, sl, dgamma, dbeta, C, slots_deferred));
       if (colsum_done && colsum_ps) *colsum_done = 1;
       if (dxr2) *dxr2_done = 1;
       return 0;
@@ -1423,26 +1357,17 @@ int gn_bwd_t(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const
   double* gsums = (double*)ctx->scratch;     // zero on entry; shared with the forward sums (stream-ordered)
   int rpb; int ls = pick_lsplit(B, L, C, ctx, &rpb);
   gn_note(1, 1, V == 4, NT, 0, 0, 0);
-  float* slots = dgamma ? (float*)((char*)ctx->scratch + GN_SLOT_OFFSET) : nullptr;
-  int nslot = GN_NSLOT;
-  if (slots && eeg_deterministic()) {      // a slot per block: every partial row has one writer, the fold adds the rows in order
-    nslot = ls * B;
-    EEG_TRY(eeg_det_buffer(ctx, (size_t)nslot * 2 * C * sizeof(float), &slots));
-    HIP_TRY(hipMemsetAsync(slots, 0, (size_t)nslot * 2 * C * sizeof(float), ctx->stream));
-  }
+  EEG_TRY(gn_slots_begin(ctx, dgamma, dbeta, C, ls * B, nullptr, 0, false, &sl));      // deterministic mode: a slot per block
 #define GN_BWD_SPLIT(RS) do { \
     hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, V, RS>), dim3(ls, B), dim3(NT), 0, ctx->stream, (const T*)x, ldx, gamma, beta, stats, \
-                       (const T*)dy, lddy, gsums, slots, L, C, G, silu, rpb, nslot); \
+                       (const T*)dy, lddy, gsums, sl.slots, L, C, G, silu, rpb, sl.nslot); \
     hipLaunchKernelGGL((gn_bwd_apply_kernel<T, V, RS>), dim3(ls2, B), dim3(NT), 0, ctx->stream, (const T*)x, ldx, gamma, \
                        beta, stats, (const T*)dy, lddy, gsums, (T*)dx, lddx, (const T*)dxr, lddxr, L, C, G, silu, rpb2); } while (0)
   int rpb2; int ls2 = pick_lsplit(B, L, C, ctx, &rpb2, 16, 8);
   if (resample == 0) GN_BWD_SPLIT(0); else if (resample == 1) GN_BWD_SPLIT(1); else GN_BWD_SPLIT(2);
 #undef GN_BWD_SPLIT
   LAUNCH_CHECK();
-  const int n_gs = 2 * B * G;
-  hipLaunchKernelGGL(gn_slot_reduce_kernel, dim3(((2 * C > n_gs ? 2 * C : n_gs) + 255) / 256), dim3(256), 0, ctx->stream, slots, dgamma, dbeta, C, gsums, n_gs, nslot);
-  LAUNCH_CHECK();
-  return 0;
+  return gn_slots_end(ctx, sl, dgamma, dbeta, C, nullptr, 2 * B * G);      // runs AFTER the apply kernel: it zeroes the group sums too
 }
 
 // ------------------------------------------------------------------ thin AutoencoderKL layers: G = 1, C in {1, 2, 4, 8}, contiguous samples
@@ -1757,26 +1682,17 @@ int gn_flat_bwd_c(eegldm_ctx* ctx, const void* x, const float* gamma, const floa
 template <typename T>
 int gn_flat_bwd(eegldm_ctx* ctx, const void* x, const float* gamma, const float* beta, const float* stats, const void* dy, void* dx, const void* dxr,
                 float* dgamma, float* dbeta, int B, int L, int C, int silu) {
-  float* slots = dgamma ? (float*)((char*)ctx->scratch + GN_SLOT_OFFSET) : nullptr;
-  int nslot = GN_NSLOT;
-  if (slots && eeg_deterministic()) {
-    nslot = B;
-    EEG_TRY(eeg_det_buffer(ctx, (size_t)nslot * 2 * C * sizeof(float), &slots));
-    HIP_TRY(hipMemsetAsync(slots, 0, (size_t)nslot * 2 * C * sizeof(float), ctx->stream));
-  }
+  GnSlots sl;
+  EEG_TRY(gn_slots_begin(ctx, dgamma, dbeta, C, B, nullptr, 0, false, &sl));
   int rc;
   switch (C) {
-    case 1: rc = gn_flat_bwd_c<T, 1>(ctx, x, gamma, beta, stats, dy, dx, dxr, slots, B, L * C, silu, nslot); break;
-    case 2: rc = gn_flat_bwd_c<T, 2>(ctx, x, gamma, beta, stats, dy, dx, dxr, slots, B, L * C, silu, nslot); break;
-    case 4: rc = gn_flat_bwd_c<T, 4>(ctx, x, gamma, beta, stats, dy, dx, dxr, slots, B, L * C, silu, nslot); break;
-    default: rc = gn_flat_bwd_c<T, 8>(ctx, x, gamma, beta, stats, dy, dx, dxr, slots, B, L * C, silu, nslot); break;
+    case 1: rc = gn_flat_bwd_c<T, 1>(ctx, x, gamma, beta, stats, dy, dx, dxr, sl.slots, B, L * C, silu, sl.nslot); break;
+    case 2: rc = gn_flat_bwd_c<T, 2>(ctx, x, gamma, beta, stats, dy, dx, dxr, sl.slots, B, L * C, silu, sl.nslot); break;
+    case 4: rc = gn_flat_bwd_c<T, 4>(ctx, x, gamma, beta, stats, dy, dx, dxr, sl.slots, B, L * C, silu, sl.nslot); break;
+    default: rc = gn_flat_bwd_c<T, 8>(ctx, x, gamma, beta, stats, dy, dx, dxr, sl.slots, B, L * C, silu, sl.nslot); break;
   }
   if (rc) return rc;
-  if (slots) {
-    hipLaunchKernelGGL(gn_slot_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, slots, dgamma, dbeta, C, (double*)ctx->scratch, 0, nslot);
-    LAUNCH_CHECK();
-  }
-  return 0;
+  return gn_slots_end(ctx, sl, dgamma, dbeta, C, nullptr);
 }
 
 int gn_check(eegldm_ctx* ctx, int B, int L, int C, int G, int resample, long ldx) {
@@ -1797,28 +1713,16 @@ extern "C" int eegldm_groupnorm_fwd(eegldm_ctx* ctx, const void* x, long ldx, co
                                     void* y, long ldy, float* stats, int B, int L, int C, int G, float eps,
                                     int fuse_silu, int resample, void* xr, long ldxr, int dtype) {
   EEG_TRY(gn_check(ctx, B, L, C, G, resample, ldx));
-  if (gn_flat_ok(L, C, G, resample, ldx, ldy, 0, 0)) {
-    if (dtype == EEGLDM_F32) return gn_flat_fwd<float>(ctx, x, gamma, beta, y, stats, B, L, C, eps, fuse_silu);
-    if (dtype == EEGLDM_BF16) return gn_flat_fwd<bf16_t>(ctx, x, gamma, beta, y, stats, B, L, C, eps, fuse_silu);
-    if (dtype == EEGLDM_F16) return gn_flat_fwd<f16_t>(ctx, x, gamma, beta, y, stats, B, L, C, eps, fuse_silu);
-  }
-  if (gn_flat_wide_ok(L, C, G, resample, ldx, ldy) && (dtype != EEGLDM_F32 || (long)L * C <= (long)WIDE_NT * 8 * 6)) {   // fp32: 12 chunks of 8 floats would spill
-    if (dtype == EEGLDM_F32) return gn_flat_fwd_wide<float>(ctx, x, gamma, beta, y, stats, B, L, C, eps, fuse_silu);
-    if (dtype == EEGLDM_BF16) return gn_flat_fwd_wide<bf16_t>(ctx, x, gamma, beta, y, stats, B, L, C, eps, fuse_silu);
-    if (dtype == EEGLDM_F16) return gn_flat_fwd_wide<f16_t>(ctx, x, gamma, beta, y, stats, B, L, C, eps, fuse_silu);
-  }
+  const bool flat = gn_flat_ok(L, C, G, resample, ldx, ldy, 0, 0);
+  const bool wide = gn_flat_wide_ok(L, C, G, resample, ldx, ldy) && (dtype != EEGLDM_F32 || (long)L * C <= (long)WIDE_NT * 8 * 6);   // fp32: 12 chunks of 8 floats would spill
   const bool v4 = vec4_ok(C, G, ldx, ldy, xr ? ldxr : 0, 0);
-  if (dtype == EEGLDM_F32) {
-    return v4 ? gn_fwd_t<float, 4>(ctx, x, ldx, gamma, beta, y, ldy, stats, B, L, C, G, eps, fuse_silu, resample, xr, ldxr)
-              : gn_fwd_t<float, 1>(ctx, x, ldx, gamma, beta, y, ldy, stats, B, L, C, G, eps, fuse_silu, resample, xr, ldxr);
-  } else if (dtype == EEGLDM_BF16) {
-    return v4 ? gn_fwd_t<bf16_t, 4>(ctx, x, ldx, gamma, beta, y, ldy, stats, B, L, C, G, eps, fuse_silu, resample, xr, ldxr)
-              : gn_fwd_t<bf16_t, 1>(ctx, x, ldx, gamma, beta, y, ldy, stats, B, L, C, G, eps, fuse_silu, resample, xr, ldxr);
-  } else if (dtype == EEGLDM_F16) {
-    return v4 ? gn_fwd_t<f16_t, 4>(ctx, x, ldx, gamma, beta, y, ldy, stats, B, L, C, G, eps, fuse_silu, resample, xr, ldxr)
-              : gn_fwd_t<f16_t, 1>(ctx, x, ldx, gamma, beta, y, ldy, stats, B, L, C, G, eps, fuse_silu, resample, xr, ldxr);
-  }
-  EEG_FAIL(EEGLDM_ERR_UNSUPPORTED, "dtype %d", dtype);
+  return gn_dtype_switch(dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    if (flat) return gn_flat_fwd<T>(ctx, x, gamma, beta, y, stats, B, L, C, eps, fuse_silu);
+    if (wide) return gn_flat_fwd_wide<T>(ctx, x, gamma, beta, y, stats, B, L, C, eps, fuse_silu);
+    return v4 ? gn_fwd_t<T, 4>(ctx, x, ldx, gamma, beta, y, ldy, stats, B, L, C, G, eps, fuse_silu, resample, xr, ldxr)
+              : gn_fwd_t<T, 1>(ctx, x, ldx, gamma, beta, y, ldy, stats, B, L, C, G, eps, fuse_silu, resample, xr, ldxr);
+  });
 }
 
 // colsum_ps (optional): per-sample column sums of dx [B][ldps] fp32; *colsum_done tells the caller whether the
@@ -1831,19 +1735,16 @@ int op_groupnorm_bwd(eegldm_ctx* ctx, const void* x, long ldx, const float* gamm
   if (dxr2_done) *dxr2_done = 0;
   if (slots_deferred) *slots_deferred = 0;
   EEG_TRY(gn_check(ctx, B, L, C, G, resample, ldx));
-  if (gn_flat_ok(L, C, G, resample, ldx, lddy, lddx, dxr ? lddxr : 0)) {
-    if (colsum_done) *colsum_done = 0;
-    if (dtype == EEGLDM_F32) return gn_flat_bwd<float>(ctx, x, gamma, beta, stats, dy, dx, dxr, dgamma, dbeta, B, L, C, fuse_silu);
-    if (dtype == EEGLDM_BF16) return gn_flat_bwd<bf16_t>(ctx, x, gamma, beta, stats, dy, dx, dxr, dgamma, dbeta, B, L, C, fuse_silu);
-    if (dtype == EEGLDM_F16) return gn_flat_bwd<f16_t>(ctx, x, gamma, beta, stats, dy, dx, dxr, dgamma, dbeta, B, L, C, fuse_silu);
-  }
+  const bool flat = gn_flat_ok(L, C, G, resample, ldx, lddy, lddx, dxr ? lddxr : 0);
   const bool v4 = vec4_ok(C, G, ldx, lddy, lddx, dxr ? lddxr : 0);
+  if (flat && colsum_done) *colsum_done = 0;
+  return gn_dtype_switch(dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    if (flat) return gn_flat_bwd<T>(ctx, x, gamma, beta, stats, dy, dx, dxr, dgamma, dbeta, B, L, C, fuse_silu);
 #define GN_BWD_ARGS ctx, x, ldx, gamma, beta, stats, dy, lddy, dx, lddx, dgamma, dbeta, B, L, C, G, fuse_silu, resample, dxr, lddxr, colsum_ps, ldps, colsum_done, dxr2, lddxr2, dxr2_done, slots_deferred, defer_region
-  if (dtype == EEGLDM_F32) return v4 ? gn_bwd_t<float, 4>(GN_BWD_ARGS) : gn_bwd_t<float, 1>(GN_BWD_ARGS);
-  if (dtype == EEGLDM_BF16) return v4 ? gn_bwd_t<bf16_t, 4>(GN_BWD_ARGS) : gn_bwd_t<bf16_t, 1>(GN_BWD_ARGS);
-  if (dtype == EEGLDM_F16) return v4 ? gn_bwd_t<f16_t, 4>(GN_BWD_ARGS) : gn_bwd_t<f16_t, 1>(GN_BWD_ARGS);
+    return v4 ? gn_bwd_t<T, 4>(GN_BWD_ARGS) : gn_bwd_t<T, 1>(GN_BWD_ARGS);
 #undef GN_BWD_ARGS
-  EEG_FAIL(EEGLDM_ERR_UNSUPPORTED, "dtype %d", dtype);
+  });
 }
 
 // folds the second slot area into dgamma / dbeta (and re-zeroes it): the deferred half of op_groupnorm_bwd(..., slots_deferred)
@@ -1883,8 +1784,7 @@ int op_gn_fold_flush(eegldm_ctx* ctx) {
 }
 
 int op_gn_slot_reduce_deferred(eegldm_ctx* ctx, float* dgamma, float* dbeta, int C, int region) {
-  float* slots = (float*)((char*)ctx->scratch + gn_slot_region(region));
-  hipLaunchKernelGGL(gn_slot_reduce_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, ctx->stream, slots, dgamma, dbeta, C, (double*)ctx->scratch, 0);
+  hipLaunchKernelGGL(gn_slot_reduce_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, ctx->stream, gn_deferred_slots(ctx, region), dgamma, dbeta, C, (double*)ctx->scratch, 0);
   LAUNCH_CHECK();
   return 0;
 }

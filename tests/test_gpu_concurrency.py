@@ -2,7 +2,7 @@
 
 Round 3 found (tools/debug/gn_conc2.py .. gn_conc4.py, DESIGN.md "concurrent-kernel hazard") that the NARROW-block variant of
 gn_bwd_resident (256 / 512 threads, opt-in through EEGLDM_GN_BWD_NTH) returns wrong sums when it shares a CU with the fused 3-tap
-weight-gradient kernel (LDS-DMA build) of another stream.  Round 4 (tools/debug/gn_hazard.sh): the wrong values are the LOW lanes of the
+weight-gradient kernel (LDS-DMA build) of another stream.  Round 4 (logs in profiles/r04_hazard_*.txt): the wrong values are the LOW lanes of the
 packed-fp32 VALU instructions the compiler's SLP vectoriser had made of the per-channel math; the library is now built without them.  Pinned here:
   * the default 1024-thread blocks own a CU -- results beside the noisy neighbour are BIT-identical to a quiet run;
   * with a second context alive (or the side stream on) the library refuses the narrow blocks whatever EEGLDM_GN_BWD_NTH says (the fence,

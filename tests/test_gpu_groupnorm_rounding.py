@@ -218,7 +218,9 @@ def _buf(G_, rows, C, ld, dt):
     return t, t[:, :C]
 
 
-def _run_case(G_, c, case, dt, env_switches, poison=None):
+def _run_case(G_, c, case, dt, env_switches, poison=None, twice=False):
+    """forward, then the backward once per mode (default; deterministic twice more on a "det" case).  twice: default and deterministic mode,
+    each backward run a second time right behind the first (dgamma, dbeta zeroed, dx NaN-filled again): the SECOND call's results are returned"""
     name, (B, L, C, Gr), _dts, silu, rs, off, scale, opts, env, want_f, want_b = case
     fmt = FMT[dt]; tag = f"{name} [{fmt}]"
     env_switches(**env)
@@ -247,15 +249,18 @@ def _run_case(G_, c, case, dt, env_switches, poison=None):
         return out
     dyd = G_.nlc(dy, dt); dxrd = G_.nlc(dxr, dt) if dxr is not None else None
     runs = []
-    for det in ((None, "1", "1") if "det" in opts else (None,)):
+    for det in ((None, "1") if twice else (None, "1", "1") if "det" in opts else (None,)):
         env_switches(EEGLDM_DETERMINISTIC=det)
         dxb, dxd = _buf(G_, B * L, C, C, dt)
         dga = torch.zeros(C, device=G_.DEV); dbe = torch.zeros(C, device=G_.DEV)
-        G_.check(G_.lib.eegldm_groupnorm_bwd(c.h, G_.ptr(xd), ld, G_.ptr(gad), G_.ptr(bed), G_.ptr(st), G_.ptr(dyd), C, G_.ptr(dxb), C,
-                                             G_.ptr(dga), G_.ptr(dbe), B, L, C, Gr, silu, rs, G_.ptr(dxrd) if dxrd is not None else None,
-                                             C if dxrd is not None else 0, dt))
-        torch.cuda.synchronize()
-        _confirm(G_, 1, want_b, tag + (" deterministic" if det else ""), dt)
+        for call in range(2 if twice else 1):
+            if call:
+                dxb.fill_(math.nan); dga.zero_(); dbe.zero_()
+            G_.check(G_.lib.eegldm_groupnorm_bwd(c.h, G_.ptr(xd), ld, G_.ptr(gad), G_.ptr(bed), G_.ptr(st), G_.ptr(dyd), C, G_.ptr(dxb), C,
+                                                 G_.ptr(dga), G_.ptr(dbe), B, L, C, Gr, silu, rs, G_.ptr(dxrd) if dxrd is not None else None,
+                                                 C if dxrd is not None else 0, dt))
+            torch.cuda.synchronize()
+            _confirm(G_, 1, want_b, tag + (" deterministic" if det else "") + (" second call" if call else ""), dt)
         runs.append(dict(det=bool(det), dx=G_.ncl(dxd, B, L).double(), dga=dga.cpu().double(), dbe=dbe.cpu().double()))
     env_switches(EEGLDM_DETERMINISTIC=None)
     out["bwd"] = runs
@@ -264,6 +269,34 @@ def _run_case(G_, c, case, dt, env_switches, poison=None):
 
 def _ids(cases):
     return [c[0] for c in cases]
+
+
+def _check_backward(o, runs, case, fmt, stats, tag):
+    """the backward checks of the module docstring on every run of `runs`; stats = (mean, rstd, e_mean, e_rstd) of _stat_bounds"""
+    name, (B, L, C, Gr), _dts, silu, rs, _off, _scale, _opts, _env, _want_f, _want_b = case
+    x, ga, be, dy, dxr = o["x"], o["ga"], o["be"], o["dy"], o["dxr"]
+    mean, rstd, em, er = stats
+    rep = lambda t: t.repeat_interleave(C // Gr, dim=1)[:, :, None]
+    xhat = (x - rep(mean)) * rep(rstd)
+    dx_ref, dga_ref, dbe_ref = N.gn_bwd(x, Gr, ga, be, dy, EPS, silu, rs, dxr)
+    dx_em, _g, _b = N.gn_bwd(x.float(), Gr, ga.float(), be.float(), dy.float(), EPS, silu, rs, dxr.float() if dxr is not None else None, torch_norm=True)
+    de = _dy_eff(dy, rs)
+    for r in runs:
+        mode = " det" if r["det"] else ""
+        if fmt != "f32":
+            N.check_b(r["dx"], dx_ref, dx_em, fmt, route=tag + " dx" + mode)
+        else:
+            # fp32 data gradient: no rounding cell to take statistics of.  dx = rstd (dz gamma - m1 - xhat m2) is linear in dz with
+            # coefficients made of rstd and xhat, which the kernel holds to e_rstd and |xhat| e_rstd + rstd e_mean; three such terms with
+            # |xhat| <= 8, and the fp32 group sums m1, m2 over cpg L elements: relative to max |dx|
+            tol = 3 * 9 * float((er + rstd * em).max()) + N.gamma(C // Gr * L)
+            err = float((r["dx"] - dx_ref).abs().max() / dx_ref.abs().max())
+            print(f"[numerics] {tag} dx{mode}: max error {err:.2e} of max |dx| (bound {tol:.2e})")
+            assert err <= tol, f"{tag} dx{mode}: {err:.3e} > {tol:.3e}"
+        if not silu:
+            N.check(r["dbe"], dbe_ref, de.abs().sum((0, 2)), B * L, "f32", route=tag + " dbeta" + mode)
+            dgd = N.gamma(B * L) * (de * xhat).abs().sum((0, 2)) + (de.abs() * (xhat.abs() * rep(er) + rep(rstd) * rep(em))).sum((0, 2))
+            N.check(r["dga"], dga_ref, dgd / N.gamma(0), 0, "f32", route=tag + " dgamma" + mode)
 
 
 @pytest.mark.parametrize("case", CASES, ids=_ids(CASES))
@@ -300,27 +333,8 @@ def test_groupnorm_route_against_float64(case, env_switches):
             N.check(o["xr"], xr_ref, xr_ref.abs(), 0, fmt, route=tag + " xr")
         if want_b is None:
             continue
-        # ---- backward
-        dx_ref, dga_ref, dbe_ref = N.gn_bwd(x, Gr, ga, be, dy, EPS, silu, rs, dxr)
-        dx_em, _g, _b = N.gn_bwd(x.float(), Gr, ga.float(), be.float(), dy.float(), EPS, silu, rs, dxr.float() if dxr is not None else None, torch_norm=True)
-        de = _dy_eff(dy, rs)
+        _check_backward(o, o["bwd"][:2], case, fmt, (mean, rstd, em, er), tag)
         dets = [r for r in o["bwd"] if r["det"]]
-        for r in o["bwd"][:2]:
-            mode = " det" if r["det"] else ""
-            if fmt != "f32":
-                N.check_b(r["dx"], dx_ref, dx_em, fmt, route=tag + " dx" + mode)
-            else:
-                # fp32 data gradient: no rounding cell to take statistics of.  dx = rstd (dz gamma - m1 - xhat m2) is linear in dz with
-                # coefficients made of rstd and xhat, which the kernel holds to e_rstd and |xhat| e_rstd + rstd e_mean; three such terms with
-                # |xhat| <= 8, and the fp32 group sums m1, m2 over cpg L elements: relative to max |dx|
-                tol = 3 * 9 * float((er + rstd * em).max()) + N.gamma(C // Gr * L)
-                err = float((r["dx"] - dx_ref).abs().max() / dx_ref.abs().max())
-                print(f"[numerics] {tag} dx{mode}: max error {err:.2e} of max |dx| (bound {tol:.2e})")
-                assert err <= tol, f"{tag} dx{mode}: {err:.3e} > {tol:.3e}"
-            if not silu:
-                N.check(r["dbe"], dbe_ref, de.abs().sum((0, 2)), B * L, "f32", route=tag + " dbeta" + mode)
-                dgd = N.gamma(B * L) * (de * xhat).abs().sum((0, 2)) + (de.abs() * (xhat.abs() * rep(er) + rep(rstd) * rep(em))).sum((0, 2))
-                N.check(r["dga"], dga_ref, dgd / N.gamma(0), 0, "f32", route=tag + " dgamma" + mode)
         if len(dets) == 2:
             for k in ("dx", "dga", "dbe"):
                 assert torch.equal(dets[0][k], dets[1][k]), f"{tag}: {k} differs between two deterministic-mode runs"
@@ -337,6 +351,22 @@ def _pattern(got, ref, what):
 
 
 NONFINITE = [c for c in CASES if c[0] in ("resident 1024 R6", "pipelined bwd 256-channel slabs", "flat C8 n24576", "split 4-wide (resident off)")]
+
+
+@pytest.mark.parametrize("case", NONFINITE, ids=_ids(NONFINITE))
+def test_second_backward_call_holds_the_first_call_bounds(case, env_switches):
+    """The dgamma / dbeta slot areas are shared between launches and re-zeroed by the fold that follows each launch; a launch whose partials
+    go to one area and whose fold reads (or clears) another is right once and wrong from the next call on.  One case per backward family
+    (split, resident, pipelined, flat), in the default and in the deterministic mode: the backward runs twice in a row, dgamma and dbeta
+    zeroed in between, and the SECOND call's dx, dgamma and dbeta are held to the bounds of the first."""
+    G_ = _G(); c = G_.ctx()
+    name, (B, L, C, Gr), dts, silu, rs, off, scale, opts, env, want_f, want_b = case
+    for dt in dts:
+        fmt = FMT[dt]; tag = f"{name} [{fmt}] second call"
+        o = _run_case(G_, c, case, dt, env_switches, twice=True)
+        mean, _var, rstd, em, er = _stat_bounds(o["x"], Gr, want_f["family"], fmt)
+        assert [r["det"] for r in o["bwd"]] == [False, True], tag
+        _check_backward(o, o["bwd"], case, fmt, (mean, rstd, em, er), tag)
 
 
 @pytest.mark.parametrize("case", NONFINITE, ids=_ids(NONFINITE))

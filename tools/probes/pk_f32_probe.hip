@@ -1,7 +1,7 @@
 // Probe for the concurrent-kernel hazard of DESIGN.md 3.3 (round 4): are the results of PACKED fp32 VALU instructions (v_pk_fma_f32,
 // v_pk_add_f32, v_pk_mul_f32 -- what hipcc's SLP vectoriser makes of adjacent scalar f32 math) of one wave disturbed by LDS-DMA traffic
 // (global_load_lds_dwordx4) of OTHER workgroups on the same CU?
-// Finding that led here (tools/debug/gn_hazard*.sh): the 256-thread GroupNorm backward returns wrong sums in EVEN channels only (= the
+// Finding that led here (logs in profiles/r04_hazard_*.txt): the 256-thread GroupNorm backward returns wrong sums in EVEN channels only (= the
 // low lane of every v_pk_*_f32) beside the LDS-DMA weight-gradient GEMM of another stream; built with -fno-slp-vectorize it is exact.
 //   victim : every thread runs the same chain twice -- packed (inline asm v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32) and scalar
 //            (v_fma_f32 / v_add_f32 / v_mul_f32 on the two halves) -- and counts bitwise mismatches of the low / high lane.
