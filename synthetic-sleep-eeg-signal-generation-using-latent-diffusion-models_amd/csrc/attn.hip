@@ -581,11 +581,11 @@ bool attn_chain_ok(int dtype, int T, int C, long ldq, long ldo) {
 
 // forward: probs written, out = softmax(alpha q k^T) v
 template <typename T16>
-static int chain_fwd_t(eegldm_ctx* ctx, const void* qkv, long ldq, void* out, long ldo, void* probs, int B, int T, int C, const void* resid, long ldr) {
+static int chain_fwd_t(eegldm_ctx* ctx, const AttnIn& in, void* out, long ldo, void* probs, int B, int T, int C, const void* resid, long ldr) {
   ChainArgs a = {};
   a.R = (const bf16_t*)resid; a.ldr = ldr; a.sR = (long)T * ldr;
-  const bf16_t* q = (const bf16_t*)qkv;
-  a.A1 = q; a.lda1 = ldq; a.sA1 = (long)T * ldq; a.B1 = q + C; a.ldb1 = ldq; a.sB1 = (long)T * ldq; a.B2 = q + 2 * C; a.ldb2 = ldq; a.sB2 = (long)T * ldq;
+  a.A1 = (const bf16_t*)in.q; a.lda1 = in.ldq; a.sA1 = (long)T * in.ldq; a.B1 = (const bf16_t*)in.k; a.ldb1 = in.ldk; a.sB1 = (long)T * in.ldk;
+  a.B2 = (const bf16_t*)in.v; a.ldb2 = in.ldv; a.sB2 = (long)T * in.ldv;
   a.P = (bf16_t*)probs; a.sP = (long)T * T; a.O = (bf16_t*)out; a.ldo = ldo; a.sO = (long)T * ldo; a.T = T; a.C = C; a.alpha = 1.0f / sqrtf((float)C);
   switch (T / 64) {
     case 1: return launch_chain<1, 0, T16>(ctx, a, B);
@@ -602,16 +602,15 @@ bool attn_chain_bwd_fuses_kv(eegldm_ctx* ctx, int B, int T) {
   return !off && !no_whole && T == 192 && B >= ctx->num_cu / 2;
 }
 template <typename T16>
-static int chain_bwd_t(eegldm_ctx* ctx, const void* qkv, long ldq, const void* probs, const void* dout, long lddo, void* dq, long lddq,
+static int chain_bwd_t(eegldm_ctx* ctx, const AttnIn& in, const void* probs, const void* dout, long lddo, const AttnGrad& g,
                        void* dS, int B, int T, int C, int fuse_kv) {
   ChainArgs a = {};
-  const bf16_t* q = (const bf16_t*)qkv;
-  a.A1 = (const bf16_t*)dout; a.lda1 = lddo; a.sA1 = (long)T * lddo; a.B1 = q + 2 * C; a.ldb1 = ldq; a.sB1 = (long)T * ldq;
-  a.B2 = q + C; a.ldb2 = ldq; a.sB2 = (long)T * ldq; a.P = (bf16_t*)probs; a.sP = (long)T * T; a.dS = (bf16_t*)dS; a.sdS = (long)T * T;
-  a.O = (bf16_t*)dq; a.ldo = lddq; a.sO = (long)T * lddq; a.T = T; a.C = C; a.alpha = 1.0f / sqrtf((float)C);
+  a.A1 = (const bf16_t*)dout; a.lda1 = lddo; a.sA1 = (long)T * lddo; a.B1 = (const bf16_t*)in.v; a.ldb1 = in.ldv; a.sB1 = (long)T * in.ldv;
+  a.B2 = (const bf16_t*)in.k; a.ldb2 = in.ldk; a.sB2 = (long)T * in.ldk; a.P = (bf16_t*)probs; a.sP = (long)T * T; a.dS = (bf16_t*)dS; a.sdS = (long)T * T;
+  a.O = (bf16_t*)g.dq; a.ldo = g.ld; a.sO = (long)T * g.ld; a.T = T; a.C = C; a.alpha = 1.0f / sqrtf((float)C);
   if (fuse_kv) {
     EEG_CHECK(attn_chain_bwd_fuses_kv(ctx, B, T), "fused dK / dV needs whole-sample blocks");
-    a.fuse_kv = fuse_kv == 2 ? 2 : 1; a.Q3 = q; a.ldq3 = ldq; a.sQ3 = (long)T * ldq; a.dK = (bf16_t*)dq + C; a.dV = (bf16_t*)dq + 2 * C;
+    a.fuse_kv = fuse_kv == 2 ? 2 : 1; a.Q3 = (const bf16_t*)in.q; a.ldq3 = in.ldq; a.sQ3 = (long)T * in.ldq; a.dK = (bf16_t*)g.dk; a.dV = (bf16_t*)g.dv;
   }
   switch (T / 64) {
     case 1: return launch_chain<1, 1, T16>(ctx, a, B);
@@ -622,14 +621,20 @@ static int chain_bwd_t(eegldm_ctx* ctx, const void* qkv, long ldq, const void* p
   }
 }
 
-int attn_chain_fwd(eegldm_ctx* ctx, const void* qkv, long ldq, void* out, long ldo, void* probs, int B, int T, int C, int dtype,
+// (the kernel fetches 16-byte chunks of the Q / K / V rows: every operand 16-byte aligned, every leading dimension a multiple of 8)
+static bool chain_operands_ok(const AttnIn& in) {
+  return (((size_t)in.q | (size_t)in.k | (size_t)in.v) & 15) == 0 && in.ldq % 8 == 0 && in.ldk % 8 == 0 && in.ldv % 8 == 0;
+}
+int attn_chain_fwd(eegldm_ctx* ctx, const AttnIn& in, void* out, long ldo, void* probs, int B, int T, int C, int dtype,
                    const void* resid, long ldr) {
   EEG_CHECK(!resid || (ldr % 4 == 0 && (size_t)resid % 8 == 0), "attention residual rows must be 8-byte aligned");
-  return dtype == EEGLDM_F16 ? chain_fwd_t<f16_t>(ctx, qkv, ldq, out, ldo, probs, B, T, C, resid, ldr)
-                             : chain_fwd_t<bf16_t>(ctx, qkv, ldq, out, ldo, probs, B, T, C, resid, ldr);
+  EEG_CHECK(chain_operands_ok(in), "attention operands must be 16-byte aligned");
+  return dtype == EEGLDM_F16 ? chain_fwd_t<f16_t>(ctx, in, out, ldo, probs, B, T, C, resid, ldr)
+                             : chain_fwd_t<bf16_t>(ctx, in, out, ldo, probs, B, T, C, resid, ldr);
 }
-int attn_chain_bwd(eegldm_ctx* ctx, const void* qkv, long ldq, const void* probs, const void* dout, long lddo, void* dq, long lddq,
+int attn_chain_bwd(eegldm_ctx* ctx, const AttnIn& in, const void* probs, const void* dout, long lddo, const AttnGrad& g,
                    void* dS, int B, int T, int C, int fuse_kv, int dtype) {
-  return dtype == EEGLDM_F16 ? chain_bwd_t<f16_t>(ctx, qkv, ldq, probs, dout, lddo, dq, lddq, dS, B, T, C, fuse_kv)
-                             : chain_bwd_t<bf16_t>(ctx, qkv, ldq, probs, dout, lddo, dq, lddq, dS, B, T, C, fuse_kv);
+  EEG_CHECK(chain_operands_ok(in), "attention operands must be 16-byte aligned");
+  return dtype == EEGLDM_F16 ? chain_bwd_t<f16_t>(ctx, in, probs, dout, lddo, g, dS, B, T, C, fuse_kv)
+                             : chain_bwd_t<bf16_t>(ctx, in, probs, dout, lddo, g, dS, B, T, C, fuse_kv);
 }

@@ -4,6 +4,10 @@
 //   refresh (NetBase::sync_weights):         E = [Wq ; Wk ; round(Wp Wv)] (16-bit), be = [bq | bk | Wp bv + bp] (fp32)
 //   back-transform (NetBase::flush_attn_folds), from the scratch gradient g = d/dE, gb = d/dbe of one backward:
 //     dWq, dWk += g rows;  dWv += Wp^T g_v;  dWp += g_v Wv^T + gb_v bv^T;  dbq, dbk += gb;  dbv += Wp^T gb_v;  dbp += gb_v
+// The K projection folded into Q on top of that: the terms of Q_i . K_j that depend on the query row alone cancel in the row softmax,
+//   softmax_j(Q_i . K_j) = softmax_j(Q'_i . xn_j)      with Q' = xn W'^T + c, W' = Wk^T Wq, c = Wk^T bq      (the key operand is xn itself)
+//   refresh: E gains the rows round(W') behind Wvp (4C rows in all), be gains c; the route's weight is the 2C x C sub-matrix [Wvp ; W']
+//   back-transform, G = d/dW', gc = d/dc:  dWq += Wk G;  dWk += Wq G^T + bq gc^T;  dbq += Wk gc;  dbk gets nothing (its true gradient is 0)
 // All of it runs on the fp32 master parameters with plain FMA loops in a fixed order: one thread (or one block) owns an output element,
 // nothing is added atomically, so the results are bit-reproducible run to run whatever EEGLDM_DETERMINISTIC says.
 #include "common.h"
@@ -84,56 +88,70 @@ __global__ __launch_bounds__(256) void fold_gemm_kernel(const FoldGemmBatch p) {
   }
 }
 
-// refresh, everything but the product: Q / K rows of the 16-bit weight copied, the effective bias.  Block (x, y): slice x of block y.
-// bv'[m] = sum_k Wp[m][k] bv[k] + bp[m]: one wave per row, lanes across k (coalesced), butterfly sum (a fixed order)
-__global__ __launch_bounds__(256) void fold_refresh_misc_kernel(const FoldMiscBatch p) {
-  const FoldMisc f = p.f[blockIdx.y];
-  const int C = p.n, t = threadIdx.x, wave = t >> 6, lane = t & 63;
-  const long nchunk = (long)2 * C * C / 8;        // 16-byte chunks of the Q and K rows
-  for (long i = (long)blockIdx.x * blockDim.x + t; i < nchunk; i += (long)gridDim.x * blockDim.x)
-    ((uint4*)f.e16)[i] = ((const uint4*)f.w16)[i];
-  for (int i = blockIdx.x * blockDim.x + t; i < 2 * C; i += gridDim.x * blockDim.x) f.be[i] = f.bqkv[i];
+// out[m] (+)= sum_k M[m][k] v[k] (+ add[m]), m < C: one wave per row, lanes across k (coalesced), butterfly sum (a fixed order)
+template <bool ACC>
+__device__ __forceinline__ void fold_matvec(const float* M, const float* v, const float* add, float* out, int C) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int m = blockIdx.x * 4 + wave; m < C; m += gridDim.x * 4) {
     float s = 0.f;
-    for (int k = lane; k < C; k += 64) s = fmaf(f.wp[(long)m * C + k], f.bqkv[2 * C + k], s);
+    for (int k = lane; k < C; k += 64) s = fmaf(M[(long)m * C + k], v[k], s);
     s = wave_sum(s);
-    if (lane == 0) f.be[2 * C + m] = s + f.bp[m];
+    if (lane == 0) { if (add) s += add[m]; out[m] = ACC ? out[m] + s : s; }
   }
 }
-
-// back-transform, everything but the two products: the Q / K rows and biases pass through, dbv += Wp^T gb_v, dbp += gb_v.
-// dbv[k] += sum_m Wp[m][k] gb_v[m]: a block takes 16 columns k, its 16 thread rows a 16th of the m range each (ascending), and thread
-// k folds the 16 partial sums in slice order
-__global__ __launch_bounds__(256) void fold_back_misc_kernel(const FoldMiscBatch p) {
-  __shared__ float part[16][17];
-  const FoldMisc f = p.f[blockIdx.y];
-  const int C = p.n, t = threadIdx.x;
-  const long n4 = (long)2 * C * C / 4;
-  for (long i = (long)blockIdx.x * blockDim.x + t; i < n4; i += (long)gridDim.x * blockDim.x) {
-    const float4 s = ((const float4*)f.g)[i];
-    float4 d = ((float4*)f.dwqkv)[i];
-    d.x += s.x; d.y += s.y; d.z += s.z; d.w += s.w;
-    ((float4*)f.dwqkv)[i] = d;
-  }
-  for (int i = blockIdx.x * blockDim.x + t; i < 3 * C; i += gridDim.x * blockDim.x) {
-    if (i < 2 * C) f.dbqkv[i] += f.gb[i];
-    else f.dbp[i - 2 * C] += f.gb[i];
-  }
-  const int sl = t >> 4, c = t & 15, per = C / 16;
+// out[k] (+)= sum_m M[m][k] v[m], k < C: a block takes 16 columns k, its 16 thread rows a 16th of the m range each (ascending), and thread
+// k folds the 16 partial sums in slice order.  256 threads, C % 16 == 0.
+template <bool ACC>
+__device__ __forceinline__ void fold_tmatvec(const float* M, const float* v, float* out, int C, float (*part)[17]) {
+  const int t = threadIdx.x, sl = t >> 4, c = t & 15, per = C / 16;
   for (int cb = blockIdx.x; cb < C / 16; cb += gridDim.x) {      // (block-uniform trip count: the barriers are safe)
     const int k = cb * 16 + c;
     float s = 0.f;
-    for (int m = sl * per; m < (sl + 1) * per; m++) s = fmaf(f.wp[(long)m * C + k], f.gb[2 * C + m], s);
+    for (int m = sl * per; m < (sl + 1) * per; m++) s = fmaf(M[(long)m * C + k], v[m], s);
     part[sl][c] = s;
     __syncthreads();
     if (t < 16) {
       float tot = 0.f;
 #pragma unroll
       for (int j = 0; j < 16; j++) tot += part[j][t];
-      f.dbqkv[2 * C + cb * 16 + t] += tot;
+      out[cb * 16 + t] = ACC ? out[cb * 16 + t] + tot : tot;
     }
     __syncthreads();
   }
+}
+
+// refresh, everything but the products: Q / K rows of the 16-bit weight copied, the effective bias.  Block (x, y): slice x of block y.
+// bv' = Wp bv + bp, c = Wk^T bq
+__global__ __launch_bounds__(256) void fold_refresh_misc_kernel(const FoldMiscBatch p) {
+  __shared__ float part[16][17];
+  const FoldMisc f = p.f[blockIdx.y];
+  const int C = p.n, t = threadIdx.x;
+  const long nchunk = (long)2 * C * C / 8;        // 16-byte chunks of the Q and K rows
+  for (long i = (long)blockIdx.x * blockDim.x + t; i < nchunk; i += (long)gridDim.x * blockDim.x)
+    ((uint4*)f.e16)[i] = ((const uint4*)f.w16)[i];
+  for (int i = blockIdx.x * blockDim.x + t; i < 2 * C; i += gridDim.x * blockDim.x) f.be[i] = f.bqkv[i];
+  fold_matvec<false>(f.wp, f.bqkv + 2 * C, f.bp, f.be + 2 * C, C);
+  fold_tmatvec<false>(f.wqkv + (long)C * C, f.bqkv, f.be + 3 * C, C, part);
+}
+
+// back-transform, everything but the products: dbv += Wp^T gb_v, dbp += gb_v; then the Q / K rows and biases pass through (qk == 0), or
+// dbq += Wk gc and nothing for the K rows, whose gradient the products carry, and for bk (qk != 0; f.qk is uniform over the block)
+__global__ __launch_bounds__(256) void fold_back_misc_kernel(const FoldMiscBatch p) {
+  __shared__ float part[16][17];
+  const FoldMisc f = p.f[blockIdx.y];
+  const int C = p.n, t = threadIdx.x;
+  if (!f.qk) {
+    const long n4 = (long)2 * C * C / 4;
+    for (long i = (long)blockIdx.x * blockDim.x + t; i < n4; i += (long)gridDim.x * blockDim.x) {
+      const float4 s = ((const float4*)f.g)[i];
+      float4 d = ((float4*)f.dwqkv)[i];
+      d.x += s.x; d.y += s.y; d.z += s.z; d.w += s.w;
+      ((float4*)f.dwqkv)[i] = d;
+    }
+    for (int i = blockIdx.x * blockDim.x + t; i < 2 * C; i += gridDim.x * blockDim.x) f.dbqkv[i] += f.gb[i];
+  } else fold_matvec<true>(f.wqkv + (long)C * C, f.gb + 3 * C, nullptr, f.dbqkv, C);
+  for (int i = blockIdx.x * blockDim.x + t; i < C; i += gridDim.x * blockDim.x) f.dbp[i] += f.gb[2 * C + i];
+  fold_tmatvec<true>(f.wp, f.gb + 2 * C, f.dbqkv + 2 * C, C, part);
 }
 
 }  // namespace

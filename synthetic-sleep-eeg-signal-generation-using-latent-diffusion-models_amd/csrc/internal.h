@@ -94,11 +94,23 @@ int op_linear_dgrad(eegldm_ctx*, int dtype, const void* dy, long lddy, const voi
                     int M, int N, int K, int out_f32);
 int op_linear_wgrad(eegldm_ctx*, int dtype, const void* x, long ldx, const void* dy, long lddy, float* dw, long lddw,
                     int M, int N, int K);
+// Attention operands as three pointers with their own leading dimensions: the packed [q | k | v] rows of a qkv projection (attn_packed), or
+// column views of different tensors (the QK-folded AttentionBlock: k is the normalised input itself).  Gradients share one leading dimension.
+struct AttnIn { const void* q; long ldq; const void* k; long ldk; const void* v; long ldv; };
+struct AttnGrad { void* dq; void* dk; void* dv; long ld; };
+static inline AttnIn attn_packed(const void* qkv, long ld, int C, int dtype) {
+  const char* q = (const char*)qkv; const size_t cb = (size_t)C * dtype_size(dtype);
+  return {q, ld, q + cb, ld, q + 2 * cb, ld};
+}
+static inline AttnGrad attn_packed_grad(void* dqkv, long ld, int C, int dtype) {
+  char* q = (char*)dqkv; const size_t cb = (size_t)C * dtype_size(dtype);
+  return {q, q + cb, q + 2 * cb, ld};
+}
 // resid (optional): out = resid + attention(..); only the fused kernel takes it (attn_chain_ok), the composition refuses
-int op_attention_fwd(eegldm_ctx*, int dtype, const void* qkv, long ldq, void* out, long ldo, void* probs, float* logits,
+int op_attention_fwd(eegldm_ctx*, int dtype, const AttnIn& in, void* out, long ldo, void* probs, float* logits,
                      int B, int T, int C, const void* resid = nullptr, long ldr = 0);
-int op_attention_bwd(eegldm_ctx*, int dtype, const void* qkv, long ldq, const void* probs, const void* dout, long lddo,
-                     void* dqkv, long lddq, float* dprobs, void* dlogits, int B, int T, int C);
+int op_attention_bwd(eegldm_ctx*, int dtype, const AttnIn& in, const void* probs, const void* dout, long lddo,
+                     const AttnGrad& g, float* dprobs, void* dlogits, int B, int T, int C);
 // GroupNorm backward with an optional fused per-sample column sum of dx (norm.hip); *colsum_done = 1 when produced
 int op_groupnorm_bwd(eegldm_ctx*, const void* x, long ldx, const float* gamma, const float* beta, const float* stats,
                      const void* dy, long lddy, void* dx, long lddx, float* dgamma, float* dbeta, int B, int L, int C, int G,
@@ -111,24 +123,28 @@ bool pre_conv3_ok(int dtype, int Cin, int Cout, int L);
 int pre_conv3_launch(eegldm_ctx*, const void* x, const double* in_stats, const float* gamma, const float* beta, const void* w,
                      const float* bias, const void* resid, void* y, double* out_stats, int B, int L, int Cin, int Cout, float eps, int dtype);
 int sample_stats_launch(eegldm_ctx*, const void* x, long n_per_sample, int B, double* stats, int dtype);
-// proj_out folded into the V projection (attn_fold.hip): small fp32 products on the master parameters, batched over the blocks of a network
-constexpr int FOLD_MAX_BATCH = 12;
+// proj_out folded into the V projection and the K projection folded into Q (attn_fold.hip): small fp32 products on the master parameters,
+// batched over the blocks of a network (a backward of six blocks on the QK route hands over 24 products: one launch)
+constexpr int FOLD_MAX_BATCH = 24;
 // C[m][n] = sum_k A(m, k) B(k, n) + u[m] v[n]; square n x n, leading dimension n.  ta: A is stored [k][m]; tb: B is stored [n][k].
 // out16 != null: the rounded result is WRITTEN there (16-bit); else it is ADDED into acc (fp32).  u / v: optional (both or neither).
 struct FoldGemm { const float* A; const float* B; const float* u; const float* v; float* acc; void* out16; int ta, tb; };
 struct FoldGemmBatch { FoldGemm g[FOLD_MAX_BATCH]; int n; };
 int fold_gemm_launch(eegldm_ctx*, const FoldGemm* probs, int nprob, int n, int dtype);
-// per block, refresh (back = 0): e16 rows [0, 2C) = w16 rows [0, 2C) (16-bit), be = [bqkv[0 .. 2C) | Wp bqkv[2C .. 3C) + bp]
-//            back-transform (back = 1): dwqkv rows [0, 2C) += g rows, dbqkv[0 .. 2C) += gb, dbqkv[2C .. 3C) += Wp^T gb[2C .. 3C), dbp += gb[2C .. 3C)
-struct FoldMisc { const void* w16; void* e16; const float* bqkv; const float* wp; const float* bp; float* be;
-                  const float* g; const float* gb; float* dwqkv; float* dbqkv; float* dbp; };
+// per block, refresh (back = 0): e16 rows [0, 2C) = w16 rows [0, 2C) (16-bit), be = [bqkv[0 .. 2C) | Wp bqkv[2C .. 3C) + bp | Wk^T bqkv[0 .. C)]
+//            back-transform (back = 1), g / gb laid out like the effective weight / bias (4C rows):
+//              dbqkv[2C .. 3C) += Wp^T gb[2C .. 3C), dbp += gb[2C .. 3C), and
+//              qk == 0: dwqkv rows [0, 2C) += g rows, dbqkv[0 .. 2C) += gb;      qk != 0: dbqkv[0 .. C) += Wk gb[3C .. 4C)
+// wqkv: the fp32 master qkv weight (its K rows are read)
+struct FoldMisc { const void* w16; void* e16; const float* wqkv; const float* bqkv; const float* wp; const float* bp; float* be;
+                  const float* g; const float* gb; float* dwqkv; float* dbqkv; float* dbp; int qk; };
 struct FoldMiscBatch { FoldMisc f[FOLD_MAX_BATCH]; int n; };
 int fold_misc_launch(eegldm_ctx*, const FoldMisc* blocks, int nblock, int C, int back);
 // fused short-sequence attention (attn.hip)
 bool attn_chain_ok(int dtype, int T, int C, long ldq, long ldo);
 // resid (optional, [B * T][ldr]): out = resid + softmax(..) v, added in fp32 ahead of the one rounding of the store
-int attn_chain_fwd(eegldm_ctx*, const void* qkv, long ldq, void* out, long ldo, void* probs, int B, int T, int C, int dtype,
+int attn_chain_fwd(eegldm_ctx*, const AttnIn& in, void* out, long ldo, void* probs, int B, int T, int C, int dtype,
                    const void* resid = nullptr, long ldr = 0);
-int attn_chain_bwd(eegldm_ctx*, const void* qkv, long ldq, const void* probs, const void* dout, long lddo, void* dq, long lddq,
+int attn_chain_bwd(eegldm_ctx*, const AttnIn& in, const void* probs, const void* dout, long lddo, const AttnGrad& g,
                    void* dS, int B, int T, int C, int fuse_kv, int dtype);
 bool attn_chain_bwd_fuses_kv(eegldm_ctx*, int B, int T);      // whole-sample blocks: the backward kernel also writes dK and dV (no TN GEMMs)

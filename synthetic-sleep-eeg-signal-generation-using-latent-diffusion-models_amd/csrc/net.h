@@ -57,11 +57,15 @@ struct AttnDesc { int c; long n_w, n_b, qkv_w, qkv_b, pr_w, pr_b; int heads = 1;
 struct RsDesc { int c = 0, up = 0, conv = 0; long w = -1, b = -1; };
 struct RsTape { View x, xu; int B, Lin, Lout; };
 struct ResTape { View x, a1, xr, h1, a2, hn; float *st1, *st2; int B, Lin, Lout; unsigned long long drop_off = 0; bool dropped = false; };
-struct AttnTape { View x, xn, qkv, o; void* probs; float* st; int B, T; int fold = -1; };      // fold >= 0: index into NetBase::folds, qkv holds V' and o is not allocated
-// proj_out folded into the V projection (attn_fold.hip): per foldable block (16-bit storage, one head, C % 256 == 0) an effective
-// qkv weight [3C][C] = [Wq ; Wk ; round(Wp Wv)] at element e_off of NetBase::wE (its data-gradient copy at the same offset of wET), an fp32
-// effective bias [bq | bk | Wp bv + bp] at b_off of bE, and an fp32 gradient scratch [3C][C] + [3C] at g_off of gE
+// fold >= 0: index into NetBase::folds, qkv holds V' and o is not allocated; qk: the block ran the QK route, qkv is 2C wide = [V' | Q'] and the
+// key operand is xn (the backward follows the forward's choice)
+struct AttnTape { View x, xn, qkv, o; void* probs; float* st; int B, T; int fold = -1; bool qk = false; };
+// proj_out folded into the V projection and K folded into Q (attn_fold.hip): per foldable block (16-bit storage, one head,
+// C % 256 == 0) an effective weight [4C][C] = [Wq ; Wk ; round(Wp Wv) ; round(Wk^T Wq)] at element e_off of NetBase::wE (its data-gradient copy at
+// the same offset of wET), an fp32 effective bias [bq | bk | Wp bv + bp | Wk^T bq] at b_off of bE, and an fp32 gradient scratch [4C][C] + [4C]
+// of the same layout at g_off of gE.  Rows [0, 3C) serve the proj_out fold alone, rows [2C, 4C) = [Wvp ; W'] are the 2C x C weight of the QK route.
 struct AttnFold { AttnDesc a; long e_off, b_off, g_off; };
+struct FoldPend { int fold; bool qk; };
 
 struct NetBase {
   eegldm_ctx* ctx = nullptr;
@@ -110,12 +114,16 @@ struct NetBase {
   // folded AttentionBlocks: the creators list their blocks in attn_list, bind() allocates, sync_weights() -- and nothing else -- refreshes wE / wET / bE.
   // A backward sends the qkv weight gradient of a folded block to its scratch (zeroed there) and lists the block in fold_pending;
   // flush_attn_folds() back-transforms everything listed into the real gradient slots (+=) once the launches that complete it are out.
-  std::vector<AttnDesc> attn_list; std::vector<AttnFold> folds; std::vector<int> fold_pending;
+  std::vector<AttnDesc> attn_list; std::vector<AttnFold> folds; std::vector<FoldPend> fold_pending;
+  // the QK route without EEGLDM_ATTN_QK_FOLD in the environment: networks built by eegldm_unet_create take it at C >= 512 (the width it was
+  // measured at), stand-alone blocks do not; EEGLDM_ATTN_QK_FOLD=1 / =0 decides for every foldable block
+  bool qk_fold_default = false;
   void* wE = nullptr; void* wET = nullptr; void* d_kbe = nullptr; int n_kbe = 0; long kbe_chunks = 0;
   float* bE = nullptr; float* gE = nullptr;
   int find_fold(const AttnDesc& a) const { for (size_t i = 0; i < folds.size(); i++) if (folds[i].a.qkv_w == a.qkv_w) return (int)i; return -1; }
   bool fold_usable() const { return !folds.empty() && (size_t)params % 16 == 0 && (size_t)grads % 16 == 0; }      // (the fold kernels move float4s)
   const void* WE(const AttnFold& f) const { return (const char*)wE + (size_t)f.e_off * 2; }
+  const void* WE_qk(const AttnFold& f) const { return (const char*)WE(f) + (size_t)2 * f.a.c * f.a.c * 2; }      // [Wvp ; W']
   int refresh_attn_folds();
   int flush_attn_folds();
 

@@ -60,13 +60,13 @@ int NetBase::bind(float* p, float* g) {
       }
     }
   }
-  // proj_out folded into the V projection (net.h AttnFold): buffers for every 16-bit single-head block the fused attention kernel can serve
+  // proj_out folded into the V projection, K folded into Q (net.h AttnFold): buffers for every 16-bit single-head block the fused attention kernel can serve
   if (dtype != EEGLDM_F32 && folds.empty()) {
     long eo = 0, bo = 0, go = 0;
     for (const AttnDesc& a : attn_list) {
       if (a.heads != 1 || a.c % 256 != 0 || a.qkv_w % 8 != 0 || a.pr_w % 8 != 0 || a.qkv_b % 4 != 0) continue;
       AttnFold f; f.a = a; f.e_off = eo; f.b_off = bo; f.g_off = go;
-      eo += (long)3 * a.c * a.c; bo += 3 * a.c; go += (long)3 * a.c * a.c + 3 * a.c;
+      eo += (long)4 * a.c * a.c; bo += 4 * a.c; go += (long)4 * a.c * a.c + 4 * a.c;
       folds.push_back(f);
     }
     if (!folds.empty()) {
@@ -76,14 +76,18 @@ int NetBase::bind(float* p, float* g) {
       if (!no_kblk) {      // the data gradient of the qkv conv finds its [Cout / 32][Cin][32] copy under the effective weight's address, like qkv.weight's under W()
         std::vector<KbDesc> tab; long chunks = 0;
         for (const AttnFold& f : folds) {
-          KbDesc d; d.off = f.e_off; d.chunk0 = chunks; d.cout = 3 * f.a.c; d.cin = f.a.c;
-          chunks += (long)3 * f.a.c * f.a.c / 8; tab.push_back(d);
+          KbDesc d; d.off = f.e_off; d.chunk0 = chunks; d.cout = 4 * f.a.c; d.cin = f.a.c;
+          chunks += (long)4 * f.a.c * f.a.c / 8; tab.push_back(d);
         }
         HIP_TRY(hipMalloc(&wET, (size_t)eo * 2));
         HIP_TRY(hipMalloc(&d_kbe, tab.size() * sizeof(KbDesc)));
         HIP_TRY(hipMemcpy(d_kbe, tab.data(), tab.size() * sizeof(KbDesc), hipMemcpyHostToDevice));
         n_kbe = (int)tab.size(); kbe_chunks = chunks;
-        for (const AttnFold& f : folds) ctx->kblk_t[WE(f)] = (const char*)wET + (size_t)f.e_off * 2;
+        // (rows [2C, 4C) of the [Cout / 32][Cin][32] copy are its second half: the QK route's sub-matrix finds its own copy there)
+        for (const AttnFold& f : folds) {
+          ctx->kblk_t[WE(f)] = (const char*)wET + (size_t)f.e_off * 2;
+          ctx->kblk_t[WE_qk(f)] = (const char*)wET + ((size_t)f.e_off + (size_t)2 * f.a.c * f.a.c) * 2;
+        }
       }
     }
   }
@@ -103,7 +107,9 @@ int NetBase::refresh_attn_folds() {
       char* e = (char*)wE + (size_t)f.e_off * 2;
       FoldGemm g = {}; g.A = P(a.pr_w); g.B = P(a.qkv_w) + (long)2 * C * C; g.out16 = e + (size_t)2 * C * C * 2;      // Wvp = Wp Wv
       gs.push_back(g);
-      FoldMisc m = {}; m.w16 = W(a.qkv_w); m.e16 = e; m.bqkv = P(a.qkv_b); m.wp = P(a.pr_w); m.bp = P(a.pr_b); m.be = bE + f.b_off;
+      FoldGemm gq = {}; gq.A = P(a.qkv_w) + (long)C * C; gq.ta = 1; gq.B = P(a.qkv_w); gq.out16 = e + (size_t)3 * C * C * 2;      // W' = Wk^T Wq
+      gs.push_back(gq);
+      FoldMisc m = {}; m.w16 = W(a.qkv_w); m.e16 = e; m.wqkv = P(a.qkv_w); m.bqkv = P(a.qkv_b); m.wp = P(a.pr_w); m.bp = P(a.pr_b); m.be = bE + f.b_off;
       ms.push_back(m);
     }
     EEG_TRY(fold_misc_launch(ctx, ms.data(), (int)ms.size(), C, 0));
@@ -114,22 +120,30 @@ int NetBase::refresh_attn_folds() {
 // gradients with respect to the effective weights (scratch) -> the real slots, added: one batched launch pair per channel count, fixed
 // summation order and no atomics (bit-reproducible).  Runs behind the launches that complete the scratch and ahead of the gradient hook.
 int NetBase::flush_attn_folds() {
-  std::vector<int> pend; pend.swap(fold_pending);
+  std::vector<FoldPend> pend; pend.swap(fold_pending);
   std::vector<char> done(pend.size(), 0);
   for (size_t i = 0; i < pend.size(); i++) {
     if (done[i]) continue;
-    const int C = folds[pend[i]].a.c;
+    const int C = folds[pend[i].fold].a.c;
     std::vector<FoldGemm> gs; std::vector<FoldMisc> ms;
     for (size_t j = i; j < pend.size(); j++) {
-      if (done[j] || folds[pend[j]].a.c != C) continue;
+      if (done[j] || folds[pend[j].fold].a.c != C) continue;
       done[j] = 1;
-      const AttnFold& f = folds[pend[j]]; const AttnDesc& a = f.a;
-      const float* gw = gE + f.g_off; const float* gb = gw + (long)3 * C * C; const float* gv = gw + (long)2 * C * C;
+      const AttnFold& f = folds[pend[j].fold]; const AttnDesc& a = f.a;
+      const float* gw = gE + f.g_off; const float* gb = gw + (long)4 * C * C; const float* gv = gw + (long)2 * C * C;
       FoldGemm g1 = {}; g1.A = P(a.pr_w); g1.ta = 1; g1.B = gv; g1.acc = G(a.qkv_w) + (long)2 * C * C;                    // dWv += Wp^T dWvp
       FoldGemm g2 = {}; g2.A = gv; g2.B = P(a.qkv_w) + (long)2 * C * C; g2.tb = 1; g2.u = gb + 2 * C; g2.v = P(a.qkv_b) + 2 * C;
       g2.acc = G(a.pr_w);                                                                                                 // dWp += dWvp Wv^T + dbv' bv^T
       gs.push_back(g1); gs.push_back(g2);
-      FoldMisc m = {}; m.wp = P(a.pr_w); m.g = gw; m.gb = gb; m.dwqkv = G(a.qkv_w); m.dbqkv = G(a.qkv_b); m.dbp = G(a.pr_b);
+      if (pend[j].qk) {
+        const float* gq = gw + (long)3 * C * C;      // G = d/dW', gc = gb + 3C
+        FoldGemm g3 = {}; g3.A = P(a.qkv_w) + (long)C * C; g3.B = gq; g3.acc = G(a.qkv_w);                                  // dWq += Wk G
+        FoldGemm g4 = {}; g4.A = P(a.qkv_w); g4.B = gq; g4.tb = 1; g4.u = P(a.qkv_b); g4.v = gb + 3 * C;
+        g4.acc = G(a.qkv_w) + (long)C * C;                                                                                  // dWk += Wq G^T + bq gc^T
+        gs.push_back(g3); gs.push_back(g4);
+      }
+      FoldMisc m = {}; m.wqkv = P(a.qkv_w); m.wp = P(a.pr_w); m.g = gw; m.gb = gb; m.dwqkv = G(a.qkv_w); m.dbqkv = G(a.qkv_b); m.dbp = G(a.pr_b);
+      m.qk = pend[j].qk ? 1 : 0;
       ms.push_back(m);
     }
     EEG_TRY(fold_misc_launch(ctx, ms.data(), (int)ms.size(), C, 1));
@@ -162,7 +176,7 @@ void NetBase::release_kblk() {      // the two copies are independent: a model m
     (void)hipFree(wKT); (void)hipFree(d_kbt); wKT = nullptr; d_kbt = nullptr; n_kbt = 0;
   }
   if (wE) {      // the effective qkv weights of the folded AttentionBlocks and their data-gradient copies
-    if (wET) for (const AttnFold& f : folds) ctx->kblk_t.erase(WE(f));
+    if (wET) for (const AttnFold& f : folds) { ctx->kblk_t.erase(WE(f)); ctx->kblk_t.erase(WE_qk(f)); }
     (void)hipFree(wE); (void)hipFree(bE); (void)hipFree(gE); wE = nullptr; bE = nullptr; gE = nullptr;
     if (wET) { (void)hipFree(wET); (void)hipFree(d_kbe); wET = nullptr; d_kbe = nullptr; n_kbe = 0; }
     folds.clear(); fold_pending.clear();
@@ -398,7 +412,19 @@ int attn_forward(NetBase* u, const AttnDesc& a, const View& x, int B, int T, con
   AttnTape t; t.x = x; t.B = B; t.T = T;
   ALLOC_OR_FAIL(t.st, (float*)u->arena.alloc(sizeof(float) * 2 * B * AG));
   ALLOC_OR_FAIL(t.xn.p, u->alloc_act((long)B * T, C)); t.xn.ld = C;
-  ALLOC_OR_FAIL(t.qkv.p, u->alloc_act((long)B * T, 3 * C)); t.qkv.ld = 3 * C;
+  // proj_out folded into the V projection (net.h AttnFold): the qkv conv takes the effective weight and bias, the attention kernel writes
+  // out = x + P V' and there is no proj_out launch.  Training and the normal eval forward only: the few-row eval route keeps its own fusion,
+  // and a shape the fused attention kernel does not serve keeps the composition (whose last GEMM has no batched residual operand).
+  EEG_ENV_VAR(bool, no_fold, getenv("EEGLDM_NO_ATTN_FOLD") != nullptr);
+  if (!no_fold && !u->eval_fuse && a.heads == 1 && u->fold_usable() && attn_chain_ok(dt, T, C, 3 * C, out.ld) &&
+      x.ld % 4 == 0 && (size_t)x.p % 8 == 0 && (size_t)out.p % 8 == 0)
+    t.fold = u->find_fold(a);
+  const AttnFold* f = t.fold >= 0 ? &u->folds[t.fold] : nullptr;
+  // K folded into Q on top of that: the conv is 2C wide, [V' | Q'] from [Wvp ; W'], and the key operand is xn itself
+  EEG_ENV_VAR(int, qk_env, getenv("EEGLDM_ATTN_QK_FOLD") ? (atoi(getenv("EEGLDM_ATTN_QK_FOLD")) != 0 ? 1 : 0) : -1);
+  t.qk = f && (qk_env >= 0 ? qk_env == 1 : (u->qk_fold_default && C >= 512));
+  const int QW = t.qk ? 2 * C : 3 * C;      // width of the tape's qkv tensor
+  ALLOC_OR_FAIL(t.qkv.p, u->alloc_act((long)B * T, QW)); t.qkv.ld = QW;
   // eval, few rows: the preceding ResBlock's conv2 left this tensor's statistics; the qkv projection normalises on load (NetBase::eval_fuse)
   const NetBase::PartReg* in_part = u->eval_fuse ? u->find_part(x.p) : nullptr;
   int rcq = 0;
@@ -408,22 +434,17 @@ int attn_forward(NetBase* u, const AttnDesc& a, const View& x, int B, int T, con
     if (rcq < 0) return rcq;
     if (rcq == 1) u->fused_used = true;
   }
-  // proj_out folded into the V projection (net.h AttnFold): the qkv conv takes the effective weight and bias, the attention kernel writes
-  // out = x + P V' and there is no proj_out launch.  Training and the normal eval forward only: the few-row eval route keeps its own fusion,
-  // and a shape the fused attention kernel does not serve keeps the composition (whose last GEMM has no batched residual operand).
-  EEG_ENV_VAR(bool, no_fold, getenv("EEGLDM_NO_ATTN_FOLD") != nullptr);
-  if (!no_fold && !u->eval_fuse && a.heads == 1 && u->fold_usable() && attn_chain_ok(dt, T, C, 3 * C, out.ld) &&
-      x.ld % 4 == 0 && (size_t)x.p % 8 == 0 && (size_t)out.p % 8 == 0)
-    t.fold = u->find_fold(a);
-  const AttnFold* f = t.fold >= 0 ? &u->folds[t.fold] : nullptr;
   if (rcq != 1) {
     EEG_TRY(eegldm_groupnorm_fwd(ctx, x.p, x.ld, u->P(a.n_w), u->P(a.n_b), t.xn.p, C, t.st, B, T, C, AG, GN_EPS, 0, 0, nullptr, 0, dt));
-    EEG_TRY(op_conv_fwd(ctx, dt, t.xn.p, C, f ? u->WE(*f) : u->W(a.qkv_w), f ? u->bE + f->b_off : u->P(a.qkv_b), t.qkv.p, 3 * C, B, T, C, 3 * C, 1, 1, 0, 0,
-                        nullptr, 0, nullptr, 0));
+    const void* w = t.qk ? u->WE_qk(*f) : (f ? u->WE(*f) : u->W(a.qkv_w));
+    const float* b = f ? u->bE + f->b_off + (t.qk ? 2 * C : 0) : u->P(a.qkv_b);
+    EEG_TRY(op_conv_fwd(ctx, dt, t.xn.p, C, w, b, t.qkv.p, QW, B, T, C, QW, 1, 1, 0, 0, nullptr, 0, nullptr, 0));
   }
   if (f) {      // out = x + P V': no `o`, no projection (the fused kernel needs no logits scratch)
     ALLOC_OR_FAIL(t.probs, u->alloc_act((long)B * T, T));
-    EEG_TRY(op_attention_fwd(ctx, dt, t.qkv.p, 3 * C, out.p, out.ld, t.probs, nullptr, B, T, C, x.p, x.ld));
+    const size_t cb = (size_t)C * dtype_size(dt);
+    const AttnIn in = t.qk ? AttnIn{(const char*)t.qkv.p + cb, QW, t.xn.p, C, t.qkv.p, QW} : attn_packed(t.qkv.p, QW, C, dt);
+    EEG_TRY(op_attention_fwd(ctx, dt, in, out.p, out.ld, t.probs, nullptr, B, T, C, x.p, x.ld));
     u->at.push_back(t);
     return 0;
   }
@@ -435,7 +456,7 @@ int attn_forward(NetBase* u, const AttnDesc& a, const View& x, int B, int T, con
   Arena::Mark mk = u->arena.mark();
   float* logits; ALLOC_OR_FAIL(logits, (float*)u->arena.alloc(sizeof(float) * (size_t)B * T * T));
   for (int h = 0; h < H; h++)
-    EEG_TRY(op_attention_fwd(ctx, dt, (const char*)t.qkv.p + (size_t)h * 3 * ch * es, 3 * C, (char*)t.o.p + (size_t)h * ch * es, C,
+    EEG_TRY(op_attention_fwd(ctx, dt, attn_packed((const char*)t.qkv.p + (size_t)h * 3 * ch * es, 3 * C, ch, dt), (char*)t.o.p + (size_t)h * ch * es, C,
                              (char*)t.probs + (size_t)h * B * T * T * es, logits, B, T, ch));
   u->arena.release(mk);
   // eval, few rows: the projection leaves the statistics of the block output for the next ResBlock's first GroupNorm
@@ -476,20 +497,30 @@ int attn_backward(NetBase* u, const AttnDesc& a, const AttnTape& t, const View& 
   void* dlogits; ALLOC_OR_FAIL(dlogits, u->alloc_act((long)B * T, T));
   {
     const int H = a.heads, ch = C / H; const size_t es = dtype_size(dt);
-    for (int h = 0; h < H; h++)
-      EEG_TRY(op_attention_bwd(ctx, dt, (const char*)t.qkv.p + (size_t)h * 3 * ch * es, 3 * C, (const char*)t.probs + (size_t)h * B * T * T * es,
-                               (const char*)d_o.p + (size_t)h * ch * es, d_o.ld, (char*)dqkv + (size_t)h * 3 * ch * es, 3 * C, dprobs, dlogits, B, T, ch));
+    // QK route: the scratch is [dV' | dQ' | dK'], so that [dV' | dQ'] is the 2C-wide gradient of the conv's output and dK' a gradient of xn
+    if (t.qk) {
+      const AttnIn in = {(const char*)t.qkv.p + C * es, 2 * C, t.xn.p, C, t.qkv.p, 2 * C};
+      const AttnGrad gr = {(char*)dqkv + C * es, (char*)dqkv + 2 * C * es, dqkv, 3 * C};
+      EEG_TRY(op_attention_bwd(ctx, dt, in, t.probs, d_o.p, d_o.ld, gr, dprobs, dlogits, B, T, C));
+    } else for (int h = 0; h < H; h++)
+      EEG_TRY(op_attention_bwd(ctx, dt, attn_packed((const char*)t.qkv.p + (size_t)h * 3 * ch * es, 3 * C, ch, dt), (const char*)t.probs + (size_t)h * B * T * T * es,
+                               (const char*)d_o.p + (size_t)h * ch * es, d_o.ld, attn_packed_grad((char*)dqkv + (size_t)h * 3 * ch * es, 3 * C, ch, dt),
+                               dprobs, dlogits, B, T, ch));
   }
+  const int NW = t.qk ? 2 * C : 3 * C;      // output channels of the qkv conv the forward ran
   if (!f) EEG_TRY(op_conv_wgrad(ctx, dt, t.xn.p, C, dqkv, 3 * C, u->G(a.qkv_w), u->G(a.qkv_b), B, T, C, 3 * C, 1, 1, 0, 0));
   else if (u->param_grads) {
-    float* gw = u->gE + f->g_off;
-    HIP_TRY(hipMemsetAsync(gw, 0, sizeof(float) * ((size_t)3 * C * C + 3 * C), ctx->stream));
-    EEG_TRY(op_conv_wgrad(ctx, dt, t.xn.p, C, dqkv, 3 * C, gw, gw + (long)3 * C * C, B, T, C, 3 * C, 1, 1, 0, 0));
-    u->fold_pending.push_back(t.fold);
+    // scratch laid out like the effective weight and bias, [4C][C] + [4C]: rows and bias entries [0, 3C), or [2C, 4C) on the QK route
+    float* gw = u->gE + f->g_off; float* gb = gw + (long)4 * C * C;
+    const long r0 = t.qk ? 2 * C : 0;
+    HIP_TRY(hipMemsetAsync(gw + r0 * C, 0, sizeof(float) * ((size_t)(4 * C - r0) * C + 4 * C), ctx->stream));
+    EEG_TRY(op_conv_wgrad(ctx, dt, t.xn.p, C, dqkv, 3 * C, gw + r0 * C, gb + r0, B, T, C, NW, 1, 1, 0, 0));
+    u->fold_pending.push_back({t.fold, t.qk});
     if (!ctx->defer_wgrad) EEG_TRY(u->flush_attn_folds());
   }
   void* dxn; ALLOC_OR_FAIL(dxn, u->alloc_act((long)B * T, C));
-  EEG_TRY(op_conv_dgrad(ctx, dt, dqkv, 3 * C, f ? u->WE(*f) : u->W(a.qkv_w), dxn, C, B, T, C, 3 * C, 1, 1, 0, 0, nullptr, 0));
+  const void* wd = t.qk ? u->WE_qk(*f) : (f ? u->WE(*f) : u->W(a.qkv_w));
+  EEG_TRY(op_conv_dgrad(ctx, dt, dqkv, 3 * C, wd, dxn, C, B, T, C, NW, 1, 1, 0, 0, t.qk ? (const char*)dqkv + (size_t)2 * C * dtype_size(dt) : nullptr, 3 * C));
   // (dgamma / dbeta slot fold: batched with all the others in the grouped mode, else right here)
   int gn_deferred = 0;
   EEG_TRY(op_groupnorm_bwd(ctx, t.x.p, t.x.ld, u->P(a.n_w), u->P(a.n_b), t.st, dxn, C, dx.p, dx.ld, u->G(a.n_w), u->G(a.n_b),

@@ -272,34 +272,32 @@ int op_linear_wgrad(eegldm_ctx* ctx, int dtype, const void* x, long ldx, const v
 }
 
 // ------------------------------------------------------------------ attention (unet.py:107-125)
-int op_attention_fwd(eegldm_ctx* ctx, int dtype, const void* qkv, long ldq, void* out, long ldo, void* probs, float* logits,
+int op_attention_fwd(eegldm_ctx* ctx, int dtype, const AttnIn& in, void* out, long ldo, void* probs, float* logits,
                      int B, int T, int C, const void* resid, long ldr) {
-  if (attn_chain_ok(dtype, T, C, ldq, ldo)) return attn_chain_fwd(ctx, qkv, ldq, out, ldo, probs, B, T, C, dtype, resid, ldr);
+  const void* q = in.q; const void* k = in.k; const void* v = in.v; const long ldq = in.ldq, ldk = in.ldk, ldv = in.ldv;
+  if (attn_chain_ok(dtype, T, C, ldq, ldo) && ldk % 8 == 0 && ldv % 8 == 0) return attn_chain_fwd(ctx, in, out, ldo, probs, B, T, C, dtype, resid, ldr);
   EEG_CHECK(!resid, "the residual operand of the attention output needs the fused kernel");
-  const size_t es = dtype_size(dtype);
-  const char* q = (const char*)qkv; const char* k = q + (size_t)C * es; const char* v = q + (size_t)2 * C * es;
   GemmArgs a = {};
-  a.dtype = dtype; a.amode = GA_PLAIN; a.bmode = GB_NT; a.A = q; a.lda = ldq; a.sAb = (long)T * ldq; a.B = k; a.ldb = ldq;
-  a.sBb = (long)T * ldq; a.C = logits; a.ldc = T; a.sCb = (long)T * T; a.M = T; a.N = T; a.K = C; a.batch = B; a.taps = 1;
+  a.dtype = dtype; a.amode = GA_PLAIN; a.bmode = GB_NT; a.A = q; a.lda = ldq; a.sAb = (long)T * ldq; a.B = k; a.ldb = ldk;
+  a.sBb = (long)T * ldk; a.C = logits; a.ldc = T; a.sCb = (long)T * T; a.M = T; a.N = T; a.K = C; a.batch = B; a.taps = 1;
   a.alpha = 1.0f / sqrtf((float)C);   // (q*s)(k*s), s = C^-1/4
   a.out_f32 = 1;
   EEG_TRY(gemm_launch(ctx, a));
   EEG_TRY(ew_softmax(ctx, logits, probs, (long)B * T, T, dtype));
   GemmArgs b = {};
-  b.dtype = dtype; b.amode = GA_PLAIN; b.bmode = GB_TR; b.A = probs; b.lda = T; b.sAb = (long)T * T; b.B = v; b.ldb = ldq;
-  b.sBb = (long)T * ldq; b.C = out; b.ldc = ldo; b.sCb = (long)T * ldo; b.M = T; b.N = C; b.K = T; b.batch = B; b.taps = 1;
+  b.dtype = dtype; b.amode = GA_PLAIN; b.bmode = GB_TR; b.A = probs; b.lda = T; b.sAb = (long)T * T; b.B = v; b.ldb = ldv;
+  b.sBb = (long)T * ldv; b.C = out; b.ldc = ldo; b.sCb = (long)T * ldo; b.M = T; b.N = C; b.K = T; b.batch = B; b.taps = 1;
   b.alpha = 1.0f;
   return gemm_launch(ctx, b);
 }
 
-int op_attention_bwd(eegldm_ctx* ctx, int dtype, const void* qkv, long ldq, const void* probs, const void* dout, long lddo,
-                     void* dqkv, long lddq, float* dprobs, void* dlogits, int B, int T, int C) {
-  const size_t es = dtype_size(dtype);
-  const char* q = (const char*)qkv; const char* k = q + (size_t)C * es; const char* v = q + (size_t)2 * C * es;
-  char* dq = (char*)dqkv; char* dk = dq + (size_t)C * es; char* dv = dq + (size_t)2 * C * es;
+int op_attention_bwd(eegldm_ctx* ctx, int dtype, const AttnIn& in, const void* probs, const void* dout, long lddo,
+                     const AttnGrad& gr, float* dprobs, void* dlogits, int B, int T, int C) {
+  const void* q = in.q; const void* k = in.k; const void* v = in.v; const long ldq = in.ldq, ldk = in.ldk, ldv = in.ldv;
+  void* dq = gr.dq; void* dk = gr.dk; void* dv = gr.dv; const long lddq = gr.ld;
   const float alpha = 1.0f / sqrtf((float)C);
   GemmArgs g = {};
-  const bool fused = attn_chain_ok(dtype, T, C, ldq, lddo) && lddq % 8 == 0;
+  const bool fused = attn_chain_ok(dtype, T, C, ldq, lddo) && ldk % 8 == 0 && ldv % 8 == 0 && lddq % 8 == 0;
   // whole-sample blocks: the fused backward kernel also produces dK and (round 5) dV -- no batched TN GEMMs with K = T = 192 (three K
   // stages per tile: 220-260 TF/s, 43 us per launch x 6)
   EEG_ENV_VAR(bool, no_fused_v, getenv("EEGLDM_ATTN_NO_FUSED_DV") != nullptr);
@@ -314,20 +312,20 @@ int op_attention_bwd(eegldm_ctx* ctx, int dtype, const void* qkv, long ldq, cons
     // dP = dO V^T, dS = alpha P o (dP - rowsum(dP o P)), dQ = dS K in one launch; whole-sample blocks also produce dK = dS^T Q (a second
     // pass over the score tile in LDS, read transposed: no batched TN GEMM with K = T = 192 -- three K stages per tile, 260 TF/s -- and
     // no re-read of dS); otherwise dK below from the written dS
-    EEG_TRY(attn_chain_bwd(ctx, qkv, ldq, probs, dout, lddo, dq, lddq, dlogits, B, T, C, fk, dtype));
+    EEG_TRY(attn_chain_bwd(ctx, in, probs, dout, lddo, gr, dlogits, B, T, C, fk, dtype));
     if (fk) return 0;
   } else {
   // dP[t][s] = sum_c dO[t][c] V[s][c]
   g = GemmArgs{};
-  g.dtype = dtype; g.amode = GA_PLAIN; g.bmode = GB_NT; g.A = dout; g.lda = lddo; g.sAb = (long)T * lddo; g.B = v; g.ldb = ldq;
-  g.sBb = (long)T * ldq; g.C = dprobs; g.ldc = T; g.sCb = (long)T * T; g.M = T; g.N = T; g.K = C; g.batch = B; g.taps = 1; g.alpha = 1.f;
+  g.dtype = dtype; g.amode = GA_PLAIN; g.bmode = GB_NT; g.A = dout; g.lda = lddo; g.sAb = (long)T * lddo; g.B = v; g.ldb = ldv;
+  g.sBb = (long)T * ldv; g.C = dprobs; g.ldc = T; g.sCb = (long)T * T; g.M = T; g.N = T; g.K = C; g.batch = B; g.taps = 1; g.alpha = 1.f;
   g.out_f32 = 1;
   EEG_TRY(gemm_launch(ctx, g));
   EEG_TRY(ew_softmax_bwd(ctx, dprobs, probs, dlogits, (long)B * T, T, alpha, dtype));
   // dQ[t][c] = sum_s dS[t][s] K[s][c]
   g = GemmArgs{};
-  g.dtype = dtype; g.amode = GA_PLAIN; g.bmode = GB_TR; g.A = dlogits; g.lda = T; g.sAb = (long)T * T; g.B = k; g.ldb = ldq;
-  g.sBb = (long)T * ldq; g.C = dq; g.ldc = lddq; g.sCb = (long)T * lddq; g.M = T; g.N = C; g.K = T; g.batch = B; g.taps = 1; g.alpha = 1.f;
+  g.dtype = dtype; g.amode = GA_PLAIN; g.bmode = GB_TR; g.A = dlogits; g.lda = T; g.sAb = (long)T * T; g.B = k; g.ldb = ldk;
+  g.sBb = (long)T * ldk; g.C = dq; g.ldc = lddq; g.sCb = (long)T * lddq; g.M = T; g.N = C; g.K = T; g.batch = B; g.taps = 1; g.alpha = 1.f;
   EEG_TRY(gemm_launch(ctx, g));
   }
   // dK[s][c] = sum_t dS[t][s] Q[t][c]
@@ -459,10 +457,11 @@ extern "C" int eegldm_linear_bwd(eegldm_ctx* ctx, const void* x, long ldx, const
 extern "C" int eegldm_attention_fwd(eegldm_ctx* ctx, const void* qkv, long ldqkv, void* out, long ldo, void* probs, float* scratch_logits,
                                     int B, int T, int C, int dtype) {
   EEG_CHECK(ctx && qkv && out && probs && scratch_logits, "null pointer");
-  return op_attention_fwd(ctx, dtype, qkv, ldqkv, out, ldo, probs, scratch_logits, B, T, C);
+  return op_attention_fwd(ctx, dtype, attn_packed(qkv, ldqkv, C, dtype), out, ldo, probs, scratch_logits, B, T, C);
 }
 extern "C" int eegldm_attention_bwd(eegldm_ctx* ctx, const void* qkv, long ldqkv, const void* probs, const void* dout, long lddo,
                                     void* dqkv, long lddqkv, float* scratch_dprobs, void* scratch_dlogits, int B, int T, int C, int dtype) {
   EEG_CHECK(ctx && qkv && probs && dout && dqkv && scratch_dprobs && scratch_dlogits, "null pointer");
-  return op_attention_bwd(ctx, dtype, qkv, ldqkv, probs, dout, lddo, dqkv, lddqkv, scratch_dprobs, scratch_dlogits, B, T, C);
+  return op_attention_bwd(ctx, dtype, attn_packed(qkv, ldqkv, C, dtype), probs, dout, lddo, attn_packed_grad(dqkv, lddqkv, C, dtype),
+                          scratch_dprobs, scratch_dlogits, B, T, C);
 }

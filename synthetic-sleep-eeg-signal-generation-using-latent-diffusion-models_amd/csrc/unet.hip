@@ -253,6 +253,7 @@ static int unet_create(eegldm_ctx* ctx, const eegldm_unet_cfg* cfg, int num_clas
   EEG_CHECK(cfg->dtype == EEGLDM_F32 || cfg->dtype == EEGLDM_BF16 || cfg->dtype == EEGLDM_F16, "bad dtype");
   eegldm_unet* u = new eegldm_unet();
   u->ctx = ctx; u->cfg = *cfg; u->dtype = cfg->dtype; u->num_classes = num_classes; u->context_channels = context_channels;
+  u->qk_fold_default = true;      // single-head AttentionBlocks fold K into Q (net.h AttnFold)
   int rc = build_plan(u);
   if (rc) { delete u; return rc; }
   *out = u;
