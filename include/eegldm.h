@@ -1021,6 +1021,41 @@ int eegldm_fir_same(eegldm_ctx*, const float* x, long ldx, const float* taps, in
 int eegldm_threshold_events(eegldm_ctx*, const float* s, long lds_, const float* aux, long ldaux, const float* thr, long B, int L,
                             int min_len, int max_len, int merge_gap, int drop_edge, int max_events, int* counts, int* ev_i, float* ev_f);
 
+/* ---- time-frequency primitives (spectrograms, band courses and phase-amplitude coupling of eegldm.metrics; csrc/tfr.hip).  Additive, ABI 8.
+ * eegldm_stft_num_frames (host only): frames of a row of L samples.  centre 0: frame f covers [f hop, f hop + n_win), F = L >= n_win ?
+ * (L - n_win) / hop + 1 : 0.  centre 1: with h = n_win / 2 frame f covers [f hop - h, f hop - h + n_win), F = (L - 1) / hop + 1 (0 for L == 0).
+ * Returns -1 for L < 0, n_win < 1, hop < 1 or centre outside {0, 1}.
+ * eegldm_stft_power: short-time multitaper power of B rows of L fp32 samples (row stride ldx >= L floats).  n_fft in {64, 128, ..., 4096},
+ * 1 <= n_win <= n_fft (the frame is zero-padded behind its n_win samples), hop >= 1, K in 1..8; tapers is a DEVICE array [K][n_win], w2_host [K]
+ * the squared taper weights (finite, >= 0).  With centre 1 samples outside [0, L) are zeros (edge 0) or the whole-sample reflection of
+ * eegldm_fir_same (edge 1: xe[-i] = x[i], xe[L-1+i] = x[L-1-i]; needs h <= L - 1); with centre 0 edge is ignored.
+ *   v_t[n] = taper_t[n] (xe[s_f + n] - m), m the fp32 mean of the frame's n_win extended samples (detrend 1) or 0 (detrend 0);
+ *   X_t[k] = sum_n v_t[n] e^{-2 pi i k n / n_fft};   P[b][f][k] = scale c_k sum_t w2[t] |X_t[k]|^2,
+ *   c_k = 2 when onesided and 0 < k < n_fft / 2, else 1.  All physical normalisation is the host's (scale).
+ * Outputs, both optional but not both NULL, contiguous fp32: power [B][F][k1 - k0], the bins 0 <= k0 < k1 <= n_fft / 2 + 1 (ignored when
+ * power is NULL); bands [B][F][NB], NB in 1..16 host bin ranges bands_host [NB][2] = [lo, hi) with 0 <= lo < hi <= n_fft / 2 + 1, independent
+ * of k0 / k1: the fp32 sum of P[b][f][k] over the range in ascending k from +0, of the same fp32 values a full call stores.  A bands-only
+ * call never writes the spectrogram and equals the fold of a full call bit for bit.
+ * Every sequence is transformed on its own (radix-2 in LDS, roots of unity by sincospif): a frame's bits depend only on its own n_win
+ * samples, the tapers, the weights and scale; not on B, F, the frame index, the row, the other frames of its workgroup or the launch
+ * geometry.  A non-finite sample makes non-finite exactly the frames whose support [s_f, s_f + n_win) holds it (reflected copies included,
+ * also under a zero taper value).  No atomics, no memset, one writer per element: a result repeats bit for bit.  x, tapers, power, bands
+ * need 4-byte alignment only.  F == 0 or B == 0 is a successful no-op; every refusal is made before the device is touched and leaves both
+ * outputs untouched. */
+long eegldm_stft_num_frames(long L, int n_win, int hop, int centre);
+int eegldm_stft_power(eegldm_ctx*, const float* x, long ldx, long B, long L, const float* tapers, const float* w2_host, int K, int n_win,
+                      int n_fft, int hop, int centre, int edge /* 0 zeros, 1 reflect */, int detrend, int onesided, float scale, int k0, int k1,
+                      float* power, const int* bands_host, int NB, float* bands);
+/* eegldm_pac_intervals: phase-amplitude sums over intervals.  pr, pi, amp are fp32 rows (B, L) with their own strides (>= L); iv is a DEVICE
+ * int32 [NI][3] of (row, start, length), or NULL with NI == B for one interval per whole row.  out is a DEVICE double [NI][4] =
+ * (n, sum a, sum a pr / h, sum a pi / h), h = sqrt(pr^2 + pi^2), every term in float64 from the fp32 inputs.  A sample takes part iff a, pr, pi
+ * are finite and h > 0; n counts those.  An interval with a row outside [0, B), start < 0, length < 1 or start + length > L is no fault: it
+ * writes (-1, 0, 0, 0).  One wave per interval: a lane's chain runs over samples start + lane, + 64, ... in ascending order from +0, a fixed
+ * xor butterfly (offsets 32 .. 1) follows: an interval's bits do not depend on NI or on the other intervals.  out needs 8-byte alignment,
+ * everything else 4.  The mean vector length hypot(c, s) / sum a and the preferred phase atan2(s, c) are host float64 algebra on out. */
+int eegldm_pac_intervals(eegldm_ctx*, const float* pr, long ldr, const float* pi, long ldi, const float* amp, long lda, long B, long L,
+                         const int* iv, long NI, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -238,6 +238,9 @@ SIGNATURES = {
     "eegldm_kernel_matmul": [_vp, _vp, _l, _vp, _vp, _l, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _f, _f, C.POINTER(_f), _i, _l, _i, _vp, _l],
     "eegldm_fir_same": [_vp, _vp, _l, _vp, _i, _vp, _l, _l, _i, _i, _i],
     "eegldm_threshold_events": [_vp, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "eegldm_stft_num_frames": [_l, _i, _i, _i],
+    "eegldm_stft_power": [_vp, _vp, _l, _l, _l, _vp, C.POINTER(_f), _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp, C.POINTER(_i), _i, _vp],
+    "eegldm_pac_intervals": [_vp, _vp, _l, _vp, _l, _vp, _l, _l, _l, _vp, _l, _vp],
     "eegldm_resblock_create": [_vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)],
     "eegldm_attnblock_create": [_vp, _i, _i, _i, C.POINTER(_vp)],
     "eegldm_block_destroy": [_vp],
@@ -250,7 +253,8 @@ SIGNATURES = {
     "eegldm_timestep_embedding": [_vp, _vp, _vp, _i, _i],
     "eegldm_conv1d_fwd_gn": [_vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _l, _i, _i, _i, _i, _vp, _l, _vp, _l, _i],
 }
-for _n in ("eegldm_block_num_params", "eegldm_aekl_num_params", "eegldm_disc_num_params", "eegldm_disc_num_buffers", "eegldm_usleep_num_params", "eegldm_usleep_num_buffers", "eegldm_usleep_last_launches"):
+for _n in ("eegldm_block_num_params", "eegldm_aekl_num_params", "eegldm_disc_num_params", "eegldm_disc_num_buffers", "eegldm_usleep_num_params", "eegldm_usleep_num_buffers", "eegldm_usleep_last_launches",
+           "eegldm_stft_num_frames"):
     if hasattr(lib, _n):
         getattr(lib, _n).restype = C.c_long
 

@@ -8,6 +8,8 @@ evaluation code uses:
   (multitaper, DPSS half-bandwidth 4, low-bias tapers, normalization "length").  The DPSS tapers (a few KB, once per window
   length) come from scipy on the host; everything per window runs in libeegldm (eegldm_psd_multitaper).
 * `band_powers`: integrates a PSD over the classical sleep-EEG bands.
+* `stft_power`, `spectrogram`, `band_course_stats`, `spindle_so_coupling`: how the spectrum moves in time, and phase-amplitude coupling
+  (csrc/tfr.hip; the section "time-frequency" below).
 * `USleep(...)` (forward, `train_step`, `backward`, `predict`), `fid_features(model, windows)`, `FIDMetric()(y_pred, y)`, `FeatureMoments`
 * `balanced_class_weights(labels, n_classes)`, `stage_report(pred, true)`: class weights and the scores of a sleep stager (host numpy)
   -- the FID of /root/reference/src/compute_fid.py:341-419: the U-Sleep feature extractor (/root/reference/src/models/usleep.py:101-287,
@@ -1395,4 +1397,344 @@ def compare_events(real, fake):
             ok = a.size > 0 and b.size > 0
             out[f] = {"n_real": int(a.size), "n_synthetic": int(b.size), "ks": ks_statistic(a, b) if ok else None,
                       "wasserstein": wasserstein_1d(a, b) if ok else None}
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- time-frequency
+# How a window's (or a night's) spectrum moves in time, and whether spindles ride on the up-state of the slow oscillation, on two device
+# primitives (csrc/tfr.hip): eegldm_stft_power, short-time multitaper power with optional band sums, and eegldm_pac_intervals, float64
+# phase-amplitude sums over intervals.  As above: what is not a pass over the samples is float64 numpy in functions that take tables as
+# input, and every refusal is a ValueError before the device is touched.
+# THE DEFAULT BANDS, WINDOW LENGTHS AND THE SLOW-OSCILLATION BAND ARE THE LITERATURE'S; NOBODY HAS VALIDATED THEM ON THIS PROJECT'S
+# 18-Hz-LOW-PASSED DATA, AND MATCHING STATISTICS ARE NOT EVIDENCE OF REALISM ON THEIR OWN.
+STFT_NFFT = (64, 128, 256, 512, 1024, 2048, 4096)
+STFT_MAX_TAPERS, STFT_MAX_BANDS = 8, 16
+STFT_WINDOWS = ("dpss", "hann")
+COURSE_FEATURES = ("mean", "cv", "lag1")
+
+
+def stft_n_fft(n_win):
+    """The smallest transform length eegldm_stft_power takes that holds a frame of n_win samples."""
+    for n in STFT_NFFT:
+        if n >= int(n_win) >= 1:
+            return n
+    raise ValueError(f"frames of 1..{STFT_NFFT[-1]} samples are taken, got {n_win}")
+
+
+def stft_num_frames(length, n_win, hop, centre=True):
+    """Frames of a row of `length` samples (eegldm_stft_num_frames: the rule lives in the library)."""
+    f = int(lib.eegldm_stft_num_frames(int(length), int(n_win), int(hop), 1 if centre else 0))
+    if f < 0:
+        raise ValueError(f"need length >= 0, n_win >= 1 and hop >= 1, got {length}, {n_win}, {hop}")
+    return f
+
+
+def _bin_ranges(ranges, nbin, what):
+    r = np.asarray(ranges, np.int64).reshape(-1, 2) if len(ranges) else np.zeros((0, 2), np.int64)
+    if np.any(np.asarray(ranges, np.float64).reshape(-1, 2) != r):
+        raise ValueError(f"{what}: bin ranges must be integers, got {ranges!r}")
+    if np.any(r[:, 0] < 0) or np.any(r[:, 0] >= r[:, 1]) or np.any(r[:, 1] > nbin):
+        raise ValueError(f"{what}: need 0 <= lo < hi <= {nbin}, got {r.tolist()}")
+    return r
+
+
+def stft_power(x, tapers, weights=None, n_fft=None, hop=None, centre=True, edge="reflect", detrend=True, scale=1.0, onesided=True, bins=None,
+               bands=None, ctx=None):
+    """Short-time multitaper power of every row (eegldm_stft_power; include/eegldm.h has the definition): P[b][f][k] = scale c_k sum_t
+    weights[t]^2 |FFT_n_fft(tapers[t] (frame - mean))[k]|^2.  x (B, L) or (B, 1, L), any L; tapers (K, n_win) or (n_win,), K <= 8; n_fft
+    defaults to the next listed size >= n_win, hop to n_win // 2.  bins = (k0, k1) picks the stored bins (None: all n_fft / 2 + 1; False: no
+    spectrogram); bands = [(lo, hi), ...] are up to 16 bin ranges summed per frame (None: none).  Returns {"power": (B, F, k1 - k0) or None,
+    "bands": (B, F, NB) or None, "n_frames": F}, fp32 tensors on the device."""
+    x = _rows_any_length(x, "x")
+    tp = np.asarray(tapers.detach().cpu().numpy() if torch.is_tensor(tapers) else tapers, np.float32)
+    if tp.ndim == 1:
+        tp = tp[None]
+    if tp.ndim != 2 or not 1 <= tp.shape[0] <= STFT_MAX_TAPERS or tp.shape[1] < 1:
+        raise ValueError(f"tapers (K, n_win) with K in 1..{STFT_MAX_TAPERS} expected, got shape {tp.shape}")
+    if not np.all(np.isfinite(tp)):
+        raise ValueError("non-finite tapers (as fp32)")
+    k, n_win = int(tp.shape[0]), int(tp.shape[1])
+    n_fft = stft_n_fft(n_win) if n_fft is None else n_fft
+    if n_fft not in STFT_NFFT:
+        raise ValueError(f"n_fft must be one of {STFT_NFFT}, got {n_fft!r}")
+    if n_win > n_fft:
+        raise ValueError(f"n_win {n_win} exceeds n_fft {n_fft}")
+    hop = max(1, n_win // 2) if hop is None else hop
+    if int(hop) != hop or hop < 1:
+        raise ValueError(f"hop must be an integer >= 1, got {hop!r}")
+    if edge not in FIR_EDGES:
+        raise ValueError(f"edge must be one of {tuple(FIR_EDGES)}, got {edge!r}")
+    w = np.ones(k) if weights is None else np.asarray(weights, np.float64).reshape(-1)
+    with np.errstate(over="ignore"):
+        w2 = (w * w).astype(np.float32)
+    if w.size != k or not np.all(np.isfinite(w2)):
+        raise ValueError(f"{k} finite weights expected, got {w!r}")
+    with np.errstate(over="ignore"):
+        scale_ok = np.isfinite(np.float32(scale))
+    if not scale_ok:
+        raise ValueError(f"scale must be finite as fp32, got {scale!r}")
+    nbin = n_fft // 2 + 1
+    want_power = bins is not False
+    k0, k1 = (0, nbin) if bins is None or bins is False else (int(v) for v in _bin_ranges([bins], nbin, "bins")[0])
+    br = None if bands is None else _bin_ranges(list(bands), nbin, "bands")
+    if br is not None and not 1 <= len(br) <= STFT_MAX_BANDS:
+        raise ValueError(f"1..{STFT_MAX_BANDS} bands are taken, got {len(br)}")
+    if not want_power and br is None:
+        raise ValueError("nothing to compute: bins=False and bands=None")
+    b, length = int(x.shape[0]), int(x.shape[1])
+    if centre and edge == "reflect" and length >= 1 and n_win // 2 > length - 1:
+        raise ValueError(f"reflect needs n_win // 2 <= L - 1, got n_win {n_win} for rows of {length} samples")
+    f = stft_num_frames(length, n_win, int(hop), centre)
+    ctx = ctx or default_context(0)
+    dev = torch.device("cuda", ctx.device)
+    power = torch.empty(b, f, k1 - k0, device=dev) if want_power else None
+    bsum = torch.empty(b, f, len(br), device=dev) if br is not None else None
+    if b and f:
+        xd = _dev_rows(x, dev)
+        td = torch.from_numpy(np.ascontiguousarray(tp)).to(dev)
+        nb = 0 if br is None else len(br)
+        bh = (C.c_int * max(2 * nb, 1))(*([int(v) for v in br.reshape(-1)] if nb else [0]))
+        check(lib.eegldm_stft_power(ctx.h, ptr(xd), _ld(xd), b, length, ptr(td), (C.c_float * k)(*w2.tolist()), k, n_win, int(n_fft), int(hop),
+                                    1 if centre else 0, FIR_EDGES[edge], 1 if detrend else 0, 1 if onesided else 0, float(scale), k0, k1,
+                                    ptr(power), bh if nb else None, nb, ptr(bsum)))
+    return {"power": power, "bands": bsum, "n_frames": f}
+
+
+def spectrogram_tapers(n_win, window="dpss", half_nbw=2.0, n_tapers=None):
+    """(tapers (K, n_win) float64 of unit energy, weights (K,) of ones): K = 2 half_nbw - 1 DPSS tapers from scipy (as `dpss_tapers` gets
+    them), or the one periodic Hann window."""
+    n_win = int(n_win)
+    if n_win < 1:
+        raise ValueError(f"n_win must be >= 1, got {n_win}")
+    if window == "hann":
+        if n_tapers not in (None, 1):
+            raise ValueError("the Hann window is one taper")
+        t = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n_win) / n_win))[None] if n_win > 1 else np.ones((1, 1))
+    elif window == "dpss":
+        k = int(round(2.0 * float(half_nbw) - 1.0)) if n_tapers is None else n_tapers
+        if int(k) != k or not 1 <= k <= STFT_MAX_TAPERS or not half_nbw > 0:
+            raise ValueError(f"1..{STFT_MAX_TAPERS} tapers and half_nbw > 0 are needed, got n_tapers {k!r}, half_nbw {half_nbw!r}")
+        if n_win < 2 * int(k):
+            raise ValueError(f"{k} DPSS tapers need frames of at least {2 * int(k)} samples, got {n_win}")
+        from scipy.signal.windows import dpss
+        t = np.atleast_2d(dpss(n_win, float(half_nbw), int(k), sym=False, norm=2)).astype(np.float64)
+    else:
+        raise ValueError(f"window must be one of {STFT_WINDOWS}, got {window!r}")
+    t = t / np.sqrt(np.sum(t * t, axis=1, keepdims=True))
+    return t, np.ones(t.shape[0])
+
+
+def band_bin_ranges(bands, sfreq, n_fft):
+    """{name: (lo, hi) Hz} -> (names, [(k_lo, k_hi)]): the bins with lo <= k df < hi, df = sfreq / n_fft."""
+    df = float(sfreq) / int(n_fft)
+    freqs = np.arange(int(n_fft) // 2 + 1) * df
+    names, ranges = [], []
+    for name, (lo, hi) in bands.items():
+        k_lo, k_hi = int(np.searchsorted(freqs, lo, side="left")), int(np.searchsorted(freqs, hi, side="left"))
+        if not k_lo < k_hi:
+            raise ValueError(f"band {name!r} = ({lo}, {hi}) Hz holds no bin at df = {df:g} Hz")
+        names.append(name); ranges.append((k_lo, k_hi))
+    return names, ranges
+
+
+def spectrogram(x, sfreq=100.0, win_s=2.0, step_s=0.5, window="dpss", half_nbw=2.0, n_tapers=None, fmin=0.0, fmax=None, bands=None, keep_power=True,
+                centre=True, edge="reflect", detrend=True, ctx=None):
+    """Multitaper (or Hann) spectrogram of every row as a power density in V^2/Hz, with the time course of the power in each band.
+    Frames of win_s seconds every step_s seconds; tapers of unit energy, unit weights, n_fft the next listed size >= the frame, scale = 1 /
+    (sfreq sum w^2), one-sided.  bands {name: (lo, hi) Hz} (default: the module's BANDS) become bin ranges lo <= f < hi; band_power is their
+    sum times df (V^2), float64 on the device.  keep_power=False never writes the spectrogram: a night's band courses cost F x NB floats.
+    Returns {"power" (B, F, n_freqs) or None, "freqs", "times" (frame centres, s), "band_power" (B, F, NB), "band_names", "df", "n_fft",
+    "n_frames"}.  The default bands and window lengths are the literature's; they have not been validated on this 18-Hz-low-passed data."""
+    if not (sfreq > 0 and win_s > 0 and step_s > 0):
+        raise ValueError(f"sfreq, win_s and step_s must be positive, got {sfreq}, {win_s}, {step_s}")
+    n_win, hop = int(round(float(win_s) * float(sfreq))), int(round(float(step_s) * float(sfreq)))
+    if n_win < 1 or hop < 1:
+        raise ValueError(f"win_s = {win_s} s or step_s = {step_s} s is shorter than a sample at sfreq = {sfreq}")
+    n_fft = stft_n_fft(n_win)
+    tapers, w = spectrogram_tapers(n_win, window, half_nbw, n_tapers)
+    df = float(sfreq) / n_fft
+    freqs = np.arange(n_fft // 2 + 1) * df
+    fmax = 0.5 * float(sfreq) if fmax is None else fmax
+    k0, k1 = int(np.searchsorted(freqs, fmin, side="left")), int(np.searchsorted(freqs, fmax, side="right"))
+    if not k0 < k1:
+        raise ValueError(f"no bin in [{fmin}, {fmax}] Hz at df = {df:g} Hz")
+    names, ranges = band_bin_ranges(BANDS if bands is None else bands, sfreq, n_fft)
+    res = stft_power(x, tapers, w, n_fft=n_fft, hop=hop, centre=centre, edge=edge, detrend=detrend, scale=1.0 / (float(sfreq) * float(np.sum(w * w))),
+                     onesided=True, bins=(k0, k1) if keep_power else False, bands=ranges, ctx=ctx)
+    f = res["n_frames"]
+    times = (np.arange(f) * hop + (0.0 if centre else 0.5 * n_win)) / float(sfreq)
+    return {"power": res["power"], "freqs": freqs[k0:k1], "times": times, "band_power": res["bands"].double() * df, "band_names": names, "df": df,
+            "n_fft": n_fft, "n_frames": f}
+
+
+def band_course_stats(band_power):
+    """What an average PSD cannot say about a band: per window and band, over the frames, the temporal mean, the coefficient of variation
+    (population sd / mean) and the lag-1 autocorrelation of log power.  band_power (B, F, NB) -> {"mean", "cv", "lag1"}, (B, NB) float64;
+    NaN where undefined (fewer than two frames, a zero mean, a non-positive power, no variance)."""
+    p = band_power.detach().cpu().numpy() if torch.is_tensor(band_power) else band_power
+    p = np.asarray(p, np.float64)
+    if p.ndim != 3:
+        raise ValueError(f"band_power (B, F, NB) expected, got shape {p.shape}")
+    b, f, nb = p.shape
+    nan = np.full((b, nb), np.nan)
+    if f == 0:
+        return {"mean": nan, "cv": nan.copy(), "lag1": nan.copy()}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = p.mean(axis=1)
+        cv = np.where(mean != 0, p.std(axis=1) / mean, np.nan)
+        y = np.where(p > 0, np.log(np.where(p > 0, p, 1.0)), np.nan)
+        d = y - y.mean(axis=1, keepdims=True)
+        den = np.sum(d * d, axis=1)
+        lag1 = np.where(den > 0, np.sum(d[:, :-1] * d[:, 1:], axis=1) / np.where(den > 0, den, 1.0), np.nan) if f >= 2 else nan.copy()
+    return {"mean": mean, "cv": cv, "lag1": lag1}
+
+
+def compare_band_courses(real, fake, names=None):
+    """Per band and feature of `band_course_stats` (mean, cv, lag1): the KS statistic and the Wasserstein distance of the real against the
+    synthetic windows (the finite values of each), with the sample sizes; None where a side has none."""
+    nb = np.asarray(real["mean"]).shape[1]
+    names = [str(i) for i in range(nb)] if names is None else list(names)
+    out = {}
+    for j, name in enumerate(names):
+        out[name] = {}
+        for feat in COURSE_FEATURES:
+            a, c = np.asarray(real[feat], np.float64)[:, j], np.asarray(fake[feat], np.float64)[:, j]
+            a, c = a[np.isfinite(a)], c[np.isfinite(c)]
+            ok = a.size > 0 and c.size > 0
+            out[name][feat] = {"n_real": int(a.size), "n_synthetic": int(c.size), "ks": ks_statistic(a, c) if ok else None,
+                               "wasserstein": wasserstein_1d(a, c) if ok else None}
+    return out
+
+
+def fir_design_analytic(sfreq, lo, hi, trans_hz=2.0):
+    """(re_taps, im_taps), float64: the low-pass prototype h = fir_design(sfreq, hi=(hi - lo) / 2, trans_hz) shifted to the band centre,
+    re = 2 h cos(w0 m), im = -2 h sin(w0 m), m = n - (M - 1) / 2, w0 = 2 pi (lo + hi) / (2 sfreq).  Under `fir_filter`'s correlation form
+    y[n] = sum_m g[m] x[n + m] the pair passes e^{+i w n} in the band and rejects its mirror: a real cos(w0 n) comes out as e^{i w0 n}."""
+    if lo is None or hi is None or not 0.0 <= float(lo) < float(hi) < 0.5 * float(sfreq):
+        raise ValueError(f"band ({lo}, {hi}) Hz: need 0 <= lo < hi < sfreq / 2 = {0.5 * float(sfreq)}")
+    h = fir_design(sfreq, hi=0.5 * (float(hi) - float(lo)), trans_hz=trans_hz)
+    m = np.arange(h.size, dtype=np.float64) - 0.5 * (h.size - 1)
+    w0 = 2.0 * np.pi * (float(lo) + float(hi)) / (2.0 * float(sfreq))
+    return 2.0 * h * np.cos(w0 * m), -2.0 * h * np.sin(w0 * m)
+
+
+def analytic_band(windows, lo, hi, sfreq=100.0, trans_hz=2.0, edge="reflect", ctx=None):
+    """(re, im): the analytic signal of the windows' (lo, hi) Hz band, two passes of `fir_filter` with the taps of `fir_design_analytic`;
+    (N, L) fp32 on the device, L <= 4096.  The loader's 3072-sample windows lose their zero pads first."""
+    w = _windows2d(windows, "windows")
+    re_t, im_t = fir_design_analytic(sfreq, lo, hi, trans_hz)
+    _check_taps(re_t, w.shape[1], edge)
+    return fir_filter(w, re_t, edge, ctx=ctx), fir_filter(w, im_t, edge, ctx=ctx)
+
+
+def pac_from_out(out):
+    """eegldm_pac_intervals' table (NI, 4) = (n, sum a, c, s) -> {"n" int64, "sum_a", "mvl" = hypot(c, s) / sum a, "phase" = atan2(s, c)}, float64;
+    mvl and phase are NaN where no sample took part (n <= 0; n = -1 marks an interval outside its row) or sum a is not positive."""
+    o = np.asarray(out, np.float64).reshape(-1, 4)
+    ok = (o[:, 0] > 0) & (o[:, 1] > 0)
+    safe = np.where(ok, o[:, 1], 1.0)
+    return {"n": o[:, 0].astype(np.int64), "sum_a": o[:, 1].copy(), "mvl": np.where(ok, np.hypot(o[:, 2], o[:, 3]) / safe, np.nan),
+            "phase": np.where(ok, np.arctan2(o[:, 3], o[:, 2]), np.nan)}
+
+
+def phase_amplitude_coupling(phase_re, phase_im, amp, intervals=None, ctx=None):
+    """Amplitude-weighted mean vector of the phase signal (phase_re, phase_im) over intervals (eegldm_pac_intervals, float64 sums on the device):
+    rows (B, L) fp32; intervals (NI, 3) int = (row, start, length), or None for one interval per row.  Returns `pac_from_out`'s dict."""
+    pr, pi, am = (_rows_any_length(t, n) for t, n in ((phase_re, "phase_re"), (phase_im, "phase_im"), (amp, "amp")))
+    if not tuple(pr.shape) == tuple(pi.shape) == tuple(am.shape):
+        raise ValueError(f"shapes differ: {tuple(pr.shape)}, {tuple(pi.shape)}, {tuple(am.shape)}")
+    b, length = int(pr.shape[0]), int(pr.shape[1])
+    if length < 1:
+        raise ValueError("rows of at least one sample are needed")
+    iv = None
+    if intervals is not None:
+        iv = np.asarray(intervals)
+        if iv.ndim != 2 or iv.shape[1] != 3 or not np.issubdtype(iv.dtype, np.integer) or (iv.size and np.abs(iv).max() > 0x7fffffff):
+            raise ValueError(f"intervals (NI, 3) int32 = (row, start, length) expected, got shape {iv.shape} dtype {iv.dtype}")
+        iv = np.ascontiguousarray(iv, np.int32)
+    ni = b if iv is None else int(iv.shape[0])
+    ctx = ctx or default_context(0)
+    dev = torch.device("cuda", ctx.device)
+    out = torch.empty(ni, 4, dtype=torch.float64, device=dev)
+    if ni:
+        prd, pid, amd = _dev_rows(pr, dev), _dev_rows(pi, dev), _dev_rows(am, dev)
+        ivd = None if iv is None else torch.from_numpy(iv).to(dev)
+        check(lib.eegldm_pac_intervals(ctx.h, ptr(prd), _ld(prd), ptr(pid), _ld(pid), ptr(amd), _ld(amd), b, length, ptr(ivd), ni, ptr(out)))
+    return pac_from_out(out.cpu().numpy())
+
+
+def rayleigh_p(n, r):
+    """p-value of the Rayleigh test of uniformity for n angles with resultant length r: z = n r^2, p = exp(-z) (1 + (2 z - z^2) / (4 n) -
+    (24 z - 132 z^2 + 76 z^3 - 9 z^4) / (288 n^2)) (Zar, Biostatistical Analysis, eq. 27.4), clipped to [0, 1]."""
+    z = n * r * r
+    p = np.exp(-z) * (1.0 + (2.0 * z - z * z) / (4.0 * n) - (24.0 * z - 132.0 * z ** 2 + 76.0 * z ** 3 - 9.0 * z ** 4) / (288.0 * n * n))
+    return float(min(max(p, 0.0), 1.0))
+
+
+def circular_summary(phases):
+    """{"n", "mean" (rad, in (-pi, pi]), "R" (resultant length), "z" = n R^2, "p" (Rayleigh)} of the finite angles; None fields when there are none."""
+    a = np.asarray(phases, np.float64).reshape(-1)
+    a = a[np.isfinite(a)]
+    if a.size == 0:
+        return {"n": 0, "mean": None, "R": None, "z": None, "p": None}
+    c, s = np.mean(np.cos(a)), np.mean(np.sin(a))
+    r = float(np.hypot(c, s))
+    return {"n": int(a.size), "mean": float(np.arctan2(s, c)), "R": r, "z": float(a.size * r * r), "p": rayleigh_p(a.size, r)}
+
+
+def circular_distance(a, b):
+    """|a - b| on the circle, in [0, pi]; None when either is None."""
+    if a is None or b is None:
+        return None
+    return float(abs(np.angle(np.exp(1j * (float(a) - float(b))))))
+
+
+def spindle_so_coupling(windows, spindles, sfreq=100.0, so_band=(0.5, 1.25), so_trans_hz=0.5, sigma_band=(11.0, 16.0), half_s=0.5, sigma_trans_hz=2.0,
+                        ctx=None):
+    """Do the spindles of `spindles` (a `detect_spindles` table of these windows) ride on a preferred phase of the slow oscillation?  The SO
+    phase is the analytic so_band signal, the spindle amplitude the modulus of the analytic sigma_band signal.  Per event: the SO phase at the
+    envelope peak (`argmax`), and the mean vector length and preferred phase of the amplitude-weighted SO phase over peak +- half_s; events
+    whose interval leaves the window are dropped and counted.  Per set: `circular_summary` of the peak phases and of the preferred phases.
+    Phase 0 is the SO's positive peak.  The SO band is the literature's; it has not been validated on this 18-Hz-low-passed data."""
+    if len(so_band) != 2 or len(sigma_band) != 2:
+        raise ValueError(f"bands must be (lo, hi), got {so_band!r} and {sigma_band!r}")
+    half = _seconds_to_samples(sfreq, half_s=half_s)["half_s"]
+    w = _windows2d(windows, "windows")
+    n_win, length = int(w.shape[0]), int(w.shape[1])
+    win, peak = np.asarray(spindles["window"], np.int64), np.asarray(spindles["argmax"], np.int64)
+    if win.shape != peak.shape or (win.size and (win.min() < 0 or win.max() >= n_win or peak.min() < 0 or peak.max() >= length)):
+        raise ValueError("the spindle table does not belong to these windows")
+    for band, trans in ((so_band, so_trans_hz), (sigma_band, sigma_trans_hz)):
+        _check_taps(fir_design_analytic(sfreq, band[0], band[1], trans)[0], length, "reflect")
+    keep = (peak - half >= 0) & (peak + half + 1 <= length)
+    win, peak = win[keep], peak[keep]
+    res = {"n_events": int(win.size), "n_dropped": int(np.sum(~keep)), "window": win, "peak": peak}
+    if win.size == 0:
+        res.update(peak_phase=np.zeros(0), mvl=np.zeros(0), phase=np.zeros(0))
+    else:
+        so_r, so_i = analytic_band(w, so_band[0], so_band[1], sfreq, so_trans_hz, ctx=ctx)
+        sg_r, sg_i = analytic_band(w, sigma_band[0], sigma_band[1], sfreq, sigma_trans_hz, ctx=ctx)
+        amp = torch.hypot(sg_r, sg_i)
+        wi, pk = torch.from_numpy(win).to(so_r.device), torch.from_numpy(peak).to(so_r.device)
+        res["peak_phase"] = np.arctan2(so_i[wi, pk].double().cpu().numpy(), so_r[wi, pk].double().cpu().numpy())
+        pac = phase_amplitude_coupling(so_r, so_i, amp, np.stack([win, peak - half, np.full_like(win, 2 * half + 1)], axis=1), ctx=ctx)
+        res["mvl"], res["phase"] = pac["mvl"], pac["phase"]
+    res["peak_phase_stats"] = circular_summary(res["peak_phase"])
+    res["preferred_phase_stats"] = circular_summary(res["phase"])
+    return res
+
+
+def compare_coupling(real, fake):
+    """Two `spindle_so_coupling` results side by side: both sets' circular summaries, the circular distance of their mean phases (peak and
+    preferred), and the KS statistic and Wasserstein distance of the per-event mean vector lengths (None where a side has no events)."""
+    out = {}
+    for side, r in (("real", real), ("synthetic", fake)):
+        out[side] = {"n_events": int(r["n_events"]), "n_dropped": int(r["n_dropped"]), "peak_phase": r["peak_phase_stats"],
+                     "preferred_phase": r["preferred_phase_stats"]}
+    out["peak_phase_distance"] = circular_distance(real["peak_phase_stats"]["mean"], fake["peak_phase_stats"]["mean"])
+    out["preferred_phase_distance"] = circular_distance(real["preferred_phase_stats"]["mean"], fake["preferred_phase_stats"]["mean"])
+    a, b = (np.asarray(r["mvl"], np.float64)[np.isfinite(np.asarray(r["mvl"], np.float64))] for r in (real, fake))
+    ok = a.size > 0 and b.size > 0
+    out["mvl"] = {"n_real": int(a.size), "n_synthetic": int(b.size), "ks": ks_statistic(a, b) if ok else None,
+                  "wasserstein": wasserstein_1d(a, b) if ok else None}
     return out
