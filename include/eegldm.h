@@ -939,13 +939,32 @@ int eegldm_usleep_conv_bwd(eegldm_ctx*, const float* a, int Ca, int La, int ups,
 int eegldm_usleep_elu_bn_bwd(eegldm_ctx*, const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma, float* dz,
                              float* dgamma, float* dbeta, int B, int C, int L);
 /* MaxPool1d(2) over ConstantPad1d(1, 0) at odd L, backward: x (nrows, L), dpool (nrows, Lo), dx = (dskip ? dskip : 0) + gradient at the
- * arg-max (equal values: the lower padded index; the pad's zero wins: dropped).  Exact. */
+ * arg-max (the first NaN of a pair, else the larger value; equal values: the lower padded index; the pad's zero wins: dropped).  Exact. */
 int eegldm_usleep_maxpool_bwd(eegldm_ctx*, const float* x, const float* dpool, const float* dskip /* nullable */, float* dx, long nrows, int L);
 /* Classifier head + loss, forward and backward: x (B, C1, L) decoder output; weights / grads: {clf.0.weight, clf.0.bias, clf.3.weight, clf.3.bias,
  * clf.5.weight, clf.5.bias} (grads +=); writes *loss_out, logits (B, n_classes, L / input_size) and dx (B, C1, L; 0 past S * input_size). */
 int eegldm_usleep_clf_loss(eegldm_ctx*, const float* x, const float* const* weights, float* const* grads, const int64_t* labels,
                            const float* class_weight /* nullable */, int B, int C1, int L, int input_size, int n_classes, float grad_scale,
                            float* loss_out, float* logits, float* dx, int* label_flag /* nullable */);
+/* Primitives of the forward, exported for the tests (additive, ABI 8); they add no launch to any model path.
+ * layer_fwd: one conv1d 'same' -> + bias -> ELU -> BatchNorm [-> ConstantPad1d(1, 0) at odd L + MaxPool1d(2)] layer over the virtual input
+ * [a (B, Ca, La), nearest x2 when ups | b2 (B, Cb, Lb)], both cropped to L, through the launch helpers the model runs.
+ *   mode 0: the inference path in eval mode (BatchNorm folded from the running statistics into the conv's epilogue);
+ *   mode 1: the inference path on batch statistics (fp64 atomics, finalize, affine pass), running statistics and counter updated;
+ *   mode 2: the training path (written fp64 partials folded in order, stats, apply or the fused apply + pool), the same update; left must be
+ *           (K - 1) / 2.
+ * y (B, Cout, L) is written; pooled (B, Cout, Lo), Lo = (L + (L odd ? 2 : 0)) / 2, z (the ELU output before BatchNorm; modes 1 and 2) and
+ * stat (mean [Cout] | rstd [Cout]; mode 2) are optional.  A NaN in either position of a pooled pair is the pair's maximum, as in torch.
+ * Modes 1 and 2 need B * L >= 2.  The call returns after the stream has drained. */
+int eegldm_usleep_layer_fwd(eegldm_ctx*, int mode, const float* a, int Ca, int La, int ups, const float* b2 /* nullable */, int Cb, int Lb, int L,
+                            const float* w, const float* bias, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                            float* num_batches_tracked, int B, int Cout, int K, int left, float* y, float* pooled /* nullable */,
+                            float* z /* nullable */, float* stat /* nullable */);
+/* ConstantPad1d(1, 0) at odd L + MaxPool1d(2) alone: x (nrows, L) -> y (nrows, Lo); the zeros take part in the max, a NaN wins its pair. */
+int eegldm_usleep_maxpool_fwd(eegldm_ctx*, const float* x, float* y, long nrows, int L);
+/* The inference classifier head: x (B, C1, L) -> y (B, ncls, L / win); weights as in eegldm_usleep_clf_loss; positions past (L / win) * win
+ * are not read. */
+int eegldm_usleep_clf_fwd(eegldm_ctx*, const float* x, const float* const* weights, int B, int C1, int L, int win, int ncls, float* y);
 /* First and second moments of a feature batch (N, D), accumulated in fp64 device buffers the caller zeroed: sum[D] += sum_n f[n],
  * outer[D][D] += sum_n f[n] f[n]^T.  mean = sum / N, covariance = (outer - N mean mean^T) / (N - 1) are the inputs of the Frechet
  * distance (compute_fid.py:412-414 = monai-generative FIDMetric: torch.mean, unbiased _cov, trace of the matrix square root). */

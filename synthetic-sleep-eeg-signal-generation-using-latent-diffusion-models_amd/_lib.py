@@ -230,6 +230,9 @@ SIGNATURES = {
     "eegldm_usleep_elu_bn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i],
     "eegldm_usleep_maxpool_bwd": [_vp, _vp, _vp, _vp, _vp, _l, _i],
     "eegldm_usleep_clf_loss": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "eegldm_usleep_layer_fwd": [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "eegldm_usleep_maxpool_fwd": [_vp, _vp, _vp, _l, _i],
+    "eegldm_usleep_clf_fwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "eegldm_feature_moments": [_vp, _vp, _l, _i, _vp, _vp],
     "eegldm_knn_update": [_vp, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _l, _l, _vp, _vp],
     "eegldm_rows_sqnorm": [_vp, _vp, _l, _l, _i, _vp],

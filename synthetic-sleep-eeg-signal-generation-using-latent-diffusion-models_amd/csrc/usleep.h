@@ -19,7 +19,17 @@ struct ConvSrc {
 };
 
 struct BnDesc { long w, b, rm, rv, nbt, fold; int C; };
+
+// The max of a pooled pair as torch's max_pool1d takes it: NaN when either value is NaN (fmaxf alone returns the finite partner).  For two
+// finite values, or infinities, it is fmaxf.
+__device__ __forceinline__ float pool_max(float a, float b) { return a != a ? a : (b != b ? b : fmaxf(a, b)); }
 }  // namespace
+
+// usleep_train.hip: one layer of the training forward on plain pointers, for eegldm_usleep_layer_fwd (mode 2).  buffers: running_mean [Cout] |
+// running_var [Cout] | counter; pooled, z, stat nullable.
+int usleep_layer_train_entry(eegldm_ctx* ctx, const float* a, int Ca, int La, int ups, const float* b2, int Cb, int Lb, int L, const float* w,
+                             const float* bias, const float* gamma, const float* beta, float* buffers, int B, int Cout, int K, float* y, float* pooled,
+                             float* z, float* stat);
 
 struct UConv { long w, b; int cin, cout, k; };
 // one conv -> ELU -> BatchNorm layer of a training forward: what its backward reads (all in the arena)

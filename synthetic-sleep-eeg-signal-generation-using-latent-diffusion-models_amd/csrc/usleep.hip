@@ -10,7 +10,8 @@
 //   usleep_bn_*             fold (eval: gamma / sqrt(running_var + eps) ...), finalize (train: batch statistics -> affine, running
 //                           statistics with momentum 0.1 and the unbiased variance, num_batches_tracked), apply
 //   usleep_maxpool_kernel   ConstantPad1d(1, 0) on BOTH sides when the length is odd, then MaxPool1d(2) (usleep.py:44-51): the zeros take
-//                           part in the max
+//                           part in the max; a NaN in either position of a pair is the pair's maximum, as in torch's max_pool1d (fmaxf
+//                           would return the finite partner and leave the encoder with fewer poisoned positions than the model it mirrors)
 //   usleep_clf_kernel       conv1 -> tanh -> AvgPool1d(input_size) -> conv1 -> ELU -> conv1 (usleep.py:218-247)
 //   feat_accumulate_kernel  sum x and sum x x^T of a feature batch in fp64 (mean / unbiased covariance of the Frechet distance; the
 //                           302 x 302 matrix square root is host linear algebra, as in the reference's FIDMetric)
@@ -114,7 +115,7 @@ __global__ void usleep_maxpool_kernel(const float* __restrict__ x, float* __rest
     const long r = i / Lo; const int o = (int)(i % Lo);
     const int p0 = 2 * o - odd, p1 = p0 + 1;             // positions in the un-padded row; out of range = the zero pad
     const float a = (p0 >= 0 && p0 < L) ? x[r * L + p0] : 0.f, b = (p1 >= 0 && p1 < L) ? x[r * L + p1] : 0.f;
-    y[i] = fmaxf(a, b);
+    y[i] = pool_max(a, b);
   }
 }
 // one block per (sample, pooling window): mean over the window of tanh(W0 x + b0), then the two 1x1 convs on that vector
@@ -185,13 +186,14 @@ void add_bn(eegldm_usleep* u, const std::string& p, int C) {
   u->bns.push_back(d);
 }
 
-int launch_conv(eegldm_usleep* u, const ConvSrc& s, const UConv& c, int left, const float* fold, float* y, double* sums, int B) {
+// (the layer helpers take plain pointers: the model passes slices of its flat parameter / buffer / fold arrays, eegldm_usleep_layer_fwd its own)
+int launch_conv(eegldm_ctx* ctx, const ConvSrc& s, const float* w, const float* bias, int cout, int k, int left, const float* fold, float* y, double* sums,
+                int B) {
   const long rows = (long)B * s.L;
   if (rows == 0) return 0;
-  const dim3 grid((unsigned)((rows + UROWS - 1) / UROWS), (unsigned)((c.cout + UCO - 1) / UCO));
-  const float* w = u->params + c.w; const float* bias = u->params + c.b;
-#define ULAUNCH(KT) hipLaunchKernelGGL((usleep_conv_kernel<KT>), grid, dim3(UT), 0, u->ctx->stream, s, w, bias, fold, y, sums, rows, c.cout, c.k, left)
-  switch (c.k) {
+  const dim3 grid((unsigned)((rows + UROWS - 1) / UROWS), (unsigned)((cout + UCO - 1) / UCO));
+#define ULAUNCH(KT) hipLaunchKernelGGL((usleep_conv_kernel<KT>), grid, dim3(UT), 0, ctx->stream, s, w, bias, fold, y, sums, rows, cout, k, left)
+  switch (k) {
     case 1: ULAUNCH(1); break;
     case 2: ULAUNCH(2); break;
     case 3: ULAUNCH(3); break;
@@ -205,20 +207,38 @@ int launch_conv(eegldm_usleep* u, const ConvSrc& s, const UConv& c, int left, co
   LAUNCH_CHECK();
   return 0;
 }
-// conv -> ELU -> BatchNorm of one layer; bn_idx indexes u->bns
-int conv_elu_bn(eegldm_usleep* u, const ConvSrc& s, const UConv& c, int left, int bn_idx, float* y, int B, int training) {
-  const BnDesc& d = u->bns[bn_idx];
-  if (!training) return launch_conv(u, s, c, left, u->fold + d.fold, y, nullptr, B);
-  EEG_TRY(launch_conv(u, s, c, left, nullptr, y, u->sums, B));
-  const long n = (long)B * c.cout * s.L;
-  hipLaunchKernelGGL(usleep_bn_finalize_kernel, dim3(1), dim3(256), 0, u->ctx->stream, d, u->params, u->buffers, u->fold, u->sums,
-                     (double)B * (double)s.L, 1e-5f, 0.1f);
+// conv -> ELU -> BatchNorm of one layer.  d's offsets index params (gamma, beta), buffers (running statistics, counter) and fold; sums: 2 * cout
+// zeroed doubles (train mode; left zeroed).  z_out (train mode, nullable): a copy of the ELU output, taken before the affine pass overwrites it.
+int conv_elu_bn(eegldm_ctx* ctx, const ConvSrc& s, const float* w, const float* bias, int cout, int k, int left, const BnDesc& d, const float* params,
+                float* buffers, float* fold, double* sums, float* y, int B, int training, float* z_out) {
+  if (!training) return launch_conv(ctx, s, w, bias, cout, k, left, fold + d.fold, y, nullptr, B);
+  EEG_TRY(launch_conv(ctx, s, w, bias, cout, k, left, nullptr, y, sums, B));
+  const long n = (long)B * cout * s.L;
+  hipLaunchKernelGGL(usleep_bn_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, d, params, buffers, fold, sums, (double)B * (double)s.L, 1e-5f, 0.1f);
   LAUNCH_CHECK();
+  if (z_out && n > 0) HIP_TRY(hipMemcpyAsync(z_out, y, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
   if (n > 0) {
     const long blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(usleep_affine_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, u->ctx->stream, y, u->fold + d.fold, n, c.cout, s.L);
+    hipLaunchKernelGGL(usleep_affine_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, ctx->stream, y, fold + d.fold, n, cout, s.L);
     LAUNCH_CHECK();
   }
+  return 0;
+}
+int conv_elu_bn(eegldm_usleep* u, const ConvSrc& s, const UConv& c, int left, int bn_idx, float* y, int B, int training) {
+  return conv_elu_bn(u->ctx, s, u->params + c.w, u->params + c.b, c.cout, c.k, left, u->bns[bn_idx], u->params, u->buffers, u->fold, u->sums, y, B, training,
+                     nullptr);
+}
+inline int pooled_len(int L) { return (L + ((L & 1) ? 2 : 0)) / 2; }
+int launch_maxpool(eegldm_ctx* ctx, const float* x, float* y, long nrows, int L) {
+  const int Lo = pooled_len(L);
+  const long n = nrows * Lo, blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(usleep_maxpool_kernel, dim3((unsigned)(blocks < 4096 ? (blocks < 1 ? 1 : blocks) : 4096)), dim3(256), 0, ctx->stream, x, y, nrows, L, Lo);
+  LAUNCH_CHECK();
+  return 0;
+}
+int launch_clf(eegldm_ctx* ctx, const float* x, const float* const* W, float* y, int B, int C1, int L, int win, int S, int ncls) {
+  hipLaunchKernelGGL(usleep_clf_kernel, dim3((unsigned)(B * S)), dim3(UT), 0, ctx->stream, x, W[0], W[1], W[2], W[3], W[4], W[5], y, C1, L, win, S, ncls);
+  LAUNCH_CHECK();
   return 0;
 }
 }  // namespace
@@ -307,11 +327,9 @@ extern "C" int eegldm_usleep_forward(eegldm_usleep* u, const float* x, float* y_
     ConvSrc s = {cur, Cc, Lc, 0, nullptr, 0, 0, Lc};
     EEG_TRY(conv_elu_bn(u, s, u->enc_c[i], left, i, y, B, training));
     res[i] = y; resL[i] = Lc;
-    const int Lo = (Lc + ((Lc & 1) ? 2 : 0)) / 2;
+    const int Lo = pooled_len(Lc);
     float* p; ALLOC_OR_FAIL(p, falloc((long)B * ch[i + 1] * Lo));
-    const long n = (long)B * ch[i + 1] * Lo, blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(usleep_maxpool_kernel, dim3((unsigned)(blocks < 4096 ? (blocks < 1 ? 1 : blocks) : 4096)), dim3(256), 0, ctx->stream, y, p, (long)B * ch[i + 1], Lc, Lo);
-    LAUNCH_CHECK();
+    EEG_TRY(launch_maxpool(ctx, y, p, (long)B * ch[i + 1], Lc));
     cur = p; Lc = Lo; Cc = ch[i + 1];
   }
   float* bot; ALLOC_OR_FAIL(bot, falloc((long)B * ch[d + 1] * Lc));
@@ -335,9 +353,8 @@ extern "C" int eegldm_usleep_forward(eegldm_usleep* u, const float* x, float* y_
     const int S = Lc / u->cfg.input_size;
     EEG_CHECK(S >= 1, "decoder output length %d is shorter than the pooling window %d", Lc, u->cfg.input_size);
     const float* P = u->params;
-    hipLaunchKernelGGL(usleep_clf_kernel, dim3((unsigned)(B * S)), dim3(UT), 0, ctx->stream, cur, P + u->clf0.w, P + u->clf0.b, P + u->clf3.w, P + u->clf3.b,
-                       P + u->clf5.w, P + u->clf5.b, y_pred, ch[1], Lc, u->cfg.input_size, S, u->cfg.n_classes);
-    LAUNCH_CHECK();
+    const float* const W[6] = {P + u->clf0.w, P + u->clf0.b, P + u->clf3.w, P + u->clf3.b, P + u->clf5.w, P + u->clf5.b};
+    EEG_TRY(launch_clf(ctx, cur, W, y_pred, B, ch[1], Lc, u->cfg.input_size, S, u->cfg.n_classes));
   }
   return 0;
 }
@@ -353,4 +370,72 @@ extern "C" int eegldm_feature_moments(eegldm_ctx* ctx, const float* feats, long 
   hipLaunchKernelGGL(feat_accumulate_kernel, dim3(nt, nt, (unsigned)((N + rpz - 1) / rpz)), dim3(UT), 0, ctx->stream, feats, N, D, sum, outer, rpz);
   LAUNCH_CHECK();
   return 0;
+}
+
+// ---------------------------------------------------------------- primitive exports (tests)
+// One conv 'same' -> + bias -> ELU -> BatchNorm [-> pad + MaxPool(2)] layer through the launch helpers the model runs.  mode 0: the inference
+// path in eval mode (fold kernel + conv with the fold); 1: the inference path on batch statistics (conv with fp64 atomics, finalize, affine);
+// 2: the training path (usleep_train.hip: conv with written partials, stats, apply or the fused apply + pool).  The BatchNorm operands are packed
+// into one workspace laid out as the model's flat arrays ([gamma | beta], [running_mean | running_var | counter], fold, sums), so the kernels
+// see the descriptors they see in the model; the running statistics are copied back in modes 1 and 2.
+extern "C" int eegldm_usleep_layer_fwd(eegldm_ctx* ctx, int mode, const float* a, int Ca, int La, int ups, const float* b2, int Cb, int Lb, int L,
+                                       const float* w, const float* bias, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                       float* num_batches_tracked, int B, int Cout, int K, int left, float* y, float* pooled, float* z, float* stat) {
+  EEG_CHECK(ctx && a && w && bias && gamma && beta && running_mean && running_var && num_batches_tracked && y, "null argument");
+  EEG_CHECK(mode >= 0 && mode <= 2, "mode %d not in 0..2", mode);
+  EEG_CHECK(B >= 1 && Cout >= 1 && Cout <= 65535 && Ca >= 1 && La >= 1 && L >= 1 && L <= (ups ? 2 * La : La), "bad sizes");
+  EEG_CHECK(Cb == 0 || (b2 && Lb >= L), "virtual input: part b2 (C=%d, L=%d) against L=%d", Cb, Lb, L);
+  EEG_CHECK(K >= 1 && K <= UKMAX && left >= 0 && left < K, "kernel size %d / left pad %d", K, left);
+  EEG_CHECK(mode == 0 || (long)B * L >= 2, "batch statistics need B * L >= 2");
+  EEG_CHECK(mode == 2 || !stat, "stat is an output of mode 2");
+  EEG_CHECK(mode != 0 || !z, "mode 0 folds BatchNorm into the conv: there is no stored ELU output");
+  EEG_CHECK(mode != 2 || left == (K - 1) / 2, "the training path pads (K - 1) / 2 on the left");
+  const ConvSrc s = {a, Ca, La, ups ? 1 : 0, b2, Cb, Lb, L};
+  const size_t C = (size_t)Cout, fbytes = sizeof(float) * (2 * C + 2 * C + 1 + 2 * C + 1), dbytes = sizeof(double) * 2 * C;
+  char* ws = nullptr;
+  HIP_TRY(hipMalloc(&ws, dbytes + sizeof(BnDesc) + fbytes));
+  double* sums = (double*)ws; BnDesc* d_tab = (BnDesc*)(ws + dbytes);
+  float* params = (float*)(ws + dbytes + sizeof(BnDesc)); float* buffers = params + 2 * C; float* fold = buffers + 2 * C + 2;
+  BnDesc d; d.C = Cout; d.w = 0; d.b = (long)C; d.rm = 0; d.rv = (long)C; d.nbt = 2 * (long)C; d.fold = 0;
+  auto run = [&]() -> int {
+    HIP_TRY(hipMemsetAsync(sums, 0, dbytes, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_tab, &d, sizeof(BnDesc), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(params, gamma, sizeof(float) * C, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(params + C, beta, sizeof(float) * C, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(buffers, running_mean, sizeof(float) * C, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(buffers + C, running_var, sizeof(float) * C, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(buffers + 2 * C, num_batches_tracked, sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    if (mode == 2) {
+      EEG_TRY(usleep_layer_train_entry(ctx, a, Ca, La, s.ups, b2, Cb, Lb, L, w, bias, params, params + C, buffers, B, Cout, K, y, pooled, z, stat));
+    } else {
+      if (mode == 0) {
+        hipLaunchKernelGGL(usleep_bn_fold_kernel, dim3(1), dim3(64), 0, ctx->stream, d_tab, params, buffers, fold, 1e-5f);
+        LAUNCH_CHECK();
+      }
+      EEG_TRY(conv_elu_bn(ctx, s, w, bias, Cout, K, left, d, params, buffers, fold, sums, y, B, mode, z));
+      if (pooled) EEG_TRY(launch_maxpool(ctx, y, pooled, (long)B * Cout, L));
+    }
+    if (mode != 0) {
+      HIP_TRY(hipMemcpyAsync(running_mean, buffers, sizeof(float) * C, hipMemcpyDeviceToDevice, ctx->stream));
+      HIP_TRY(hipMemcpyAsync(running_var, buffers + C, sizeof(float) * C, hipMemcpyDeviceToDevice, ctx->stream));
+      HIP_TRY(hipMemcpyAsync(num_batches_tracked, buffers + 2 * C, sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+  };
+  const int rc = run();
+  if (rc != 0) (void)hipStreamSynchronize(ctx->stream);
+  (void)hipFree(ws);
+  return rc;
+}
+extern "C" int eegldm_usleep_maxpool_fwd(eegldm_ctx* ctx, const float* x, float* y, long nrows, int L) {
+  EEG_CHECK(ctx && x && y && nrows >= 1 && L >= 1, "bad argument");
+  return launch_maxpool(ctx, x, y, nrows, L);
+}
+extern "C" int eegldm_usleep_clf_fwd(eegldm_ctx* ctx, const float* x, const float* const* weights, int B, int C1, int L, int win, int ncls, float* y) {
+  EEG_CHECK(ctx && x && weights && y, "null argument");
+  for (int i = 0; i < 6; i++) EEG_CHECK(weights[i], "null parameter pointer %d", i);
+  EEG_CHECK(B >= 1 && C1 >= 1 && C1 <= 16 && ncls >= 1 && ncls <= 16 && win >= 1, "bad sizes");
+  EEG_CHECK(L >= win, "L=%d is shorter than the pooling window %d", L, win);
+  return launch_clf(ctx, x, weights, y, B, C1, L, win, L / win, ncls);
 }

@@ -5,13 +5,15 @@
 //
 //   usleep_conv_train_kernel<K>   the forward's conv -> + bias -> ELU, writing z and per-(row block, channel) fp64 (sum, sum of squares)
 //   usleep_bn_stats_kernel        ordered fold of those -> mean, rstd; running statistics (momentum 0.1, unbiased variance, counter)
-//   usleep_bn_apply(_pool)_kernel y = zhat * gamma + beta out of place (z stays for the backward); encoder: + pad / MaxPool(2) in the same pass
+//   usleep_bn_apply(_pool)_kernel y = zhat * gamma + beta out of place (z stays for the backward); encoder: + pad / MaxPool(2) in the same pass.
+//                                 A NaN in either position of a pooled pair is the pair's maximum, as in torch's max_pool1d
 //   usleep_bn_bwd_part / _fold / _apply_kernel   sums of dy and dy * zhat (fp64 partials, ordered fold), dgamma / dbeta +=,
 //                                 dz = ELU'(z) * gamma * rstd * (dy - mean(dy) - zhat * mean(dy * zhat))
 //   usleep_conv_dgrad_kernel<K>   data gradient of one part (a or b2) of the virtual input; ups: dA[q] = dv[2q] + dv[2q + 1]; cropped positions 0
 //   usleep_conv_wgrad_kernel<K>   weight + bias gradient, wave = (4 output channels, 1 input channel, K taps), rows split over blockIdx.z
 //   usleep_fold_kernel            grads[i] += sum_p partials[p][i] in the order p = 0, 1, ... (fp64 accumulator)
-//   usleep_maxpool_bwd_kernel     gradient to the arg-max (tie: lower padded index; pad wins: dropped) + the skip connection's gradient
+//   usleep_maxpool_bwd_kernel     gradient to the arg-max (the first NaN of a pair, else the larger; tie: lower padded index; pad wins: dropped)
+//                                 + the skip connection's gradient
 //   usleep_clf_fwd_train / usleep_ce / usleep_clf_bwd / usleep_clf_dpre_kernel   classifier head and weighted cross-entropy
 #include <cmath>
 #include <cstring>
@@ -117,10 +119,11 @@ __global__ void usleep_bn_apply_pool_kernel(const float* __restrict__ z, const f
     float a = 0.f, b = 0.f;
     if (p0 >= 0 && p0 < L) { a = fmaf((z[r * L + p0] - mean) * rstd, g, be); y[r * L + p0] = a; }
     if (p1 >= 0 && p1 < L) { b = fmaf((z[r * L + p1] - mean) * rstd, g, be); y[r * L + p1] = b; }
-    pooled[i] = fmaxf(a, b);
+    pooled[i] = pool_max(a, b);
   }
 }
-// dx[p] = dskip[p] + (p is the arg-max of its window ? dpool[window] : 0); the first of two equal values wins, as in torch
+// dx[p] = dskip[p] + (p is the arg-max of its window ? dpool[window] : 0); the first of two equal values wins, as in torch; a NaN is the
+// maximum of its pair (pool_max), so the gradient goes to the first NaN of the pair
 __global__ void usleep_maxpool_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dpool, const float* __restrict__ dskip,
                                           float* __restrict__ dx, long nrows, int L, int Lo) {
   const int odd = L & 1;
@@ -130,7 +133,7 @@ __global__ void usleep_maxpool_bwd_kernel(const float* __restrict__ x, const flo
     float g = 0.f;
     if (o < Lo) {
       const float a = (p0 >= 0 && p0 < L) ? x[r * L + p0] : 0.f, b = (p1 >= 0 && p1 < L) ? x[r * L + p1] : 0.f;
-      const int win = a >= b ? p0 : p1;
+      const int win = (a != a || a >= b) ? p0 : p1;       // b NaN, a not: a >= b is false
       if (win == p) g = dpool[r * Lo + o];
     }
     dx[i] = dskip ? dskip[i] + g : g;
@@ -564,40 +567,54 @@ int clf_backward(eegldm_ctx* ctx, const float* x, const ClfW& P, const ClfG& G, 
   return 0;
 }
 
-int launch_conv_train(eegldm_usleep* u, const ConvSrc& s, const UConv& c, int left, float* z, double* part, int B) {
+// (the layer helpers take plain pointers: the model passes slices of its flat parameter / buffer arrays, usleep_layer_train_entry its own)
+int launch_conv_train(eegldm_ctx* ctx, const ConvSrc& s, const float* w, const float* bias, int cout, int k, int left, float* z, double* part, int B,
+                      long* launches) {
   const long rows = (long)B * s.L;
-  const dim3 grid((unsigned)((rows + UROWS - 1) / UROWS), (unsigned)((c.cout + UCO - 1) / UCO));
-  const float* w = u->params + c.w; const float* bias = u->params + c.b;
-#define TL(KT) hipLaunchKernelGGL((usleep_conv_train_kernel<KT>), grid, dim3(UT), 0, u->ctx->stream, s, w, bias, z, part, rows, c.cout, c.k, left)
-  KSWITCH(c.k, TL)
+  const dim3 grid((unsigned)((rows + UROWS - 1) / UROWS), (unsigned)((cout + UCO - 1) / UCO));
+#define TL(KT) hipLaunchKernelGGL((usleep_conv_train_kernel<KT>), grid, dim3(UT), 0, ctx->stream, s, w, bias, z, part, rows, cout, k, left)
+  KSWITCH(k, TL)
 #undef TL
-  LAUNCH_CHECK(); ++u->launches;
+  LAUNCH_CHECK(); ++*launches;
   return 0;
 }
-// conv -> ELU -> train-mode BatchNorm of one layer, taped; pooled != nullptr: the encoder's pad + MaxPool(2) rides on the affine pass
+inline int pooled_len(int L) { return (L + ((L & 1) ? 2 : 0)) / 2; }
+// conv -> ELU -> train-mode BatchNorm of one layer: z, stat (mean | rstd) and y (B, cout, L) written, the running statistics at d's offsets in
+// `buffers` updated; pooled != nullptr (B, cout, pooled_len(L)): the encoder's pad + MaxPool(2) rides on the affine pass
+int conv_elu_bn_train(eegldm_ctx* ctx, const ConvSrc& s, const float* w, const float* bias, int cout, int k, const BnDesc& d, const float* gamma,
+                      const float* beta, float* buffers, float* z, float* stat, float* y, float* pooled, int B, long* launches) {
+  const long rows = (long)B * s.L, n = rows * cout, nblk = (rows + UROWS - 1) / UROWS;
+  float* scratch; EEG_TRY(eeg_det_buffer(ctx, sizeof(double) * 2 * (size_t)nblk * cout, &scratch));
+  double* part = (double*)scratch;
+  EEG_TRY(launch_conv_train(ctx, s, w, bias, cout, k, (k - 1) / 2, z, part, B, launches));
+  hipLaunchKernelGGL(usleep_bn_stats_kernel, dim3((unsigned)cout), dim3(UT), 0, ctx->stream, d, part, nblk, buffers, stat, (double)rows, 1e-5f, 0.1f);
+  LAUNCH_CHECK(); ++*launches;
+  if (pooled) {
+    const int Lo = pooled_len(s.L);
+    hipLaunchKernelGGL(usleep_bn_apply_pool_kernel, dim3(ew_blocks((long)B * cout * Lo)), dim3(256), 0, ctx->stream, z, stat, gamma, beta, y, pooled,
+                       (long)B * cout, cout, s.L, Lo);
+  } else {
+    hipLaunchKernelGGL(usleep_bn_apply_kernel, dim3(ew_blocks(n)), dim3(256), 0, ctx->stream, z, stat, gamma, beta, y, n, cout, s.L);
+  }
+  LAUNCH_CHECK(); ++*launches;
+  return 0;
+}
+// the same, taped in the model's arena
 int layer_train(eegldm_usleep* u, const ConvSrc& s, const UConv& c, int bn_idx, int B, float** y_out, float** pooled_out, int* Lo_out) {
   const BnDesc& d = u->bns[bn_idx];
-  const long rows = (long)B * s.L, n = rows * c.cout, nblk = (rows + UROWS - 1) / UROWS;
+  const long n = (long)B * s.L * c.cout;
   ULayerTape t; t.src = s; t.c = c; t.bn = bn_idx; t.pool_Lo = 0;
   ALLOC_OR_FAIL(t.z, u->arena.alloc(sizeof(float) * (size_t)n));
   ALLOC_OR_FAIL(t.y, u->arena.alloc(sizeof(float) * (size_t)n));
   ALLOC_OR_FAIL(t.stat, u->arena.alloc(sizeof(float) * 2 * (size_t)c.cout));
-  float* scratch; EEG_TRY(eeg_det_buffer(u->ctx, sizeof(double) * 2 * (size_t)nblk * c.cout, &scratch));
-  double* part = (double*)scratch;
-  EEG_TRY(launch_conv_train(u, s, c, (c.k - 1) / 2, t.z, part, B));
-  hipLaunchKernelGGL(usleep_bn_stats_kernel, dim3((unsigned)c.cout), dim3(UT), 0, u->ctx->stream, d, part, nblk, u->buffers, t.stat, (double)rows, 1e-5f, 0.1f);
-  LAUNCH_CHECK(); ++u->launches;
-  const float* gamma = u->params + d.w; const float* beta = u->params + d.b;
+  float* p = nullptr;
   if (pooled_out) {
-    const int Lo = (s.L + ((s.L & 1) ? 2 : 0)) / 2;
-    float* p; ALLOC_OR_FAIL(p, u->arena.alloc(sizeof(float) * (size_t)B * c.cout * Lo));
-    hipLaunchKernelGGL(usleep_bn_apply_pool_kernel, dim3(ew_blocks((long)B * c.cout * Lo)), dim3(256), 0, u->ctx->stream, t.z, t.stat, gamma, beta, t.y, p,
-                       (long)B * c.cout, c.cout, s.L, Lo);
+    const int Lo = pooled_len(s.L);
+    ALLOC_OR_FAIL(p, u->arena.alloc(sizeof(float) * (size_t)B * c.cout * Lo));
     *pooled_out = p; *Lo_out = Lo; t.pool_Lo = Lo;
-  } else {
-    hipLaunchKernelGGL(usleep_bn_apply_kernel, dim3(ew_blocks(n)), dim3(256), 0, u->ctx->stream, t.z, t.stat, gamma, beta, t.y, n, c.cout, s.L);
   }
-  LAUNCH_CHECK(); ++u->launches;
+  EEG_TRY(conv_elu_bn_train(u->ctx, s, u->params + c.w, u->params + c.b, c.cout, c.k, d, u->params + d.w, u->params + d.b, u->buffers, t.z, t.stat, t.y, p, B,
+                            &u->launches));
   *y_out = t.y;
   u->tape.push_back(t);
   return 0;
@@ -721,6 +738,21 @@ int backward(eegldm_usleep* u, const float* dy_pred, float* dx) {
   return 0;
 }
 }  // namespace
+
+int usleep_layer_train_entry(eegldm_ctx* ctx, const float* a, int Ca, int La, int ups, const float* b2, int Cb, int Lb, int L, const float* w,
+                             const float* bias, const float* gamma, const float* beta, float* buffers, int B, int Cout, int K, float* y, float* pooled,
+                             float* z, float* stat) {
+  const ConvSrc s = {a, Ca, La, ups, b2, Cb, Lb, L};
+  EEG_TRY(src_check(s, K));
+  BnDesc d; d.C = Cout; d.w = 0; d.b = 0; d.rm = 0; d.rv = Cout; d.nbt = 2 * (long)Cout; d.fold = 0;
+  float* tmp = nullptr;                                     // the tape's z and stat when the caller does not ask for them
+  const size_t nz = (size_t)B * Cout * L;
+  if (!z || !stat) HIP_TRY(hipMalloc(&tmp, sizeof(float) * (nz + 2 * (size_t)Cout)));
+  long launches = 0;
+  const int rc = conv_elu_bn_train(ctx, s, w, bias, Cout, K, d, gamma, beta, buffers, z ? z : tmp, stat ? stat : tmp + nz, y, pooled, B, &launches);
+  if (tmp) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(tmp); }
+  return rc;
+}
 
 extern "C" int eegldm_usleep_bind_grads(eegldm_usleep* u, float* grads) {
   EEG_CHECK(u && grads, "null argument");

@@ -141,6 +141,7 @@ class USleep:
                 raise ValueError("time_conv_size must be an odd number to accomodate the upsampling step in the decoder blocks.")   # usleep.py:160-163
         self.in_chans, self.depth, self.n_classes, self.apply_softmax = in_chans, depth, n_classes, apply_softmax
         self.input_size = int(np.ceil(input_size_s * sfreq))
+        self.with_skip_connection = bool(with_skip_connection)
         self.ctx = ctx or default_context(device if isinstance(device, int) else torch.device(device).index or 0)
         self.device = torch.device("cuda", self.ctx.device)
         cfg = USleepCfg(in_chans, depth, n_time_filters, n_classes, k, self.input_size, 1 if with_skip_connection else 0, float(complexity_factor))
@@ -210,6 +211,13 @@ class USleep:
     def to(self, *a, **k):
         return self
 
+    def _decoder_len(self, T):
+        """Length of the decoder output: T with the skip connections (every block is cropped to its skip); without them nothing is cropped and
+        it is the bottleneck length doubled `depth` times, longer than T unless T is a multiple of 2^depth."""
+        if self.with_skip_connection:
+            return T
+        return usleep_bottleneck_length(T, self.depth) << self.depth
+
     def forward(self, x, features_only=False):
         """(B, C, T) or (B, S, C, T) -> (y_pred, decoder output, bottleneck) as usleep.py:249-287; `features_only` skips the decoder and
         returns (None, None, bottleneck)."""
@@ -230,8 +238,9 @@ class USleep:
             return None, None, bottom
         if T < self.input_size:
             raise ValueError(f"T={T} is shorter than input_size={self.input_size} (the classifier's AvgPool1d window)")
-        S = T // self.input_size
-        y = torch.empty(B, self.n_classes, S, device=self.device); dec = torch.empty(B, self.channels[1], T, device=self.device)
+        Ld = self._decoder_len(T)
+        S = Ld // self.input_size
+        y = torch.empty(B, self.n_classes, S, device=self.device); dec = torch.empty(B, self.channels[1], Ld, device=self.device)
         check(lib.eegldm_usleep_forward(self.h, ptr(x), ptr(y), ptr(dec), ptr(bottom), B, T, 1 if self.training else 0))
         if self.apply_softmax:
             y = torch.softmax(y, dim=1)
@@ -258,6 +267,9 @@ class USleep:
             raise ValueError(f"USleep expects (B, {self.in_chans}, T) or (B, S, {self.in_chans}, T), got {tuple(x.shape)}")
         B, _c, T = x.shape
         check_train_shapes(B, T, self.depth, self.input_size)
+        if self._decoder_len(T) != T:
+            raise ValueError(f"training without skip connections needs T to be a multiple of 2^depth = {1 << self.depth} (the logits and dx are laid out "
+                             f"for a decoder output of length T; T={T} gives {self._decoder_len(T)})")
         return x.contiguous(), B, T
 
     def forward_train(self, x):

@@ -38,36 +38,11 @@ def rnd(shape, seed, scale=1.0):
 
 
 # ---------------------------------------------------------------------------------------------------- convolution backward
-def conv_ref(a, b2, w, bias, ups, L):
-    """The forward's virtual input [a (nearest x2 when ups) | b2], both cropped to L, through conv1d 'same' (even K: extra zero on the right)."""
-    v = F.interpolate(a, scale_factor=2, mode="nearest") if ups else a
-    v = v[..., :L]
-    if b2 is not None:
-        v = torch.cat([v, b2[..., :L]], 1)
-    K = w.shape[-1]; left = (K - 1) // 2
-    return F.conv1d(F.pad(v, (left, K - 1 - left)), w, bias)
+from usleep_reference import ROWS, conv_case, conv_ref  # noqa: E402  (shared with tests/test_gpu_usleep_fwd.py)
 
-
-ROWS = {1: (1, 1), 63: (3, 21), 64: (2, 32), 65: (5, 13), 130: (5, 26)}     # B * L -> (B, L): odd and even lengths, tiles ending inside samples
 BASE = dict(rows=65, Cout=17, Cin=33, K=7)
 SWEEP = [dict(BASE, rows=r) for r in ROWS] + [dict(BASE, Cout=c) for c in (1, 4, 15, 16, 17)] + [dict(BASE, Cin=c) for c in (1, 31, 32, 33, 65)] + \
         [dict(BASE, K=k) for k in (1, 2, 3, 7, 9, 13)] + [dict(rows=130, Cout=16, Cin=65, K=13), dict(rows=1, Cout=1, Cin=1, K=2), dict(rows=64, Cout=4, Cin=32, K=9)]
-
-
-def conv_case(form, rows, Cout, Cin, K, seed):
-    B, L = ROWS[rows]
-    if form == "plain":
-        Ca, La, ups, Cb, Lb = Cin, L + (seed % 2), 0, 0, 0           # (every other case: one cropped-off position at the end of a)
-    elif form == "ups":
-        Ca, La, ups, Cb, Lb = Cin, (L + 1) // 2, 1, 0, 0             # L = 2 La (even) or 2 La - 1 (odd: the last doubled sample is cropped)
-    else:                                                            # upsampled + concatenated skip; odd L: the skip is one sample shorter than 2 La
-        Ca = max(1, Cin // 2); Cb = Cin - Ca; ups = 1               # even L: the skip is one sample longer and is the one cropped
-        La, Lb = (L + 1) // 2, (L if L % 2 else L + 1)
-    a = rnd((B, Ca, La), seed)
-    b2 = rnd((B, Cb, Lb), seed + 1) if Cb else None
-    w = rnd((Cout, Cin, K), seed + 2, 1.0 / np.sqrt(Cin * K))
-    dz = rnd((B, Cout, L), seed + 3)
-    return dict(B=B, L=L, Ca=Ca, La=La, ups=ups, Cb=Cb, Lb=Lb, a=a, b2=b2, w=w, dz=dz, Cout=Cout, K=K)
 
 
 def conv_ref_grads(c, absolute=False):
@@ -243,6 +218,36 @@ def test_maxpool_bwd_exact(L):
         check(lib.eegldm_usleep_maxpool_bwd(ctx.h, ptr(x_d), ptr(dpool_d), ptr(skip_d), ptr(dx), nrows, L))
         torch.cuda.synchronize()
         assert torch.equal(dx.cpu(), want if skip is None else want + skip), (L, skip is not None)
+    # NaN rows: a NaN is the maximum of its pair (the forward's pool_max), so its position takes the gradient.  One NaN per pair is judged against
+    # torch (first or second position of a pair, against the pad at both ends of an odd row, against +-inf); where BOTH values of a pair are NaN
+    # the gradient goes to the first, the rule of usleep_train.hip (torch's CPU kernel picks the second there).
+    nan = float("nan")
+    xn = x.clone()
+    xn[6, 0] = nan; xn[7, L - 1] = nan; xn[8, 0] = nan
+    if L != 2:                                                  # (at L = 2 the two ends are one pair)
+        xn[8, L - 1] = nan
+    xn[9, 0] = float("inf"); xn[10, L - 1] = float("-inf"); xn[11, 0] = float("inf"); xn[11, L - 1] = nan
+    if L >= 3:
+        xn[12, 1] = nan; xn[13, 2] = nan; xn[14, L // 2] = nan
+    want = maxpool_ref(xn, dpool)
+    odd = L % 2
+    both = torch.zeros(nrows, L, dtype=torch.bool)
+    if L >= 3:
+        p0 = 2 - odd                                            # a pair inside the row: padded window 1 -> positions p0, p0 + 1
+        xn[15, p0] = nan; xn[15, p0 + 1] = nan; xn[16] = nan
+        want = maxpool_ref(xn, dpool)
+        for r in (15, 16):                                      # both NaN: first position takes dpool, the second nothing
+            for o in range(Lo):
+                q0 = 2 * o - odd
+                if 0 <= q0 and q0 + 1 < L and bool(torch.isnan(xn[r, q0])) and bool(torch.isnan(xn[r, q0 + 1])):
+                    want[r, q0] = dpool[r, o]; want[r, q0 + 1] = 0.0; both[r, q0] = True
+    assert int(torch.isnan(xn).sum()) >= 4 and (L < 3 or bool(both.any()))
+    assert float(want[6, 0]) == float(dpool[6, 0]) and float(want[7, L - 1]) == float(dpool[7, Lo - 1])     # the NaN, not its partner or the pad
+    dx = torch.full((nrows, L), float("nan"), device=DEV)
+    x_d, dpool_d = dev(xn), dev(dpool)
+    check(lib.eegldm_usleep_maxpool_bwd(ctx.h, ptr(x_d), ptr(dpool_d), None, ptr(dx), nrows, L))
+    torch.cuda.synchronize()
+    assert torch.equal(dx.cpu(), want), (L, "NaN rows", (dx.cpu() != want).nonzero()[:4].tolist())
 
 
 # ---------------------------------------------------------------------------------------------------- classifier head + loss
