@@ -1075,6 +1075,35 @@ int eegldm_stft_power(eegldm_ctx*, const float* x, long ldx, long B, long L, con
 int eegldm_pac_intervals(eegldm_ctx*, const float* pr, long ldr, const float* pi, long ldi, const float* amp, long lda, long B, long L,
                          const int* iv, long NI, double* out);
 
+/* ---- signal-complexity primitives (Hjorth parameters, permutation entropy, sample entropy of eegldm.metrics; csrc/complexity.hip).  fp32
+ * rows of L samples in 1..4096 with row stride ldx >= L floats; additive, ABI 8.  Float pointers need 4-byte alignment only, the int64 and
+ * double outputs 8.  B == 0 is a no-op.  Every refusal returns its code, sets eegldm_last_error, launches nothing and leaves the outputs
+ * untouched; no output has to be zeroed by the caller.  A row's result does not depend on B, on the other rows or on the launch geometry, and
+ * a result repeats bit for bit: the integer results make every summation order exact, the float64 ones use a fixed order.
+ * eegldm_row_moments: out [B][8] = (mean, m2_x, m2_d1, m2_d2, line_length, sign_changes, min, max), every term float64 formed from the fp32
+ * samples.  d1[n] = x[n+1] - x[n], d2[n] = d1[n+1] - d1[n]; mean_v = (sum v) / count; m2_v = sum (v - mean_v)^2 about that mean, in a second pass
+ * over the LDS-resident row (0 for an empty and for a finite one-element v); line_length = sum |d1|; sign_changes = #{n in [1, L) : (c[n-1] < 0)
+ * != (c[n] < 0)}, c = x - mean; min / max by exact fp32 comparison, both NaN when the row holds a NaN.  A non-finite sample propagates by IEEE
+ * rules into the moments it enters; other rows keep their bits.  Hjorth activity, mobility and complexity are host algebra on this table:
+ * var = m2 / count, mobility = sqrt(var_d1 / var_x), complexity = sqrt(var_d2 / var_d1) / mobility. */
+int eegldm_row_moments(eegldm_ctx*, const float* x, long ldx, long B, int L, double* out /* [B][8] */);
+/* eegldm_ordinal_counts: ordinal-pattern histogram.  order in 2..6, delay >= 1, (order - 1) * delay < L.  For every position p in
+ * [0, L - (order - 1) delay) with v_k = x[p + k delay], k < order: the pattern index is the Lehmer code sum_k c_k (order - 1 - k)!, c_k =
+ * #{l > k : v_l < v_k}, by exact fp32 `<` (ties rank by position, -0 == +0); counts [B][order!] holds the positions per index.  A position
+ * whose vector holds a NaN or an infinity is counted in skipped [B] and in no bin.  Permutation entropy -sum p ln p (optionally / ln(order!))
+ * is host float64 algebra on the counts. */
+int eegldm_ordinal_counts(eegldm_ctx*, const float* x, long ldx, long B, int L, int order, int delay, int* counts /* [B][order!] */,
+                          int* skipped /* [B] */);
+/* eegldm_template_matches: the pair counts of (multiscale) sample entropy.  m in 1..4, scale in 1..64, N = L / scale with N - m >= 2; r is a
+ * DEVICE array [B] of tolerances.  y[j] = (x[j s] + ... + x[j s + s - 1]) / (float)s, the sum in fp32 in ascending order from +0, one IEEE
+ * divide (scale 1: y compares as x; samples past N s are not read).  Templates are i in [0, N - m), the same set for both lengths (Richman
+ * and Moorman 2000).  counts [B][2]:
+ *   counts[b][0] = #{i < j : |y[i+k] - y[j+k]| <= r[b] for all k < m},   counts[b][1] = the same for all k <= m.
+ * The test is fabsf(a - b) <= r with one fp32 rounding of the difference: anything with a NaN in y or r, and inf - inf, is no match; r = inf
+ * matches every pair that produces no NaN; a negative r matches nothing.  SampEn = -ln(counts[b][1] / counts[b][0]) is host algebra. */
+int eegldm_template_matches(eegldm_ctx*, const float* x, long ldx, long B, int L, int m, int scale, const float* r /* device [B] */,
+                            long long* counts /* [B][2] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -244,6 +244,9 @@ SIGNATURES = {
     "eegldm_stft_num_frames": [_l, _i, _i, _i],
     "eegldm_stft_power": [_vp, _vp, _l, _l, _l, _vp, C.POINTER(_f), _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp, C.POINTER(_i), _i, _vp],
     "eegldm_pac_intervals": [_vp, _vp, _l, _vp, _l, _vp, _l, _l, _l, _vp, _l, _vp],
+    "eegldm_row_moments": [_vp, _vp, _l, _l, _i, _vp],
+    "eegldm_ordinal_counts": [_vp, _vp, _l, _l, _i, _i, _i, _vp, _vp],
+    "eegldm_template_matches": [_vp, _vp, _l, _l, _i, _i, _i, _vp, _vp],
     "eegldm_resblock_create": [_vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)],
     "eegldm_attnblock_create": [_vp, _i, _i, _i, C.POINTER(_vp)],
     "eegldm_block_destroy": [_vp],

@@ -10,6 +10,8 @@ evaluation code uses:
 * `band_powers`: integrates a PSD over the classical sleep-EEG bands.
 * `stft_power`, `spectrogram`, `band_course_stats`, `spindle_so_coupling`: how the spectrum moves in time, and phase-amplitude coupling
   (csrc/tfr.hip; the section "time-frequency" below).
+* `row_moments`, `hjorth`, `ordinal_counts`, `permutation_entropy`, `template_match_counts`, `sample_entropy`, `complexity_features`,
+  `compare_features`: how regular a window is (csrc/complexity.hip; the section "signal complexity" below).
 * `USleep(...)` (forward, `train_step`, `backward`, `predict`), `fid_features(model, windows)`, `FIDMetric()(y_pred, y)`, `FeatureMoments`
 * `balanced_class_weights(labels, n_classes)`, `stage_report(pred, true)`: class weights and the scores of a sleep stager (host numpy)
   -- the FID of /root/reference/src/compute_fid.py:341-419: the U-Sleep feature extractor (/root/reference/src/models/usleep.py:101-287,
@@ -1749,4 +1751,239 @@ def compare_coupling(real, fake):
     ok = a.size > 0 and b.size > 0
     out["mvl"] = {"n_real": int(a.size), "n_synthetic": int(b.size), "ks": ks_statistic(a, b) if ok else None,
                   "wasserstein": wasserstein_1d(a, b) if ok else None}
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- signal complexity
+# How REGULAR a window is: Hjorth parameters, permutation entropy and (multiscale) sample entropy, on three device primitives
+# (csrc/complexity.hip): eegldm_row_moments, float64 two-pass moments of a row and of its first and second differences;
+# eegldm_ordinal_counts, the histogram of ordinal patterns; eegldm_template_matches, the O(L^2) pair counts of sample entropy with the
+# coarse-graining of the multiscale variant fused in.  As above: what is not a pass over the samples is float64 numpy in functions that take
+# tables as input, and every refusal is a ValueError before the device is touched.  The loader's 3072-sample windows lose their zero pads first.
+# NOBODY HAS MEASURED WHAT THESE FEATURES SHOW ON THIS PROJECT'S 18-Hz-LOW-PASSED DATA: they are offered as distributions to compare, not as
+# detectors of stages or of bad samples.
+CX_MAX_LEN, CX_MIN_ORDER, CX_MAX_ORDER, CX_MAX_M, CX_MAX_SCALE = 4096, 2, 6, 4, 64
+MOMENT_FIELDS = ("mean", "m2_x", "m2_d1", "m2_d2", "line_length", "sign_changes", "min", "max")
+R_MODES = ("sd", "abs")
+
+
+def _as_int(v, name):
+    if isinstance(v, bool) or int(v) != v:
+        raise ValueError(f"{name} must be an integer, got {v!r}")
+    return int(v)
+
+
+def _cx_rows(windows, name="windows", min_len=1):
+    w = _windows2d(windows, name)
+    if not min_len <= int(w.shape[1]) <= CX_MAX_LEN:
+        raise ValueError(f"{name}: rows of {min_len}..{CX_MAX_LEN} samples are taken, got {int(w.shape[1])}")
+    return w
+
+
+def _check_ordinal_args(length, order, delay):
+    order, delay = _as_int(order, "order"), _as_int(delay, "delay")
+    if not CX_MIN_ORDER <= order <= CX_MAX_ORDER:
+        raise ValueError(f"order must lie in {CX_MIN_ORDER}..{CX_MAX_ORDER}, got {order}")
+    if delay < 1:
+        raise ValueError(f"delay must be >= 1, got {delay}")
+    if (order - 1) * delay >= int(length):
+        raise ValueError(f"(order - 1) * delay = {(order - 1) * delay} leaves no position in a row of {length} samples")
+    return order, delay
+
+
+def _check_template_args(length, m, scale):
+    m, scale = _as_int(m, "m"), _as_int(scale, "scale")
+    if not 1 <= m <= CX_MAX_M:
+        raise ValueError(f"m must lie in 1..{CX_MAX_M}, got {m}")
+    if not 1 <= scale <= CX_MAX_SCALE:
+        raise ValueError(f"scale must lie in 1..{CX_MAX_SCALE}, got {scale}")
+    if int(length) // scale - m < 2:
+        raise ValueError(f"a row of {length} samples at scale {scale} has {int(length) // scale} points: m = {m} needs at least {m + 2}")
+    return m, scale
+
+
+def _check_r(r, n=None):
+    """A positive finite tolerance, or one per row: (n,) float32."""
+    a = np.asarray(r.detach().cpu().numpy() if torch.is_tensor(r) else r, np.float64)
+    if a.ndim > 1 or (a.ndim == 1 and n is not None and a.shape != (n,)) or (a.ndim == 1 and n is None):
+        raise ValueError(f"r must be a float{'' if n is None else f' or ({n},)'}, got shape {a.shape}")
+    with np.errstate(over="ignore"):
+        a32 = a.astype(np.float32)                              # as uploaded
+    if not (np.all(np.isfinite(a32)) and np.all(a32 > 0)):
+        raise ValueError("r must be positive and finite (as fp32)")
+    return a32
+
+
+def _moments_dev(x, ctx):
+    out = torch.empty(x.shape[0], 8, dtype=torch.float64, device=x.device)
+    if x.shape[0]:
+        check(lib.eegldm_row_moments(ctx.h, ptr(x), _ld(x), int(x.shape[0]), int(x.shape[1]), ptr(out)))
+    return out
+
+
+def row_moments(windows, ctx=None):
+    """(N, 8) float64 numpy, columns MOMENT_FIELDS: mean, the central sums of squares of the row, of its first and of its second differences
+    (two passes, float64), line length sum |d1|, sign changes of x - mean, min, max (eegldm_row_moments; include/eegldm.h has the definition)."""
+    w = _cx_rows(windows)
+    ctx = ctx or default_context(0)
+    return _moments_dev(_dev_rows(w, torch.device("cuda", ctx.device)), ctx).cpu().numpy()
+
+
+def hjorth_from_moments(table, length):
+    """(N, 3) float64 = (activity, mobility, complexity) from `row_moments`' table of rows of `length` >= 3 samples: activity = var x, mobility =
+    sqrt(var d1 / var x), complexity = sqrt(var d2 / var d1) / mobility, population variances m2 / count.  A constant row gives NaN (0 / 0)."""
+    t = np.asarray(table, np.float64).reshape(-1, 8)
+    n = _as_int(length, "length")
+    if n < 3:
+        raise ValueError(f"Hjorth parameters need rows of at least 3 samples, got {n}")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v0, v1, v2 = t[:, 1] / n, t[:, 2] / (n - 1), t[:, 3] / (n - 2)
+        mob = np.sqrt(v1 / v0)
+        return np.stack([v0, mob, np.sqrt(v2 / v1) / mob], 1)
+
+
+def hjorth(windows, ctx=None):
+    """Hjorth activity, mobility and complexity of every window: (N, 3) float64 numpy (`row_moments` + `hjorth_from_moments`)."""
+    w = _cx_rows(windows, min_len=3)
+    return hjorth_from_moments(row_moments(w, ctx=ctx), int(w.shape[1]))
+
+
+def ordinal_counts(windows, order=3, delay=1, ctx=None):
+    """(counts (N, order!) int32, skipped (N,) int32) numpy: how often each ordinal pattern of `order` samples `delay` apart occurs in a window
+    (index = Lehmer code, ties rank by position), and the positions left out because they hold a NaN or an infinity (eegldm_ordinal_counts)."""
+    w = _cx_rows(windows)
+    order, delay = _check_ordinal_args(w.shape[1], order, delay)
+    ctx = ctx or default_context(0)
+    dev = torch.device("cuda", ctx.device)
+    x = _dev_rows(w, dev)
+    nb = int(np.prod(np.arange(1, order + 1)))
+    counts = torch.empty(x.shape[0], nb, dtype=torch.int32, device=dev)
+    skipped = torch.empty(x.shape[0], dtype=torch.int32, device=dev)
+    if x.shape[0]:
+        check(lib.eegldm_ordinal_counts(ctx.h, ptr(x), _ld(x), int(x.shape[0]), int(x.shape[1]), order, delay, ptr(counts), ptr(skipped)))
+    return counts.cpu().numpy(), skipped.cpu().numpy()
+
+
+def permutation_entropy_from_counts(counts, normalize=True):
+    """-sum p ln p of every row of a pattern histogram (N, order!), p = counts / their sum, 0 ln 0 = 0; divided by ln(order!) when normalize.
+    A row without a counted position gives NaN."""
+    c = np.asarray(counts, np.float64)
+    if c.ndim != 2 or c.shape[1] < 2:
+        raise ValueError(f"counts (N, order!) expected, got shape {c.shape}")
+    tot = c.sum(1, keepdims=True)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = c / tot
+        h = -np.sum(np.where(c > 0, p * np.log(np.where(c > 0, p, 1.0)), 0.0), 1)
+    h = np.where(tot[:, 0] > 0, h, np.nan)
+    return h / np.log(c.shape[1]) if normalize else h
+
+
+def permutation_entropy(windows, order=3, delay=1, normalize=True, ctx=None):
+    """Permutation entropy (Bandt and Pompe 2002) of every window: (N,) float64, in [0, 1] when normalize."""
+    return permutation_entropy_from_counts(ordinal_counts(windows, order, delay, ctx=ctx)[0], normalize)
+
+
+def _template_counts_dev(x, r_dev, m, scale, ctx):
+    counts = torch.empty(x.shape[0], 2, dtype=torch.int64, device=x.device)
+    if x.shape[0]:
+        check(lib.eegldm_template_matches(ctx.h, ptr(x), _ld(x), int(x.shape[0]), int(x.shape[1]), m, scale, ptr(r_dev), ptr(counts)))
+    return counts
+
+
+def template_match_counts(windows, m=2, r=None, scale=1, ctx=None):
+    """(N, 2) int64 numpy = (B, A): the pairs of templates i < j of the window coarse-grained by `scale` that match within the absolute
+    tolerance r (a float or (N,)) at length m and at length m + 1, over the same N / scale - m templates (eegldm_template_matches)."""
+    w = _cx_rows(windows)
+    m, scale = _check_template_args(w.shape[1], m, scale)
+    if r is None:
+        raise ValueError("r, the absolute tolerance (a float or one per window), is needed")
+    r32 = _check_r(r, int(w.shape[0]))
+    if r32.ndim == 0:
+        r32 = np.full(int(w.shape[0]), r32, np.float32)
+    ctx = ctx or default_context(0)
+    dev = torch.device("cuda", ctx.device)
+    return _template_counts_dev(_dev_rows(w, dev), torch.from_numpy(r32).to(dev), m, scale, ctx).cpu().numpy()
+
+
+def sample_entropy_from_counts(counts):
+    """SampEn = -ln(A / B) of (..., 2) = (B, A) pair counts, float64: NaN where B == 0 (nothing to condition on), +inf where A == 0 < B."""
+    c = np.asarray(counts, np.float64)
+    if c.shape[-1] != 2:
+        raise ValueError(f"counts (..., 2) expected, got shape {c.shape}")
+    b, a = c[..., 0], c[..., 1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(b > 0, -np.log(np.where(b > 0, a / np.where(b > 0, b, 1.0), 1.0)), np.nan)
+
+
+def _check_scales(length, m, scales):
+    s = tuple(scales) if np.ndim(scales) else (scales,)
+    if not s:
+        raise ValueError("at least one scale is needed")
+    return tuple(_check_template_args(length, m, v)[1] for v in s)
+
+
+def sample_entropy(windows, m=2, r=0.2, r_mode="sd", scales=(1,), ctx=None):
+    """(Multiscale) sample entropy (Richman and Moorman 2000; Costa et al. 2002) of every window: (N, len(scales)) float64 numpy.  r_mode "sd":
+    the tolerance is r times the population standard deviation of the RAW window at every scale (Costa's convention), taken on the device from
+    the moments table; "abs": r is the tolerance itself."""
+    w = _cx_rows(windows)
+    if r_mode not in R_MODES:
+        raise ValueError(f"r_mode must be one of {R_MODES}, got {r_mode!r}")
+    m = _check_template_args(w.shape[1], m, 1)[0]
+    scales = _check_scales(w.shape[1], m, scales)
+    _check_r(r)
+    ctx = ctx or default_context(0)
+    dev = torch.device("cuda", ctx.device)
+    x = _dev_rows(w, dev)
+    if r_mode == "sd":                                          # float64 on the device, one rounding to the fp32 the kernel compares with
+        r_dev = (float(r) * torch.sqrt(_moments_dev(x, ctx)[:, 1] / float(x.shape[1]))).float()
+    else:
+        r_dev = torch.full((x.shape[0],), float(r), dtype=torch.float32, device=dev)
+    counts = torch.stack([_template_counts_dev(x, r_dev, m, s, ctx) for s in scales], 1)
+    return sample_entropy_from_counts(counts.cpu().numpy())
+
+
+def complexity_feature_names(orders=(3, 4, 5), scales=(1, 2, 5, 10, 20)):
+    return (["activity", "mobility", "complexity", "sign_change_rate", "line_length_per_sample"] + [f"perm_entropy_o{int(o)}" for o in orders]
+            + [f"sample_entropy_s{int(s)}" for s in scales])
+
+
+def complexity_features(windows, orders=(3, 4, 5), delay=1, m=2, r=0.2, r_mode="sd", scales=(1, 2, 5, 10, 20), ctx=None):
+    """(features (N, F) float64 numpy, names): Hjorth activity, mobility and complexity, sign changes of x - mean and line length per
+    difference (both / (L - 1)), normalised permutation entropy at `orders`, sample entropy at `scales`.  Rows are windows: the matrix goes
+    into `mmd2`, `kid`, `knn` and `precision_recall_coverage` as it is (drop non-finite rows first), a column into `compare_features`."""
+    w = _cx_rows(windows, min_len=3)
+    length = int(w.shape[1])
+    orders = tuple(orders) if np.ndim(orders) else (orders,)
+    orders = tuple(_check_ordinal_args(length, o, delay)[0] for o in orders)
+    delay = _as_int(delay, "delay")
+    if r_mode not in R_MODES:
+        raise ValueError(f"r_mode must be one of {R_MODES}, got {r_mode!r}")
+    m = _check_template_args(length, m, 1)[0]
+    scales = _check_scales(length, m, scales)
+    _check_r(r)
+    ctx = ctx or default_context(0)
+    w = _dev_rows(w, torch.device("cuda", ctx.device))
+    mom = row_moments(w, ctx=ctx)
+    cols = [hjorth_from_moments(mom, length), mom[:, 5:6] / (length - 1), mom[:, 4:5] / (length - 1)]
+    cols += [permutation_entropy(w, o, delay, True, ctx=ctx)[:, None] for o in orders]
+    if scales:
+        cols.append(sample_entropy(w, m, r, r_mode, scales, ctx=ctx))
+    return np.concatenate(cols, 1), complexity_feature_names(orders, scales)
+
+
+def compare_features(real, fake, names):
+    """Per column of two feature matrices (N_real, F) and (N_fake, F): the two-sample KS statistic and the 1-D Wasserstein distance over the
+    FINITE values of each side (None where a side has none), with the counts of finite and of non-finite values beside them."""
+    a, b = np.asarray(real, np.float64), np.asarray(fake, np.float64)
+    names = list(names)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != len(names) or b.shape[1] != len(names):
+        raise ValueError(f"feature matrices (N, {len(names)}) expected, got {a.shape} and {b.shape}")
+    out = {}
+    for k, name in enumerate(names):
+        u, v = a[:, k][np.isfinite(a[:, k])], b[:, k][np.isfinite(b[:, k])]
+        ok = u.size > 0 and v.size > 0
+        out[name] = {"n_real": int(u.size), "n_synthetic": int(v.size), "n_real_nonfinite": int(a.shape[0] - u.size),
+                     "n_synthetic_nonfinite": int(b.shape[0] - v.size), "ks": ks_statistic(u, v) if ok else None,
+                     "wasserstein": wasserstein_1d(u, v) if ok else None}
     return out
