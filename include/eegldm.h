@@ -50,7 +50,8 @@ extern "C" {
  *    and long recordings (eegldm_canvas_gather, eegldm_canvas_step, eegldm_canvas_compose, eegldm_sample_long) and their editing
  *    (eegldm_canvas_edit_step, eegldm_sample_long_edit) and resampled repair (eegldm_edit_jump, eegldm_sample_edit_resample,
  *    eegldm_sample_long_edit_resample) and context conditioning (eegldm_unet_create_ctx, eegldm_unet_set_context, eegldm_context_mask,
- *    eegldm_add_noise_context, eegldm_context_window, eegldm_ldm_train_step_ctx, eegldm_sample_edit_ctx, eegldm_sample_long_edit_ctx). */
+ *    eegldm_add_noise_context, eegldm_context_window, eegldm_ldm_train_step_ctx, eegldm_sample_edit_ctx, eegldm_sample_long_edit_ctx)
+ *    and the developer entries of the fused frozen encoder (eegldm_debug_pre_conv3, eegldm_debug_sample_stats, eegldm_debug_aekl_encode_route). */
 #define EEGLDM_ABI_VERSION 8
 
 /* Storage / operand type of activations and compute-copy weights (accumulation, statistics, master weights and optimizer state are
@@ -132,6 +133,23 @@ int eegldm_debug_dconv_last_route(int which, int* out8_host);
  * instead.  All zero before the first call.  The route-aware tests confirm from it that a case ran on the kernels it names.
  * No reference counterpart. */
 int eegldm_debug_aekl_last_route(const eegldm_aekl*, int* out10_host);
+/* developer aid: what served the last eegldm_aekl_encode on this handle, as three ints: fused frozen-encoder path taken (1: csrc/enc_fused.hip;
+ * 0: the layer-by-layer path, which is also what a shape or dtype that the fused kernels do not cover and EEGLDM_AEKL_NO_FUSED_ENC give),
+ * pre_conv3 launches, sample_stats launches (both 0 on the layer-by-layer path).  All zero before the first call.  Host-side bookkeeping
+ * only.  No reference counterpart. */
+int eegldm_debug_aekl_encode_route(const eegldm_aekl*, int* out3_host);
+/* developer aids: the two kernels of the fused frozen encoder (csrc/enc_fused.hip) alone, as eegldm_aekl_encode chains them.  bf16 / fp16.
+ *   eegldm_debug_pre_conv3     y [B * L][Cout] = bias + conv3(silu(GroupNorm_{G = 1}(x [B * L][Cin]))) (+ resid [B * L][Cout], nullable); zero
+ *                              padding of the ACTIVATED tensor at the sample edges.  in_stats: fp64 [B][2] = (sum, sum of squares) of each
+ *                              sample of x; out_stats (nullable): fp64 [B][2], the same sums of the ROUNDED y are ADDED to it.  w packed
+ *                              [3][Cout][Cin] in `dtype`; gamma, beta, bias fp32.  EEGLDM_ERR_UNSUPPORTED where the eligibility check says no
+ *                              (channel counts other than 32 / 64, L not a multiple of 256, fp32).
+ *   eegldm_debug_sample_stats  stats [B][2] (fp64) += (sum, sum of squares) of each sample of x [B][n_per_sample]; n_per_sample % 8 != 0
+ *                              (samples that are not whole 16-byte chunks) is refused.
+ * No reference counterpart. */
+int eegldm_debug_pre_conv3(eegldm_ctx*, int dtype, const void* x, const double* in_stats, const float* gamma, const float* beta, const void* w,
+                           const float* bias, const void* resid, void* y, double* out_stats, int B, int L, int Cin, int Cout, float eps);
+int eegldm_debug_sample_stats(eegldm_ctx*, int dtype, const void* x, long n_per_sample, int B, double* stats);
 /* developer aid: BatchNorm statistics (and the running-statistics update) from per-block column partials parts_dev [nb][2 C] fp32 (interleaved
  * sum, sum of squares) -- the fold that follows a conv whose epilogue left them.  No reference counterpart. */
 int eegldm_debug_bn_stats_from_parts(eegldm_ctx*, const float* parts_dev, int nb, float* stats, float* running_mean, float* running_var,
@@ -157,7 +175,8 @@ int eegldm_debug_conv1d_fwd_colstats(eegldm_ctx*, const void* x, long ldx, const
 /* EEGLDM_DETERMINISTIC=1 (environment variable, read like the developer switches; eegldm.set_deterministic() in the Python mirror):
  * bit-reproducible losses, parameter gradients and optimiser steps run to run.  Every order-dependent reduction -- fp32 atomics of
  * the bias / GroupNorm / thin-conv gradients and of the loss sums, fused column sums inside the weight-gradient GEMM, split-K without
- * a workspace -- takes a written-partials + fixed-order-fold route; forward results are unchanged.  Reference counterpart:
+ * a workspace -- takes a written-partials + fixed-order-fold route; forward results are unchanged, except that eegldm_aekl_encode takes
+ * its layer-by-layer path (the fused frozen encoder adds its per-sample statistics with fp64 atomics across tiles).  Reference counterpart:
  * torch.use_deterministic_algorithms(True) around src/train_ldm.py / src/train_autoencoderkl.py (the reference itself does not set it). */
 
 /* ------------------------------------------------------------------ layout / packing */

@@ -54,6 +54,9 @@ SIGNATURES = {
     "eegldm_debug_bn_last_route": [_i, _vp],
     "eegldm_debug_dconv_last_route": [_i, _vp],
     "eegldm_debug_aekl_last_route": [_vp, _vp],
+    "eegldm_debug_aekl_encode_route": [_vp, _vp],
+    "eegldm_debug_pre_conv3": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f],
+    "eegldm_debug_sample_stats": [_vp, _i, _vp, _l, _i, _vp],
     "eegldm_debug_bn_stats_from_parts": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _l, _i],
     "eegldm_debug_disc_tail_fwd": [_vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i],
     "eegldm_debug_disc_tail_bwd": [_vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _f, _vp, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i],

@@ -214,6 +214,8 @@ struct eegldm_aekl : SeqNet {
   int thin_fail_L = -1;          // length for which the whole-network program did not fit (LDS footprint): use the general path
   // what served the last forward ([0]) / backward ([1]) on this handle (eegldm_debug_aekl_last_route): host-side bookkeeping only
   struct Route { int thin, nfwd, nbwd, maxt, lds_fail; } route[2] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
+  // what served the last eegldm_aekl_encode (eegldm_debug_aekl_encode_route): fused path taken, its pre_conv3 / sample_stats launches
+  struct EncRoute { int fused, npre, nstats; } enc_route = {0, 0, 0};
   ~eegldm_aekl() { thin_free(&thin); }
 };
 
@@ -461,6 +463,7 @@ int aekl_encode_impl(eegldm_aekl* a, const float* x, const float* eps, int B, in
   View x0; ALLOC_OR_FAIL(x0.p, a->alloc_act((long)B * L, cin)); x0.ld = cin; x0.C = cin;
   EEG_TRY(eegldm_ncl_to_nlc(ctx, x, x0.p, cin, B, cin, L, dt));
   int Lc = L;
+  if (frozen) a->enc_route = {0, 0, 0};
   if (frozen && enc_fused_eligible(a, L)) EEG_TRY(aekl_encode_fused_seq(a, x0, B, Lc, &a->h_enc));      // no tape: the caller never back-propagates
   else EEG_TRY(a->forward_seq(a->enc, x0, B, Lc, &a->h_enc, a->tape_enc, 1));
   a->Ll = Lc;
@@ -485,6 +488,7 @@ int aekl_encode_impl(eegldm_aekl* a, const float* x, const float* eps, int B, in
 // (eegldm_aekl_encode = Stage1Wrapper / encode_stage_2_inputs under no_grad, train_ldm.py:145-148, training.py:417-421).
 bool enc_fused_eligible(const eegldm_aekl* a, int L) {
   if (getenv("EEGLDM_AEKL_NO_FUSED_ENC") != nullptr) return false;      // (read per call: tests toggle it inside one process)
+  if (eeg_deterministic()) return false;      // the per-sample sums of the fused kernels meet in fp64 atomics across tiles: their order shows in the last bit
   if ((a->dtype != EEGLDM_BF16 && a->dtype != EEGLDM_F16) || a->cfg.norm_num_groups != 1) return false;
   int Lc = L; bool any = false;
   for (const Op& o : a->enc) {
@@ -496,6 +500,7 @@ bool enc_fused_eligible(const eegldm_aekl* a, int L) {
 }
 int aekl_encode_fused_seq(eegldm_aekl* a, View x, int B, int& L, View* out) {
   eegldm_ctx* ctx = a->ctx; const int dt = a->dtype;
+  a->enc_route.fused = 1;
   // one statistics slot (sum, sum of squares per sample) per tensor that a GroupNorm reads: zeroed together, filled by the producers
   size_t nslots = 0;
   for (const Op& o : a->enc) nslots += (o.kind == OP_RES) ? 2 : 0;
@@ -513,13 +518,14 @@ int aekl_encode_fused_seq(eegldm_aekl* a, View x, int B, int& L, View* out) {
       EEG_TRY(op_conv_fwd(ctx, dt, x.p, x.ld, a->W(o.w), o.b >= 0 ? a->P(o.b) : nullptr, y.p, y.ld, B, L, o.cin, o.cout, o.k, o.stride, o.pl, o.pr,
                           nullptr, 0, nullptr, 0));
       L = Lo; x = y; cur_stats = nullptr;
-      if (next_res) { cur_stats = next_slot(); EEG_TRY(sample_stats_launch(ctx, x.p, (long)L * x.C, B, cur_stats, a->dtype)); }
+      if (next_res) { cur_stats = next_slot(); EEG_TRY(sample_stats_launch(ctx, x.p, (long)L * x.C, B, cur_stats, a->dtype)); a->enc_route.nstats++; }
     } else if (o.kind == OP_RES) {
       const ResDesc& r = o.r;
       EEG_CHECK(cur_stats, "fused encoder: no statistics for a ResBlock input");
       View h1; ALLOC_OR_FAIL(h1.p, a->alloc_act((long)B * L, r.cout)); h1.ld = r.cout; h1.C = r.cout;
       double* st_h1 = next_slot();
       EEG_TRY(pre_conv3_launch(ctx, x.p, cur_stats, a->P(r.gn1_w), a->P(r.gn1_b), a->W(r.c1_w), a->P(r.c1_b), nullptr, h1.p, st_h1, B, L, r.cin, r.cout, GN_EPS, a->dtype));
+      a->enc_route.npre++;
       View res = x;
       if (r.sk_w >= 0) {
         ALLOC_OR_FAIL(res.p, a->alloc_act((long)B * L, r.cout)); res.ld = r.cout; res.C = r.cout;
@@ -528,6 +534,7 @@ int aekl_encode_fused_seq(eegldm_aekl* a, View x, int B, int& L, View* out) {
       View y; ALLOC_OR_FAIL(y.p, a->alloc_act((long)B * L, r.cout)); y.ld = r.cout; y.C = r.cout;
       double* st_y = next_res ? next_slot() : nullptr;          // (a ResBlock followed by a conv / the final norm: nobody reads them)
       EEG_TRY(pre_conv3_launch(ctx, h1.p, st_h1, a->P(r.gn2_w), a->P(r.gn2_b), a->W(r.c2_w), a->P(r.c2_b), res.p, y.p, st_y, B, L, r.cout, r.cout, GN_EPS, a->dtype));
+      a->enc_route.npre++;
       x = y; cur_stats = st_y;
     } else {  // OP_GN (the final norm, no activation): the flat one-launch kernel
       View y; ALLOC_OR_FAIL(y.p, a->alloc_act((long)B * L, x.C)); y.ld = x.C; y.C = x.C;
@@ -645,6 +652,11 @@ extern "C" int eegldm_debug_aekl_last_route(const eegldm_aekl* a, int* out10_hos
     int* o = out10_host + 5 * d;
     o[0] = r.thin; o[1] = r.nfwd; o[2] = r.nbwd; o[3] = r.maxt; o[4] = r.lds_fail;
   }
+  return 0;
+}
+extern "C" int eegldm_debug_aekl_encode_route(const eegldm_aekl* a, int* out3_host) {
+  EEG_CHECK(a && out3_host, "null argument");
+  out3_host[0] = a->enc_route.fused; out3_host[1] = a->enc_route.npre; out3_host[2] = a->enc_route.nstats;
   return 0;
 }
 

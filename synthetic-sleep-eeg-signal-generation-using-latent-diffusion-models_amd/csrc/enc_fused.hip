@@ -3,9 +3,14 @@
 // never read back (SURVEY hard part (iv) / VERDICT r2 item 1a, for the one sub-network where nothing has to be saved for a backward:
 // the stage-1 AutoencoderKL [32, 32, 64] that train_ldm.py:145-148 runs under no_grad in every LDM step).
 //
-//   y[b, l, :] = bias + sum_t W[t] . act(x[b, l + t - 1, :])  (+ resid[b, l, :]),   act(v) = silu(v * scale_b[c] + shift_b[c])
-//   scale_b[c] = gamma[c] * rstd_b,  shift_b[c] = beta[c] - mean_b * scale_b[c],    (mean_b, rstd_b) from in_stats[b] = (sum, sum of squares)
+//   y[b, l, :] = bias + sum_t W[t] . act(x[b, l + t - 1, :])  (+ resid[b, l, :]),   act(v) = silu((v - mean_b) * scale_b[c] + beta[c])
+//   scale_b[c] = gamma[c] * rstd_b,    (mean_b, rstd_b) from in_stats[b] = (sum, sum of squares)
 //   out_stats[b] += (sum, sum of squares) of the bf16-ROUNDED y -- exactly what a GroupNorm kernel reading the stored tensor would see
+//
+// Both statistics producers sum in fp32 about a PIVOT p (pre_conv3: per lane, the first of its outputs; sample_stats: the sample's first
+// element), D1 = sum (v - p), D2 = sum (v - p)^2, and rebuild sum v = D1 + n p, sum v^2 = D2 + p (2 D1 + n p) in fp64 before the fp64 atomics:
+// the fp32 roundings then act on centred magnitudes, and var = S2 / n - mean^2 keeps no 1 + mean^2 / var amplification (one-pass sums about
+// zero lost a relative 1e-5 of rstd at a mean of 30 sigma: tests/test_gpu_enc_fused_rounding.py, profiles/enc_fused_numerics.txt).
 //
 // One block = one tile = 256 consecutive positions of one sample, all output channels (32 or 64).  The (256 + 2) x CI input slab is one contiguous
 // run of 16-byte chunks (rows are CI * 2 bytes), transformed in registers, written once to LDS as bf16 (the same rounding point as the
@@ -60,14 +65,19 @@ __global__ __launch_bounds__(256) void pre_conv3_kernel(const bf16_t* __restrict
   {
     const int b = tile / tps, l0 = (tile - b * tps) * TR;
     // ---- per-sample normalisation constants of this thread's 8 channels
-    float sc[8], sh[8];
+    float sc[8], sh[8], mh;
     {
       const double n = (double)CI * (double)L;
       const double mean = in_stats[2 * b] / n;
       double var = in_stats[2 * b + 1] / n - mean * mean; if (var < 0.0) var = 0.0;
-      const float rstd = (float)(1.0 / sqrt(var + (double)eps)), mf = (float)mean;
+      const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+      // centred apply: z = (x - mh) sc + (beta - ml sc) with mean = mh + ml split into two floats.  x - mh is exact for a 16-bit x near the
+      // mean, so every fp32 rounding acts on the centred value (x - mean) sc: the error of z does not grow with |mean| / sigma (a folded
+      // shift beta - mean sc is rounded at the magnitude |mean| sc, the same way for every element of a channel)
+      mh = (float)mean;
+      const double ml = mean - (double)mh;
 #pragma unroll
-      for (int e = 0; e < 8; e++) { sc[e] = ga[e] * rstd; sh[e] = be[e] - mf * sc[e]; }
+      for (int e = 0; e < 8; e++) { sc[e] = ga[e] * rstd; sh[e] = (float)((double)be[e] - ml * (double)sc[e]); }
     }
     // ---- slab -> act -> LDS.  Row r of the slab is position l0 - 1 + r; rows outside the sample are the conv's zero padding (of the
     // ACTIVATED tensor: zeros, not act(0))
@@ -81,7 +91,7 @@ __global__ __launch_bounds__(256) void pre_conv3_kernel(const bf16_t* __restrict
           unsigned ov[4];
 #pragma unroll
           for (int e = 0; e < 4; e++) {
-            const float v0 = w16_lo<T16>(in[e]), v1 = w16_hi<T16>(in[e]);
+            const float v0 = w16_lo<T16>(in[e]) - mh, v1 = w16_hi<T16>(in[e]) - mh;
             ov[e] = pack16x2<T16>(silu_f(fmaf(v0, sc[2 * e], sh[2 * e])), silu_f(fmaf(v1, sc[2 * e + 1], sh[2 * e + 1])));
           }
           o = make_uint4(ov[0], ov[1], ov[2], ov[3]);
@@ -91,7 +101,7 @@ __global__ __launch_bounds__(256) void pre_conv3_kernel(const bf16_t* __restrict
     }
     __syncthreads();
     // ---- MFMA: wave wv owns rows 64 wv .. + 64 (4 row fragments); tap t reads slab row (row + t); 32 output channels per pass
-    float s1 = 0.f, s2 = 0.f;
+    float s1 = 0.f, s2 = 0.f, pv = 0.f;      // sums of (r - pv), (r - pv)^2 over this lane's CO outputs; pv = the first of them (row 64 wv + lm, channel 4 q)
 #pragma unroll
     for (int h = 0; h < NH; h++) {
       uint4 wf[3][KS][NFH];       // B fragments (n = h*32 + j*16 + lm, k-chunk q of k-step ks, tap t): 6-24 KB of weights, L1 / L2 hits
@@ -134,17 +144,24 @@ __global__ __launch_bounds__(256) void pre_conv3_kernel(const bf16_t* __restrict
           }
           uint2 o; o.x = pack16x2<T16>(v[0], v[1]); o.y = pack16x2<T16>(v[2], v[3]);
           *(uint2*)(y + row * CO + col) = o;
-          const float r0 = w16_lo<T16>(o.x), r1 = w16_hi<T16>(o.x);
-          const float r2 = w16_lo<T16>(o.y), r3 = w16_hi<T16>(o.y);
+          if (h == 0 && j == 0 && i == 0) pv = w16_lo<T16>(o.x);
+          const float r0 = w16_lo<T16>(o.x) - pv, r1 = w16_hi<T16>(o.x) - pv;
+          const float r2 = w16_lo<T16>(o.y) - pv, r3 = w16_hi<T16>(o.y) - pv;
           s1 += (r0 + r1) + (r2 + r3);
           s2 += fmaf(r0, r0, r1 * r1) + fmaf(r2, r2, r3 * r3);
         }
       }
     }
     if (out_stats) {
+      // this lane's CO values about its own pivot -> their (sum, sum of squares) in fp64, then the wave in fp64.  (A pivot shared by the wave
+      // needs a cross-lane read inside the epilogue; with it hipcc hoists the second half's weight loads: 142 VGPRs instead of 110 at 64 -> 64,
+      // and the encode at (256, 3072) took 560 instead of 552 us.  Skipping the arithmetic where out_stats is null, at run time or as a
+      // template variant, had the same effect on the registers: 556-571 us.)
+      const double p = (double)pv, cnt = (double)CO, d1 = (double)s1;
+      double t1 = d1 + cnt * p, t2 = (double)s2 + p * (2.0 * d1 + cnt * p);
 #pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) { s1 += __shfl_xor(s1, d, 64); s2 += __shfl_xor(s2, d, 64); }
-      if (lane == 0) { atomicAdd(out_stats + 2 * b, (double)s1); atomicAdd(out_stats + 2 * b + 1, (double)s2); }
+      for (int d = 32; d >= 1; d >>= 1) { t1 += __shfl_xor(t1, d, 64); t2 += __shfl_xor(t2, d, 64); }
+      if (lane == 0) { atomicAdd(out_stats + 2 * b, t1); atomicAdd(out_stats + 2 * b + 1, t2); }
     }
   }
 }
@@ -156,24 +173,29 @@ __global__ __launch_bounds__(256) void sample_stats_kernel(const bf16_t* __restr
   const int b = blockIdx.y;
   const uint4* p = (const uint4*)(x + (long)b * n);
   const long nch = n / 8;
-  float s1 = 0.f, s2 = 0.f;
+  const float pv = w16_lo<T16>(*(const unsigned*)p);      // pivot: the sample's first element (n >= 8)
+  float s1 = 0.f, s2 = 0.f; int cnt = 0;                  // sums of (v - pv), (v - pv)^2 and the number of chunks behind them
   for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < nch; c += (long)gridDim.x * 256) {
     const uint4 v = p[c];
     const unsigned in[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int e = 0; e < 4; e++) {
-      const float v0 = w16_lo<T16>(in[e]), v1 = w16_hi<T16>(in[e]);
+      const float v0 = w16_lo<T16>(in[e]) - pv, v1 = w16_hi<T16>(in[e]) - pv;
       s1 += v0 + v1; s2 += fmaf(v0, v0, v1 * v1);
     }
+    cnt++;
   }
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) { s1 += __shfl_xor(s1, d, 64); s2 += __shfl_xor(s2, d, 64); }
-  __shared__ float r1[4], r2[4];
-  if ((threadIdx.x & 63) == 0) { r1[threadIdx.x >> 6] = s1; r2[threadIdx.x >> 6] = s2; }
+  for (int d = 32; d >= 1; d >>= 1) { s1 += __shfl_xor(s1, d, 64); s2 += __shfl_xor(s2, d, 64); cnt += __shfl_xor(cnt, d, 64); }
+  __shared__ float r1[4], r2[4]; __shared__ int rc[4];
+  if ((threadIdx.x & 63) == 0) { r1[threadIdx.x >> 6] = s1; r2[threadIdx.x >> 6] = s2; rc[threadIdx.x >> 6] = cnt; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    atomicAdd(stats + 2 * b, (double)r1[0] + (double)r1[1] + (double)r1[2] + (double)r1[3]);
-    atomicAdd(stats + 2 * b + 1, (double)r2[0] + (double)r2[1] + (double)r2[2] + (double)r2[3]);
+    const double pd = (double)pv, m = 8.0 * (double)(rc[0] + rc[1] + rc[2] + rc[3]);
+    const double d1 = (double)r1[0] + (double)r1[1] + (double)r1[2] + (double)r1[3];
+    const double d2 = (double)r2[0] + (double)r2[1] + (double)r2[2] + (double)r2[3];
+    atomicAdd(stats + 2 * b, d1 + m * pd);
+    atomicAdd(stats + 2 * b + 1, d2 + pd * (2.0 * d1 + m * pd));
   }
 }
 
@@ -207,4 +229,19 @@ int sample_stats_launch(eegldm_ctx* ctx, const void* x, long n_per_sample, int B
   else hipLaunchKernelGGL(sample_stats_kernel<bf16_t>, dim3((unsigned)per, B), dim3(256), 0, ctx->stream, (const bf16_t*)x, n_per_sample, stats);
   LAUNCH_CHECK();
   return 0;
+}
+
+// ---------------------------------------------------------------- developer exports: the two kernels alone, behind their eligibility checks
+// (tests/test_gpu_enc_fused_rounding.py holds every instantiation to float64; the encoder calls the launchers above directly)
+extern "C" int eegldm_debug_pre_conv3(eegldm_ctx* ctx, int dtype, const void* x, const double* in_stats, const float* gamma, const float* beta,
+                                      const void* w, const float* bias, const void* resid, void* y, double* out_stats, int B, int L, int Cin,
+                                      int Cout, float eps) {
+  EEG_CHECK(ctx && x && in_stats && gamma && beta && w && bias && y && B > 0 && L > 0, "bad argument");
+  if (!pre_conv3_ok(dtype, Cin, Cout, L)) EEG_FAIL(EEGLDM_ERR_UNSUPPORTED, "pre_conv3: dtype %d, %d -> %d channels, L %d not eligible", dtype, Cin, Cout, L);
+  return pre_conv3_launch(ctx, x, in_stats, gamma, beta, w, bias, resid, y, out_stats, B, L, Cin, Cout, eps, dtype);
+}
+extern "C" int eegldm_debug_sample_stats(eegldm_ctx* ctx, int dtype, const void* x, long n_per_sample, int B, double* stats) {
+  EEG_CHECK(ctx && x && stats && B > 0 && n_per_sample > 0, "bad argument");
+  if (dtype != EEGLDM_BF16 && dtype != EEGLDM_F16) EEG_FAIL(EEGLDM_ERR_UNSUPPORTED, "sample_stats: 16-bit storage only (dtype %d)", dtype);
+  return sample_stats_launch(ctx, x, n_per_sample, B, stats, dtype);
 }

@@ -773,3 +773,209 @@ def col_stats(y_unrounded):
     """(sum, sum of squares) per column of a (rows, N) float64 matrix"""
     y = _f64(y_unrounded)
     return y.sum(0), (y * y).sum(0)
+
+
+# ---------------------------------------------------------------- fused frozen encoder (csrc/enc_fused.hip) and the other normalise-on-load conv
+# y[b, :, l] = bias + sum_t W[:, :, t] a[b, :, l + t - 1] (+ row[b, :]) (+ resid[b, :, l]),  a = RNE_fmt(silu(x scale_b + shift_b)), zero outside the
+# sample (the padding is of the ACTIVATED tensor).  NCL layout: x (B, Cin, L), w (Cout, Cin, 3), resid (B, Cout, L), row (B, Cout).
+# Two forms of the fp32 apply (act_on_load's `form`):
+#   "fp32" (eegldm_conv1d_fwd_gn's table kernel; pre_conv3_kernel before its shift moved to fp64): everything in fp32,
+#       rstd' = fl(rstd), mean' = fl(mean), scale' = fl(gamma rstd'), shift' = fl(beta - fl(mean' scale')), z' = fl(x scale' + shift') (one fma),
+#     so scale' carries 2u, mean' scale' 4u and the subtraction and the fma one rounding each:
+#       |z' - z| <= u (2 |x scale| + 5 |mean scale| + |beta| + |z|) + O(u^2);  d_z spends one more u on every term for the O(u^2) part.
+#     The errors act on the UNcentred magnitudes |x| rstd and |mean| rstd: at a mean of m sigma d_z is ~ 9 m u.
+#   "centred" (pre_conv3_kernel): (mean, rstd) are fp64 values from the (sum, sum of squares) slots; scale' = fl(gamma fl(rstd)) as above,
+#     mean = mh + ml with mh = fl(mean), and z' = fl(fl(x - mh) scale' + fl(beta - ml scale')): x - mh is exact for a 16-bit x within a factor
+#     of two of the mean and carries u |x - mh| otherwise, the small shift u (|beta| + u |mean scale|), the fma u |z|:
+#       |z' - z| <= u (3 |x - mean| |scale| + |beta| + |z|) + 2 u^2 |mean scale| + O(u^2);  again one more u per term below.
+#     Every rounding acts on the centred value: d_z does not grow with |mean| / sigma.
+def enc_affine(in_stats, n, gamma, beta, eps):
+    """(mean (B,), var (B,) clamped at 0, rstd (B,), scale (B, C), shift (B, C)), float64, from per-sample (sum, sum of squares) slots over n
+    elements -- the kernel's own fp64 expressions (eps is the fp32 value the kernel is handed, widened)"""
+    S = _f64(in_stats).reshape(-1, 2)
+    mean = S[:, 0] / n
+    var = torch.clamp(S[:, 1] / n - mean * mean, min=0.0)
+    var = torch.where(torch.isnan(S[:, 1] / n - mean * mean), S[:, 1] / n - mean * mean, var)       # (clamp keeps NaN in torch; explicit all the same)
+    rstd = 1.0 / torch.sqrt(var + float(np.float32(eps)))
+    scale = _f64(gamma)[None, :] * rstd[:, None]
+    shift = _f64(beta)[None, :] - mean[:, None] * scale
+    return mean, var, rstd, scale, shift
+
+
+def gn_affine(stats, C, gamma, beta):
+    """the same per-(sample, channel) scale and shift from a (B, G, 2) buffer of (mean, rstd) -- eegldm_conv1d_fwd_gn's operand; returns
+    (mean (B, C), scale (B, C), shift (B, C))"""
+    st = _f64(stats)
+    B, G, _ = st.shape
+    mean = st[:, :, 0].repeat_interleave(C // G, dim=1); rstd = st[:, :, 1].repeat_interleave(C // G, dim=1)
+    scale = _f64(gamma)[None, :] * rstd
+    return mean, scale, _f64(beta)[None, :] - mean * scale
+
+
+def act_on_load(x, mean, scale, shift, beta, silu=True, form="centred"):
+    """(a, d_a): float64 silu(x scale + shift) and the fp32 bound of the apply derived above; through silu_f (z * rcp(1 + __expf(-z)), slope
+    <= 1.1) it is 1.1 d + 8u |a|, the model tests/test_gpu_groupnorm_rounding.py uses for the same device function.  mean: (B,) or (B, C)."""
+    x = _f64(x)
+    sc, sh = scale[:, :, None], shift[:, :, None]
+    mn = mean[:, None, None] if mean.dim() == 1 else mean[:, :, None]
+    z = x * sc + sh
+    if form == "fp32":
+        d = U32 * (3 * (x * sc).abs() + 6 * (mn * sc).abs() + 2 * _f64(beta).abs()[None, :, None] + 2 * z.abs())
+    else:
+        d = U32 * (4 * ((x - mn) * sc).abs() + 2 * _f64(beta).abs()[None, :, None] + 2 * z.abs()) + 4 * U32 ** 2 * (mn * sc).abs()
+    if not silu:
+        return z, d
+    a = F.silu(z)
+    return a, 1.1 * d + 8 * U32 * a.abs()
+
+
+def _conv3(a, w):
+    return F.conv1d(F.pad(a, (1, 1)), w)
+
+
+def _epilogue(y, bias, row, resid, mag=False):
+    f = (lambda t: _f64(t).abs()) if mag else _f64
+    if bias is not None:
+        y = y + f(bias)[None, :, None]
+    if row is not None:
+        y = y + f(row)[:, :, None]
+    if resid is not None:
+        y = y + f(resid)
+    return y
+
+
+def conv3_on_load_ref(a, d_a, w, bias, resid, fmt, row=None):
+    """(y_ref, mag, d) of the 3-tap conv whose operand is RNE_fmt(a') for SOME a' within d_a of a (the kernel rounds the activated operand to
+    `fmt` before the MFMA, a point no test can observe): a_lo = RNE(a - d_a) <= operand <= a_hi = RNE(a + d_a) element by element, so
+      y_ref = conv(RNE(a)) + bias + row + resid,   d = gamma(3 Cin) mag + conv(|w|, a_hi - a_lo),
+    mag = the same operation on |operands| (the larger of |a_lo|, |a_hi| for the operand)."""
+    w = _f64(w)
+    Cin = w.shape[1]
+    a_lo, a_hi = rne(a - d_a, fmt), rne(a + d_a, fmt)
+    y_ref = _epilogue(_conv3(rne(a, fmt), w), bias, row, resid)
+    mag = _epilogue(_conv3(torch.maximum(a_lo.abs(), a_hi.abs()), w.abs()), bias, row, resid, mag=True)
+    d = gamma(3 * Cin) * mag + _conv3(a_hi - a_lo, w.abs())
+    return y_ref, mag, d
+
+
+def pre_conv3_ref(x, in_stats, gamma, beta, w, bias, resid, fmt, eps, gn_stats=None, row=None):
+    """(y_ref, mag, d) of pre_conv3_kernel (in_stats: (B, 2) fp64 sums, one group) or, with gn_stats (B, G, 2) = (mean, rstd) in place of
+    in_stats, of eegldm_conv1d_fwd_gn with G groups and a per-sample row vector.  Check A: numerics.check(y, y_ref, d / gamma(0), 0, fmt)."""
+    x = _f64(x)
+    B, C, L = x.shape
+    if gn_stats is None:
+        mean, _var, _rstd, scale, shift = enc_affine(in_stats, C * L, gamma, beta, eps)
+    else:
+        mean, scale, shift = gn_affine(gn_stats, C, gamma, beta)
+    a, d_a = act_on_load(x, mean, scale, shift, beta, form="centred" if gn_stats is None else "fp32")
+    return conv3_on_load_ref(a, d_a, w, bias, resid, fmt, row=row)
+
+
+def pre_conv3_emul(x, G, gamma, beta, w, bias, resid, fmt, eps, row=None):
+    """check B's emulation: torch fp32 group_norm + SiLU -> RNE -> F.conv1d -> + bias + row + resid (float32; `check` rounds it)"""
+    x32 = _f64(x).float()
+    a = F.silu(F.group_norm(x32, G, _f64(gamma).float(), _f64(beta).float(), eps=eps))
+    a = rne(a.double(), fmt).float()
+    y = F.conv1d(F.pad(a, (1, 1)), _f64(w).float())
+    f32 = lambda t: None if t is None else _f64(t).float()
+    return _epilogue(y, f32(bias), f32(row), f32(resid))
+
+
+def sums_bound(values, depth, n64=0, preload=0.0):
+    """bound of a one-pass fp32 sum of `values` (summed over the last dimension) whose every element passes through at most `depth`
+    fp32 additions, in any order: gamma(depth) sum|v|; n64 further fp64 additions (block partials, atomics onto `preload`) add
+    gamma64(n64) (sum|v| + |preload|)"""
+    s = _f64(values).abs().sum(-1)
+    return gamma(depth) * s + (gamma64(n64) * (s + _f64(torch.as_tensor(preload)).abs()) if n64 else 0.0)
+
+
+def sample_stats_depth(n_per_sample):
+    """additions behind one element of sample_stats_kernel: 8 per 16-byte chunk of a thread's grid-stride loop, 6 shuffle levels, 2 spare;
+    `per` blocks of 256 threads per sample as sample_stats_launch computes it"""
+    nch = n_per_sample // 8
+    per = min(64, max(1, (nch + 255) // 256))
+    return 8 * -(-nch // (per * 256)) + 6 + 2
+
+
+PRE_CONV3_STATS_DEPTH = 64 + 6          # pre_conv3 epilogue: at most 64 values per lane (kept for every shape: any-order bound), 6 shuffle levels
+
+
+def pre_conv3_pivots(y):
+    """y (B, Cout, L) -> the pivot of every element: a lane of pre_conv3_kernel owns rows 64 w + 16 i + lm (i = 0..3) and channels
+    32 h + 16 j + 4 q + (0..3) of a tile and sums them about the first, y[64 w + lm, 4 q]"""
+    y = _f64(y)
+    _B, C, L = y.shape
+    li = torch.arange(L); ci = torch.arange(C)
+    return y[:, ((ci % 16) // 4 * 4)[:, None], ((li // 64) * 64 + li % 16)[None, :]]
+
+
+def pivot_sums_bounds(v, pivot, depth, n64=0, preload=None):
+    """(e_S1, e_S2), each (B,): bounds of the (sum, sum of squares) of v (B, ...) as the kernels of csrc/enc_fused.hip form them -- fp32 sums
+    D1 = sum d, D2 = sum d^2 of d = fl(v - p) about a pivot p that is itself an element of the tensor (`pivot`: broadcastable to v; pre_conv3:
+    pre_conv3_pivots, one pivot per lane; sample_stats: the sample's first element), rebuilt in fp64 as S1 = D1 + g p, S2 = D2 + p (2 D1 + g p)
+    per group of g elements that share a pivot:
+      e(D1) = gamma(depth + 1) sum |d|            (the subtraction is one more rounding of every term)
+      e(D2) = gamma(depth + 4) sum d^2            (d carries u, its square 2u, the fma one more)
+      e_S1 = e(D1),   e_S2 = e(D2) + 2 gamma(depth + 1) sum |p| |d|,   plus gamma64(n64) of the magnitudes for the fp64 additions and atomics.
+    pivot = None: p = 0, one-pass sums about zero (gamma(depth), gamma(depth + 2))."""
+    v = _f64(v)
+    B = v.shape[0]
+    extra = 0 if pivot is None else 1
+    p = torch.zeros_like(v) if pivot is None else _f64(pivot).expand_as(v)
+    d = (v - p).reshape(B, -1); p = p.reshape(B, -1); vf = v.reshape(B, -1)
+    pre = torch.zeros(B, 2, dtype=torch.float64) if preload is None else _f64(preload)
+    f64 = gamma64(n64) if n64 else 0.0
+    e_s1 = gamma(depth + extra) * d.abs().sum(-1) + f64 * (vf.abs().sum(-1) + pre[:, 0].abs())
+    e_s2 = gamma(depth + 2 + 2 * extra) * (d * d).sum(-1) + 2 * gamma(depth + extra) * (p.abs() * d.abs()).sum(-1) + f64 * ((vf * vf).sum(-1) + pre[:, 1].abs())
+    return e_s1, e_s2
+
+
+def enc_stats_bounds(v, depth, eps, n64=0, pivot=None):
+    """v: (B, ...) float64 values of the stored tensor.  The statistics a consumer derives in fp64 from the (sum, sum of squares) slots, and
+    their bounds.  With the pivots of pivot_sums_bounds the errors of the slots are dS1 = sum_g dD1_g, dS2 = sum_g dD2_g + 2 p_g dD1_g, so for
+    mean = S1 / n, var = S2 / n - mean^2:
+      e_mean = gamma(depth + 1) sum |d| / n
+      e_var  = gamma(depth + 4) sum d^2 / n + (2 / n) gamma(depth + 1) sum |p - mean| |d| + e_mean^2
+      e_rstd (relative) = (1 - r)^(-1/2) - 1 with r = e_var / (var + eps): e_var / (2 (var + eps)) to first order.
+    Sums about zero (pivot = None: p = 0, d = v) are the "split kernels" formulas of tests/test_gpu_groupnorm_rounding.py with m = mean: the
+    first term then holds var + mean^2 and the second 2 |mean| e_mean -- the 1 + 3 mean^2 / var amplification.  About pivots that are
+    elements of the tensor both terms are of the size of var: no mean^2 / var term, at any mean.
+    Returns dict(mean, var, rstd, e_mean, e_var, e_rstd), each (B,)."""
+    v = _f64(v)
+    B = v.shape[0]
+    extra = 0 if pivot is None else 1
+    p = (torch.zeros_like(v) if pivot is None else _f64(pivot).expand_as(v)).reshape(B, -1)
+    vf = v.reshape(B, -1)
+    n = vf.shape[1]
+    d = vf - p
+    epsf = float(np.float32(eps))
+    mean = vf.mean(-1)
+    var = ((vf - mean[:, None]) ** 2).mean(-1)
+    f64 = gamma64(n64) if n64 else 0.0
+    e_mean = gamma(depth + extra) * d.abs().mean(-1) + f64 * vf.abs().mean(-1)
+    e_var = gamma(depth + 2 + 2 * extra) * (d * d).mean(-1) + 2 * gamma(depth + extra) * ((p - mean[:, None]).abs() * d.abs()).mean(-1) + e_mean ** 2 \
+        + f64 * (2 * (vf * vf).mean(-1) + 2 * mean.abs() * vf.abs().mean(-1))
+    r = e_var / (var + epsf)
+    e_rstd = torch.where(r < 1, (1 - torch.clamp(r, max=1 - 1e-12)) ** -0.5 - 1, torch.full_like(r, math.inf))
+    return dict(mean=mean, var=var, rstd=1.0 / torch.sqrt(var + epsf), e_mean=e_mean, e_var=e_var, e_rstd=e_rstd)
+
+
+def check_rows(got, ref, d, fmt, rows, route="", report=True):
+    """check A with the absolute bound d on single positions l of (B, C, L) tensors, one verdict per (sample, row): a defect at a tile or
+    sample seam is named by its row instead of being averaged over the tensor.  rows: positions (negative: from the end); those outside
+    the tensor are skipped.  Returns the list of failure messages (one per failing row, each naming "sample b row l")."""
+    got, ref, d = _f64(got), _f64(ref), _f64(d)
+    B, _C, L = ref.shape
+    ls = sorted({r % L for r in rows if -L <= r < L})
+    fails, worst = [], []
+    for l in ls:
+        ok, ratio = _within(got[:, :, l], ref[:, :, l], d[:, :, l], fmt)
+        worst.append(float(ratio.max()))
+        for b in range(B):
+            if not bool(ok[b].all()):
+                i = int(torch.argmax(torch.nan_to_num(ratio[b], posinf=1e300)))
+                fails.append(f"{route} [{fmt}]: sample {b} row {l}: {int((~ok[b]).sum())} of {ok.shape[1]} channels outside the bound (channel {i}: got "
+                             f"{got[b, i, l].item()!r}, ref {ref[b, i, l].item()!r}, {float(ratio[b, i]):.3g} x its bound)")
+    if report:
+        print(f"[numerics] {route} rows " + " ".join(f"{l}:{w:.2f}" for l, w in zip(ls, worst)) + " (worst error / bound per row, all samples)")
+    return fails
