@@ -51,7 +51,8 @@ extern "C" {
  *    (eegldm_canvas_edit_step, eegldm_sample_long_edit) and resampled repair (eegldm_edit_jump, eegldm_sample_edit_resample,
  *    eegldm_sample_long_edit_resample) and context conditioning (eegldm_unet_create_ctx, eegldm_unet_set_context, eegldm_context_mask,
  *    eegldm_add_noise_context, eegldm_context_window, eegldm_ldm_train_step_ctx, eegldm_sample_edit_ctx, eegldm_sample_long_edit_ctx)
- *    and the developer entries of the fused frozen encoder (eegldm_debug_pre_conv3, eegldm_debug_sample_stats, eegldm_debug_aekl_encode_route). */
+ *    and the developer entries of the fused frozen encoder (eegldm_debug_pre_conv3, eegldm_debug_sample_stats, eegldm_debug_aekl_encode_route)
+ *    and the sampling loop by descriptor (eegldm_sample_desc, eegldm_sample_run), of which every eegldm_sample_* export is a shorthand. */
 #define EEGLDM_ABI_VERSION 8
 
 /* Storage / operand type of activations and compute-copy weights (accumulation, statistics, master weights and optimizer state are
@@ -835,6 +836,78 @@ int eegldm_sample_long_edit_ctx(eegldm_unet*, eegldm_aekl* ae, const float* nois
                                 float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
                                 int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class,
                                 const float* context, int context_rows);
+
+/* ------------------------------------------------------------------ the sampling loop by descriptor (additive; ABI 8)
+ * ONE loop serves every eegldm_sample_* export above: each of them fills this descriptor from its argument list and calls
+ * eegldm_sample_run, so they are its fixed-form shorthands and a caller may fill the descriptor itself.  Zero-initialise it, set `size`
+ * and what the call uses: a NULL pointer or a zero count means "this part is not used".  HOST arrays hold n_steps entries, one per forward;
+ * everything else is a device buffer of fp32 that stays valid and unwritten during the call.  Every rule below is checked before the first
+ * launch or allocation, and a refused call leaves no state behind.  Group by group:
+ *   size              sizeof(eegldm_sample_desc); anything else is refused before another member is read.
+ *   unet, ae, noise   the denoiser; the autoencoder that decodes the result (NULL: pixel-space model, x IS the window; else it shares the
+ *                     UNet's context); the caller's ONE noise tensor -- x starts as `noise`, and every re-noising of `known` uses it.
+ *   B, L              window form: x is (B, C, L), C the UNet's x channels (== its out_channels).
+ *   R, W, m, r,       canvas form, selected by R > 0 (B is then not read; needs the multistep step): the R * W <= 0x3fffffff forward rows
+ *   canvas_out,       are the overlapping slices of R canvases (window length L, margin m, ramp r >= 0, L >= 3 m + 2 r: "Long recordings"
+ *   recording_out     above).  noise / known / mask / context are canvas-shaped (R, ., Lc); x starts as the gathered canvas, and every step
+ *                     is ONE eegldm_canvas_step (with `known`: eegldm_canvas_edit_step) launch that updates the canvas AND rewrites the
+ *                     slices the next forward reads.  canvas_out (R, C, Lc) receives the final canvas; recording_out (R, Co, down * Lc)
+ *                     the cross-fade (eegldm_canvas_compose) of the R * W windows decoded from the gathered canvas times inv_scale_factor,
+ *                     without `ae` the canvas itself.  One of the two is required; latents_out / windows_out are not read.
+ *   n_steps,          HOST: per forward the timestep the UNet sees and alphas_cumprod there.  The embedding rows of all (timestep, class)
+ *   timesteps, a_t    pairs are computed once per call.
+ *   a_prev, beta_t,   the DDIM step (eta 0; eegldm_ddim_step, guided: eegldm_guided_step) onto a_prev[i] (HOST; 1 for the final step), or
+ *   ancestral,        with ancestral != 0 the DDPM step (eegldm_ddpm_step), which also needs beta_t (HOST) and draws its noise on the device:
+ *   noise_seed        Philox key noise_seed, step i at offset i * ceil(n / 4), n = B C L.  noise_seed is also the key of the jumps below;
+ *                     the two never occur together (the ancestral step is refused with `known`).
+ *   cx, c0, c1,       HOST.  cx != NULL selects the linear multistep step (eegldm_multistep_step, one launch behind every forward; the
+ *   a_next            history buffer belongs to the library): a_prev is then not read and ancestral must be 0.  c1[0] must be 0: the first
+ *                     executed step has no history.  a_next[i], the noise level step i lands on, is needed with `known` (the DDIM form
+ *                     lands on a_prev[i]).
+ *   pred_type,        EEGLDM_PRED_*; clamp the data prediction to [-1, 1]; windows_out / recording_out decode x * inv_scale_factor
+ *   clip_sample,      (1 / scale_factor; read only with `ae`, and a zeroed value there is a factor of 0, not "off").
+ *   inv_scale_factor
+ *   labels,           HOST, one class in [0, num_classes) per forward row (canvas form: recording-major).  Required for a UNet built with
+ *   guidance_scale,   classes, refused for one without.  guidance_scale and null_class are read only when labels are given, and a zeroed
+ *   null_class        guidance_scale there means w = 0 (the null class alone), NOT "off": w = 1 is the plain conditional sampler.  w != 1
+ *                     runs every forward on twice the rows -- the samples with their labels, then the same latents with null_class, which
+ *                     must lie in [0, num_classes) -- and the step forms out_u + w (out_c - out_u) on the raw model output.  NaN is refused.
+ *   known, mask       the edit start and the blend ("Editing" above).  known != NULL: x starts as k(a_t[0]) of `known` and `noise`
+ *                     (eegldm_edit_start) and every step is ONE eegldm_edit_step launch; deterministic steps only.  mask != NULL (needs
+ *                     known): that launch also blends towards k(level the step lands on); without a mask the same launch runs without
+ *                     the blend, so an all-zero mask and no mask give the same bytes.  The null-class half receives the blended latents.
+ *   jump_x, jump_n    HOST, both or neither; need known and mask ("Resampled repair" above).  In front of forward i with jump_n[i] != 0
+ *                     ONE eegldm_edit_jump launch takes x in place (out2 = the null-class half when guided) back up to the level a_t[i]:
+ *                     fresh = NULL, seed = noise_seed, offset = jump_index * ((n + 3) / 4), jump_index counting the call's jumps from 0;
+ *                     on the canvas the jump runs on the n = R C Lc canvas elements and an eegldm_canvas_gather rewrites the window rows.
+ *                     jump_n[0] must be 0, no entry may be NaN, and c1[i] must be 0 behind a jump: the history is not cleared, only unread.
+ *   context,          on a UNet from eegldm_unet_create_ctx only: device (context_rows, context_channels, L) with B % context_rows == 0 --
+ *   context_rows      sample b reads row b % context_rows -- or, canvas form, (R, context_channels, Lc) with context_rows == R, gathered
+ *                     ONCE per call into window rows.  The loop copies it into a buffer of its own (one row per forward row, both halves
+ *                     of a guided batch) and points the handle there: a captured graph outlives the call and never reads the caller's
+ *                     pointer.  A context UNet without a context runs on zeros.
+ *   latents_out,      window form, one of them required: the final x (B, C, L), and its decode (B, Co, down * L) -- without `ae` x itself.
+ *   windows_out
+ *   use_graph,        use_graph != 0: the UNet forward is captured once per (forward rows, L) into a hipGraph and replayed (launch-bound at
+ *   graph_used        small B); *graph_used (HOST, nullable) reports whether the replay path ran.  Eager launches are the default.
+ * One context = one thread: the call swaps the context's stream for its duration. */
+typedef struct eegldm_sample_desc {
+  uint32_t size;
+  eegldm_unet* unet; eegldm_aekl* ae; const float* noise;
+  int B, L;
+  int R, W, m, r; float *canvas_out, *recording_out;
+  int n_steps; const int64_t* timesteps; const float* a_t;
+  const float *a_prev, *beta_t; int ancestral; uint64_t noise_seed;
+  const float *cx, *c0, *c1, *a_next;
+  int pred_type, clip_sample; float inv_scale_factor;
+  const int64_t* labels; float guidance_scale; int64_t null_class;
+  const float *known, *mask;
+  const float *jump_x, *jump_n;
+  const float* context; int context_rows;
+  float *latents_out, *windows_out;
+  int use_graph; int* graph_used;
+} eegldm_sample_desc;
+int eegldm_sample_run(const eegldm_sample_desc* desc);
 
 /* ------------------------------------------------------------------ data-parallel collectives (RCCL over xGMI)
  * One communicator per process / GPU.  Stands where the reference gathers gradients with single-process nn.DataParallel

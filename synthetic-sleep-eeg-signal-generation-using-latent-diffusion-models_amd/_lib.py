@@ -292,6 +292,30 @@ class UNetCfg(C.Structure):
                 ("resample_pool_only", _i)]
 
 
+class SampleDesc(C.Structure):
+    """eegldm_sample_desc (include/eegldm.h describes the members): one call of the sampling loop.  Zero-initialised by ctypes; set `size`
+    and what the call uses.  An array assigned to a pointer member is kept alive by the structure (_objects); device buffers are plain
+    addresses, which the caller keeps alive."""
+    _pf, _pl = C.POINTER(_f), C.POINTER(C.c_int64)
+    _fields_ = [("size", C.c_uint32),
+                ("unet", _vp), ("ae", _vp), ("noise", _vp),
+                ("B", _i), ("L", _i),
+                ("R", _i), ("W", _i), ("m", _i), ("r", _i), ("canvas_out", _vp), ("recording_out", _vp),
+                ("n_steps", _i), ("timesteps", _pl), ("a_t", _pf),
+                ("a_prev", _pf), ("beta_t", _pf), ("ancestral", _i), ("noise_seed", C.c_uint64),
+                ("cx", _pf), ("c0", _pf), ("c1", _pf), ("a_next", _pf),
+                ("pred_type", _i), ("clip_sample", _i), ("inv_scale_factor", _f),
+                ("labels", _pl), ("guidance_scale", _f), ("null_class", C.c_int64),
+                ("known", _vp), ("mask", _vp),
+                ("jump_x", _pf), ("jump_n", _pf),
+                ("context", _vp), ("context_rows", _i),
+                ("latents_out", _vp), ("windows_out", _vp),
+                ("use_graph", _i), ("graph_used", C.POINTER(_i))]
+
+
+SIGNATURES["eegldm_sample_run"] = [C.POINTER(SampleDesc)]
+
+
 def _bind():
     for name, args in SIGNATURES.items():
         fn = getattr(lib, name, None)
@@ -373,7 +397,7 @@ def set_deterministic(on=True):
     """Bit-reproducible train steps (EEGLDM_DETERMINISTIC): every order-dependent reduction of the library -- fp32 atomics of the bias /
     GroupNorm / thin-conv gradients and of the loss sums, fused column sums inside the weight-gradient GEMM, split-K without a workspace --
     takes a written-partials + fixed-order-fold route.  Same arithmetic up to summation order; a few per cent slower.  The reference's
-    counterpart is `torch.use_deterministic_algorithms(True)` around /root/reference/src/train_ldm.py / train_autoencoderkl.py."""
+    counterpart is `torch.use_deterministic_algorithms(True)` around the reference's src/train_ldm.py / train_autoencoderkl.py."""
     if on:
         os.environ["EEGLDM_DETERMINISTIC"] = "1"
     else:

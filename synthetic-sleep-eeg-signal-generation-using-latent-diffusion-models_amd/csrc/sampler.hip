@@ -1,4 +1,4 @@
-// DDIM / DDPM sampling as ONE native call: the loop of /root/reference/src/sample_trials.py:149-170
+// DDIM / DDPM sampling as ONE native call: the loop of the reference's src/sample_trials.py:149-170
 // (noise -> [UNet, scheduler.step] x N -> decode(z / scale_factor)) and of sample_trials_ddpm.py:99-104 /
 // util.py:261-285 (pixel-space model, 1000-step ancestral sampler).  Host code only.
 //
@@ -79,72 +79,80 @@ void sampler_release(const eegldm_unet* u) {
   }
 }
 
-// labels (class-conditional UNets; NULL otherwise): one class per sample.  guidance_scale != 1 runs every forward on 2B rows -- the B
-// samples with their labels, then the same latents with null_class -- and mixes the two outputs inside the scheduler step (cfg_step_kernel)
-// ms (eegldm_sample_multistep; NULL otherwise): the per-step coefficients of the linear multistep update, which then replaces the DDIM /
-// DDPM step -- one eegldm_multistep_step launch behind every forward; a_prev / beta_t / ancestral are not read
-struct MultistepCoef { const float *cx, *c0, *c1; };
-// ed (eegldm_sample_edit; NULL otherwise): x starts from `known` noised to a_t[0] with `noise` instead of from `noise`; with a mask, every
-// step is one eegldm_edit_step launch -- the same step plus the blend towards `known` noised to the level the step lands on (a_prev, or
-// a_next[i] in the multistep form); mask NULL: the same launch without the blend.
-struct EditBlock { const float *known, *mask, *a_next; };
-// lg (eegldm_sample_long; NULL otherwise; needs ms): the B = R * W forward rows are overlapping slices of R canvases (window length L,
-// margin m, ramp r: include/eegldm.h).  `noise` is canvas-shaped, x starts as its slices, and every step is one eegldm_canvas_step launch,
-// which updates the canvas AND rewrites the slices the next forward reads.  latents_out / windows_out are not used: the canvas goes to
-// canvas_out, the cross-faded decode (pixel-space model: the canvas itself) to recording_out.
-// lg and ed together (eegldm_sample_long_edit): known / mask are canvas-shaped, the canvas starts as `known` noised to a_t[0] with `noise`,
-// and every step is one eegldm_canvas_edit_step launch (the canvas step and the blend; mask NULL: the canvas step alone).
-struct LongBlock { int R, W, m, r; float *canvas_out, *recording_out; };
-// rs (eegldm_sample_edit_resample / eegldm_sample_long_edit_resample; NULL otherwise; needs ed with a mask -- resample_preamble checks
-// that, both jump arrays and the entries behind a jump before the block is built): every host array holds one
-// entry per FORWARD, and in front of the forwards with jump_n[i] != 0 one eegldm_edit_jump launch takes x -- the canvas, then a gather --
-// back up to the level a_t[i] with noise drawn inside the kernel: Philox key `seed`, jump k of the call at offset k * ceil(elements / 4).
-// The hist buffers are not cleared: c1[i] == 0 behind a jump keeps the step from reading them.
-struct ResampleBlock { const float *jump_x, *jump_n; uint64_t seed; };
-// context / context_rows (eegldm_sample_edit_ctx / eegldm_sample_long_edit_ctx on a UNet from eegldm_unet_create_ctx; NULL otherwise): device
-// (rows, context_channels, L) with B % rows == 0 -- sample b reads row b % rows -- or, with lg, canvas-shaped (R, context_channels, Lc), gathered
-// once into window rows.  The loop copies it into the state's own buffer (one row per forward row, both halves of a guided batch) and
-// points the handle there; a context UNet without a context runs on zeros.
-// One call of the loop.  The exports fill the leading members in the order of their own argument lists and name the rest.
-struct SampleCall {
-  eegldm_unet* u; eegldm_aekl* ae; const float* noise; const int64_t* timesteps; const float* a_t; int n_steps, pred_type, clip_sample;
-  float inv_scale_factor; float *latents_out, *windows_out; int B, L, use_graph; int* graph_used; const int64_t* labels; float guidance_scale;
-  int64_t null_class;
-  const float *a_prev = nullptr, *beta_t = nullptr; int ancestral = 0; uint64_t noise_seed = 0;      // the DDIM / DDPM step
-  const MultistepCoef* ms = nullptr; const EditBlock* ed = nullptr; const LongBlock* lg = nullptr; const ResampleBlock* rs = nullptr;
-  const float* context = nullptr; int context_rows = 0;
-};
-static int sample_impl(const SampleCall& q) {
-  eegldm_unet* const u = q.u; eegldm_aekl* const ae = q.ae;
-  const int B = q.B, L = q.L;
-  const MultistepCoef* const ms = q.ms; const EditBlock* const ed = q.ed; const LongBlock* const lg = q.lg; const ResampleBlock* const rs = q.rs;
-  EEG_CHECK(u && q.noise && q.timesteps && q.a_t && (q.a_prev || ms), "null argument");
-  EEG_CHECK(!q.ancestral || q.beta_t, "the ancestral (DDPM) step needs beta_t");
-  EEG_CHECK(q.n_steps >= 1 && B >= 1 && L >= 1, "bad sizes");
-  EEG_CHECK(lg || q.latents_out || q.windows_out, "nothing to return: pass latents_out and/or windows_out");
-  EEG_CHECK(!lg || (ms && lg->R >= 1 && lg->W >= 1 && (long)lg->R * lg->W == B), "the canvas form needs the multistep coefficients and B == R * W");
-  EEG_CHECK(!lg || lg->canvas_out || lg->recording_out, "nothing to return: pass canvas_out and/or recording_out");
-  EEG_CHECK(!ed || (ed->known && !q.ancestral), "editing needs the known signal and a deterministic step");
-  EEG_CHECK(!ed || !ms || ed->a_next, "the multistep form needs a_next");
+
+// Every precondition of a call of the loop, each stated once; include/eegldm.h (eegldm_sample_desc) describes the groups.  Host reads only:
+// it runs ahead of the state lock and of every launch and allocation, so a refused call leaves nothing behind.
+static int sample_check(const eegldm_sample_desc& d) {
+  eegldm_unet* const u = d.unet;
+  const bool ms = d.cx != nullptr, ed = d.known != nullptr, lg = d.R > 0;
+  // null handles and arrays
+  EEG_CHECK(u, "null argument: unet");
+  EEG_CHECK(d.noise && d.timesteps && d.a_t, "null argument: noise, timesteps and a_t are required");
+  // sizes
+  EEG_CHECK(d.n_steps >= 1 && d.L >= 1 && (lg ? d.W >= 1 : d.B >= 1), "bad sizes");
+  EEG_CHECK(!lg || (long)d.R * d.W <= 0x3fffffffL, "R * W = %ld rows: too many", (long)d.R * d.W);
+  const int B = lg ? d.R * d.W : d.B;
+  // exactly one step form: DDIM (a_prev), DDPM (a_prev, ancestral, beta_t) or multistep (cx, c0, c1)
+  EEG_CHECK(ms ? (d.c0 && d.c1) : d.a_prev != nullptr, "null argument: the step needs a_prev (DDIM / DDPM) or cx, c0 and c1 (multistep)");
+  EEG_CHECK(!d.ancestral || !ms, "the ancestral (DDPM) step and the multistep coefficients exclude each other");
+  EEG_CHECK(!d.ancestral || d.beta_t, "null argument: the ancestral (DDPM) step needs beta_t");
+  EEG_CHECK(!d.ancestral || !ed, "editing (known) needs a deterministic step");
+  EEG_CHECK(!ms || d.c1[0] == 0.0f, "the first executed step has no history: c1[0] must be 0 (got %g)", ms ? (double)d.c1[0] : 0.0);
+  // classes
+  const int K = unet_num_classes(u);
+  if (d.labels) {
+    EEG_CHECK(K > 0, "labels for a UNet built without classes");
+    EEG_CHECK(d.guidance_scale == d.guidance_scale, "guidance_scale is NaN");
+    for (int b = 0; b < B; b++) EEG_CHECK(d.labels[b] >= 0 && d.labels[b] < K, "label %lld of sample %d outside [0, %d)", (long long)d.labels[b], b, K);
+    EEG_CHECK(d.guidance_scale == 1.0f || (d.null_class >= 0 && d.null_class < K), "null_class %lld outside [0, %d)", (long long)d.null_class, K);
+  } else {
+    EEG_CHECK(K == 0, "this UNet is class-conditional: pass labels");
+  }
+  // edit
+  EEG_CHECK(ed || !d.mask, "a mask needs the known signal");
+  EEG_CHECK(!ed || !ms || d.a_next, "null argument: known with the multistep step needs a_next");
+  // canvas
+  EEG_CHECK(!lg || ms, "the canvas form needs the multistep coefficients");
+  EEG_CHECK(!lg || (d.m >= 0 && d.r >= 0 && (long)d.L >= 3L * d.m + 2L * d.r && d.L - (2 * d.m + d.r) >= 1),
+            "window length %d, margin %d, ramp %d: needs m, r >= 0 and L >= 3 m + 2 r", d.L, d.m, d.r);
+  // something to return
+  EEG_CHECK(lg ? (d.canvas_out || d.recording_out) : (d.latents_out || d.windows_out),
+            "nothing to return: pass %s", lg ? "canvas_out and/or recording_out" : "latents_out and/or windows_out");
+  // jumps
+  if (d.jump_x || d.jump_n) {
+    EEG_CHECK(d.jump_x && d.jump_n, "null argument: jump_x and jump_n must both be NULL or both be set");
+    EEG_CHECK(ed && d.mask, "resampling needs the known signal and the mask");
+    EEG_CHECK(d.jump_n[0] == 0.0f, "no jump can stand in front of the first forward (jump_n[0] = %g)", (double)d.jump_n[0]);
+    for (int i = 0; i < d.n_steps; i++) {
+      EEG_CHECK(d.jump_x[i] == d.jump_x[i] && d.jump_n[i] == d.jump_n[i], "jump coefficient %d is NaN", i);
+      EEG_CHECK(d.jump_n[i] == 0.0f || !ms || d.c1[i] == 0.0f, "the step behind the jump at entry %d has no history: c1 must be 0 (got %g)", i,
+                ms ? (double)d.c1[i] : 0.0);
+    }
+  }
+  // model and context
+  EEG_CHECK(unet_out_channels(u) == unet_x_channels(u), "sampling needs x channels == out_channels");
+  EEG_CHECK(!d.ae || aekl_ctx(d.ae) == unet_ctx(u), "the autoencoder and the UNet must share one context");
+  EEG_CHECK(!d.context || unet_context_channels(u) > 0, "a context for a UNet built without context channels");
+  EEG_CHECK(!d.context || (lg ? d.context_rows == d.R : (d.context_rows >= 1 && B % d.context_rows == 0)),
+            "%d context rows: the canvas form needs one per recording, the others a divisor of B = %d", d.context_rows, B);
+  return 0;
+}
+
+// The loop itself (include/eegldm.h, eegldm_sample_desc: what each group of members selects).
+static int sample_impl(const eegldm_sample_desc& d) {
+  EEG_TRY(sample_check(d));
+  eegldm_unet* const u = d.unet; eegldm_aekl* const ae = d.ae;
+  const bool ms = d.cx != nullptr, ed = d.known != nullptr, lg = d.R > 0, rs = d.jump_n != nullptr;
+  const int B = lg ? d.R * d.W : d.B, L = d.L;
   eegldm_ctx* ctx = unet_ctx(u);
   const int C = unet_x_channels(u), Cc = unet_context_channels(u);
-  EEG_CHECK(unet_out_channels(u) == C, "sampling needs x channels == out_channels");
-  EEG_CHECK(!q.context || Cc > 0, "a context for a UNet built without context channels");
-  EEG_CHECK(!q.context || (lg ? q.context_rows == lg->R : (q.context_rows >= 1 && B % q.context_rows == 0)),
-            "%d context rows: the canvas form needs one per recording, the others a divisor of B = %d", q.context_rows, B);
-  EEG_CHECK(!ae || aekl_ctx(ae) == ctx, "the autoencoder and the UNet must share one context");
   const int K = unet_num_classes(u);
-  const bool cond = q.labels != nullptr;
-  const bool guided = cond && q.guidance_scale != 1.0f;      // w == 1 is the plain conditional sampler: the null-class half is not run
+  const bool cond = d.labels != nullptr;
+  const float w = cond ? d.guidance_scale : 1.0f;             // (read only with labels: a zeroed descriptor without them is not w = 0)
+  const bool guided = cond && w != 1.0f;                    // w == 1 is the plain conditional sampler: the null-class half is not run
   const int Bf = guided ? 2 * B : B;                        // rows of every forward
-  bool shared = true;                                       // every forward row reads the same embedding row (row stride 0)
-  if (cond) {
-    for (int b = 0; b < B; b++) {
-      EEG_CHECK(q.labels[b] >= 0 && q.labels[b] < K, "label %lld of sample %d outside [0, %d)", (long long)q.labels[b], b, K);
-      if (q.labels[b] != q.labels[0]) shared = false;
-    }
-    if (guided) { EEG_CHECK(q.null_class >= 0 && q.null_class < K, "null_class %lld outside [0, %d)", (long long)q.null_class, K); shared = false; }
-  }
+  bool shared = !guided;                                    // every forward row reads the same embedding row (row stride 0)
+  for (int b = 1; cond && b < B; b++) if (d.labels[b] != d.labels[0]) shared = false;
   const long n = (long)B * C * L, nf = (long)Bf * C * L;
   std::lock_guard<std::recursive_mutex> lock(states_mutex());
   SamplerState& s = states()[GraphKey{u, Bf, L}];
@@ -159,12 +167,9 @@ static int sample_impl(const SampleCall& q) {
   const long ncx = (long)B * Cc * L;                                 // context values of one half of the forward rows
   if (Cc > 0 && !s.cx) HIP_TRY(hipMalloc(&s.cx, sizeof(float) * (size_t)Bf * Cc * L));
   if (ms && !lg && !s.hist) HIP_TRY(hipMalloc(&s.hist, sizeof(float) * nf));      // (nf: the state is shared like nz)
-  const int Sl = lg ? L - (2 * lg->m + lg->r) : 0;                 // (checked by the first eegldm_canvas_gather / eegldm_canvas_step below)
-  const long Lc = lg ? (long)(lg->W - 1) * Sl + L : 0, ncv = lg ? (long)lg->R * C * Lc : 0;
-  if (lg) {
-    EEG_CHECK(lg->m >= 0 && lg->r >= 0 && (long)L >= 3L * lg->m + 2L * lg->r && Sl >= 1, "window length %d, margin %d, ramp %d: needs m, r >= 0 and L >= 3 m + 2 r", L, lg->m, lg->r);
-    if (!s.canvas) { HIP_TRY(hipMalloc(&s.canvas, sizeof(float) * nf)); HIP_TRY(hipMalloc(&s.chist, sizeof(float) * nf)); }      // (ncv <= n <= nf)
-  }
+  const int Sl = lg ? L - (2 * d.m + d.r) : 0;
+  const long Lc = lg ? (long)(d.W - 1) * Sl + L : 0, ncv = lg ? (long)d.R * C * Lc : 0;
+  if (lg && !s.canvas) { HIP_TRY(hipMalloc(&s.canvas, sizeof(float) * nf)); HIP_TRY(hipMalloc(&s.chist, sizeof(float) * nf)); }      // (ncv <= n <= nf)
   // the whole loop runs on the sampler's own stream (a capture cannot start on the NULL stream the caller may have given the context):
   // it waits for the caller's stream first and the caller's stream waits for it at the end
   hipStream_t caller = ctx->stream;
@@ -172,7 +177,7 @@ static int sample_impl(const SampleCall& q) {
   // Eager launches (the default) stay on the caller's stream: a second stream is a second hardware queue, and alternating queues
   // measured +8 % on the one-window chain (47.5 vs 51.8 ms, the same as GPU_MAX_HW_QUEUES=1 gives with the own stream).
   EEG_ENV_VAR(bool, force_own, getenv("EEGLDM_SAMPLE_OWN_STREAM") != nullptr);
-  const bool own = q.use_graph || force_own;
+  const bool own = d.use_graph || force_own;
   const hipStream_t run = own ? s.stream : caller;
   if (own) {
     HIP_TRY(hipEventRecord(s.ev_in, caller));
@@ -180,27 +185,27 @@ static int sample_impl(const SampleCall& q) {
   }
   ctx->stream = run;
   if (lg) {
-    if (ed) EEG_TRY(eegldm_edit_start(ctx, ed->known, 1.0f, q.noise, q.a_t[0], nullptr, s.canvas, ncv));
-    else HIP_TRY(hipMemcpyAsync(s.canvas, q.noise, sizeof(float) * ncv, hipMemcpyDeviceToDevice, run));
-    EEG_TRY(eegldm_canvas_gather(ctx, s.canvas, lg->R, C, lg->W, L, Sl, s.x, guided ? s.x + n : nullptr));
-  } else if (ed) EEG_TRY(eegldm_edit_start(ctx, ed->known, 1.0f, q.noise, q.a_t[0], nullptr, s.x, n));
-  else HIP_TRY(hipMemcpyAsync(s.x, q.noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
-  if (guided && !lg) HIP_TRY(hipMemcpyAsync(s.x + n, ed ? s.x : q.noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));     // the null-class half: same latents
+    if (ed) EEG_TRY(eegldm_edit_start(ctx, d.known, 1.0f, d.noise, d.a_t[0], nullptr, s.canvas, ncv));
+    else HIP_TRY(hipMemcpyAsync(s.canvas, d.noise, sizeof(float) * ncv, hipMemcpyDeviceToDevice, run));
+    EEG_TRY(eegldm_canvas_gather(ctx, s.canvas, d.R, C, d.W, L, Sl, s.x, guided ? s.x + n : nullptr));
+  } else if (ed) EEG_TRY(eegldm_edit_start(ctx, d.known, 1.0f, d.noise, d.a_t[0], nullptr, s.x, n));
+  else HIP_TRY(hipMemcpyAsync(s.x, d.noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
+  if (guided && !lg) HIP_TRY(hipMemcpyAsync(s.x + n, ed ? s.x : d.noise, sizeof(float) * n, hipMemcpyDeviceToDevice, run));     // the null-class half: same latents
   struct ClearContext { eegldm_unet* u; ~ClearContext() { if (u) (void)eegldm_unet_set_context(u, nullptr, 0); } } clear_context{Cc > 0 ? u : nullptr};
   if (Cc > 0) {
-    if (!q.context) HIP_TRY(hipMemsetAsync(s.cx, 0, sizeof(float) * (size_t)Bf * Cc * L, run));
-    else if (lg) EEG_TRY(eegldm_canvas_gather(ctx, q.context, lg->R, Cc, lg->W, L, Sl, s.cx, guided ? s.cx + ncx : nullptr));
+    if (!d.context) HIP_TRY(hipMemsetAsync(s.cx, 0, sizeof(float) * (size_t)Bf * Cc * L, run));
+    else if (lg) EEG_TRY(eegldm_canvas_gather(ctx, d.context, d.R, Cc, d.W, L, Sl, s.cx, guided ? s.cx + ncx : nullptr));
     else {
-      const long nrow = (long)q.context_rows * Cc * L;
-      for (long k = 0; k < (long)Bf / q.context_rows; k++)
-        HIP_TRY(hipMemcpyAsync(s.cx + k * nrow, q.context, sizeof(float) * nrow, hipMemcpyDeviceToDevice, run));
+      const long nrow = (long)d.context_rows * Cc * L;
+      for (long k = 0; k < (long)Bf / d.context_rows; k++)
+        HIP_TRY(hipMemcpyAsync(s.cx + k * nrow, d.context, sizeof(float) * nrow, hipMemcpyDeviceToDevice, run));
     }
     EEG_TRY(eegldm_unet_set_context(u, s.cx, Bf));
   }
   if (cond) {
     HIP_TRY(hipStreamSynchronize(run));             // (the host arrays below are rewritten: an earlier call's copies from them must be done)
-    s.lab_host.assign(q.labels, q.labels + B);
-    if (guided) s.lab_host.resize(Bf, q.null_class);
+    s.lab_host.assign(d.labels, d.labels + B);
+    if (guided) s.lab_host.resize(Bf, d.null_class);
     HIP_TRY(hipMemcpyAsync(s.lab, s.lab_host.data(), sizeof(int64_t) * Bf, hipMemcpyHostToDevice, run));
   }
   const int64_t* fwd_lab = cond ? s.lab : nullptr;
@@ -213,7 +218,7 @@ static int sample_impl(const SampleCall& q) {
   const bool table = !no_table;
   const int mode = !table ? 0 : (shared ? 1 : 2);
   if (mode == 2 && !s.emb_rows) HIP_TRY(hipMalloc(&s.emb_rows, sizeof(float) * (size_t)Bf * etot));
-  if (q.use_graph && !ctx->prof_on && !s.capture_failed) {
+  if (d.use_graph && !ctx->prof_on && !s.capture_failed) {
     // Round 5: the captured forward reads its embedding projections from ONE fixed row (s.emb_row) that the loop below refills from the
     // table of all timesteps before every replay -- until round 4 the graph path recomputed the embedding MLP and the 21 projections
     // inside every replay (six launches, ~100 us at B = 1: 5 of the 10.6 ms by which the replayed DDIM-50 trailed the eager one).
@@ -230,7 +235,7 @@ static int sample_impl(const SampleCall& q) {
     }
     if (!s.exec) {
       // eager warm-up: grows the arena / workspaces (hipMalloc is not capturable), then capture the identical launch sequence
-      set_t(q.timesteps[0]);
+      set_t(d.timesteps[0]);
       if (mode == 2) HIP_TRY(hipMemsetAsync(s.emb_rows, 0, sizeof(float) * (size_t)Bf * etot, run));
       EEG_TRY(unet_forward_labels(u, s.x, s.tt, fwd_lab, s.out, Bf, L, 0));
       HIP_TRY(hipStreamSynchronize(run));
@@ -248,7 +253,7 @@ static int sample_impl(const SampleCall& q) {
       }
     } else graph_ok = true;
   }
-  if (q.graph_used) *q.graph_used = graph_ok ? 1 : 0;
+  if (d.graph_used) *d.graph_used = graph_ok ? 1 : 0;
 
   // Eager path: the timesteps are known up front and shared by all samples, so the timestep-embedding MLP and the ResBlocks' embedding
   // projections run ONCE for all n_steps (one batch of n_steps rows) instead of six launches (~100 us at B = 1) inside every step;
@@ -257,7 +262,7 @@ static int sample_impl(const SampleCall& q) {
   // or -- several classes or guidance -- each step gathers its rows into s.emb_rows (row stride etot).
   if (!graph_ok) unet_set_shared_emb(u, mode == 2 ? s.emb_rows : nullptr, mode == 2 ? etot : 0);      // (a failed capture falls back to the eager path below)
   const int Kt = cond ? K : 1;
-  const int rows = q.n_steps * Kt;
+  const int rows = d.n_steps * Kt;
   if (table) {
     if (s.emb_cap < rows) {
       HIP_TRY(hipStreamSynchronize(run));
@@ -274,27 +279,27 @@ static int sample_impl(const SampleCall& q) {
     }
     if (cond) {
       s.tab_t.resize(rows); s.tab_y.resize(rows);
-      for (int i = 0; i < q.n_steps; i++) for (int c = 0; c < K; c++) { s.tab_t[(size_t)i * K + c] = q.timesteps[i]; s.tab_y[(size_t)i * K + c] = c; }
+      for (int i = 0; i < d.n_steps; i++) for (int c = 0; c < K; c++) { s.tab_t[(size_t)i * K + c] = d.timesteps[i]; s.tab_y[(size_t)i * K + c] = c; }
       HIP_TRY(hipMemcpyAsync(s.steps_dev, s.tab_t.data(), sizeof(int64_t) * rows, hipMemcpyHostToDevice, run));
       HIP_TRY(hipMemcpyAsync(s.tab_y_dev, s.tab_y.data(), sizeof(int64_t) * rows, hipMemcpyHostToDevice, run));
     } else {
-      HIP_TRY(hipMemcpyAsync(s.steps_dev, q.timesteps, sizeof(int64_t) * q.n_steps, hipMemcpyHostToDevice, run));
+      HIP_TRY(hipMemcpyAsync(s.steps_dev, d.timesteps, sizeof(int64_t) * d.n_steps, hipMemcpyHostToDevice, run));
     }
     EEG_TRY(unet_embed_table(u, s.steps_dev, cond ? s.tab_y_dev : nullptr, rows, s.emb_table, s.emb_work));
-    set_t(q.timesteps[0]);                       // s.tt is not read on this path; keep it defined
+    set_t(d.timesteps[0]);                       // s.tt is not read on this path; keep it defined
   }
 
-  const size_t row0 = cond ? (size_t)q.labels[0] : 0;
+  const size_t row0 = cond ? (size_t)d.labels[0] : 0;
   uint64_t jump_index = 0;
-  for (int i = 0; i < q.n_steps; i++) {
-    if (rs && rs->jump_n[i] != 0.0f) {
+  for (int i = 0; i < d.n_steps; i++) {
+    if (rs && d.jump_n[i] != 0.0f) {
       if (lg) {
-        EEG_TRY(eegldm_edit_jump(ctx, s.canvas, rs->jump_x[i], rs->jump_n[i], nullptr, rs->seed, jump_index * (uint64_t)((ncv + 3) / 4), ed->known,
-                                 q.noise, ed->mask, q.a_t[i], s.canvas, nullptr, ncv));
-        EEG_TRY(eegldm_canvas_gather(ctx, s.canvas, lg->R, C, lg->W, L, Sl, s.x, guided ? s.x + n : nullptr));
+        EEG_TRY(eegldm_edit_jump(ctx, s.canvas, d.jump_x[i], d.jump_n[i], nullptr, d.noise_seed, jump_index * (uint64_t)((ncv + 3) / 4), d.known,
+                                 d.noise, d.mask, d.a_t[i], s.canvas, nullptr, ncv));
+        EEG_TRY(eegldm_canvas_gather(ctx, s.canvas, d.R, C, d.W, L, Sl, s.x, guided ? s.x + n : nullptr));
       } else {
-        EEG_TRY(eegldm_edit_jump(ctx, s.x, rs->jump_x[i], rs->jump_n[i], nullptr, rs->seed, jump_index * (uint64_t)((n + 3) / 4), ed->known, q.noise,
-                                 ed->mask, q.a_t[i], s.x, guided ? s.x + n : nullptr, n));
+        EEG_TRY(eegldm_edit_jump(ctx, s.x, d.jump_x[i], d.jump_n[i], nullptr, d.noise_seed, jump_index * (uint64_t)((n + 3) / 4), d.known, d.noise,
+                                 d.mask, d.a_t[i], s.x, guided ? s.x + n : nullptr, n));
       }
       jump_index++;
     }
@@ -302,50 +307,50 @@ static int sample_impl(const SampleCall& q) {
     if (mode == 2) EEG_TRY(ew_emb_gather(ctx, step_rows, s.lab, Kt, etot, s.emb_rows, Bf));
     else if (table && graph_ok) HIP_TRY(hipMemcpyAsync(s.emb_row, step_rows + row0 * etot, sizeof(float) * (size_t)etot, hipMemcpyDeviceToDevice, run));
     else if (table) unet_set_shared_emb(u, step_rows + row0 * etot, 0);
-    else set_t(q.timesteps[i]);
+    else set_t(d.timesteps[i]);
     if (graph_ok) HIP_TRY(hipGraphLaunch(s.exec, run));
     else EEG_TRY(unet_forward_labels(u, s.x, s.tt, fwd_lab, s.out, Bf, L, 0));
     if (ed && lg) {
-      EEG_TRY(eegldm_canvas_edit_step(ctx, s.out, q.guidance_scale, guided ? 1 : 0, s.canvas, s.chist, q.a_t[i], ed->a_next[i], q.pred_type, q.clip_sample,
-                                      ms->cx[i], ms->c0[i], ms->c1[i], lg->R, C, lg->W, L, lg->m, lg->r, ed->known, q.noise, ed->mask, s.canvas, s.x,
-                                      guided ? s.x + n : nullptr, nullptr));
+      EEG_TRY(eegldm_canvas_edit_step(ctx, s.out, w, guided ? 1 : 0, s.canvas, s.chist, d.a_t[i], d.a_next[i], d.pred_type, d.clip_sample, d.cx[i],
+                                      d.c0[i], d.c1[i], d.R, C, d.W, L, d.m, d.r, d.known, d.noise, d.mask, s.canvas, s.x, guided ? s.x + n : nullptr,
+                                      nullptr));
       continue;
     }
     if (ed) {      // (without a mask too: an all-zero mask and no mask are then the same bytes in every form)
-      const float coef[3] = {ms ? ms->cx[i] : 0.0f, ms ? ms->c0[i] : 0.0f, ms ? ms->c1[i] : 0.0f};
-      EEG_TRY(eegldm_edit_step(ctx, s.out, q.guidance_scale, guided ? 1 : 0, s.x, ms ? s.hist : nullptr, q.a_t[i], ms ? ed->a_next[i] : q.a_prev[i],
-                               q.pred_type, q.clip_sample, ms ? coef : nullptr, ed->known, q.noise, ed->mask, s.x, guided ? s.x + n : nullptr, nullptr, n));
+      const float coef[3] = {ms ? d.cx[i] : 0.0f, ms ? d.c0[i] : 0.0f, ms ? d.c1[i] : 0.0f};
+      EEG_TRY(eegldm_edit_step(ctx, s.out, w, guided ? 1 : 0, s.x, ms ? s.hist : nullptr, d.a_t[i], ms ? d.a_next[i] : d.a_prev[i], d.pred_type,
+                               d.clip_sample, ms ? coef : nullptr, d.known, d.noise, d.mask, s.x, guided ? s.x + n : nullptr, nullptr, n));
       continue;
     }
     if (lg) {
-      EEG_TRY(eegldm_canvas_step(ctx, s.out, q.guidance_scale, guided ? 1 : 0, s.canvas, s.chist, q.a_t[i], q.pred_type, q.clip_sample, ms->cx[i], ms->c0[i],
-                                 ms->c1[i], lg->R, C, lg->W, L, lg->m, lg->r, s.canvas, s.x, guided ? s.x + n : nullptr, nullptr));
+      EEG_TRY(eegldm_canvas_step(ctx, s.out, w, guided ? 1 : 0, s.canvas, s.chist, d.a_t[i], d.pred_type, d.clip_sample, d.cx[i], d.c0[i], d.c1[i], d.R, C,
+                                 d.W, L, d.m, d.r, s.canvas, s.x, guided ? s.x + n : nullptr, nullptr));
       continue;
     }
     if (ms) {
-      EEG_TRY(eegldm_multistep_step(ctx, s.out, q.guidance_scale, guided ? 1 : 0, s.x, s.hist, q.a_t[i], q.pred_type, q.clip_sample, ms->cx[i], ms->c0[i],
-                                    ms->c1[i], s.x, guided ? s.x + n : nullptr, nullptr, n));
+      EEG_TRY(eegldm_multistep_step(ctx, s.out, w, guided ? 1 : 0, s.x, s.hist, d.a_t[i], d.pred_type, d.clip_sample, d.cx[i], d.c0[i], d.c1[i], s.x,
+                                    guided ? s.x + n : nullptr, nullptr, n));
       continue;
     }
-    const bool last = q.a_prev[i] >= 1.0f;
-    if (q.ancestral && !last) EEG_TRY(eegldm_randn(ctx, s.nz, n, q.noise_seed, (uint64_t)i * (uint64_t)((n + 3) / 4)));
+    const bool last = d.a_prev[i] >= 1.0f;
+    if (d.ancestral && !last) EEG_TRY(eegldm_randn(ctx, s.nz, n, d.noise_seed, (uint64_t)i * (uint64_t)((n + 3) / 4)));
     if (guided) {
-      EEG_TRY(eegldm_guided_step(ctx, s.out, q.guidance_scale, s.x, last ? nullptr : s.nz, q.a_t[i], q.a_prev[i], q.ancestral ? q.beta_t[i] : 0.0f,
-                                 q.ancestral, q.pred_type, q.clip_sample, s.x, s.x + n, n));
-    } else if (q.ancestral) {
-      EEG_TRY(eegldm_ddpm_step(ctx, s.out, s.x, last ? nullptr : s.nz, q.a_t[i], q.a_prev[i], q.beta_t[i], q.pred_type, q.clip_sample, s.x, nullptr, n));
+      EEG_TRY(eegldm_guided_step(ctx, s.out, w, s.x, last ? nullptr : s.nz, d.a_t[i], d.a_prev[i], d.ancestral ? d.beta_t[i] : 0.0f, d.ancestral,
+                                 d.pred_type, d.clip_sample, s.x, s.x + n, n));
+    } else if (d.ancestral) {
+      EEG_TRY(eegldm_ddpm_step(ctx, s.out, s.x, last ? nullptr : s.nz, d.a_t[i], d.a_prev[i], d.beta_t[i], d.pred_type, d.clip_sample, s.x, nullptr, n));
     } else {
-      EEG_TRY(eegldm_ddim_step(ctx, s.out, s.x, q.a_t[i], q.a_prev[i], q.pred_type, q.clip_sample, s.x, nullptr, n));
+      EEG_TRY(eegldm_ddim_step(ctx, s.out, s.x, d.a_t[i], d.a_prev[i], d.pred_type, d.clip_sample, s.x, nullptr, n));
     }
   }
   if (lg) {
-    if (lg->canvas_out) HIP_TRY(hipMemcpyAsync(lg->canvas_out, s.canvas, sizeof(float) * ncv, hipMemcpyDeviceToDevice, run));
-    if (lg->recording_out && !ae) HIP_TRY(hipMemcpyAsync(lg->recording_out, s.canvas, sizeof(float) * ncv, hipMemcpyDeviceToDevice, run));    // pixel space
-    if (lg->recording_out && ae) {
+    if (d.canvas_out) HIP_TRY(hipMemcpyAsync(d.canvas_out, s.canvas, sizeof(float) * ncv, hipMemcpyDeviceToDevice, run));
+    if (d.recording_out && !ae) HIP_TRY(hipMemcpyAsync(d.recording_out, s.canvas, sizeof(float) * ncv, hipMemcpyDeviceToDevice, run));    // pixel space
+    if (d.recording_out && ae) {
       // the slices of the final canvas, decoded window by window (one GroupNorm statistic per 30-s window, as in training), cross-faded
       const int down = aekl_down(ae), Co = aekl_out_channels(ae);
-      EEG_TRY(eegldm_canvas_gather(ctx, s.canvas, lg->R, C, lg->W, L, Sl, s.x, nullptr));
-      if (q.inv_scale_factor != 1.0f) EEG_TRY(eegldm_axpy(ctx, s.x, s.x, q.inv_scale_factor - 1.0f, n));
+      EEG_TRY(eegldm_canvas_gather(ctx, s.canvas, d.R, C, d.W, L, Sl, s.x, nullptr));
+      if (d.inv_scale_factor != 1.0f) EEG_TRY(eegldm_axpy(ctx, s.x, s.x, d.inv_scale_factor - 1.0f, n));
       const size_t nd = (size_t)B * Co * L * down;              // (a guided call and a plain one share this state at different B)
       if (s.dec_cap < nd) {
         HIP_TRY(hipStreamSynchronize(run));
@@ -355,16 +360,16 @@ static int sample_impl(const SampleCall& q) {
         s.dec_cap = nd;
       }
       EEG_TRY(eegldm_aekl_decode(ae, s.x, s.dec, B, L));
-      EEG_TRY(eegldm_canvas_compose(ctx, s.dec, lg->R, Co, lg->W, L * down, Sl * down, lg->m * down, lg->r * down, lg->recording_out));
+      EEG_TRY(eegldm_canvas_compose(ctx, s.dec, d.R, Co, d.W, L * down, Sl * down, d.m * down, d.r * down, d.recording_out));
     }
   }
-  if (q.latents_out) HIP_TRY(hipMemcpyAsync(q.latents_out, s.x, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
-  if (q.windows_out) {
+  if (!lg && d.latents_out) HIP_TRY(hipMemcpyAsync(d.latents_out, s.x, sizeof(float) * n, hipMemcpyDeviceToDevice, run));
+  if (!lg && d.windows_out) {
     if (ae) {
-      if (q.inv_scale_factor != 1.0f) EEG_TRY(eegldm_axpy(ctx, s.x, s.x, q.inv_scale_factor - 1.0f, n));     // z / scale_factor (sample_trials.py:166)
-      EEG_TRY(eegldm_aekl_decode(ae, s.x, q.windows_out, B, L));
+      if (d.inv_scale_factor != 1.0f) EEG_TRY(eegldm_axpy(ctx, s.x, s.x, d.inv_scale_factor - 1.0f, n));     // z / scale_factor (sample_trials.py:166)
+      EEG_TRY(eegldm_aekl_decode(ae, s.x, d.windows_out, B, L));
     } else {
-      HIP_TRY(hipMemcpyAsync(q.windows_out, s.x, sizeof(float) * n, hipMemcpyDeviceToDevice, run));    // pixel-space model: x IS the window
+      HIP_TRY(hipMemcpyAsync(d.windows_out, s.x, sizeof(float) * n, hipMemcpyDeviceToDevice, run));    // pixel-space model: x IS the window
     }
   }
   if (own) {
@@ -374,178 +379,68 @@ static int sample_impl(const SampleCall& q) {
   return 0;
 }
 
+extern "C" int eegldm_sample_run(const eegldm_sample_desc* desc) {
+  EEG_CHECK(desc, "null argument: desc");
+  EEG_CHECK(desc->size == sizeof(eegldm_sample_desc), "eegldm_sample_desc.size is %u, this library's is %u", (unsigned)desc->size,
+            (unsigned)sizeof(eegldm_sample_desc));
+  return sample_impl(*desc);
+}
+
+// ---- the positional exports: each fills a descriptor from its argument list (include/eegldm.h) and runs it.  What a NULL optional argument
+// means falls out of the descriptor's own NULL semantics; the rules are sample_check's.  The edit and the canvas families stand
+// with their widest argument list first.
+
+// The members every export sets.  guidance_scale passes through only with labels.
+static eegldm_sample_desc desc_of(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps, const float* a_t, int n_steps,
+                                  int pred_type, int clip_sample, float inv_scale_factor, int L, int use_graph, int* graph_used,
+                                  const int64_t* labels, float guidance_scale, int64_t null_class) {
+  eegldm_sample_desc d = {};
+  d.size = sizeof d;
+  d.unet = u; d.ae = ae; d.noise = noise; d.L = L;
+  d.n_steps = n_steps; d.timesteps = timesteps; d.a_t = a_t;
+  d.pred_type = pred_type; d.clip_sample = clip_sample; d.inv_scale_factor = inv_scale_factor;
+  d.labels = labels; d.guidance_scale = labels ? guidance_scale : 1.0f; d.null_class = null_class;
+  d.use_graph = use_graph; d.graph_used = graph_used;
+  return d;
+}
+
 extern "C" int eegldm_sample(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
                              const float* a_prev_host, const float* beta_t_host, int n_steps, int ancestral, int pred_type, int clip_sample,
                              float inv_scale_factor, uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
                              int* graph_used_host) {
-  EEG_CHECK(u, "null argument");
+  EEG_CHECK(u, "null argument: unet");
   EEG_CHECK(unet_num_classes(u) == 0, "this UNet is class-conditional: use eegldm_sample_cond");
-  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph,
-               graph_used_host, nullptr, 1.0f, 0};
-  q.a_prev = a_prev_host; q.beta_t = beta_t_host; q.ancestral = ancestral; q.noise_seed = noise_seed;
-  return sample_impl(q);
+  eegldm_sample_desc d = desc_of(u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, L, use_graph,
+                                 graph_used_host, nullptr, 1.0f, 0);
+  d.B = B; d.latents_out = latents_out; d.windows_out = windows_out;
+  d.a_prev = a_prev_host; d.beta_t = beta_t_host; d.ancestral = ancestral; d.noise_seed = noise_seed;
+  return eegldm_sample_run(&d);
 }
 
 extern "C" int eegldm_sample_cond(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
                                   const float* a_prev_host, const float* beta_t_host, int n_steps, int ancestral, int pred_type, int clip_sample,
                                   float inv_scale_factor, uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
                                   int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
-  EEG_CHECK(u && labels_host, "null argument");
+  EEG_CHECK(u && labels_host, "null argument: unet and labels_host are required");
   EEG_CHECK(unet_num_classes(u) > 0, "this UNet was built without classes: use eegldm_sample");
-  EEG_CHECK(guidance_scale == guidance_scale, "guidance_scale is NaN");
-  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph,
-               graph_used_host, labels_host, guidance_scale, null_class};
-  q.a_prev = a_prev_host; q.beta_t = beta_t_host; q.ancestral = ancestral; q.noise_seed = noise_seed;
-  return sample_impl(q);
+  eegldm_sample_desc d = desc_of(u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, L, use_graph,
+                                 graph_used_host, labels_host, guidance_scale, null_class);
+  d.B = B; d.latents_out = latents_out; d.windows_out = windows_out;
+  d.a_prev = a_prev_host; d.beta_t = beta_t_host; d.ancestral = ancestral; d.noise_seed = noise_seed;
+  return eegldm_sample_run(&d);
 }
 
-// What the multistep, edit and long exports check ahead of sample_impl.  multistep: the form needs its three coefficient arrays (false: the
-// DDIM form of eegldm_sample_edit, which has none).  R, W: the canvas forms' rows, else 1, 1.  step0: how the message names the step without
-// a history.  labels_host NULL: an unconditional UNet; non-NULL: a class-conditional one, guidance as in eegldm_sample_cond.
-static int sample_preamble(eegldm_unet* u, bool multistep, const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int R,
-                           int W, const char* step0, const int64_t* labels_host, float guidance_scale) {
-  EEG_CHECK(u && (!multistep || (cx_host && c0_host && c1_host)), "null argument");
-  EEG_CHECK(n_steps >= 1 && R >= 1 && W >= 1, "bad sizes");
-  EEG_CHECK((long)R * W <= 0x3fffffffL, "R * W = %ld rows: too many", (long)R * W);
-  if (multistep) EEG_CHECK(c1_host[0] == 0.0f, "%s has no history: c1[0] must be 0 (got %g)", step0, (double)c1_host[0]);
-  if (labels_host) {
-    EEG_CHECK(unet_num_classes(u) > 0, "labels for a UNet built without classes");
-    EEG_CHECK(guidance_scale == guidance_scale, "guidance_scale is NaN");
-  } else {
-    EEG_CHECK(unet_num_classes(u) == 0, "this UNet is class-conditional: pass labels_host");
-  }
-  return 0;
-}
-
-// The same call with a linear multistep solver (DPM-Solver++ 2M, include/eegldm.h) in place of the DDIM / DDPM step.
 extern "C" int eegldm_sample_multistep(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
                                        const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int pred_type,
                                        int clip_sample, float inv_scale_factor, float* latents_out, float* windows_out, int B, int L,
                                        int use_graph, int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
-  EEG_TRY(sample_preamble(u, true, cx_host, c0_host, c1_host, n_steps, 1, 1, "step 0", labels_host, guidance_scale));
-  const MultistepCoef ms{cx_host, c0_host, c1_host};
-  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph,
-               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
-  q.ms = &ms;
-  return sample_impl(q);
+  eegldm_sample_desc d = desc_of(u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, L, use_graph,
+                                 graph_used_host, labels_host, guidance_scale, null_class);
+  d.B = B; d.latents_out = latents_out; d.windows_out = windows_out;
+  d.cx = cx_host; d.c0 = c0_host; d.c1 = c1_host;
+  return eegldm_sample_run(&d);
 }
 
-// The same loops from an input (include/eegldm.h): cx_host NULL = DDIM, else the multistep form.
-extern "C" int eegldm_sample_edit(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
-                                  const int64_t* timesteps_host, const float* a_t_host, const float* a_prev_host, const float* cx_host,
-                                  const float* c0_host, const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
-                                  float inv_scale_factor, float* latents_out, float* windows_out, int B, int L, int use_graph, int* graph_used_host,
-                                  const int64_t* labels_host, float guidance_scale, int64_t null_class) {
-  EEG_TRY(sample_preamble(u, cx_host != nullptr, cx_host, c0_host, c1_host, n_steps, 1, 1, "the first executed step", labels_host, guidance_scale));
-  EEG_CHECK(known || !mask, "a mask needs the known signal");
-  EEG_CHECK(cx_host || a_prev_host, "the DDIM form needs a_prev_host");
-  EEG_CHECK(!cx_host || !known || a_next_host, "the multistep form needs a_next_host");
-  const MultistepCoef ms{cx_host, c0_host, c1_host};
-  const EditBlock ed{known, mask, a_next_host};
-  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph,
-               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
-  if (cx_host) q.ms = &ms; else q.a_prev = a_prev_host;
-  if (known) q.ed = &ed;
-  return sample_impl(q);
-}
-
-// Long recordings (include/eegldm.h): R canvases of W overlapping windows each, sampled as one batch of R * W rows.
-extern "C" int eegldm_sample_long(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
-                                  const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int pred_type, int clip_sample,
-                                  float inv_scale_factor, float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
-                                  int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
-  return eegldm_sample_long_edit(u, ae, noise, nullptr, nullptr, timesteps_host, a_t_host, cx_host, c0_host, c1_host, nullptr, n_steps, pred_type,
-                                 clip_sample, inv_scale_factor, canvas_out, recording_out, R, W, L, m, r, use_graph, graph_used_host, labels_host,
-                                 guidance_scale, null_class);
-}
-
-// The same loop from a real recording (include/eegldm.h): the canvas form with the edit block.  known == NULL: the plain form.
-extern "C" int eegldm_sample_long_edit(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
-                                       const int64_t* timesteps_host, const float* a_t_host, const float* cx_host, const float* c0_host,
-                                       const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
-                                       float inv_scale_factor, float* canvas_out, float* recording_out, int R, int W, int L, int m, int r,
-                                       int use_graph, int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
-  EEG_CHECK(known || !mask, "a mask needs the known signal");
-  EEG_CHECK(!known || a_next_host, "the run from an input needs a_next_host");
-  EEG_TRY(sample_preamble(u, true, cx_host, c0_host, c1_host, n_steps, R, W, known ? "the first executed step" : "step 0", labels_host,
-                          guidance_scale));
-  const MultistepCoef ms{cx_host, c0_host, c1_host};
-  const EditBlock ed{known, mask, a_next_host};
-  const LongBlock lg{R, W, m, r, canvas_out, recording_out};
-  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, nullptr, nullptr, R * W, L, use_graph,
-               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
-  q.ms = &ms; q.lg = &lg;
-  if (known) q.ed = &ed;
-  return sample_impl(q);
-}
-
-// What the resampling exports check ahead of the loop (include/eegldm.h): both jump arrays, no jump in front of the first forward, no
-// history read behind a jump, and the known signal with its mask.
-static int resample_preamble(const float* jump_x_host, const float* jump_n_host, const float* c1_host, int n_steps, const float* known,
-                             const float* mask) {
-  EEG_CHECK(jump_x_host && jump_n_host, "jump_x_host and jump_n_host must both be NULL or both be set");
-  EEG_CHECK(known && mask, "resampling needs the known signal and the mask");
-  EEG_CHECK(n_steps >= 1, "bad sizes");
-  EEG_CHECK(jump_n_host[0] == 0.0f, "no jump can stand in front of the first forward (jump_n[0] = %g)", (double)jump_n_host[0]);
-  for (int i = 0; i < n_steps; i++) {
-    EEG_CHECK(jump_x_host[i] == jump_x_host[i] && jump_n_host[i] == jump_n_host[i], "jump coefficient %d is NaN", i);
-    EEG_CHECK(jump_n_host[i] == 0.0f || !c1_host || c1_host[i] == 0.0f, "the step behind the jump at entry %d has no history: c1 must be 0 (got %g)", i,
-              (double)c1_host[i]);
-  }
-  return 0;
-}
-
-// Resampled repair (include/eegldm.h): eegldm_sample_edit with one entry per forward and a jump in front of some of them.
-extern "C" int eegldm_sample_edit_resample(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
-                                           const int64_t* timesteps_host, const float* a_t_host, const float* a_prev_host, const float* cx_host,
-                                           const float* c0_host, const float* c1_host, const float* a_next_host, int n_steps, int pred_type,
-                                           int clip_sample, float inv_scale_factor, const float* jump_x_host, const float* jump_n_host,
-                                           uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
-                                           int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
-  if (!jump_x_host && !jump_n_host)
-    return eegldm_sample_edit(u, ae, noise, known, mask, timesteps_host, a_t_host, a_prev_host, cx_host, c0_host, c1_host, a_next_host, n_steps,
-                              pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph, graph_used_host, labels_host,
-                              guidance_scale, null_class);
-  EEG_TRY(sample_preamble(u, cx_host != nullptr, cx_host, c0_host, c1_host, n_steps, 1, 1, "the first executed step", labels_host, guidance_scale));
-  EEG_TRY(resample_preamble(jump_x_host, jump_n_host, cx_host ? c1_host : nullptr, n_steps, known, mask));
-  EEG_CHECK(cx_host || a_prev_host, "the DDIM form needs a_prev_host");
-  EEG_CHECK(!cx_host || a_next_host, "the multistep form needs a_next_host");
-  const MultistepCoef ms{cx_host, c0_host, c1_host};
-  const EditBlock ed{known, mask, a_next_host};
-  const ResampleBlock rs{jump_x_host, jump_n_host, noise_seed};
-  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph,
-               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
-  if (cx_host) q.ms = &ms; else q.a_prev = a_prev_host;
-  q.ed = &ed; q.rs = &rs;
-  return sample_impl(q);
-}
-
-// The same on the canvas: eegldm_sample_long_edit with one entry per forward.
-extern "C" int eegldm_sample_long_edit_resample(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
-                                                const int64_t* timesteps_host, const float* a_t_host, const float* cx_host, const float* c0_host,
-                                                const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
-                                                float inv_scale_factor, const float* jump_x_host, const float* jump_n_host, uint64_t noise_seed,
-                                                float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
-                                                int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
-  if (!jump_x_host && !jump_n_host)
-    return eegldm_sample_long_edit(u, ae, noise, known, mask, timesteps_host, a_t_host, cx_host, c0_host, c1_host, a_next_host, n_steps, pred_type,
-                                   clip_sample, inv_scale_factor, canvas_out, recording_out, R, W, L, m, r, use_graph, graph_used_host, labels_host,
-                                   guidance_scale, null_class);
-  EEG_CHECK(a_next_host, "the run from an input needs a_next_host");
-  EEG_TRY(sample_preamble(u, true, cx_host, c0_host, c1_host, n_steps, R, W, "the first executed step", labels_host, guidance_scale));
-  EEG_TRY(resample_preamble(jump_x_host, jump_n_host, c1_host, n_steps, known, mask));
-  const MultistepCoef ms{cx_host, c0_host, c1_host};
-  const EditBlock ed{known, mask, a_next_host};
-  const LongBlock lg{R, W, m, r, canvas_out, recording_out};
-  const ResampleBlock rs{jump_x_host, jump_n_host, noise_seed};
-  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, nullptr, nullptr, R * W, L, use_graph,
-               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
-  q.ms = &ms; q.lg = &lg; q.ed = &ed; q.rs = &rs;
-  return sample_impl(q);
-}
-
-// Learned repair (include/eegldm.h): the two exports above on a context UNet, with the context every forward reads.  context == NULL is the
-// predecessor itself (a context UNet then runs on zeros); jump_x_host == jump_n_host == NULL is the plain edit loop with a context.
 extern "C" int eegldm_sample_edit_ctx(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
                                       const int64_t* timesteps_host, const float* a_t_host, const float* a_prev_host, const float* cx_host,
                                       const float* c0_host, const float* c1_host, const float* a_next_host, int n_steps, int pred_type,
@@ -553,29 +448,44 @@ extern "C" int eegldm_sample_edit_ctx(eegldm_unet* u, eegldm_aekl* ae, const flo
                                       uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
                                       int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class,
                                       const float* context, int context_rows) {
-  if (!context)
-    return eegldm_sample_edit_resample(u, ae, noise, known, mask, timesteps_host, a_t_host, a_prev_host, cx_host, c0_host, c1_host, a_next_host,
-                                       n_steps, pred_type, clip_sample, inv_scale_factor, jump_x_host, jump_n_host, noise_seed, latents_out,
-                                       windows_out, B, L, use_graph, graph_used_host, labels_host, guidance_scale, null_class);
-  const bool jumps = jump_x_host || jump_n_host;
-  EEG_TRY(sample_preamble(u, cx_host != nullptr, cx_host, c0_host, c1_host, n_steps, 1, 1, "the first executed step", labels_host, guidance_scale));
-  if (jumps) EEG_TRY(resample_preamble(jump_x_host, jump_n_host, cx_host ? c1_host : nullptr, n_steps, known, mask));
-  EEG_CHECK(known || !mask, "a mask needs the known signal");
-  EEG_CHECK(cx_host || a_prev_host, "the DDIM form needs a_prev_host");
-  EEG_CHECK(!cx_host || !known || a_next_host, "the multistep form needs a_next_host");
-  const MultistepCoef ms{cx_host, c0_host, c1_host};
-  const EditBlock ed{known, mask, a_next_host};
-  const ResampleBlock rs{jump_x_host, jump_n_host, noise_seed};
-  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, latents_out, windows_out, B, L, use_graph,
-               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
-  if (cx_host) q.ms = &ms; else q.a_prev = a_prev_host;
-  if (known) q.ed = &ed;
-  if (jumps) q.rs = &rs;
-  q.context = context; q.context_rows = context_rows;
-  return sample_impl(q);
+  eegldm_sample_desc d = desc_of(u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, L, use_graph,
+                                 graph_used_host, labels_host, guidance_scale, null_class);
+  d.B = B; d.latents_out = latents_out; d.windows_out = windows_out;
+  d.a_prev = a_prev_host; d.cx = cx_host; d.c0 = c0_host; d.c1 = c1_host; d.a_next = a_next_host;
+  d.known = known; d.mask = mask;
+  d.jump_x = jump_x_host; d.jump_n = jump_n_host; d.noise_seed = noise_seed;
+  d.context = context; d.context_rows = context_rows;
+  return eegldm_sample_run(&d);
 }
 
-// The same on the canvas: context is canvas-shaped (R, context_channels, Lc), gathered once per call into window rows.
+extern "C" int eegldm_sample_edit_resample(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                                           const int64_t* timesteps_host, const float* a_t_host, const float* a_prev_host, const float* cx_host,
+                                           const float* c0_host, const float* c1_host, const float* a_next_host, int n_steps, int pred_type,
+                                           int clip_sample, float inv_scale_factor, const float* jump_x_host, const float* jump_n_host,
+                                           uint64_t noise_seed, float* latents_out, float* windows_out, int B, int L, int use_graph,
+                                           int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
+  eegldm_sample_desc d = desc_of(u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, L, use_graph,
+                                 graph_used_host, labels_host, guidance_scale, null_class);
+  d.B = B; d.latents_out = latents_out; d.windows_out = windows_out;
+  d.a_prev = a_prev_host; d.cx = cx_host; d.c0 = c0_host; d.c1 = c1_host; d.a_next = a_next_host;
+  d.known = known; d.mask = mask;
+  d.jump_x = jump_x_host; d.jump_n = jump_n_host; d.noise_seed = noise_seed;
+  return eegldm_sample_run(&d);
+}
+
+extern "C" int eegldm_sample_edit(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                                  const int64_t* timesteps_host, const float* a_t_host, const float* a_prev_host, const float* cx_host,
+                                  const float* c0_host, const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
+                                  float inv_scale_factor, float* latents_out, float* windows_out, int B, int L, int use_graph, int* graph_used_host,
+                                  const int64_t* labels_host, float guidance_scale, int64_t null_class) {
+  eegldm_sample_desc d = desc_of(u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, L, use_graph,
+                                 graph_used_host, labels_host, guidance_scale, null_class);
+  d.B = B; d.latents_out = latents_out; d.windows_out = windows_out;
+  d.a_prev = a_prev_host; d.cx = cx_host; d.c0 = c0_host; d.c1 = c1_host; d.a_next = a_next_host;
+  d.known = known; d.mask = mask;
+  return eegldm_sample_run(&d);
+}
+
 extern "C" int eegldm_sample_long_edit_ctx(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
                                            const int64_t* timesteps_host, const float* a_t_host, const float* cx_host, const float* c0_host,
                                            const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
@@ -583,25 +493,51 @@ extern "C" int eegldm_sample_long_edit_ctx(eegldm_unet* u, eegldm_aekl* ae, cons
                                            float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
                                            int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class,
                                            const float* context, int context_rows) {
-  if (!context)
-    return eegldm_sample_long_edit_resample(u, ae, noise, known, mask, timesteps_host, a_t_host, cx_host, c0_host, c1_host, a_next_host, n_steps,
-                                            pred_type, clip_sample, inv_scale_factor, jump_x_host, jump_n_host, noise_seed, canvas_out, recording_out,
-                                            R, W, L, m, r, use_graph, graph_used_host, labels_host, guidance_scale, null_class);
-  const bool jumps = jump_x_host || jump_n_host;
-  EEG_CHECK(known || !mask, "a mask needs the known signal");
-  EEG_CHECK(!known || a_next_host, "the run from an input needs a_next_host");
-  EEG_TRY(sample_preamble(u, true, cx_host, c0_host, c1_host, n_steps, R, W, known ? "the first executed step" : "step 0", labels_host,
-                          guidance_scale));
-  if (jumps) EEG_TRY(resample_preamble(jump_x_host, jump_n_host, c1_host, n_steps, known, mask));
-  const MultistepCoef ms{cx_host, c0_host, c1_host};
-  const EditBlock ed{known, mask, a_next_host};
-  const LongBlock lg{R, W, m, r, canvas_out, recording_out};
-  const ResampleBlock rs{jump_x_host, jump_n_host, noise_seed};
-  SampleCall q{u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, nullptr, nullptr, R * W, L, use_graph,
-               graph_used_host, labels_host, labels_host ? guidance_scale : 1.0f, null_class};
-  q.ms = &ms; q.lg = &lg;
-  if (known) q.ed = &ed;
-  if (jumps) q.rs = &rs;
-  q.context = context; q.context_rows = context_rows;
-  return sample_impl(q);
+  eegldm_sample_desc d = desc_of(u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, L, use_graph,
+                                 graph_used_host, labels_host, guidance_scale, null_class);
+  d.R = R; d.W = W; d.m = m; d.r = r; d.canvas_out = canvas_out; d.recording_out = recording_out;
+  d.cx = cx_host; d.c0 = c0_host; d.c1 = c1_host; d.a_next = a_next_host;
+  d.known = known; d.mask = mask;
+  d.jump_x = jump_x_host; d.jump_n = jump_n_host; d.noise_seed = noise_seed;
+  d.context = context; d.context_rows = context_rows;
+  return eegldm_sample_run(&d);
+}
+
+extern "C" int eegldm_sample_long_edit_resample(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                                                const int64_t* timesteps_host, const float* a_t_host, const float* cx_host, const float* c0_host,
+                                                const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
+                                                float inv_scale_factor, const float* jump_x_host, const float* jump_n_host, uint64_t noise_seed,
+                                                float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
+                                                int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
+  eegldm_sample_desc d = desc_of(u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, L, use_graph,
+                                 graph_used_host, labels_host, guidance_scale, null_class);
+  d.R = R; d.W = W; d.m = m; d.r = r; d.canvas_out = canvas_out; d.recording_out = recording_out;
+  d.cx = cx_host; d.c0 = c0_host; d.c1 = c1_host; d.a_next = a_next_host;
+  d.known = known; d.mask = mask;
+  d.jump_x = jump_x_host; d.jump_n = jump_n_host; d.noise_seed = noise_seed;
+  return eegldm_sample_run(&d);
+}
+
+extern "C" int eegldm_sample_long_edit(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const float* known, const float* mask,
+                                       const int64_t* timesteps_host, const float* a_t_host, const float* cx_host, const float* c0_host,
+                                       const float* c1_host, const float* a_next_host, int n_steps, int pred_type, int clip_sample,
+                                       float inv_scale_factor, float* canvas_out, float* recording_out, int R, int W, int L, int m, int r,
+                                       int use_graph, int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
+  eegldm_sample_desc d = desc_of(u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, L, use_graph,
+                                 graph_used_host, labels_host, guidance_scale, null_class);
+  d.R = R; d.W = W; d.m = m; d.r = r; d.canvas_out = canvas_out; d.recording_out = recording_out;
+  d.cx = cx_host; d.c0 = c0_host; d.c1 = c1_host; d.a_next = a_next_host;
+  d.known = known; d.mask = mask;
+  return eegldm_sample_run(&d);
+}
+
+extern "C" int eegldm_sample_long(eegldm_unet* u, eegldm_aekl* ae, const float* noise, const int64_t* timesteps_host, const float* a_t_host,
+                                  const float* cx_host, const float* c0_host, const float* c1_host, int n_steps, int pred_type, int clip_sample,
+                                  float inv_scale_factor, float* canvas_out, float* recording_out, int R, int W, int L, int m, int r, int use_graph,
+                                  int* graph_used_host, const int64_t* labels_host, float guidance_scale, int64_t null_class) {
+  eegldm_sample_desc d = desc_of(u, ae, noise, timesteps_host, a_t_host, n_steps, pred_type, clip_sample, inv_scale_factor, L, use_graph,
+                                 graph_used_host, labels_host, guidance_scale, null_class);
+  d.R = R; d.W = W; d.m = m; d.r = r; d.canvas_out = canvas_out; d.recording_out = recording_out;
+  d.cx = cx_host; d.c0 = c0_host; d.c1 = c1_host;
+  return eegldm_sample_run(&d);
 }

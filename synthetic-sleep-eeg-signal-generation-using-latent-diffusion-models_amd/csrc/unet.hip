@@ -615,15 +615,25 @@ extern "C" int eegldm_ldm_train_step(eegldm_unet* u, const float* latents, const
   EEG_CHECK(u->num_classes == 0, "this UNet is class-conditional (%d classes): use eegldm_ldm_train_step_cond", u->num_classes);
   return ldm_train_step(u, latents, noise, t, acp, pred_type, B, L, grad_scale, loss, LabelArg());
 }
+// The label arguments of the conditional train steps -> *lab, or the error.  A UNet without classes takes labels == NULL and none of the
+// rest is read; a class-conditional one needs labels, p_uncond in [0, 1] and, when labels are dropped, a null_class in range.
+static int train_labels(const eegldm_unet* u, const int64_t* labels, float p_uncond, int64_t null_class, uint64_t seed, uint64_t offset,
+                        LabelArg* lab) {
+  if (u->num_classes == 0) { EEG_CHECK(!labels, "this UNet was built without classes: pass labels = NULL"); return 0; }
+  EEG_CHECK(labels, "this UNet is class-conditional (%d classes): labels are required", u->num_classes);
+  EEG_CHECK(p_uncond >= 0.0f && p_uncond <= 1.0f, "p_uncond %g outside [0, 1]", (double)p_uncond);
+  EEG_CHECK(p_uncond == 0.0f || (null_class >= 0 && null_class < u->num_classes), "null_class %lld outside [0, %d)", (long long)null_class,
+            u->num_classes);
+  lab->y = labels; lab->p_uncond = p_uncond; lab->null_class = null_class; lab->seed = seed; lab->offset = offset;
+  return 0;
+}
 extern "C" int eegldm_ldm_train_step_cond(eegldm_unet* u, const float* latents, const float* noise, const int64_t* t, const float* acp,
                                           int pred_type, int B, int L, float grad_scale, float* loss, const int64_t* labels, float p_uncond,
                                           int64_t null_class, uint64_t seed, uint64_t offset) {
   EEG_CHECK(u && labels, "null argument");
   EEG_CHECK(u->num_classes > 0, "this UNet was built without classes: use eegldm_ldm_train_step");
-  EEG_CHECK(p_uncond >= 0.0f && p_uncond <= 1.0f, "p_uncond %g outside [0, 1]", (double)p_uncond);
-  EEG_CHECK(p_uncond == 0.0f || (null_class >= 0 && null_class < u->num_classes), "null_class %lld outside [0, %d)", (long long)null_class,
-            u->num_classes);
-  LabelArg lab; lab.y = labels; lab.p_uncond = p_uncond; lab.null_class = null_class; lab.seed = seed; lab.offset = offset;
+  LabelArg lab;
+  EEG_TRY(train_labels(u, labels, p_uncond, null_class, seed, offset, &lab));
   return ldm_train_step(u, latents, noise, t, acp, pred_type, B, L, grad_scale, loss, lab);
 }
 // The step above with eegldm_diffusion_loss in place of get_velocity + mse_loss: wtab[t_b] weights sample b (NULL: all ones), per_sample
@@ -633,14 +643,7 @@ extern "C" int eegldm_ldm_train_step_weighted(eegldm_unet* u, const float* laten
                                               const int64_t* labels, float p_uncond, int64_t null_class, uint64_t seed, uint64_t offset) {
   EEG_CHECK(u, "null unet");
   LabelArg lab;
-  if (u->num_classes == 0) EEG_CHECK(!labels, "this UNet was built without classes: pass labels = NULL");
-  else {
-    EEG_CHECK(labels, "this UNet is class-conditional (%d classes): labels are required", u->num_classes);
-    EEG_CHECK(p_uncond >= 0.0f && p_uncond <= 1.0f, "p_uncond %g outside [0, 1]", (double)p_uncond);
-    EEG_CHECK(p_uncond == 0.0f || (null_class >= 0 && null_class < u->num_classes), "null_class %lld outside [0, %d)", (long long)null_class,
-              u->num_classes);
-    lab.y = labels; lab.p_uncond = p_uncond; lab.null_class = null_class; lab.seed = seed; lab.offset = offset;
-  }
+  EEG_TRY(train_labels(u, labels, p_uncond, null_class, seed, offset, &lab));
   return ldm_train_step(u, latents, noise, t, acp, pred_type, B, L, grad_scale, loss, lab, true, wtab, per_sample);
 }
 // The weighted step on a context UNet (include/eegldm.h): eegldm_add_noise_context in place of eegldm_add_noise, the context set for the
@@ -656,13 +659,6 @@ extern "C" int eegldm_ldm_train_step_ctx(eegldm_unet* u, const float* latents, c
             u->cfg.out_channels + 1, u->context_channels);
   const CtxArg cx{ctx_latents, mask, p_none, p_prefix, span_min, span_max, mask_seed, mask_offset, mask_out};
   LabelArg lab;
-  if (u->num_classes == 0) EEG_CHECK(!labels, "this UNet was built without classes: pass labels = NULL");
-  else {
-    EEG_CHECK(labels, "this UNet is class-conditional (%d classes): labels are required", u->num_classes);
-    EEG_CHECK(p_uncond >= 0.0f && p_uncond <= 1.0f, "p_uncond %g outside [0, 1]", (double)p_uncond);
-    EEG_CHECK(p_uncond == 0.0f || (null_class >= 0 && null_class < u->num_classes), "null_class %lld outside [0, %d)", (long long)null_class,
-              u->num_classes);
-    lab.y = labels; lab.p_uncond = p_uncond; lab.null_class = null_class; lab.seed = seed; lab.offset = offset;
-  }
+  EEG_TRY(train_labels(u, labels, p_uncond, null_class, seed, offset, &lab));
   return ldm_train_step(u, latents, noise, t, acp, pred_type, B, L, grad_scale, loss, lab, true, wtab, per_sample, &cx);
 }

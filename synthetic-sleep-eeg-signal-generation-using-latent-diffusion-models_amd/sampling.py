@@ -1,4 +1,4 @@
-"""DDIM sampling of 30-s EEG windows: the loop of /root/reference/src/sample_trials.py:149-170
+"""DDIM sampling of 30-s EEG windows: the loop of the reference's src/sample_trials.py:149-170
 (noise -> UNet/DDIM steps -> decode(z / scale_factor) -> crop [36:-36]), batched over seeds instead of
 one window at a time (the reference runs batch 1, which is launch-bound), with the step count a real
 parameter (the reference hard-codes 200, sample_trials.py:144)."""
@@ -8,7 +8,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import lib, check, ptr, PRED
+from ._lib import lib, check, ptr, PRED, SampleDesc
 from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, RESAMPLE_KEY, scheduler_edit_tables, scheduler_resample_tables
 from .training import context_window, randn
 
@@ -230,6 +230,48 @@ def _form_context(unet, autoencoder, x, context, z0, m_lat, init_d, encode, nati
     return torch.cat([m1 * src, m1], 1).contiguous()
 
 
+# the host arrays of a call, under the names its tables and the descriptor share
+_DESC_TABLES = ("a_t", "a_prev", "beta_t", "cx", "c0", "c1", "a_next", "jump_x", "jump_n")
+
+
+def _run_loop(unet, autoencoder, scheduler, x, tab, lab, guidance_scale, null_class, scale_factor, use_graph, seed, info, ancestral=False,
+              known=None, mask=None, blend=True, strength=1.0, context=None, context_rows=0, **own):
+    """ONE call of the native loop (eegldm_sample_run) from the start noise x.  What ddim_sample and sample_long share is set here, by
+    member name: the schedule (tab: host lists keyed like the descriptor -- timesteps, a_t, then whichever of a_prev / beta_t / cx / c0 /
+    c1 / a_next / jump_x / jump_n the form has; the library selects the step by what is there), classes, the edit start and blend
+    (known is dropped when only the learned conditioning is asked for -- blend=False at full strength -- and the mask with it), jumps
+    (key RESAMPLE_KEY + seed; `seed` itself is the ancestral step's key, the two never meet), the context and the graph switch.  own:
+    the caller's members -- shape and outputs.  Tensors are passed as addresses and stay alive as this function's arguments; host arrays
+    are assigned to the descriptor, which keeps them.  info (optional dict) receives {"graph", "forwards"}."""
+    if use_graph is None:
+        use_graph = os.environ.get("EEGLDM_SAMPLE_GRAPH", "0") == "1" and os.environ.get("EEGLDM_NO_GRAPH") is None
+    if known is not None and not (blend or float(strength) != 1.0):
+        known = None
+    if known is None or not blend:
+        mask = None
+    n = len(tab["timesteps"])
+    used = C.c_int(0)
+    d = SampleDesc(size=C.sizeof(SampleDesc), unet=unet.h, ae=autoencoder.h if autoencoder is not None else None, noise=x.data_ptr(),
+                   n_steps=n, timesteps=(C.c_int64 * n)(*tab["timesteps"]), ancestral=1 if ancestral else 0,
+                   noise_seed=RESAMPLE_KEY + int(seed) if "jump_x" in tab else int(seed),
+                   pred_type=PRED[scheduler.prediction_type], clip_sample=int(scheduler.clip_sample), inv_scale_factor=1.0 / float(scale_factor),
+                   guidance_scale=float(guidance_scale), null_class=null_class,
+                   known=None if known is None else known.data_ptr(), mask=None if mask is None else mask.data_ptr(),
+                   context=None if context is None else context.data_ptr(), context_rows=context_rows,
+                   use_graph=1 if use_graph else 0, graph_used=C.pointer(used), **own)
+    for k in _DESC_TABLES:
+        if k in tab:
+            setattr(d, k, (C.c_float * n)(*tab[k]))
+    if lab is not None:
+        d.labels = (C.c_int64 * len(lab))(*lab)
+    check(lib.eegldm_sample_run(C.byref(d)))
+    unet._bump_tape()
+    if autoencoder is not None:
+        autoencoder._bump_tape()
+    if info is not None:
+        info["graph"], info["forwards"] = bool(used.value), n
+
+
 @torch.no_grad()
 def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, use_graph=None, seed=0, info=None, labels=None,
                 guidance_scale=1.0, null_class=None, init=None, strength=1.0, mask=None, composite=None, init_latents=None, resamples=1,
@@ -278,66 +320,32 @@ def ddim_sample(unet, autoencoder, scheduler, noise, scale_factor=1.0, crop=36, 
     if Cc != getattr(unet, "x_channels", unet.in_channels):
         raise ValueError(f"noise has {Cc} channels, the UNet takes {getattr(unet, 'x_channels', unet.in_channels)}")
     lab, nc = _labels_host(unet, labels, B, guidance_scale, null_class)
-    multistep = isinstance(scheduler, DPMSolverMultistepScheduler)
+    ancestral = False
     if edit is not None:
         tab = edit["tab"] if rt is None else rt
-        ts, a_t = tab["timesteps"], tab["a_t"]
-    elif multistep:
-        ts, a_t, cx, c0, c1 = _multistep_tables(scheduler)
+    elif isinstance(scheduler, DPMSolverMultistepScheduler):
+        tab = dict(zip(("timesteps", "a_t", "cx", "c0", "c1"), _multistep_tables(scheduler)))
     else:
         ts, a_t, a_prev, beta, ancestral = _step_tables(scheduler)
-    n = len(ts)
-    if use_graph is None:
-        use_graph = os.environ.get("EEGLDM_SAMPLE_GRAPH", "0") == "1" and os.environ.get("EEGLDM_NO_GRAPH") is None
+        tab = dict(timesteps=ts, a_t=a_t, a_prev=a_prev, beta_t=beta)
     down = autoencoder.down if autoencoder is not None else 1
     out_c = autoencoder.out_channels if autoencoder is not None else Cc
     lat = torch.empty_like(x)
     win = torch.empty(B, out_c, L * down, device=unet.device, dtype=torch.float32)
     if B == 0:
         return (win[:, :, crop:-crop] if crop else win), lat
-    used = C.c_int(0)
-    ae_h = autoencoder.h if autoencoder is not None else None
-    i64, f32 = (lambda v: (C.c_int64 * len(v))(*v)), (lambda v: (C.c_float * len(v))(*v))
-    tail = (ptr(lat), ptr(win), B, L, 1 if use_graph else 0, C.byref(used))
+    z0 = m_win = m_lat = init_d = cx_t = None
     if edit is not None:
-        z0 = m_win = m_lat = init_d = None
+        encode = lambda w, native: _encode_windows(unet, autoencoder, w, scale_factor, native)
         if init is not None or init_latents is not None:
-            z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_latents,
-                                                    lambda w, native: _encode_windows(unet, autoencoder, w, scale_factor, native))
-        nul = C.POINTER(C.c_float)()
-        coef = (f32(tab["cx"]), f32(tab["c0"]), f32(tab["c1"])) if multistep else (nul, nul, nul)
-        front = (unet.h, ae_h, ptr(x), ptr(z0), ptr(m_lat), i64(ts), f32(a_t), nul if multistep else f32(tab["a_prev"]), *coef,
-                 f32(tab["a_next"]), n, PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor))
-        back = (*tail, None if lab is None else i64(lab), float(guidance_scale), nc)
+            z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_latents, encode)
         if ctx_model:
-            cx_t = _form_context(unet, autoencoder, x, context, z0, m_lat, init_d,
-                                 lambda w, native: _encode_windows(unet, autoencoder, w, scale_factor, native))
-            known = z0 if z0 is not None and (blend or float(strength) != 1.0) else None
-            front = (*front[:3], ptr(known), ptr(m_lat) if blend and known is not None else None, *front[5:])
-            jump = (nul, nul, 0) if rt is None else (f32(rt["jump_x"]), f32(rt["jump_n"]), RESAMPLE_KEY + int(seed))
-            check(lib.eegldm_sample_edit_ctx(*front, *jump, *back, ptr(cx_t), 0 if cx_t is None else cx_t.shape[0]))
-        elif rt is None:
-            check(lib.eegldm_sample_edit(*front, *back))
-        else:
-            check(lib.eegldm_sample_edit_resample(*front, f32(rt["jump_x"]), f32(rt["jump_n"]), RESAMPLE_KEY + int(seed), *back))
-        if edit["composite"]:
-            check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_win), B, L * down, down, 0, None, ptr(init_d), ptr(win), out_c, ptr(win)))
-    elif multistep:
-        check(lib.eegldm_sample_multistep(unet.h, ae_h, ptr(x), i64(ts), f32(a_t), f32(cx), f32(c0), f32(c1), n, PRED[scheduler.prediction_type],
-                                          int(scheduler.clip_sample), 1.0 / float(scale_factor), *tail, None if lab is None else i64(lab),
-                                          float(guidance_scale), nc))
-    else:
-        args = (unet.h, ae_h, ptr(x), i64(ts), f32(a_t), f32(a_prev), f32(beta), n, 1 if ancestral else 0, PRED[scheduler.prediction_type],
-                int(scheduler.clip_sample), 1.0 / float(scale_factor), int(seed), *tail)
-        if lab is None:
-            check(lib.eegldm_sample(*args))
-        else:
-            check(lib.eegldm_sample_cond(*args, i64(lab), float(guidance_scale), nc))
-    unet._bump_tape()
-    if autoencoder is not None:
-        autoencoder._bump_tape()
-    if info is not None:
-        info["graph"], info["forwards"] = bool(used.value), n
+            cx_t = _form_context(unet, autoencoder, x, context, z0, m_lat, init_d, encode)
+    _run_loop(unet, autoencoder, scheduler, x, tab, lab, guidance_scale, nc, scale_factor, use_graph, seed, info, ancestral=ancestral,
+              known=z0, mask=m_lat, blend=blend, strength=strength, context=cx_t, context_rows=0 if cx_t is None else cx_t.shape[0],
+              B=B, L=L, latents_out=lat.data_ptr(), windows_out=win.data_ptr())
+    if edit is not None and edit["composite"]:
+        check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_win), B, L * down, down, 0, None, ptr(init_d), ptr(win), out_c, ptr(win)))
     return (win[:, :, crop:-crop] if crop else win), lat
 
 
@@ -671,48 +679,27 @@ def sample_long(unet, autoencoder, scheduler, noise, n_windows, margin=None, ram
         raise ValueError(f"noise has {Cc} channels, the UNet takes {unet.x_channels}")
     W, L = lay.n_windows, lay.window_len
     lab, nc = _labels_host(unet, labels, R * W, guidance_scale, null_class)
-    ts, a_t, cx, c0, c1 = _multistep_tables(scheduler)
-    if use_graph is None:
-        use_graph = os.environ.get("EEGLDM_SAMPLE_GRAPH", "0") == "1" and os.environ.get("EEGLDM_NO_GRAPH") is None
     down = autoencoder.down if autoencoder is not None else 1
     out_c = autoencoder.out_channels if autoencoder is not None else Cc
     canvas = torch.empty_like(x)
     rec = torch.empty(R, out_c, lay.canvas_len * down, device=unet.device, dtype=torch.float32)
-    used = C.c_int(0)
-    i64, f32 = (lambda v: (C.c_int64 * len(v))(*v)), (lambda v: (C.c_float * len(v))(*v))
-    tab = (edit["tab"] if rt is None else rt) if edit is not None else dict(timesteps=ts, a_t=a_t, cx=cx, c0=c0, c1=c1)
-    head = (unet.h, autoencoder.h if autoencoder is not None else None, ptr(x))
-    coef = (f32(tab["cx"]), f32(tab["c0"]), f32(tab["c1"]))
-    sched = (len(tab["timesteps"]), PRED[scheduler.prediction_type], int(scheduler.clip_sample), 1.0 / float(scale_factor))
-    tail = (*sched, ptr(canvas), ptr(rec),
-            R, W, L, lay.margin, lay.ramp, 1 if use_graph else 0, C.byref(used), None if lab is None else i64(lab), float(guidance_scale), nc)
+    z0 = m_win = m_lat = init_d = cx_t = None
     if edit is None:
-        check(lib.eegldm_sample_long(*head, i64(tab["timesteps"]), f32(tab["a_t"]), *coef, *tail))
+        tab = dict(zip(("timesteps", "a_t", "cx", "c0", "c1"), _multistep_tables(scheduler)))
     else:
-        z0 = m_win = m_lat = init_d = None
+        tab = edit["tab"] if rt is None else rt
         encode = lambda r, native: encode_long(autoencoder, r, lay, scale_factor, native=native)
         if init is not None or init_canvas is not None:
             z0, m_win, m_lat, init_d = _edit_inputs(unet, autoencoder, x, init, mask, init_canvas, encode, mask_erode)
-        front = (*head, ptr(z0), ptr(m_lat), i64(tab["timesteps"]), f32(tab["a_t"]), *coef, f32(tab["a_next"]))
         if ctx_model:
             cx_t = _form_context(unet, autoencoder, x, context, z0, m_lat, init_d, encode)
-            known = z0 if z0 is not None and (blend or float(strength) != 1.0) else None
-            front = (*head, ptr(known), ptr(m_lat) if blend and known is not None else None, *front[5:])
-            nul = C.POINTER(C.c_float)()
-            jump = (nul, nul, 0) if rt is None else (f32(rt["jump_x"]), f32(rt["jump_n"]), RESAMPLE_KEY + int(seed))
-            check(lib.eegldm_sample_long_edit_ctx(*front, *sched, *jump, *tail[len(sched):], ptr(cx_t), 0 if cx_t is None else R))
-        elif rt is None:
-            check(lib.eegldm_sample_long_edit(*front, *tail))
-        else:
-            check(lib.eegldm_sample_long_edit_resample(*front, *sched, f32(rt["jump_x"]), f32(rt["jump_n"]), RESAMPLE_KEY + int(seed),
-                                                       *tail[len(sched):]))
-        if edit["composite"]:
-            check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_win), R, lay.canvas_len * down, down, 0, None, ptr(init_d), ptr(rec), out_c, ptr(rec)))
-    unet._bump_tape()
-    if autoencoder is not None:
-        autoencoder._bump_tape()
+    _run_loop(unet, autoencoder, scheduler, x, tab, lab, guidance_scale, nc, scale_factor, use_graph, seed, info, known=z0, mask=m_lat,
+              blend=blend, strength=strength, context=cx_t, context_rows=0 if cx_t is None else R,
+              R=R, W=W, L=L, m=lay.margin, r=lay.ramp, canvas_out=canvas.data_ptr(), recording_out=rec.data_ptr())
+    if edit is not None and edit["composite"]:
+        check(lib.eegldm_edit_window(unet.ctx.h, ptr(m_win), R, lay.canvas_len * down, down, 0, None, ptr(init_d), ptr(rec), out_c, ptr(rec)))
     if info is not None:
-        info["graph"], info["layout"], info["forwards"] = bool(used.value), lay, len(tab["timesteps"])
+        info["layout"] = lay
         if edit is not None:
             info["n_run"] = len(edit["tab"]["timesteps"])
     return (rec[:, :, crop:-crop] if crop else rec), canvas

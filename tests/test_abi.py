@@ -38,6 +38,22 @@ def test_error_path_without_gpu():
     assert rc != 0 and b"null ctx" in lib.eegldm_last_error()
 
 
+def test_sample_descriptor_argument_checks_without_a_device():
+    """eegldm_sample_run refuses NULL and a wrong `size` before it reads anything else; with ctypes' own size the next rule answers (a
+    NULL unet), so the C struct and SampleDesc agree on the size."""
+    from eegldm._lib import lib, SampleDesc, SIGNATURES
+    assert "eegldm_sample_run" in SIGNATURES and hasattr(lib, "eegldm_sample_run")
+    assert lib.eegldm_sample_run(None) != 0 and b"null" in lib.eegldm_last_error()
+    d = SampleDesc()
+    assert d.size == 0 and lib.eegldm_sample_run(ctypes.byref(d)) != 0
+    assert b"size" in lib.eegldm_last_error() and b"null" not in lib.eegldm_last_error()
+    d.size = ctypes.sizeof(SampleDesc)
+    assert lib.eegldm_sample_run(ctypes.byref(d)) != 0
+    assert b"null" in lib.eegldm_last_error() and b"size" not in lib.eegldm_last_error()
+    d.size = ctypes.sizeof(SampleDesc) + 8
+    assert lib.eegldm_sample_run(ctypes.byref(d)) != 0 and b"size" in lib.eegldm_last_error()
+
+
 def test_product_never_imports_oracle():
     bad = []
     for dirpath, _d, files in os.walk(PKG):
