@@ -113,6 +113,21 @@ int eegldm_debug_reload_env(void);
  * threads per block, rows- (flat: chunks-) per-thread instantiation, chunk width in channels, XCD-aware block order (1 / 0).
  * The route-aware tests confirm from it that a case ran on the kernel it names.  No reference counterpart. */
 int eegldm_debug_gn_last_route(int backward, int* out6_host);
+/* developer aids of the time-embedding MLP kernels (EEGLDM_NO_EMB_MLP=1 runs the general GEMM path instead).  No reference
+ * counterparts.
+ * _launches: kernels of the purpose-built path launched by this process so far (reset != 0: and start again from zero).
+ * _plan (no device needed): the launch arithmetic for n rows, as twelve ints: tiles of the three forward products, tiles of the weight
+ *   gradients of emb_layers / time_embed.2 / time_embed.0, tiles of dsemb, its split-K count, the reduction length of one split, tiles of
+ *   dh1, and the floats of backward work space (low 31 bits, high bits).
+ * _embed: the embedding chain as every forward and the sampler's table run it: table [n][E] (E = every ResBlock's projection width),
+ *   work = the tape [e0 (n x mc) | h1 | a1 | emb | semb (n x 4 mc each)].  labels_dev: class-conditional models only.
+ * _embed_backward: the chain's backward from demb_all [n][E] and the tape that _embed left in `work`; adds into the bound gradient
+ *   buffer.  dsemb_out (optional): [n][4 mc]. */
+int eegldm_debug_emb_mlp_launches(long* out_host, int reset);
+int eegldm_debug_emb_mlp_plan(int n, int mc, int te, int E, int* out12_host);
+int eegldm_debug_unet_embed(eegldm_unet* u, const int64_t* tsteps_dev, const int64_t* labels_dev, int n, float* table, float* work);
+int eegldm_debug_unet_embed_backward(eegldm_unet* u, const int64_t* labels_dev, int n, const float* demb_all, const float* work,
+                                     float* dsemb_out);
 /* developer aid: the kernels that served the calling thread's last eegldm_batchnorm_lrelu_fwd (backward = 0) / _bwd (1), as eight ints:
  * statistics family (0 none: plain LeakyReLU, 1 eval, 2 scalar kernel + fp64 atomics, 3 4-wide partials + fold_finalize, 4 4-wide partials +
  * fold into a sum area (forward: the ordered fold of the deterministic mode; backward: always), 5 from a producing conv's partials), apply family

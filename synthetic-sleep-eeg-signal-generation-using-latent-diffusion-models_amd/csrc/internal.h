@@ -33,6 +33,19 @@ int ew_label_dropout(eegldm_ctx*, const int64_t* y, int64_t* out, int B, float p
 // out[b] = table[y_b] (rows of width w, y clamped into [0, K)): the sampler's per-row embedding gather
 int ew_emb_gather(eegldm_ctx*, const float* table, const int64_t* y, int K, int w, float* out, int B);
 
+// emb_mlp.hip: the UNet's time-embedding MLP (fp32 on the master weights) on its own tile kernel, forward in four launches (temb + three
+// products) and backward in five (six with class labels).  The old composition of op_linear / ew_* calls stays behind EEGLDM_NO_EMB_MLP=1 (unet.hip).
+struct EmbMlpNet { const float *w0, *b0, *w2, *b2, *we, *be, *label; int mc, te, E, num_classes; };      // time_embed.0 / .2, emb_layers (E rows), label_emb
+struct EmbMlpGrads { float *w0, *b0, *w2, *b2, *we, *be, *label; };
+struct EmbMlpTape { float *e0, *h1e, *a1e, *emb, *semb; };      // n x mc, then four of n x te
+bool emb_mlp_enabled();                               // the switch, read per call
+bool emb_mlp_takes(const EmbMlpNet&, int n);          // shapes the kernels serve
+int emb_mlp_fwd(eegldm_ctx*, const EmbMlpNet&, const int64_t* tsteps, const int64_t* labels, int n, const EmbMlpTape&, float* emb_all);
+long emb_mlp_bwd_work_floats(const EmbMlpNet&, int n);
+// adds the six (seven) parameter gradients; dsemb_out (optional, n x te): the gradient of semb
+int emb_mlp_bwd(eegldm_ctx*, const EmbMlpNet&, const EmbMlpGrads&, const int64_t* labels, int n, const EmbMlpTape&, const float* demb_all,
+                float* work, float* dsemb_out);
+
 // direct_conv.hip
 bool conv_is_thin(int Cin, int Cout, int dtype);
 // K-blocked weight copies (elementwise.hip): table entry = one [3][Cout][Cin] 16-bit weight at element offset `off` of both buffers

@@ -325,11 +325,22 @@ extern "C" int eegldm_unet_sync_weights(eegldm_unet* u) {
   return u->sync_weights();
 }
 
+static EmbMlpNet emb_net(const eegldm_unet* u) {
+  EmbMlpNet net = {};
+  net.w0 = u->P(u->off_te0_w); net.b0 = u->P(u->off_te0_b); net.w2 = u->P(u->off_te2_w); net.b2 = u->P(u->off_te2_b);
+  net.we = u->P(u->off_emb_w); net.be = u->P(u->off_emb_b); net.label = u->num_classes > 0 ? u->P(u->off_label) : nullptr;
+  net.mc = u->mc; net.te = u->te; net.E = u->etot; net.num_classes = u->num_classes;
+  return net;
+}
 // temb -> Linear -> SiLU -> Linear [+ label_emb(y)] -> SiLU -> every ResBlock's embedding projection in one Linear (unet.py:526-533, 316);
 // n rows; labels (class-conditional models only): device int64 [n]
 static int embed_chain(eegldm_unet* u, const int64_t* tsteps, const int64_t* labels, int n, float* e0, float* h1e, float* a1e, float* emb,
                        float* semb, float* emb_all) {
   eegldm_ctx* ctx = u->ctx; const int mc = u->mc, te = u->te, F = EEGLDM_F32;
+  {      // the purpose-built kernels (emb_mlp.hip); EEGLDM_NO_EMB_MLP=1 or a shape they do not serve: the composition below
+    const EmbMlpNet net = emb_net(u);
+    if (emb_mlp_enabled() && emb_mlp_takes(net, n)) return emb_mlp_fwd(ctx, net, tsteps, labels, n, EmbMlpTape{e0, h1e, a1e, emb, semb}, emb_all);
+  }
   EEG_TRY(ew_temb(ctx, tsteps, e0, n, mc, F));
   EEG_TRY(op_linear(ctx, F, e0, mc, u->P(u->off_te0_w), mc, u->P(u->off_te0_b), h1e, te, n, te, mc, 1));
   EEG_TRY(ew_silu(ctx, h1e, a1e, (long)n * te, F));
@@ -474,6 +485,40 @@ extern "C" int eegldm_unet_forward_cond(eegldm_unet* u, const float* x, const in
   return unet_forward_impl(u, x, tsteps, lab, y, B, L, training);
 }
 
+// Backward of embed_chain from demb_all (n x etot) and its tape: adds the gradients of time_embed.0 / .2, emb_layers and label_emb into the
+// gradient buffer.  dsemb_out (optional, n x te): the gradient of semb, for the tests.  Scratch comes from the arena.
+static int embed_chain_backward(eegldm_unet* u, const int64_t* labels, int B, const EmbMlpTape& tp, const float* demb_all, float* dsemb_out) {
+  eegldm_ctx* ctx = u->ctx; const int mc = u->mc, te = u->te;
+  {
+    const EmbMlpNet net = emb_net(u);
+    if (emb_mlp_enabled() && emb_mlp_takes(net, B)) {
+      float* work; ALLOC_OR_FAIL(work, (float*)u->arena.alloc(sizeof(float) * (size_t)emb_mlp_bwd_work_floats(net, B)));
+      const EmbMlpGrads gr = {u->G(u->off_te0_w), u->G(u->off_te0_b), u->G(u->off_te2_w), u->G(u->off_te2_b), u->G(u->off_emb_w), u->G(u->off_emb_b),
+                              u->num_classes > 0 ? u->G(u->off_label) : nullptr};
+      return emb_mlp_bwd(ctx, net, gr, labels, B, tp, demb_all, work, dsemb_out);
+    }
+  }
+  const int E = u->etot, F = EEGLDM_F32;
+  auto fbuf = [&](long n) { return (float*)u->arena.alloc(sizeof(float) * (size_t)n); };
+  EEG_TRY(ew_colsum(ctx, demb_all, E, nullptr, 0, u->G(u->off_emb_b), 1, B, E, F));
+  EEG_TRY(op_linear_wgrad(ctx, F, tp.semb, te, demb_all, E, u->G(u->off_emb_w), te, B, E, te));
+  float* dsemb; ALLOC_OR_FAIL(dsemb, fbuf((long)B * te));
+  EEG_TRY(op_linear_dgrad(ctx, F, demb_all, E, u->P(u->off_emb_w), te, dsemb, te, B, E, te, 1));
+  float* demb; ALLOC_OR_FAIL(demb, fbuf((long)B * te));
+  if (dsemb_out) HIP_TRY(hipMemcpyAsync(dsemb_out, dsemb, sizeof(float) * (size_t)B * te, hipMemcpyDeviceToDevice, ctx->stream));
+  EEG_TRY(ew_silu_bwd(ctx, dsemb, tp.emb, demb, (long)B * te, F));
+  if (u->num_classes > 0) EEG_TRY(ew_label_emb_grad(ctx, demb, te, labels, B, te, u->num_classes, u->G(u->off_label)));   // emb = .. + label_emb(y)
+  EEG_TRY(ew_colsum(ctx, demb, te, nullptr, 0, u->G(u->off_te2_b), 1, B, te, F));
+  EEG_TRY(op_linear_wgrad(ctx, F, tp.a1e, te, demb, te, u->G(u->off_te2_w), te, B, te, te));
+  float* da1; ALLOC_OR_FAIL(da1, fbuf((long)B * te));
+  EEG_TRY(op_linear_dgrad(ctx, F, demb, te, u->P(u->off_te2_w), te, da1, te, B, te, te, 1));
+  float* dh1; ALLOC_OR_FAIL(dh1, fbuf((long)B * te));
+  EEG_TRY(ew_silu_bwd(ctx, da1, tp.h1e, dh1, (long)B * te, F));
+  EEG_TRY(ew_colsum(ctx, dh1, te, nullptr, 0, u->G(u->off_te0_b), 1, B, te, F));
+  EEG_TRY(op_linear_wgrad(ctx, F, tp.e0, mc, dh1, te, u->G(u->off_te0_w), mc, B, te, mc));
+  return 0;
+}
+
 extern "C" int eegldm_unet_backward(eegldm_unet* u, const float* dy, float* dx_out) {
   EEG_CHECK(u && dy, "null argument");
   EEG_CHECK(u->have_tape, "call eegldm_unet_forward first (with training != 0: an eval-mode forward does not keep the activations)");
@@ -550,27 +595,25 @@ extern "C" int eegldm_unet_backward(eegldm_unet* u, const float* dy, float* dx_o
     EEG_TRY(eegldm_nlc_to_ncl(ctx, dx0, cin, dx_out, B, cin - u->context_channels, L, dt));      // the x columns only: the context gets no gradient
   }
   // ---- embedding MLP backward (fp32)
-  const int E = u->etot, F = EEGLDM_F32;
-  auto fbuf = [&](long n) { return (float*)u->arena.alloc(sizeof(float) * (size_t)n); };
-  EEG_TRY(ew_colsum(ctx, demb_all, E, nullptr, 0, u->G(u->off_emb_b), 1, B, E, F));
-  EEG_TRY(op_linear_wgrad(ctx, F, u->semb, te, demb_all, E, u->G(u->off_emb_w), te, B, E, te));
-  float* dsemb; ALLOC_OR_FAIL(dsemb, fbuf((long)B * te));
-  EEG_TRY(op_linear_dgrad(ctx, F, demb_all, E, u->P(u->off_emb_w), te, dsemb, te, B, E, te, 1));
-  float* demb; ALLOC_OR_FAIL(demb, fbuf((long)B * te));
-  EEG_TRY(ew_silu_bwd(ctx, dsemb, u->emb, demb, (long)B * te, F));
-  if (u->num_classes > 0) EEG_TRY(ew_label_emb_grad(ctx, demb, te, u->labels, B, te, u->num_classes, u->G(u->off_label)));   // emb = .. + label_emb(y)
-  EEG_TRY(ew_colsum(ctx, demb, te, nullptr, 0, u->G(u->off_te2_b), 1, B, te, F));
-  EEG_TRY(op_linear_wgrad(ctx, F, u->a1e, te, demb, te, u->G(u->off_te2_w), te, B, te, te));
-  float* da1; ALLOC_OR_FAIL(da1, fbuf((long)B * te));
-  EEG_TRY(op_linear_dgrad(ctx, F, demb, te, u->P(u->off_te2_w), te, da1, te, B, te, te, 1));
-  float* dh1; ALLOC_OR_FAIL(dh1, fbuf((long)B * te));
-  EEG_TRY(ew_silu_bwd(ctx, da1, u->h1e, dh1, (long)B * te, F));
-  EEG_TRY(ew_colsum(ctx, dh1, te, nullptr, 0, u->G(u->off_te0_b), 1, B, te, F));
-  EEG_TRY(op_linear_wgrad(ctx, F, u->e0, mc, dh1, te, u->G(u->off_te0_w), mc, B, te, mc));
+  EEG_TRY(embed_chain_backward(u, u->labels, B, EmbMlpTape{u->e0, u->h1e, u->a1e, u->emb, u->semb}, demb_all, nullptr));
   EEG_TRY(op_wgrad_flush(ctx));      // the remaining (input-block) weight gradients, grouped by shape
   EEG_TRY(u->flush_attn_folds());    // the folded AttentionBlocks whose qkv gradient that flush completed: back-transformed into the real slots
   EEG_TRY(op_gn_fold_flush(ctx));    // and the remaining GroupNorm dgamma / dbeta folds
   return 0;
+}
+
+// developer aids (include/eegldm.h): the embedding chain and its backward on their own, through the functions every forward / backward calls
+extern "C" int eegldm_debug_unet_embed(eegldm_unet* u, const int64_t* tsteps_dev, const int64_t* labels_dev, int n, float* table, float* work) {
+  return unet_embed_table(u, tsteps_dev, labels_dev, n, table, work);
+}
+extern "C" int eegldm_debug_unet_embed_backward(eegldm_unet* u, const int64_t* labels_dev, int n, const float* demb_all, const float* work,
+                                                float* dsemb_out) {
+  EEG_CHECK(u && u->params && u->grads && demb_all && work && n > 0, "bad argument (parameters and gradients must be bound)");
+  EEG_CHECK(u->num_classes == 0 || labels_dev, "a class-conditional UNet's embedding backward needs labels");
+  const long te = u->te;
+  float* e0 = const_cast<float*>(work); float* h1e = e0 + (long)n * u->mc; float* a1e = h1e + n * te; float* emb = a1e + n * te; float* semb = emb + n * te;
+  u->arena.reset(); u->have_tape = false;      // scratch comes from the arena: a forward's tape does not survive this call
+  return embed_chain_backward(u, labels_dev, n, EmbMlpTape{e0, h1e, a1e, emb, semb}, demb_all, dsemb_out);
 }
 
 // cx (eegldm_ldm_train_step_ctx; NULL otherwise): what the step's context is formed from, the arguments of eegldm_add_noise_context
