@@ -390,7 +390,8 @@ __global__ __launch_bounds__(NT) void l1_kernel(const float* __restrict__ a, con
   GRID_STRIDE(i, n) {
     const float d = a[i] - b[i];
     s += fabsf(d);
-    if (da) { const float g = wgrad * inv_n * (d > 0.f ? 1.0f : (d < 0.f ? -1.0f : 0.f)); da[i] = overwrite ? g : da[i] + g; }
+    // sign(0) = 0; a NaN difference (which makes the loss NaN) stays NaN in its own gradient element instead of reading as 0
+    if (da) { const float g = wgrad * inv_n * (d > 0.f ? 1.0f : (d < 0.f ? -1.0f : (d == 0.f ? 0.f : d))); da[i] = overwrite ? g : da[i] + g; }
   }
   s = wave_sum(s);
   __shared__ float red[4];

@@ -120,6 +120,9 @@ extern "C" int eegldm_ms_ssim_1d(eegldm_ctx* ctx, const float* a, const float* b
   EEG_CHECK(ksize >= 1 && ksize <= MAX_TAPS && n_scales >= 1 && n_scales <= MAX_SCALES, "kernel_size <= %d and <= %d scales", MAX_TAPS, MAX_SCALES);
   const int div = (n_scales - 1) > 1 ? (n_scales - 1) * (n_scales - 1) : 1;         // compute_mmds.py:361-369
   EEG_CHECK(L / div > ksize - 1, "for %d scales and kernel size %d the window must be longer than %d", n_scales, ksize, (ksize - 1) * div);
+  // the reference's guard above is weaker than the kernel's need for 6 to 8 scales: the window is halved n_scales - 1 times and the last scale
+  // must still hold one kernel (300 samples, 6 scales, 11 taps passes the guard with 9 samples left: a negative count of valid positions)
+  EEG_CHECK((L >> (n_scales - 1)) >= ksize, "for %d scales the last scale has %d samples, fewer than the kernel size %d", n_scales, L >> (n_scales - 1), ksize);
   SsimParams P = {};
   for (int i = 0; i < ksize; i++) P.k[i] = kernel_host[i];
   for (int i = 0; i < n_scales; i++) P.w[i] = weights_host[i];

@@ -67,6 +67,8 @@ class MultiScaleSSIMMetric:
         if L // div <= ks - 1:
             raise ValueError(f"For a given number of `weights` parameters {ns} and kernel size {ks}, the image height must be larger than "
                              f"{(ks - 1) * div}.")
+        if (L >> (ns - 1)) < ks:          # 6 to 8 scales: the guard above lets a last scale shorter than the kernel through
+            raise ValueError(f"For {ns} scales the last scale has {L >> (ns - 1)} samples, fewer than the kernel size {ks}.")
         out = torch.empty(B, 1, device=self.device)
         if B:
             check(lib.eegldm_ms_ssim_1d(self.ctx.h, ptr(a), ptr(b), ptr(out), B, Cc, L, (C.c_float * ks)(*self.kernel.tolist()), ks,
