@@ -113,6 +113,19 @@ int eegldm_debug_reload_env(void);
  * threads per block, rows- (flat: chunks-) per-thread instantiation, chunk width in channels, XCD-aware block order (1 / 0).
  * The route-aware tests confirm from it that a case ran on the kernel it names.  No reference counterpart. */
 int eegldm_debug_gn_last_route(int backward, int* out6_host);
+/* developer aid: what the calling thread's last ResBlock forward and backward (eegldm_block_forward / _backward, or the last ResBlock of a
+ * model's step) decided, as twelve ints:
+ *   [0]     forward form: 1 GroupNorm -> conv -> GroupNorm -> conv, 2 the same with use_scale_shift_norm, 3 the few-row eval form
+ *   [1..3]  backward of the second GroupNorm: family (as eegldm_debug_gn_last_route), chunk width in channels, body (1 the straight-line
+ *           full-slab kernel, 2 the predicated one, 0 outside the register-resident family);   [4..6] the same for the first GroupNorm
+ *   [7]     who wrote the per-sample column sums behind the embedding gradient: 0 nobody, 1 the GroupNorm backward, 2 the column-sum
+ *           kernel over the stored gradient, 3 the FiLM backward (use_scale_shift_norm)
+ *   [8..10] who added the gradient of out_layers.3.bias, skip_connection.bias, in_layers.2.bias: 0 no such parameter (or no parameter
+ *           gradients), 1 a column-sum kernel straight into it, 2 the weight-gradient GEMM, 3 the total of the per-sample sums, 4 the
+ *           staged vector both output-side biases can share
+ *   [11]    1 when the column-sum kernels were the ordered ones of EEGLDM_DETERMINISTIC=1
+ * It records decisions only; no launch depends on it.  No reference counterpart. */
+int eegldm_debug_res_last_route(int* out12_host);
 /* developer aids of the time-embedding MLP kernels (EEGLDM_NO_EMB_MLP=1 runs the general GEMM path instead).  No reference
  * counterparts.
  * _launches: kernels of the purpose-built path launched by this process so far (reset != 0: and start again from zero).

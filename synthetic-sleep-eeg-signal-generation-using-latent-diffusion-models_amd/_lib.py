@@ -51,6 +51,7 @@ SIGNATURES = {
     "eegldm_prof_dump": [_vp, C.c_char_p],
     "eegldm_debug_reload_env": [],
     "eegldm_debug_gn_last_route": [_i, _vp],
+    "eegldm_debug_res_last_route": [_vp],
     "eegldm_debug_emb_mlp_launches": [_vp, _i],
     "eegldm_debug_emb_mlp_plan": [_i, _i, _i, _i, _vp],
     "eegldm_debug_unet_embed": [_vp, _vp, _vp, _i, _vp, _vp],

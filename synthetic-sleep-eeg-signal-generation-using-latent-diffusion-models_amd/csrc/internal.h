@@ -130,6 +130,7 @@ int op_groupnorm_bwd(eegldm_ctx*, const void* x, long ldx, const float* gamma, c
                      int fuse_silu, int resample, const void* dxr, long lddxr, int dtype, float* colsum_ps, long ldps, int* colsum_done,
                      const void* dxr2 = nullptr, long lddxr2 = 0, int* dxr2_done = nullptr, int* slots_deferred = nullptr, int defer_region = 0);
 int op_gn_slot_reduce_deferred(eegldm_ctx*, float* dgamma, float* dbeta, int C, int region = 0);   // when *slots_deferred came back 1 (stream-ordered after the backward)   // dxr2: second, un-resampled addend [B*L][C] (skip gradient); *dxr2_done = 1 when the kernel added it
+void gn_last_bwd_route(int out3[3]);      // {family, chunk width, body (1 full-slab, 2 predicated, 0 other families)} of this thread's last GroupNorm backward
 int ew_fold_partials(eegldm_ctx*, const float* parts, int nparts, int n, float* total);
 // frozen-encoder fusion (enc_fused.hip): GroupNorm(G = 1) + SiLU on the operand load of a 3-tap conv, next layer's statistics from its epilogue
 bool pre_conv3_ok(int dtype, int Cin, int Cout, int L);

@@ -206,6 +206,28 @@ int entry_query(const NetBase* u, int i, char* name, int cap, long* offset, long
 }
 
 // ------------------------------------------------------------------ ResBlock (unet.py:307-327)
+// What the calling thread's last res_forward / res_backward decided (eegldm_debug_res_last_route; the route-aware tests confirm that a case
+// ran on the producers it names).  Host-side bookkeeping, one record per host thread; no launch depends on it.
+//   fwd      1 GroupNorm -> conv -> GroupNorm -> conv, 2 the same with use_scale_shift_norm (FiLM), 3 the few-row eval form (conv1 tried on
+//            the fused kernel, statistics left for the norm-on-load conv2)
+//   gn2, gn1 {family, chunk width, body} of the two GroupNorm backward launches (family as eegldm_debug_gn_last_route; body 1 the
+//            straight-line full-slab kernel, 2 the predicated one, 0 outside the resident family)
+//   ps       who wrote the per-sample column sums behind the embedding gradient: 0 nobody, 1 the GroupNorm backward, 2 the column-sum
+//            kernel over the stored dh1, 3 the FiLM backward
+//   b_c2, b_sk, b_c1   who added the gradient of out_layers.3.bias / skip_connection.bias / in_layers.2.bias: 0 no such parameter (or no
+//            parameter gradients), 1 a column-sum kernel straight into it, 2 the weight-gradient GEMM, 3 the total of the per-sample sums,
+//            4 the staged vector of the context scratch
+//   det      1 when the column-sum kernels were the ordered ones (EEGLDM_DETERMINISTIC)
+struct ResRoute { int fwd, gn2[3], gn1[3], ps, b_c2, b_sk, b_c1, det; };
+static thread_local ResRoute g_res_route = {};
+extern "C" int eegldm_debug_res_last_route(int* out12_host) {
+  if (!out12_host) return EEGLDM_ERR_INVALID;
+  const ResRoute& r = g_res_route;
+  const int v[12] = {r.fwd, r.gn2[0], r.gn2[1], r.gn2[2], r.gn1[0], r.gn1[1], r.gn1[2], r.ps, r.b_c2, r.b_sk, r.b_c1, r.det};
+  for (int i = 0; i < 12; i++) out12_host[i] = v[i];
+  return 0;
+}
+
 int res_forward(NetBase* u, const ResDesc& r, const View& x, int B, int Lin, const View& out) {
   eegldm_ctx* ctx = u->ctx; const int dt = u->dtype;
   const int Lout = r.updown == 1 ? Lin / 2 : (r.updown == 2 ? Lin * 2 : Lin);
@@ -236,6 +258,8 @@ int res_forward(NetBase* u, const ResDesc& r, const View& x, int B, int Lin, con
   ALLOC_OR_FAIL(t.h1.p, u->alloc_act((long)B * Lout, r.cout)); t.h1.ld = r.cout; t.h1.C = r.cout;
   bool fused = false;
   float2* area = fuse2 ? u->fuse_alloc(need) : nullptr;
+  g_res_route = ResRoute{};
+  g_res_route.fwd = area ? 3 : (r.ssn ? 2 : 1);
   if (!area && fuse1) { fuse1 = false; EEG_TRY(norm1()); }        // no room for the statistics: the plain path below needs the normalised tensor
   if (area) {
     SkinnyGn gn1 = {pa ? pa->slots : nullptr, u->P(r.gn1_w), u->P(r.gn1_b), cpg1, GN_EPS, 1};
@@ -342,6 +366,10 @@ int res_backward(NetBase* u, const ResDesc& r, const ResTape& t, const View& dou
   View da2; ALLOC_OR_FAIL(da2.p, u->alloc_act((long)B * Lout, r.cout)); da2.ld = r.cout;
   EEG_TRY(op_conv_dgrad(ctx, dt, dout.p, dout.ld, u->W(r.c2_w), da2.p, da2.ld, B, Lout, r.cout, r.cout, 3, 1, 1, 1, nullptr, 0));
   if (t.dropped) EEG_TRY(ew_dropout_rows(ctx, da2.p, da2.ld, (long)B * Lout, r.cout, u->dropout, u->drop_seed, t.drop_off, dt));      // the forward's mask, regenerated
+  ResRoute& note = g_res_route;
+  note.det = eeg_deterministic() ? 1 : 0;
+  note.b_c2 = !pg ? 0 : (fb2 ? 2 : (r.sk_w >= 0 ? 4 : 1));
+  note.b_sk = (!pg || r.sk_w < 0) ? 0 : (fbs ? 2 : 4);
   if (pg) {
     // conv2's bias gradient = column sums of dout; the skip conv's bias gradient is the same vector
     if (fb2 && (r.sk_w < 0 || fbs)) {
@@ -378,6 +406,9 @@ int res_backward(NetBase* u, const ResDesc& r, const ResTape& t, const View& dou
   // few output channels = hundreds of K splits adding into the same bias entries (+17 us at 128 channels): when the one-pass
   // GroupNorm backward already produced per-sample sums, their total is cheaper
   const bool fb1e = fb1 && !(cs_done && ps && r.cout < 256);
+  gn_last_bwd_route(note.gn2);
+  note.ps = r.ssn ? 3 : (!emb_add ? 0 : (cs_done ? 1 : 2));
+  note.b_c1 = !pg ? 0 : (fb1e ? 2 : (cs_done ? 3 : 1));
   if (pg) {
     EEG_TRY(ctx_fork(ctx));                       // dh1 is ready
     SideScope side(ctx);
@@ -397,6 +428,7 @@ int res_backward(NetBase* u, const ResDesc& r, const ResTape& t, const View& dou
   EEG_TRY(op_groupnorm_bwd(ctx, t.x.p, t.x.ld, u->P(r.gn1_w), u->P(r.gn1_b), t.st1, da1.p, da1.ld, dx.p, dx.ld, u->param_grads ? u->G(r.gn1_w) : nullptr, u->param_grads ? u->G(r.gn1_b) : nullptr,
                            B, Lin, r.cin, r.groups, 1, r.updown, dxr.p, dxr.ld, dt, nullptr, 0, nullptr,
                            extra ? extra->p : nullptr, extra ? extra->ld : 0, extra_done, pg ? &gn1_deferred : nullptr, 1 + u->gn_parity));
+  gn_last_bwd_route(note.gn1);
   if (gn1_deferred == 1) {   // folded inside the NEXT block's side-stream section (or by the executor's final flush); areas alternate, so the
     u->gn_pending.push_back({u->G(r.gn1_w), u->G(r.gn1_b), r.cin, 1 + u->gn_parity});   // block after that may write this one again
     u->gn_parity ^= 1;

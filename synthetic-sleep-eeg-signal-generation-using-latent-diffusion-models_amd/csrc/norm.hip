@@ -1071,7 +1071,12 @@ __global__ __launch_bounds__(NTB) void gn_bwd_pipe_kernel(const bf16_t* __restri
 // read-out reports the calling thread's own last launch), nothing the kernels read.
 struct GnRoute { int family, vec, nth, rpt, cc, xcd; };
 static thread_local GnRoute g_gn_route[2] = {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
-inline void gn_note(int bwd, int family, int vec, int nth, int rpt, int cc, int xcd) { g_gn_route[bwd] = GnRoute{family, vec, nth, rpt, cc, xcd}; }
+// body of the last resident backward: 1 the straight-line full-slab kernel, 2 the predicated one; 0 for every other family
+static thread_local int g_gn_bwd_body = 0;
+inline void gn_note(int bwd, int family, int vec, int nth, int rpt, int cc, int xcd) {
+  g_gn_route[bwd] = GnRoute{family, vec, nth, rpt, cc, xcd};
+  if (bwd) g_gn_bwd_body = 0;
+}
 
 // chunk width for the resident kernels: the widest whole-group chunk (<= 256 channels, dividing C) whose rows fit the
 // per-thread register budget; 0 = not eligible (fall back to the split kernels)
@@ -1329,7 +1334,9 @@ int gn_bwd_t(eegldm_ctx* ctx, const void* x, long ldx, const float* gamma, const
       gn_note(1, 2, 1, p.nth, rhi ? RHI : RLO, p.cc, p.xcd);
       // same route, same geometry; a full slab runs the straight-line body, instantiated for what this launch has (EEGLDM_GN_NO_STREAM=1: never)
       EEG_ENV_VAR(bool, no_stream, getenv("EEGLDM_GN_NO_STREAM") != nullptr);
-      if (!no_stream && p.nth == NTB && resident_full_slab(L, p.cc, rhi ? RHI : RLO)) {
+      const bool full_body = !no_stream && p.nth == NTB && resident_full_slab(L, p.cc, rhi ? RHI : RLO);
+      g_gn_bwd_body = full_body ? 1 : 2;
+      if (full_body) {
         const int sel = (dxr ? 1 : 0) | (dxr2 ? 2 : 0) | (colsum_ps ? 4 : 0) | (silu ? 8 : 0) | (rhi ? 16 : 0) | ((resample == 1 ? 1 : resample == 2 ? 2 : 0) << 5);
         gn_static_switch<96>(sel, [&](auto s) {
           constexpr int S = decltype(s)::value;
@@ -1796,6 +1803,9 @@ extern "C" int eegldm_groupnorm_bwd(eegldm_ctx* ctx, const void* x, long ldx, co
   return op_groupnorm_bwd(ctx, x, ldx, gamma, beta, stats, dy, lddy, dx, lddx, dgamma, dbeta, B, L, C, G, fuse_silu, resample,
                           dxr, lddxr, dtype, nullptr, 0, nullptr);
 }
+
+// {family, chunk width, body} of the calling thread's last backward launch, for the ResBlock executor's own record (net.hip)
+void gn_last_bwd_route(int out3[3]) { out3[0] = g_gn_route[1].family; out3[1] = g_gn_route[1].cc; out3[2] = g_gn_bwd_body; }
 
 extern "C" int eegldm_debug_gn_last_route(int backward, int* out6_host) {
   if (!out6_host || backward < 0 || backward > 1) return EEGLDM_ERR_INVALID;
