@@ -1160,6 +1160,29 @@ int eegldm_fir_same(eegldm_ctx*, const float* x, long ldx, const float* taps, in
 int eegldm_threshold_events(eegldm_ctx*, const float* s, long lds_, const float* aux, long ldaux, const float* thr, long B, int L,
                             int min_len, int max_len, int merge_gap, int drop_edge, int max_events, int* counts, int* ev_i, float* ev_f);
 
+/* ---- preparing raw recordings (eegldm.recordings: EDF in, low-passed 100 Hz rows out; csrc/resample.hip).  Additive, ABI 8.
+ * eegldm_resample_fir: zero-phase rational-rate FIR resampler over B rows of L samples, L in 1..2^30.  taps is a DEVICE array of M floats,
+ * M odd in 1..16383, c = (M - 1) / 2; U in 1..64, D in 1..4096; Lout = ceil(L U / D) in 64 bits.
+ *   v[i] = xe[b][i / U] where U divides i, else 0;      y[b][m] = sum_{k = 0..M-1} taps[k] v[m D + k - c],  m in [0, Lout).
+ * xe is the row extended by zeros (edge 0) or by the whole-sample reflection of eegldm_fir_same (edge 1: xe[-i] = x[i], xe[L-1+i] =
+ * x[L-1-i]; needs ceil(c / U) <= L - 1).  Only the taps with (m D + k - c) % U == 0 meet a sample, at most ceil(M / U) per output.  Every
+ * output is ONE fmaf chain over its own terms in ascending k from +0; under edge 0 the terms outside the row are skipped, not multiplied.
+ * So an output's bits do not depend on B, on the launch geometry or on where in a row the same samples sit, a non-finite sample makes
+ * non-finite exactly the outputs whose terms hold it, and with U = D = 1 the result is that of eegldm_fir_same(mode 0) bit for bit.
+ * xtype 0: x is fp32 rows.  xtype 1: x is int16 rows (EDF's digital samples) and gain / offset are fp32 DEVICE arrays of B values: the sample
+ * that enters the chain is fmaf((float)d, gain[b], offset[b]), one fp32 rounding (gain / offset are ignored for xtype 0 and may be NULL).
+ * ldx / ldy are row strides in elements (>= L, >= Lout); fp32 pointers need 4-byte alignment, an int16 x 2-byte alignment; x == y is
+ * refused; B == 0 is a no-op; B times the number of output segments (Lout / 2048 or Lout / 1024 by default) beyond 65535 * 2^20 workgroups is refused.
+ * No atomics, no memset, one writer per element.  Every refusal leaves y untouched. */
+int eegldm_resample_fir(eegldm_ctx*, const void* x, long ldx, int xtype /* 0 fp32, 1 int16 */, const float* gain, const float* offset,
+                        const float* taps, int M, int U, int D, float* y, long ldy, long B, long L, int edge /* 0 zeros, 1 reflect */);
+/* eegldm_epoch_stats: for B rows of L fp32 samples (row stride ldx >= L) and epochs of E samples, E in 1..12288, only the L / E whole epochs
+ * counted: out [B][L / E][4] = (min, max, mean, sd), contiguous fp32.  min / max by < / > from the epoch's first sample; the mean is a float64
+ * sum over the epoch divided by E, sd the root of the float64 mean squared deviation ABOUT THAT MEAN (two passes over the epoch held on
+ * chip), each rounded to fp32 once.  A NaN anywhere in the epoch makes all four NaN.  One workgroup per epoch, fixed reduction order: a result
+ * repeats bit for bit.  L < E or B == 0 is a no-op; B (L / E) beyond 65535 * 2^20 is refused. */
+int eegldm_epoch_stats(eegldm_ctx*, const float* x, long ldx, long B, long L, int E, float* out);
+
 /* ---- time-frequency primitives (spectrograms, band courses and phase-amplitude coupling of eegldm.metrics; csrc/tfr.hip).  Additive, ABI 8.
  * eegldm_stft_num_frames (host only): frames of a row of L samples.  centre 0: frame f covers [f hop, f hop + n_win), F = L >= n_win ?
  * (L - n_win) / hop + 1 : 0.  centre 1: with h = n_win / 2 frame f covers [f hop - h, f hop - h + n_win), F = (L - 1) / hop + 1 (0 for L == 0).

@@ -249,6 +249,8 @@ SIGNATURES = {
     "eegldm_kernel_matmul": [_vp, _vp, _l, _vp, _vp, _l, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _f, _f, C.POINTER(_f), _i, _l, _i, _vp, _l],
     "eegldm_fir_same": [_vp, _vp, _l, _vp, _i, _vp, _l, _l, _i, _i, _i],
     "eegldm_threshold_events": [_vp, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "eegldm_resample_fir": [_vp, _vp, _l, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _l, _l, _l, _i],
+    "eegldm_epoch_stats": [_vp, _vp, _l, _l, _l, _i, _vp],
     "eegldm_stft_num_frames": [_l, _i, _i, _i],
     "eegldm_stft_power": [_vp, _vp, _l, _l, _l, _vp, C.POINTER(_f), _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp, C.POINTER(_i), _i, _vp],
     "eegldm_pac_intervals": [_vp, _vp, _l, _vp, _l, _vp, _l, _l, _l, _vp, _l, _vp],
