@@ -1247,6 +1247,41 @@ int eegldm_ordinal_counts(eegldm_ctx*, const float* x, long ldx, long B, int L, 
 int eegldm_template_matches(eegldm_ctx*, const float* x, long ldx, long B, int L, int m, int scale, const float* r /* device [B] */,
                             long long* counts /* [B][2] */);
 
+/* ---- device-resident window bank (eegldm.data; csrc/window_bank.hip).  Additive, ABI 8.  A bank is ONE flat fp32 device buffer holding every
+ * recording of a loader, one channel each, row r at [row_off[r], row_off[r + 1]); rows start at any 4-byte offset and the bank may pass
+ * 2^31 elements (64-bit indices).  Every refusal returns its code, sets eegldm_last_error, launches nothing and leaves the outputs untouched.
+ *
+ * eegldm_bank_normalise: the deterministic head of the window transform, in place, row by row -- a = x * fl32(1 + 1e6), lo = min a, hi = max a,
+ * row = hi == lo ? +0 : (a - lo) / (hi - lo), every operation a separately rounded fp32 operation (no fma), so a row's bytes are those of the
+ * same three numpy expressions; lohi [n_rec][2] receives (lo, hi).  A NaN in a row makes its lo, hi and every element NaN (numpy's min / max
+ * keep a NaN) and touches no other row.  Only the sign of a zero minimum is unspecified (min(+0, -0)).  row_off is the DEVICE array of
+ * n_rec + 1 ascending int64 offsets, row_off_host the same values in host memory (the checks and the launch shape are taken from it);
+ * rows hold 1 .. 2^30 samples.  ws: 2 * (row_off[n_rec] / EEGLDM_BANK_CHUNK + n_rec + 1) floats of device workspace (contents irrelevant).
+ * Three launches -- a min / max partial per fixed chunk of EEGLDM_BANK_CHUNK samples, one fold per row, the apply pass -- without atomics or
+ * memsets; min and max are exact, so no value depends on the launch geometry and two runs agree bit for bit. */
+#define EEGLDM_BANK_CHUNK 16384
+int eegldm_bank_normalise(eegldm_ctx*, float* bank, const int64_t* row_off /* device [n_rec + 1] */, const int64_t* row_off_host, int n_rec,
+                          float* lohi /* device [n_rec][2] */, float* ws, long ws_floats);
+/* eegldm_window_batch: one launch crops, pads and labels a batch of B windows.  The sampling policy lives in the SEGMENT TABLE the caller
+ * built (eegldm.data.segment_tables): segment j is a run of consecutive valid crop starts that share a label -- seg_first[j] the bank
+ * index of its first start, seg_cum [n_seg + 1] the running count of starts (strictly ascending from 0), seg_label[j] int32 -- and a group
+ * g is the contiguous segment range [group_bounds[g], group_bounds[g + 1]) (group_bounds [n_group + 1]).  All arrays are device memory.
+ * Window b:  [lo, hi) = (seg_cum[group_bounds[g]], seg_cum[group_bounds[g + 1]]) for g = group[b], or (0, seg_cum[n_seg]) when group is
+ * NULL;  idx = idx_in[b] when idx_in is given, else lo + v % (hi - lo) with v the 64-bit word (r0 << 32) | r1 of Philox4x32-10(key seed,
+ * counter offset + b) -- lo plus what eegldm_randint(high = hi - lo, seed, offset) writes to element b;  j: seg_cum[j] <= idx <
+ * seg_cum[j + 1] (binary search);  src = seg_first[j] + idx - seg_cum[j];  out[b * ld ..] = border exact +0, bank[src .. src + window),
+ * border +0;  labels_out[b] = seg_label[j] and src_out[b] = src (int64, each nullable).  ld >= window + 2 border; the floats of a row past
+ * window + 2 border are not written.  Nothing outside [src, src + window) is read; rows whose address is a multiple of 16 bytes are stored
+ * 16 bytes at a time, others element by element, the source may have any 4-byte alignment.  One block per window: no value depends on the
+ * launch geometry.  Refused: NULL bank / tables / out, group without group_bounds, window < 1, border < 0, ld too small, B < 1, n_seg < 1,
+ * bank_len < window.  What only the device can see -- idx_in[b] outside [lo, hi), an empty range, a group outside [0, n_group), a src with
+ * [src, src + window) outside [0, bank_len) -- gives row b = NaN (all window + 2 border floats), labels_out[b] = INT64_MIN, src_out[b] = -1,
+ * reads nothing from the bank and leaves the other rows alone. */
+int eegldm_window_batch(eegldm_ctx*, const float* bank, long bank_len, const int64_t* seg_first, const int64_t* seg_cum,
+                        const int32_t* seg_label, long n_seg, const int64_t* group_bounds /* nullable */, int n_group,
+                        const int64_t* group /* nullable [B] */, const int64_t* idx_in /* nullable [B] */, uint64_t seed, uint64_t offset,
+                        int window, int border, float* out, long ld, int64_t* labels_out /* nullable */, int64_t* src_out /* nullable */, int B);
+
 #ifdef __cplusplus
 }
 #endif

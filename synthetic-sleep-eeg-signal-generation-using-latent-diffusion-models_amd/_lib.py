@@ -257,6 +257,9 @@ SIGNATURES = {
     "eegldm_row_moments": [_vp, _vp, _l, _l, _i, _vp],
     "eegldm_ordinal_counts": [_vp, _vp, _l, _l, _i, _i, _i, _vp, _vp],
     "eegldm_template_matches": [_vp, _vp, _l, _l, _i, _i, _i, _vp, _vp],
+    # device-resident window bank (csrc/window_bank.hip, eegldm.data)
+    "eegldm_bank_normalise": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _l],
+    "eegldm_window_batch": [_vp, _vp, _l, _vp, _vp, _vp, _l, _vp, _i, _vp, _vp, C.c_uint64, C.c_uint64, _i, _i, _vp, _l, _vp, _vp, _i],
     "eegldm_resblock_create": [_vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)],
     "eegldm_attnblock_create": [_vp, _i, _i, _i, C.POINTER(_vp)],
     "eegldm_block_destroy": [_vp],

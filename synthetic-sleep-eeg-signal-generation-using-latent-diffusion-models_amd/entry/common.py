@@ -213,6 +213,35 @@ class WindowLoader:
                 yield {"eeg": torch.from_numpy(np.stack([w for w, _ in items])), "label": torch.tensor([c for _, c in items], dtype=torch.int64)}
 
 
+def add_device_loader_args(p):
+    p.add_argument("--device_loader", action="store_true", help="keep the recordings in device memory (eegldm.data.WindowBank) and crop, pad and "
+                   "label every batch there in one launch, instead of the per-item numpy loop and an upload per batch.  Same distribution of "
+                   "windows as the host loader, another random stream (device Philox instead of numpy)")
+    p.add_argument("--sampling", default="recording", choices=["recording", "uniform", "balanced"], help="with --device_loader, how training "
+                   "windows are drawn: each recording once per epoch (the host loader's epoch), uniformly over every valid start of the bank, or "
+                   "class first, then uniformly within the class (needs stages).  Validation always visits recordings")
+
+
+def window_loader(args, path_pre_processed, batch_size, n_synthetic=0, sampling=None, **kw):
+    """The loader of an entry script: WindowLoader(path_pre_processed, batch_size, n_synthetic, **kw), or with --device_loader a
+    DeviceWindowLoader over a bank of exactly the files (and stage files) that loader resolved -- id CSV, directory scan and shard included.
+    sampling: None = the command line's --sampling (training), or a fixed mode (validation passes "recording")."""
+    host = WindowLoader(path_pre_processed, batch_size, n_synthetic, **kw)
+    mode = sampling or getattr(args, "sampling", "recording")
+    if not getattr(args, "device_loader", False):
+        if getattr(args, "sampling", "recording") != "recording":
+            raise ValueError("--sampling needs --device_loader")
+        return host
+    if not host.files:
+        raise ValueError("--device_loader banks recordings (--path_train_ids / --path_pre_processed), not synthetic windows")
+    if kw.get("crop_starts") is not None:
+        raise ValueError("injected crop_starts belong to the host loader")
+    from ..data import DeviceWindowLoader, WindowBank
+    bank = WindowBank(host.files, host.stage_files)
+    return DeviceWindowLoader(bank, batch_size, kw.get("seed", 0), sampling=mode, windows_per_recording=kw.get("windows_per_recording", 1),
+                              drop_last=kw.get("drop_last", False), shuffle=kw.get("shuffle", True))
+
+
 def add_ema_args(p):
     p.add_argument("--ema_decay", type=float, default=None, help="keep an exponential moving average of the UNet weights with this decay "
                    "(updated inside the Adam kernel); adds the 'ema' entry to checkpoint.pth and writes best_model_ema.pth / final_model_ema.pth")

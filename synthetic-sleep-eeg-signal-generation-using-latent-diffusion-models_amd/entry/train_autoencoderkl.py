@@ -16,8 +16,8 @@ import torch
 from .. import distributed as D
 from ..models import AutoencoderKL, PatchDiscriminator
 from ..training import Adam, aekl_train_step, randn
-from .common import (ParseListAction, WindowLoader, add_grad_clip_args, format_clip_stats, grad_clip_entry, grad_clip_resume, load_config, rng_seed,
-                     setup_run_dir)
+from .common import (ParseListAction, add_device_loader_args, add_grad_clip_args, format_clip_stats, grad_clip_entry, grad_clip_resume, load_config, rng_seed,
+                     setup_run_dir, window_loader)
 
 
 def parse_args(argv=None):
@@ -34,6 +34,7 @@ def parse_args(argv=None):
     p.add_argument("--max_steps", type=int, default=0); p.add_argument("--output_dir", default=None)
     p.add_argument("--deterministic", action="store_true", help="bit-reproducible steps (eegldm.set_deterministic(): ordered reductions instead of fp32 atomics; "
                    "what torch.use_deterministic_algorithms(True) would be for the reference's loop)")
+    add_device_loader_args(p)
     add_grad_clip_args(p, accum=False)      # (no accumulation here: BatchNorm statistics are per micro-batch)
     return p.parse_args(argv)
 
@@ -67,12 +68,13 @@ def main(args):
     adv_w, kl_w = config.models.adv_weight, config.models.kl_weight
     spec_w = config.models.get("spectral_weight", 0.0)
     bs = max(1, config.train.batch_size // world)
-    train = WindowLoader(args.path_pre_processed, bs, args.synthetic_windows, seed=rng_seed(config.train.seed, 8, rank, world), drop_last=config.train.drop_last,
-                         path_ids=args.path_train_ids, dataset=args.type_dataset, shard=(rank, world))
+    train = window_loader(args, args.path_pre_processed, bs, args.synthetic_windows, seed=rng_seed(config.train.seed, 8, rank, world), drop_last=config.train.drop_last,
+                          path_ids=args.path_train_ids, dataset=args.type_dataset, shard=(rank, world))
     # validation reads the VALID split (dataset.py:83-99); without id CSVs (synthetic / bare directory runs) it is a held-out synthetic set
     # or, as a last resort, the same directory.  Every rank scores its shard; (sum, count) are added over ranks
-    val = WindowLoader(args.path_pre_processed, bs, max(args.synthetic_windows // 4, config.train.batch_size) // world if args.synthetic_windows else 0,
-                       seed=rng_seed(config.train.seed, 9, rank, world), shuffle=False, path_ids=args.path_valid_ids, dataset=args.type_dataset, shard=(rank, world))
+    val = window_loader(args, args.path_pre_processed, bs, max(args.synthetic_windows // 4, config.train.batch_size) // world if args.synthetic_windows else 0,
+                        sampling="recording", seed=rng_seed(config.train.seed, 9, rank, world), shuffle=False, path_ids=args.path_valid_ids, dataset=args.type_dataset,
+                        shard=(rank, world))
     start_epoch, best, steps = 0, float("inf"), 0
     init_batch = None
     if resume:

@@ -13,9 +13,10 @@ from .. import distributed as D
 from ..models import UNetModel
 from ..schedulers import DDPMScheduler
 from ..training import EMA, Adam, GradScaler, NoiseLevelLoss, dm_train_step, randint, randn
-from .common import (WindowLoader, accum_factor, accum_plan, add_context_args, add_ema_args, add_grad_clip_args, add_loss_weighting_args, append_noise_level_record, context_entry,
+from .common import (accum_factor, accum_plan, add_context_args, add_device_loader_args, add_ema_args, add_grad_clip_args, add_loss_weighting_args, append_noise_level_record, context_entry,
                      context_resume, cpu_state, ema_checkpoint_entry, ema_resume,
-                     format_clip_stats, format_noise_level_table, grad_clip_entry, grad_clip_resume, load_config, loss_weighting_resume, rng_seed, setup_run_dir, step_weighting)
+                     format_clip_stats, format_noise_level_table, grad_clip_entry, grad_clip_resume, load_config, loss_weighting_resume, rng_seed, setup_run_dir, step_weighting,
+                     window_loader)
 
 
 def parse_args(argv=None):
@@ -32,6 +33,7 @@ def parse_args(argv=None):
     add_ema_args(p)
     add_loss_weighting_args(p)
     add_grad_clip_args(p)
+    add_device_loader_args(p)
     add_context_args(p)
     return p.parse_args(argv)
 
@@ -61,8 +63,8 @@ def main(args):
     scaler = GradScaler(enabled=args.grad_scaler or str(args.dtype) in ("float16", "fp16", "half"))
     spectral = args.spe == "spectral"
     bs = max(1, config.train.batch_size // world)
-    train = WindowLoader(args.path_pre_processed, bs, args.synthetic_windows, seed=rng_seed(config.train.seed, 8, rank, world), drop_last=config.train.drop_last,
-                         path_ids=args.path_train_ids, dataset=args.type_dataset, shard=(rank, world))
+    train = window_loader(args, args.path_pre_processed, bs, args.synthetic_windows, seed=rng_seed(config.train.seed, 8, rank, world), drop_last=config.train.drop_last,
+                          path_ids=args.path_train_ids, dataset=args.type_dataset, shard=(rank, world))
     s_t, s_noise = rng_seed(config.train.seed, 1, rank, world), rng_seed(config.train.seed, 3, rank, world)
     s_mask, centry, cspec = rng_seed(config.train.seed, 11, rank, world), None, None
     dev, ctx = unet.device, unet.ctx

@@ -12,9 +12,10 @@ from .. import distributed as D
 from ..models import AutoencoderKL, UNetModel
 from ..schedulers import DDPMScheduler
 from ..training import EMA, Adam, GradScaler, NoiseLevelLoss, context_mask, context_window, ldm_train_step, randint, randn
-from .common import (ParseListAction, WindowLoader, accum_factor, accum_plan, add_context_args, add_ema_args, add_grad_clip_args, add_loss_weighting_args, append_noise_level_record,
+from .common import (ParseListAction, accum_factor, accum_plan, add_context_args, add_device_loader_args, add_ema_args, add_grad_clip_args, add_loss_weighting_args, append_noise_level_record,
                      context_entry, context_resume, cpu_state, ema_checkpoint_entry,
-                     ema_resume, format_clip_stats, format_noise_level_table, grad_clip_entry, grad_clip_resume, load_config, loss_weighting_resume, rng_seed, setup_run_dir, step_weighting)
+                     ema_resume, format_clip_stats, format_noise_level_table, grad_clip_entry, grad_clip_resume, load_config, loss_weighting_resume, rng_seed, setup_run_dir, step_weighting,
+                     window_loader)
 
 
 def parse_args(argv=None):
@@ -42,6 +43,7 @@ def parse_args(argv=None):
     add_ema_args(p)
     add_loss_weighting_args(p)
     add_grad_clip_args(p)
+    add_device_loader_args(p)
     add_context_args(p)
     return p.parse_args(argv)
 
@@ -138,12 +140,12 @@ def main(args):
     opt = Adam(unet, lr=config.train.get("base_lr", 1e-4), ema=ema, max_grad_norm=args.max_grad_norm)
     scaler = GradScaler(enabled=args.grad_scaler or str(args.dtype) in ("float16", "fp16", "half"))      # fp16 activations: the loss scale is what keeps their gradients out of the subnormal range
     bs = max(1, config.train.batch_size // world)
-    train = WindowLoader(args.path_pre_processed, bs, args.synthetic_windows, seed=rng_seed(config.train.seed, 8, rank, world), drop_last=config.train.drop_last,
-                         path_ids=args.path_train_ids, dataset=args.type_dataset, shard=(rank, world), stages=cond, path_stages=args.path_stages)
+    train = window_loader(args, args.path_pre_processed, bs, args.synthetic_windows, seed=rng_seed(config.train.seed, 8, rank, world), drop_last=config.train.drop_last,
+                          path_ids=args.path_train_ids, dataset=args.type_dataset, shard=(rank, world), stages=cond, path_stages=args.path_stages)
     # validation: every rank scores its own shard (equal lengths, wrap-around: a recording may be scored twice when N % world != 0)
     # and the (sum, count) pairs are added over ranks -- model selection sees the WHOLE validation split, as the reference's does
-    valid = WindowLoader(args.path_pre_processed, bs, 0, seed=rng_seed(config.train.seed, 9, 0, world), shuffle=False, path_ids=args.path_valid_ids,
-                         dataset=args.type_dataset, shard=(rank, world), stages=cond, path_stages=args.path_stages) if args.path_valid_ids else None
+    valid = window_loader(args, args.path_pre_processed, bs, 0, sampling="recording", seed=rng_seed(config.train.seed, 9, 0, world), shuffle=False, path_ids=args.path_valid_ids,
+                          dataset=args.type_dataset, shard=(rank, world), stages=cond, path_stages=args.path_stages) if args.path_valid_ids else None
     v_seeds = tuple(rng_seed(config.train.seed, role, rank, world) for role in (5, 6, 7))
     s_t, s_eps, s_noise = (rng_seed(config.train.seed, role, rank, world) for role in (1, 2, 3))
     s_lab = rng_seed(config.train.seed, 10, rank, world)

@@ -27,7 +27,7 @@ import torch
 
 from ..metrics import USleep, _stager_input, balanced_class_weights, stage_report
 from ..training import Adam, EMA
-from .common import WindowLoader, cpu_state
+from .common import add_device_loader_args, cpu_state, window_loader
 
 
 def parse_args(argv=None):
@@ -45,6 +45,7 @@ def parse_args(argv=None):
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--depth", type=int, default=12); p.add_argument("--n_classes", type=int, default=5)
     p.add_argument("--sfreq", type=float, default=100.0); p.add_argument("--input_size_s", type=float, default=30.0)
+    add_device_loader_args(p)
     return p.parse_args(argv)
 
 
@@ -87,7 +88,7 @@ def evaluate(model, batches, n_classes):
     pred, true = [], []
     for b in batches:
         p, _logits = model.predict(b["eeg"])
-        pred.append(p.cpu().numpy()); true.append(b["label"].numpy())
+        pred.append(p.cpu().numpy()); true.append(b["label"].cpu().numpy())
     return stage_report(np.concatenate(pred), np.concatenate(true), n_classes=n_classes)
 
 
@@ -105,17 +106,19 @@ def main(args):
     torch.manual_seed(args.seed)
     if bool(args.synthetic_dir) == bool(args.path_train_ids):
         raise ValueError("give exactly one of --synthetic_dir (generated windows) and --path_train_ids (real recordings)")
+    if args.synthetic_dir and getattr(args, "device_loader", False):
+        raise ValueError("--device_loader banks recordings (--path_train_ids), not the generated windows of --synthetic_dir")
     if args.synthetic_dir:
         train = ArrayBatches(*load_labelled_windows(args.synthetic_dir), args.batch_size, args.seed)
     else:
-        train = WindowLoader(args.path_pre_processed, args.batch_size, seed=args.seed, path_ids=args.path_train_ids, dataset=args.type_dataset,
-                             windows_per_recording=args.windows_per_recording, stages=True, path_stages=args.path_stages)
+        train = window_loader(args, args.path_pre_processed, args.batch_size, seed=args.seed, path_ids=args.path_train_ids, dataset=args.type_dataset,
+                              windows_per_recording=args.windows_per_recording, stages=True, path_stages=args.path_stages)
     valid = None
     if args.valid_synthetic_dir:
         valid = ArrayBatches(*load_labelled_windows(args.valid_synthetic_dir), args.batch_size, args.seed, shuffle=False)
     elif args.path_valid_ids:
-        valid = WindowLoader(args.path_pre_processed, args.batch_size, seed=args.seed + 1, shuffle=False, path_ids=args.path_valid_ids,
-                             dataset=args.type_dataset, windows_per_recording=args.windows_per_recording, stages=True, path_stages=args.path_stages)
+        valid = window_loader(args, args.path_pre_processed, args.batch_size, sampling="recording", seed=args.seed + 1, shuffle=False, path_ids=args.path_valid_ids,
+                              dataset=args.type_dataset, windows_per_recording=args.windows_per_recording, stages=True, path_stages=args.path_stages)
     model = USleep(in_chans=2, sfreq=args.sfreq, depth=args.depth, with_skip_connection=True, n_classes=args.n_classes, input_size_s=args.input_size_s,
                    apply_softmax=False)
     model.load_state_dict(model._default_init(torch.Generator().manual_seed(args.seed)))
@@ -125,7 +128,7 @@ def main(args):
     if args.class_weights == "balanced":
         # generated windows: the labels are in memory; recordings: one pass over the training loader's labels (the crops are random, so this
         # is the class balance of one epoch's draw)
-        labels = train.labels() if isinstance(train, ArrayBatches) else np.concatenate([b["label"].numpy() for b in train])
+        labels = train.labels() if isinstance(train, ArrayBatches) else np.concatenate([b["label"].cpu().numpy() for b in train])
         cw = balanced_class_weights(labels, args.n_classes)
     history, best, start = [], {"epoch": -1, "balanced_accuracy": -1.0}, 0
     ck_path = os.path.join(args.output_dir, "checkpoint.pth")
